@@ -11,6 +11,15 @@ gradient per gradient step, --exchange mailbox = the exchange inside the gradien
 Prints ONE JSON line on rank 0, kept under 6 KB (the driver's record keeps 8 KB of tail): numbers only, 4 significant digits; what a key
 means is written HERE, not in the line.
 
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times ONE window of K vector steps and prints the headline keys
+(value, ms_per_step, windows, config, grad_steps_per_sec and the fixed descriptive keys).  Everything else below -- the roofline objects (HIP
+events inside the first window), `clock`, all_reduce_ms, timeouts, the CPU baselines, `also`, `learner_only` -- and the default of 5
+windows come with --full.  --dump-outputs DIR writes what the last timed vector step handed its caller, right after the timed region, as
+float32 DIR/<name>.npy: obs (the observations the next act would see, resets applied), reward, done, info; with a learner also loss (the
+last gradient step's, if the timed steps trained) and q_params (the acting network's flat parameters); with --rollout T obs and the last
+step of every trace (<name>_last_step).  Per-env arrays are cut to a fixed, seeded sample of envs (env_index.npy) if everything would
+exceed 64 MB.  Inputs depend on the arguments only (seeded worlds, policy, exploration and replay sampling).
+
   value / ms_per_step   the MEDIAN of `windows.n` timed windows of --steps vector steps each (every window bracketed by a barrier + device
                         synchronisation on both sides, max over ranks); windows.min / .max = the slowest / fastest window's env steps/s
   roofline              the dominant kernel of the loop, the fused IQN act kernel (`iqn_qvals_split_kernel`: the float32 network on the f16 matrix
@@ -145,6 +154,25 @@ def rocm_smi_power():
         return vals or None
     except Exception:
         return None
+
+
+def dump_outputs(path, arrays, n_envs, budget=64 << 20):
+    """Write `arrays` (name -> tensor or None) as float32 `path/<name>.npy`.  If they hold more than `budget` bytes, the arrays with one row
+    per env keep a fixed, seeded sample of rows, whose env indices go to env_index.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    out = {k: torch.as_tensor(v).detach().float().cpu().numpy() for k, v in arrays.items() if v is not None}
+    per_env = [k for k, a in out.items() if a.ndim and a.shape[0] == n_envs]
+    env_bytes = sum(out[k].nbytes for k in per_env)
+    total = sum(a.nbytes for a in out.values())
+    if total > budget:
+        keep = (budget - (total - env_bytes)) // (env_bytes // n_envs + 8)
+        idx = np.sort(np.random.RandomState(0).choice(n_envs, keep, replace=False))
+        out = {k: (a[idx] if k in per_env else a) for k, a in out.items()}
+        out["env_index"] = idx.astype(np.float64)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def _timed(device, fn, steps, warmup, state, before_timed=None):
@@ -352,7 +380,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps vector steps each; `value` is the median window")
+    ap.add_argument("--windows", type=int, default=None, help="timed windows of --steps vector steps each; `value` is the median window (default 1, 5 with --full)")
+    ap.add_argument("--full", action="store_true", help="measure everything the line can carry (rooflines, clock, CPU baselines, `also`, `learner_only`; "
+                                                        "5 windows), not just the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed vector step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--envs", type=int, default=65536, help="envs per GPU")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--replay", type=int, default=100_000)
@@ -396,9 +427,11 @@ def main():
                                                                           "episode ends per vector step is at most this (default: the library's, 5000)")
     ap.add_argument("--graph-train", action="store_true", help="the gradient steps of a training event as one captured hipGraph (IQNAgent.use_fused_graph)")
     ap.add_argument("--shared-taus", action="store_true", help="one set of 32 taus per act LAUNCH instead of per env (IQNAgent.shared_taus; opt-in, "
-                                                               "timed by the default run as also.act_shared_taus)")
+                                                               "timed by a --full run as also.act_shared_taus)")
     ap.add_argument("--no-clock-probe", action="store_true", help="skip the two ~50 ms MFMA clock probes around the timed region (cleaner rocprofv3 tables)")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
     if args.precision is None:
         args.precision = default_precision(learner=not args.no_learner)
 
@@ -412,13 +445,14 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # started as plain `python bench.py --gpus N`: re-launch as N ranks (one per GPU) under torch.distributed.run
+        # started as plain `python bench.py --gpus N`: run N ranks (one per GPU) under torch.distributed.run in a child process
         import socket
+        import subprocess
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
-        os.execvp(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                   "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        raise SystemExit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                                          "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} needs torch.distributed.run with --nproc-per-node {args.gpus} (WORLD_SIZE={world})")
     rpg = max(1, args.ranks_per_gpu)
@@ -478,6 +512,7 @@ def main():
             return getattr(self._e, k)
     loop_env = _NoAppend(env) if args.separate_append else env
     eps_seen = []
+    last = {}      # what the last vector step returned beyond the env's own buffers (--dump-outputs)
 
     def one_step(o):
         if agent is None:
@@ -486,7 +521,10 @@ def main():
             return env.reset_done()
         eps = agent.linear_eps(total_timesteps) if args.eps is None else args.eps
         eps_seen.append(eps)
-        return agent.vec_step(loop_env, o, eps, args.cvar, per_iter=n * world)[0]
+        o, _, _, _, loss = agent.vec_step(loop_env, o, eps, args.cvar, per_iter=n * world)
+        if loss is not None:
+            last["loss"] = loss
+        return o
 
     def fence():
         torch.cuda.synchronize(device)
@@ -508,7 +546,7 @@ def main():
                 o = one_step(o)
             return o
         for _ in range(k // roll):      # k vector steps as k / T launches of T steps each
-            env.rollout(roll, action_seed=rank, first_step=step_ctr[0], trace=trace)
+            last["rollout"] = env.rollout(roll, action_seed=rank, first_step=step_ctr[0], trace=trace)
             step_ctr[0] += roll
         return env.obs
 
@@ -533,13 +571,17 @@ def main():
         if guard.fallback is not None:
             resets_note = "in_front_of_act (the reset launch did not run beside the act kernel on this box: late rows timed out)"
     g0 = agent.grad_steps if agent else 0
+    # (a plain run probes too, without reporting it: the timed region starts from the clock this matrix load leaves, as it always has; measured, a
+    # 20-step window timed without the probe in front ran ~8 % slower)
     clock_before = gpu_clock_probe(device) if (rank == 0 and not args.no_clock_probe) else None      # ~50 ms of matrix load, outside the timed region
     # HIP-event pairs are recorded around the first n_prof act / step / reset launches of the FIRST window; not around all of them, because the event records
-    # of a vector step cost ~18 us of stream time (measured: 1.079 ms/step with 200 instrumented steps, 1.067 with 50, 1.061 with 1)
-    n_prof = min(args.steps // max(1, roll), int(os.environ.get("MN_BENCH_NPROF", "50")))
+    # of a vector step cost ~18 us of stream time (measured: 1.079 ms/step with 200 instrumented steps, 1.067 with 50, 1.061 with 1).  --full only: a plain
+    # run times its steps without event records
+    n_prof = min(args.steps // max(1, roll), int(os.environ.get("MN_BENCH_NPROF", "50"))) if args.full else 0
     env.profile_begin(n_prof)
     if fused:
         act_context(agent.qnetwork_local).profile_begin(n_prof)
+    last.clear()
     window_s = []
     rl_before = list(env.reset_launches)
     for w in range(max(1, args.windows)):
@@ -554,6 +596,17 @@ def main():
             el = float(t.item())
         window_s.append(el)
     elapsed = statistics.median(window_s)
+    if args.dump_outputs and rank == 0:      # what the last timed step handed its caller, before anything else runs on these buffers
+        if agent is not None and agent.reset_under_act:
+            env.join_reset()      # (the last step's resets may still be writing rows of obs)
+        if roll:
+            outputs = {"obs": env.obs, **{f"{k}_last_step": last["rollout"][k][-1] for k in trace}}
+        else:
+            outputs = {"obs": obs, "reward": env.reward, "done": env.done, "info": env.info}
+        if agent is not None:
+            outputs["loss"] = last.get("loss")
+            outputs["q_params"] = torch.cat([p.detach().reshape(-1) for p in agent.qnetwork_local.parameters()])
+        dump_outputs(args.dump_outputs, outputs, n)
     reset_ms, reset_launches = env.profile_reset_end()
     rl_timed = [b - a for a, b in zip(rl_before, env.reset_launches)]      # reset launches of the timed windows: [in front of, under] the act kernel
     step_kernel_ms, launches = env.profile_end()
@@ -561,10 +614,10 @@ def main():
     if fused:
         act_ms, act_launches = act_context(agent.qnetwork_local).profile_end()
     grad_steps = (agent.grad_steps - g0) if agent else 0
-    clock_after = gpu_clock_probe(device) if (rank == 0 and not args.no_clock_probe) else None
+    clock_after = gpu_clock_probe(device) if (rank == 0 and args.full and not args.no_clock_probe) else None
     # episodes that end per vector step (the reset kernel's work): counted over 16 more steps (mn_last_done_count synchronises: outside the timed region)
     resets_per_step = None
-    if not roll:
+    if args.full and not roll:
         cnt = []
         for _ in range(16):
             if agent is None:
@@ -579,7 +632,7 @@ def main():
         resets_per_step = sum(cnt) / len(cnt)
 
     all_reduce_ms = None
-    if use_dist and args.shared_learner:      # the shared learner's collective alone: 35 785-float bucket, back to back (max over ranks)
+    if args.full and use_dist and args.shared_learner:      # the shared learner's collective alone: 35 785-float bucket, back to back (max over ranks)
         bucket = torch.zeros(35785, dtype=torch.float32, device="cpu" if backend == "gloo" else device)
         for _ in range(20):
             dist.all_reduce(bucket)
@@ -592,20 +645,20 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         all_reduce_ms = float(tt.item())
     timeouts = None
-    if agent is not None and getattr(agent, "_fused", None) is not None:
+    if args.full and agent is not None and getattr(agent, "_fused", None) is not None:
         timeouts = agent._fused.timeouts()      # bounded waits that ran out (0: every step updated; a shared learner's ranks agree)
     late_to = None
-    if agent is not None and agent.reset_under_act and agent.use_fused_act:
+    if args.full and agent is not None and agent.reset_under_act and agent.use_fused_act:
         from distributional_rl_navigation_amd.iqn.fused_act import late_timeouts
         env.join_reset()
         late_to = late_timeouts(agent.qnetwork_local)      # act rows taken before their reset had finished (0: the reset launch ran beside the act kernel)
     also = {}
-    if world == 1 and not args.no_also and agent is not None and fused and not roll and not args.torch_train and not args.torch_act:
+    if args.full and world == 1 and not args.no_also and agent is not None and fused and not roll and not args.torch_train and not args.torch_act:
         also = also_legs(args, env, agent, obs, device, total_timesteps, use_dist)
 
     # learner alone (outside the timed region): back-to-back IQN grad steps (sample + train), batch 256, 8 quantiles
     learner_only = {}
-    if agent is not None and len(agent.memory) > agent.BATCH_SIZE and not args.no_learner_only:
+    if args.full and agent is not None and len(agent.memory) > agent.BATCH_SIZE and not args.no_learner_only:
         was_fused = agent.use_fused_train
         for mode in ("fused_hip", "eager", "hipgraph"):       # the torch modes last: they advance torch's own Adam state
             if mode == "hipgraph" and agent.distributed:
@@ -701,7 +754,7 @@ def main():
             }
         else:
             out["roofline"] = env_roof
-        if args.cpu_steps > 0 and world == 1:      # reported baseline: rank 0 at N = 1 only
+        if args.full and args.cpu_steps > 0 and world == 1:      # reported baseline: rank 0 at N = 1 only
             v, dt = cpu_baseline(args.cpu_steps, (args.cores, args.obstacles, min_dis))
             out["cpu_baseline"] = {"value": v, "unit": "env steps/s", "cores": 1, "kind": "port",
                                    "sample": f"{args.cpu_steps} steps, 1 env, C oracle, {dt:.1f} s"}
@@ -711,10 +764,14 @@ def main():
                 v, dt = cpu_baseline_all_cores(each, (args.cores, args.obstacles, min_dis), nth)
                 out["cpu_all_cores"] = {"value": v, "cores": nth, "host_cpus": os.cpu_count()}
             out["cpu_reference_python"] = 293
-        out["clock"] = {"before": clock_before, "after": clock_after, "power": rocm_smi_power()}
-        # what README leads with goes LAST: the driver's record keeps the tail of the line
-        out["also"] = also
-        out["learner_only"] = learner_only
+        if args.full:
+            out["clock"] = {"before": clock_before, "after": clock_after, "power": rocm_smi_power()}
+            # what README leads with goes LAST: a record that keeps only the tail of the line still has it
+            out["also"] = also
+            out["learner_only"] = learner_only
+        else:      # a plain run: the headline, its windows and the run's configuration
+            for k in ("all_reduce_ms", "timeouts", "roofline_env_step", "roofline"):
+                del out[k]
         out["grad_steps_per_sec"] = grad_steps * (1 if args.shared_learner else world) / sum(window_s)
         result_line = json.dumps(sig(out), separators=(",", ":"))
     if use_dist:

@@ -5,8 +5,8 @@
 # lines at N = 1 and with two ranks on the one GPU; the experiment sweep.
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${MEASURE_DIR:-m6}; mkdir -p $O; rm -f $O/pmc_summary.txt $O/pmc_shared_summary.txt
 cd $R
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --shared-taus --cpu-steps 0 --no-also --no-learner-only > $O/bench_shared_taus.json 2> $O/bench_shared_taus.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --shared-taus --cpu-steps 0 --no-also --no-learner-only > $O/bench_shared_taus.json 2> $O/bench_shared_taus.err
 python scripts/learner_bench.py 3000 > $O/learner_bench.txt 2>&1
 python scripts/reset_scaling.py f64 > $O/reset_scaling.txt 2>&1
 python scripts/reset_under_act_ab.py 200 > $O/reset_under_act_ab.txt 2>&1

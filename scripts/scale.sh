@@ -21,8 +21,8 @@ for N in 1 2 4 8; do
   [ "$N" -gt "$HAVE" ] && break
   run() { # name, extra args
     local name=$1; shift
-    if [ "$N" -eq 1 ]; then python bench.py --gpus 1 --steps 200 --warmup 20 --cpu-steps 0 --no-also --no-learner-only "$@" > "$OUT/${name}_$N.json" 2> "$OUT/${name}_$N.err"
-    else python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus "$N" --ranks-per-gpu "$RPG" --steps 200 --warmup 20 --cpu-steps 0 --no-also --no-learner-only "$@" > "$OUT/${name}_$N.json" 2> "$OUT/${name}_$N.err"; fi
+    if [ "$N" -eq 1 ]; then python bench.py --gpus 1 --steps 200 --warmup 20 --cpu-steps 0 --no-also --no-learner-only --full "$@" > "$OUT/${name}_$N.json" 2> "$OUT/${name}_$N.err"
+    else python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus "$N" --ranks-per-gpu "$RPG" --steps 200 --warmup 20 --cpu-steps 0 --no-also --no-learner-only --full "$@" > "$OUT/${name}_$N.json" 2> "$OUT/${name}_$N.err"; fi
     PORT=$((PORT + 1))
     python - "$OUT/${name}_$N.json" "$name" "$N" <<'PY'
 import json, sys

@@ -379,7 +379,7 @@ def test_bench_shared_learner_line(torch, exchange):
     all-reduce executes / the exchange rides in the step's launch) prints ONE JSON line with the contract's keys."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--shared-learner", "--cvar", "0.5", "--exchange", exchange,
-                          "--envs", "4096", "--steps", "24", "--warmup", "8", "--windows", "2", "--cpu-steps", "0", "--no-learner-only"],
+                          "--envs", "4096", "--steps", "24", "--warmup", "8", "--windows", "2", "--cpu-steps", "0", "--no-learner-only", "--full"],
                          capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     j = _bench_line(out)
     assert j["config"]["learner"] == "shared" and j["config"]["exchange"] == exchange and j["config"]["cvar"] == 0.5
@@ -408,7 +408,7 @@ def test_bench_world_size_2_branch_runs_under_torch_distributed_run(torch, confi
     steps = 12
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--ranks-per-gpu", "2", "--steps", str(steps), "--warmup", "4", "--windows", "3",
-           "--update-every", "2", "--cpu-steps", "0", "--no-learner-only", "--no-clock-probe"] + extra
+           "--update-every", "2", "--cpu-steps", "0", "--no-learner-only", "--no-clock-probe", "--full"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1200, cwd=ROOT)
     j = _bench_line(out)
     assert j["n_gpus"] == 2 and j["steps"] == steps and j["config"]["ranks_per_gpu"] == 2 and j["config"]["process_group"] == "gloo"
