@@ -1,0 +1,358 @@
+// dqn_train.hip -- fused gradient step of the DQN baseline for gfx950 (MI355X): batch draw, target and local forward, smooth-L1
+// TD loss, backward, gradient-norm clip and Adam in ONE launch.
+//
+// Replaces, for one optimizer step of DQNAgent.train (the reference's stable-baselines3 `DQN.train`, dqn/dqn.py:188-230) on a batch
+// drawn from the device replay ring:
+//     next_q   = q_net_target(next_obs).max(dim = 1)                      (:198-201)
+//     target_q = r + (1 - done) * gamma * next_q                          (:203)
+//     current  = q_net(obs).gather(1, a)                                  (:206-209)
+//     loss     = smooth_l1_loss(current, target_q)      (beta 1, mean)    (:212)
+//     backward; clip_grad_norm_(10); Adam(lr 1e-4)                        (:216-221)
+// with the network of dqn_act.hip (26 -> (16 | 16 | 176) encoders without activation, 208 -> 64 -> 64 -> 9, then 9 -> 64 -> 64 -> 9,
+// ReLU after hidden_layer, hidden_layer_2, q_net.0 and q_net.2).  27 650 parameters, ~28 k multiply-adds per sample and pass.
+//
+// Decomposition: ceil(B / 16) workgroups of 512 threads.  Workgroup w owns batch slots [16 w, 16 w + 16) -- one MFMA tile of samples --
+// and carries it through the target forward, the local forward, the loss and the whole backward with its activations in LDS.  It writes
+// its partial parameter gradient (every element exactly once) into row w of the workspace and its partial loss next to it, publishes them
+// (agent-scope release) and takes a ticket.  The workgroup that takes the LAST ticket (agent-scope acquire) sums the rows in index order,
+// forms the global norm, clips, applies Adam over the flat vectors and advances the step and call counters.  No float atomics, no waits,
+// no co-residency: the result does not depend on which workgroup finishes last.
+//
+// MFMA mapping: exact-f32 v_mfma_f32_16x16x4_f32.  Every product is a 16 x 16 tile C[i][j] = sum_k A(i, k) B(k, j), lane (l, g) =
+// (lane & 15, lane >> 4) feeding A(l, k0 + g) and B(k0 + g, l), and holding C[4 g + r][l] afterwards.  Forward tiles are [16 samples x
+// 16 outputs] (A = activations in LDS, B = the layer's weights read straight from the flat parameter vector: they change every step),
+// data-gradient tiles [16 samples x 16 inputs], weight-gradient tiles [16 outputs x 16 inputs] contracted over the 16 samples.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "marinenav_hip.h"
+#include "mn_train_shared.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int OBS = MN_OBS_DIM;      // 26
+constexpr int F = 208, H = 64, A = 9;
+constexpr int THREADS = 512, WAVES = THREADS / 64, TILE = 16, MAX_BATCH_DQN = 256;
+// flat parameter vector = DQNPolicy.q_net.named_parameters() order, nn.Linear [out][in]
+constexpr int O_VW = 0, O_VB = 32, O_GW = 48, O_GB = 80, O_SW = 96, O_SB = 3968, O_HW = 4144, O_HB = 17456, O_H2W = 17520, O_H2B = 21616,
+              O_OW = 21680, O_OB = 22256, O_Q0W = 22265, O_Q0B = 22841, O_Q2W = 22905, O_Q2B = 27001, O_Q4W = 27065, O_Q4B = 27641,
+              P_TOTAL = 27650;
+static_assert(O_Q4B + A == P_TOTAL, "flat parameter layout");
+constexpr int P_PAD = 27652;         // row stride of the partial gradients (16-byte aligned rows)
+// workspace (floats): [n_part][P_PAD] partial gradients | [16] partial losses | ticket (u32) + padding
+__host__ __device__ constexpr int64_t ws_loss(int n_part) { return (int64_t)n_part * P_PAD; }
+__host__ __device__ constexpr int64_t ws_ticket(int n_part) { return ws_loss(n_part) + 16; }
+__host__ __device__ constexpr int64_t ws_total(int n_part) { return ws_ticket(n_part) + 4; }
+
+// LDS (floats): row strides of the [16 samples][width] activation blocks
+constexpr int LDO = 28, LDF = 212, LDH = 68, LDA = 16, LDD = 212;
+constexpr int S_OBS = 0;                        // [16][LDO] states
+constexpr int S_NOBS = S_OBS + TILE * LDO;      // [16][LDO] next_states
+constexpr int S_F = S_NOBS + TILE * LDO;        // [16][LDF] encoder outputs
+constexpr int S_H1 = S_F + TILE * LDF;          // [16][LDH] relu(hidden_layer)
+constexpr int S_H2 = S_H1 + TILE * LDH;         // [16][LDH] relu(hidden_layer_2)
+constexpr int S_O = S_H2 + TILE * LDH;          // [16][LDA] output_layer (the extractor's 9 features)
+constexpr int S_Q1 = S_O + TILE * LDA;          // [16][LDH] relu(q_net.0)
+constexpr int S_Q2 = S_Q1 + TILE * LDH;         // [16][LDH] relu(q_net.2)
+constexpr int S_Q = S_Q2 + TILE * LDH;          // [16][LDA] Q values
+constexpr int S_D0 = S_Q + TILE * LDA;          // [16][LDD] gradient ping-pong buffers
+constexpr int S_D1 = S_D0 + TILE * LDD;
+constexpr int S_Y = S_D1 + TILE * LDD;          // [16] TD targets
+constexpr int S_TOTAL = S_Y + TILE;
+static_assert(S_TOTAL * 4 <= 64 * 1024, "static LDS");
+
+__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+__device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
+
+// acc[i][j] += sum_{k < K} A(i, k) B(k, j) on one 16 x 16 tile; lane (l, g) reads A(l, k) and B(k, l) for k = k0 + g
+template <int K, class FA, class FB>
+__device__ __forceinline__ f32x4 mma16(FA fa, FB fb, f32x4 acc) {
+    const int l = lane_id() & 15, g = lane_id() >> 4;
+#pragma unroll
+    for (int k0 = 0; k0 < K; k0 += 4) {
+        const int k = k0 + g;
+        const float a = k < K ? fa(l, k) : 0.f;
+        const float b = k < K ? fb(k, l) : 0.f;
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
+    }
+    return acc;
+}
+
+// forward, output tile nt of a layer with weights W [N][K], bias b: Y[s][n] = act(X[s][:K] . W[n] + b[n]); columns N.. of the last tile get 0
+template <int K, int N, bool RELU>
+__device__ __forceinline__ void fwd_tile(const float *X, int ldx, const float *__restrict__ W, const float *__restrict__ b, int nt, float *Y, int ldy) {
+    const int l = lane_id() & 15, g = lane_id() >> 4, n = 16 * nt + l;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    acc = mma16<K>([&](int i, int k) { return X[i * ldx + k]; }, [&](int k, int) { return n < N ? W[n * K + k] : 0.f; }, acc);
+    const float bn = n < N ? b[n] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float y = acc[r] + bn;
+        if (RELU) y = fmaxf(y, 0.f);
+        Y[(4 * g + r) * ldy + n] = n < N ? y : 0.f;
+    }
+}
+
+// the whole network on the 16 samples in `obs` (LDS) with the flat parameters P; activations stay in LDS
+__device__ __forceinline__ void forward(const float *__restrict__ P, const float *obs, float *S) {
+    const int wave = wave_id();
+    for (int t = wave; t < 13; t += WAVES) {      // the three encoders, no activation: 1 + 1 + 11 output tiles
+        if (t == 0) fwd_tile<2, 16, false>(obs, LDO, P + O_VW, P + O_VB, 0, S + S_F, LDF);
+        else if (t == 1) fwd_tile<2, 16, false>(obs + 2, LDO, P + O_GW, P + O_GB, 0, S + S_F + 16, LDF);
+        else fwd_tile<22, 176, false>(obs + 4, LDO, P + O_SW, P + O_SB, t - 2, S + S_F + 32, LDF);
+    }
+    __syncthreads();
+    if (wave < 4) fwd_tile<F, H, true>(S + S_F, LDF, P + O_HW, P + O_HB, wave, S + S_H1, LDH);      // hidden_layer + ReLU
+    __syncthreads();
+    if (wave < 4) fwd_tile<H, H, true>(S + S_H1, LDH, P + O_H2W, P + O_H2B, wave, S + S_H2, LDH);   // hidden_layer_2 + ReLU
+    __syncthreads();
+    if (wave == 0) fwd_tile<H, A, false>(S + S_H2, LDH, P + O_OW, P + O_OB, 0, S + S_O, LDA);       // output_layer
+    __syncthreads();
+    if (wave < 4) fwd_tile<A, H, true>(S + S_O, LDA, P + O_Q0W, P + O_Q0B, wave, S + S_Q1, LDH);    // q_net.0 + ReLU
+    __syncthreads();
+    if (wave < 4) fwd_tile<H, H, true>(S + S_Q1, LDH, P + O_Q2W, P + O_Q2B, wave, S + S_Q2, LDH);   // q_net.2 + ReLU
+    __syncthreads();
+    if (wave == 0) fwd_tile<H, A, false>(S + S_Q2, LDH, P + O_Q4W, P + O_Q4B, 0, S + S_Q, LDA);     // q_net.4: Q(s, .)
+    __syncthreads();
+}
+
+// backward through one layer Y = X W^T + b with dY [16][N] (row stride LDD) in LDS:
+//   gb[o] = sum_s dY[s][o]; gW[o][k] = sum_s dY[s][o] X[s][k] (tiles [16 o x 16 k] over the 16 samples);
+//   if DX: dX[s][k] = sum_o dY[s][o] W[o][k], times [X[s][k] > 0] when X is a ReLU output (MASK)
+template <int K, int N, bool DX, bool MASK>
+__device__ __forceinline__ void bwd_layer(const float *dY, const float *X, int ldx, const float *__restrict__ W, float *gW, float *gb, float *dX) {
+    constexpr int MT = (N + 15) / 16, KT = (K + 15) / 16, NT = MT * KT + (DX ? KT : 0);
+    const int l = lane_id() & 15, g = lane_id() >> 4;
+    if ((int)threadIdx.x < N) {
+        float s = 0.f;
+        for (int i = 0; i < TILE; ++i) s += dY[i * LDD + threadIdx.x];
+        gb[threadIdx.x] = s;
+    }
+    for (int t = wave_id(); t < NT; t += WAVES) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        if (t < MT * KT) {
+            const int mo = t / KT, k = 16 * (t % KT) + l;
+            acc = mma16<TILE>([&](int i, int s) { return dY[s * LDD + 16 * mo + i]; }, [&](int s, int) { return k < K ? X[s * ldx + k] : 0.f; }, acc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int o = 16 * mo + 4 * g + r;
+                if (o < N && k < K) gW[o * K + k] = acc[r];
+            }
+        } else {
+            const int k = 16 * (t - MT * KT) + l;
+            acc = mma16<N>([&](int i, int o) { return dY[i * LDD + o]; }, [&](int o, int) { return k < K ? W[o * K + k] : 0.f; }, acc);
+            if (k < K)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int s = 4 * g + r;
+                    dX[s * LDD + k] = (!MASK || X[s * ldx + k] > 0.f) ? acc[r] : 0.f;
+                }
+        }
+    }
+}
+
+__device__ __forceinline__ float sumsq4(float a, float b, float c, float d) { return fmaf(d, d, fmaf(c, c, fmaf(b, b, a * a))); }
+
+struct DqnTrainArgs {
+    const float *states, *next_states;
+    const int64_t *actions;
+    const float *rewards, *dones;
+    int64_t ring_size;
+    uint64_t *rng_state;         // {seed, call counter} or NULL
+    const int64_t *idx;          // given rows (rng_state == NULL)
+    int64_t *idx_out;            // or NULL
+    float *params;
+    const float *target;
+    float *ws, *grad, *loss, *m, *v;
+    int32_t *step;
+    int batch;
+    float gamma;
+    double lr, b1, b2, eps, max_norm;
+};
+
+__global__ __launch_bounds__(THREADS) void dqn_train_step_kernel(const DqnTrainArgs a) {
+    __shared__ __attribute__((aligned(16))) float S[S_TOTAL];
+    __shared__ int s_act[TILE];
+    __shared__ float s_red[WAVES];
+    __shared__ float s_misc[4];      // loss terms' sum, clip coefficient, Adam step size, sqrt of the second bias correction
+    __shared__ int s_last;
+    const int tid = threadIdx.x, n_part = gridDim.x;
+    const int slot0 = blockIdx.x * TILE;
+    float *part = a.ws + (int64_t)blockIdx.x * P_PAD;
+
+    // ---- this workgroup's 16 transitions (slots past the batch: zero observations, no gradient)
+    const uint64_t base = a.rng_state ? sample_base(a.rng_state) : 0;
+    if (tid < TILE * LDO) {
+        const int s = tid / LDO, c = tid % LDO, b = slot0 + s;
+        const bool live = b < a.batch;
+        int64_t row = 0;
+        if (live) row = a.rng_state ? (int64_t)perm_row(base, (uint32_t)a.ring_size, (uint32_t)b) : a.idx[b];
+        const bool in = live && c < OBS;
+        S[S_OBS + s * LDO + c] = in ? a.states[row * OBS + c] : 0.f;
+        S[S_NOBS + s * LDO + c] = in ? a.next_states[row * OBS + c] : 0.f;
+        if (c == 0) {
+            int64_t act = live ? a.actions[row] : 0;
+            s_act[s] = (act >= 0 && act < A) ? (int)act : 0;
+            if (live && a.idx_out) a.idx_out[b] = row;
+            S[S_Y + s] = 0.f;
+            if (live) {      // park r and done in the gradient buffer until the target forward has run
+                S[S_D0 + s] = a.rewards[row];
+                S[S_D0 + TILE + s] = a.dones[row];
+            }
+        }
+    }
+    __syncthreads();
+    float rew = 0.f, done = 0.f;
+    if (tid < TILE && slot0 + tid < a.batch) { rew = S[S_D0 + tid]; done = S[S_D0 + TILE + tid]; }
+
+    // ---- TD target: r + (1 - done) gamma max_a Q_target(s', a)
+    forward(a.target, S + S_NOBS, S);
+    if (tid < TILE && slot0 + tid < a.batch) {
+        float mx = S[S_Q + tid * LDA];
+        for (int j = 1; j < A; ++j) mx = fmaxf(mx, S[S_Q + tid * LDA + j]);
+        const float t = (1.f - done) * a.gamma;
+        S[S_Y + tid] = rew + t * mx;
+    }
+    // ---- local forward (the barrier at its head orders the TD targets), loss, dL/dQ
+    forward(a.params, S + S_OBS, S);
+    if (tid < TILE) {
+        const bool live = slot0 + tid < a.batch;
+        const float d = S[S_Q + tid * LDA + s_act[tid]] - S[S_Y + tid];
+        const float ad = fabsf(d);
+        const float term = ad < 1.f ? 0.5f * d * d : ad - 0.5f;       // smooth_l1, beta = 1
+        const float gq = (ad < 1.f ? d : copysignf(1.f, d)) * (1.f / (float)a.batch);
+        for (int j = 0; j < LDA; ++j) S[S_D0 + tid * LDD + j] = (live && j == s_act[tid]) ? gq : 0.f;
+        S[S_Y + tid] = live ? term : 0.f;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float t = 0.f;
+        for (int s = 0; s < TILE; ++s) t += S[S_Y + s];
+        a.ws[ws_loss(n_part) + blockIdx.x] = t;
+    }
+
+    // ---- backward, output layer first; D0 / D1 alternate as dY and dX
+    bwd_layer<H, A, true, true>(S + S_D0, S + S_Q2, LDH, a.params + O_Q4W, part + O_Q4W, part + O_Q4B, S + S_D1);      // q_net.4
+    __syncthreads();
+    bwd_layer<H, H, true, true>(S + S_D1, S + S_Q1, LDH, a.params + O_Q2W, part + O_Q2W, part + O_Q2B, S + S_D0);      // q_net.2
+    __syncthreads();
+    bwd_layer<A, H, true, false>(S + S_D0, S + S_O, LDA, a.params + O_Q0W, part + O_Q0W, part + O_Q0B, S + S_D1);      // q_net.0
+    __syncthreads();
+    bwd_layer<H, A, true, true>(S + S_D1, S + S_H2, LDH, a.params + O_OW, part + O_OW, part + O_OB, S + S_D0);         // output_layer
+    __syncthreads();
+    bwd_layer<H, H, true, true>(S + S_D0, S + S_H1, LDH, a.params + O_H2W, part + O_H2W, part + O_H2B, S + S_D1);      // hidden_layer_2
+    __syncthreads();
+    bwd_layer<F, H, true, false>(S + S_D1, S + S_F, LDF, a.params + O_HW, part + O_HW, part + O_HB, S + S_D0);         // hidden_layer
+    __syncthreads();
+    bwd_layer<2, 16, false, false>(S + S_D0, S + S_OBS, LDO, nullptr, part + O_VW, part + O_VB, nullptr);               // encoders
+    bwd_layer<2, 16, false, false>(S + S_D0 + 16, S + S_OBS + 2, LDO, nullptr, part + O_GW, part + O_GB, nullptr);
+    bwd_layer<22, 176, false, false>(S + S_D0 + 32, S + S_OBS + 4, LDO, nullptr, part + O_SW, part + O_SB, nullptr);
+
+    // ---- publish the row (agent-scope release before the ticket), the last arriver acquires and finishes the step
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        unsigned *ticket = reinterpret_cast<unsigned *>(a.ws + ws_ticket(n_part));
+        const unsigned old = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = old == (unsigned)n_part - 1u;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        s_last = last;
+    }
+    __syncthreads();
+    if (!s_last) return;
+
+    // ---- last workgroup: gradient = sum of the rows in index order, its squared norm in a fixed order
+    float sq = 0.f;
+    for (int q = tid; q < P_PAD / 4; q += THREADS) {
+        float4 g = reinterpret_cast<const float4 *>(a.ws)[q];
+        for (int w = 1; w < n_part; ++w) {
+            const float4 x = reinterpret_cast<const float4 *>(a.ws + (int64_t)w * P_PAD)[q];
+            g.x += x.x; g.y += x.y; g.z += x.z; g.w += x.w;
+        }
+        const float e[4] = {g.x, g.y, g.z, g.w};
+        float e2[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int p = 4 * q + c;
+            e2[c] = p < P_TOTAL ? e[c] : 0.f;
+            if (p < P_TOTAL) a.grad[p] = e[c];
+        }
+        sq += sumsq4(e2[0], e2[1], e2[2], e2[3]);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off, 64);
+    if (lane_id() == 0) s_red[wave_id()] = sq;
+    __syncthreads();
+    if (tid == 0) {
+        float tot = 0.f;
+        for (int w = 0; w < WAVES; ++w) tot += s_red[w];
+        const float norm = sqrtf(tot);
+        s_misc[1] = fminf((float)a.max_norm / (norm + 1e-6f), 1.f);      // clip_grad_norm_: coef = max_norm / (norm + 1e-6), clamped to 1
+        float l = 0.f;
+        for (int w = 0; w < n_part; ++w) l += a.ws[ws_loss(n_part) + w];
+        a.loss[0] = l / (float)a.batch;
+        const int t_step = *a.step + 1;
+        // python-float (double) scalars of torch's Adam, rounded to float32 where the tensor kernels consume them (as iqn_adam)
+        s_misc[2] = (float)(a.lr / (1.0 - pow(a.b1, (double)t_step)));
+        s_misc[3] = (float)sqrt(1.0 - pow(a.b2, (double)t_step));
+        *a.step = t_step;
+        if (a.rng_state) a.rng_state[1] = a.rng_state[1] + 1;
+    }
+    __syncthreads();
+    const float coef = s_misc[1], step_size = s_misc[2], bc2_sqrt = s_misc[3];
+    const float w1 = (float)(1.0 - a.b1), b2f = (float)a.b2, w2 = (float)(1.0 - a.b2), eps = (float)a.eps;
+    // ---- clip + Adam, same element mapping as the sum above (each thread re-reads its own gradient stores)
+    for (int q = tid; q < P_PAD / 4; q += THREADS)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int p = 4 * q + c;
+            if (p >= P_TOTAL) continue;
+            const float gq = a.grad[p] * coef;
+            a.grad[p] = gq;
+            float mm = a.m[p], vv = a.v[p], pp = a.params[p];
+            adam_update(gq, mm, vv, pp, w1, b2f, w2, step_size, bc2_sqrt, eps);
+            a.m[p] = mm;
+            a.v[p] = vv;
+            a.params[p] = pp;
+        }
+}
+
+}  // namespace
+
+extern "C" int64_t mn_dqn_train_workspace_floats(int32_t batch) {
+    if (batch <= 0 || batch > MAX_BATCH_DQN) return -1;
+    return ws_total((batch + TILE - 1) / TILE);
+}
+
+extern "C" int mn_dqn_train_step(const float *ring_states, const float *ring_next_states, const int64_t *ring_actions, const float *ring_rewards,
+                                 const float *ring_dones, int64_t ring_size, uint64_t *rng_state_dev, const int64_t *idx_dev, int64_t *idx_out,
+                                 float *params_local, const float *params_target, float *workspace, float *grad_out, float *loss_out, float *exp_avg,
+                                 float *exp_avg_sq, int32_t *step_dev, int32_t batch, float gamma, double lr, double beta1, double beta2, double eps,
+                                 double max_norm, void *stream) {
+    if (!ring_states || !ring_next_states || !ring_actions || !ring_rewards || !ring_dones || !params_local || !params_target || !workspace ||
+        !grad_out || !loss_out || !exp_avg || !exp_avg_sq || !step_dev)
+        return MN_ERR_INVALID;
+    if (batch <= 0 || batch > MAX_BATCH_DQN) return MN_ERR_INVALID;
+    if (rng_state_dev) {
+        if (ring_size < batch || ring_size > 0x7fffffff) return MN_ERR_INVALID;
+    } else if (!idx_dev) {
+        return MN_ERR_INVALID;
+    }
+    if (reinterpret_cast<uintptr_t>(workspace) % 16) return MN_ERR_INVALID;
+    DqnTrainArgs a;
+    a.states = ring_states; a.next_states = ring_next_states; a.actions = ring_actions; a.rewards = ring_rewards; a.dones = ring_dones;
+    a.ring_size = ring_size; a.rng_state = rng_state_dev; a.idx = idx_dev; a.idx_out = idx_out;
+    a.params = params_local; a.target = params_target; a.ws = workspace; a.grad = grad_out; a.loss = loss_out; a.m = exp_avg; a.v = exp_avg_sq;
+    a.step = step_dev; a.batch = batch; a.gamma = gamma; a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.max_norm = max_norm;
+    hipLaunchKernelGGL(dqn_train_step_kernel, dim3((batch + TILE - 1) / TILE), dim3(THREADS), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
+}

@@ -6,7 +6,11 @@ Same network (`ObsEncoderPolicy`, dqn/policies.py:212-240 = `dqn.policy.DQNPolic
 same schedules (`_on_step`, dqn.py:169-186: hard target copy every `target_update_interval` env steps, linear
 exploration over the first `exploration_fraction` of training), driven by `VecMarineNavEnv` and the device replay ring
 instead of DummyVecEnv (common/vec_env/dummy_vec_env.py:38-55: auto-reset, terminal observation kept for the
-transition).  PyTorch-ROCm only -- this baseline is not on the north-star path and has no HIP kernels of its own.
+transition).
+
+Acting runs on the DQN act kernel (csrc/dqn_act.hip via DQNPolicy).  The gradient step is eager PyTorch by default; with
+`fused_train=True` (GPU, batch <= 256) every step drawn from the replay ring -- `train()` without an explicit batch, hence `learn_vec`
+-- is ONE launch of the fused HIP step (csrc/dqn_train.hip, dqn/fused_train.py) on the same parameters and the same Adam state.
 """
 import copy
 import os
@@ -23,7 +27,7 @@ class DQNAgent:
     def __init__(self, state_size=26, action_size=9, learning_rate=1e-4, buffer_size=1_000_000, learning_starts=50000,
                  batch_size=32, tau=1.0, gamma=0.99, train_freq=4, gradient_steps=1, target_update_interval=10000,
                  exploration_fraction=0.1, exploration_initial_eps=1.0, exploration_final_eps=0.05, max_grad_norm=10,
-                 device="cuda:0", seed=0):
+                 device="cuda:0", seed=0, fused_train=False):
         self.device = torch.device(device)
         torch.manual_seed(seed)                                    # sb3 set_random_seed (base_class.py) before the policy is built
         self.policy = DQNPolicy(state_size, action_size, device=device)
@@ -42,11 +46,52 @@ class DQNAgent:
         self.gen.manual_seed(int(seed) + 4321)
         self.num_timesteps = 0
         self.n_updates = 0
+        self.learning_rate = learning_rate
+        self.fused_train = fused_train      # True: steps drawn from the ring run csrc/dqn_train.hip (GPU, batch <= 256)
+        self._fused, self._train_path = None, "torch"
+
+    # ---- the fused HIP gradient step -------------------------------------------------------------------------------
+    def _fused_trainer(self):
+        from .fused_train import FusedTrainer
+        if self._fused is None or not self._fused.owns(self):
+            self._fused = FusedTrainer(self)
+        return self._fused
+
+    def _uses_fused(self):
+        from .fused_train import MAX_BATCH
+        return self.fused_train and self.device.type == "cuda" and self.batch_size <= MAX_BATCH
+
+    def _enter_train_path(self, path):
+        """Both gradient-step paths update ONE Adam state (the moments are shared memory, dqn/fused_train.py); the step count is
+        handed over whenever the path changes."""
+        if self._train_path == path:
+            return
+        if self._fused is not None and self._fused.owns(self):
+            if path == "torch" and self._train_path == "hip":
+                self._fused.sync_to_optimizer(self.optimizer)
+            elif path == "hip" and self._train_path == "torch":
+                self._fused.sync_from_optimizer(self.optimizer)
+                self._fused.point_grads()
+        self._train_path = path
+
+    def train_fused(self, idx=None):
+        """One fused HIP gradient step on the replay ring: on rows `idx` [B] (i64), or (None) on a batch of `batch_size` rows drawn inside
+        the launch.  Returns the loss (device scalar)."""
+        m = self.memory
+        ft = self._fused_trainer()
+        self._enter_train_path("hip")
+        loss = ft.step((m.states, m.actions, m.rewards, m.next_states, m.dones), m.size, self.batch_size, idx)
+        self.n_updates += 1
+        return loss.clone()
 
     # ---- update rule -----------------------------------------------------------------------------------------------
     def train(self, experiences=None):
         """One gradient step of DQN.train (dqn.py:196-224) on `experiences` = (obs, actions [B,1] i64, rewards [B,1],
-        next_obs, dones [B,1] f32) or on a fresh sample of the replay ring.  Returns the loss (device scalar)."""
+        next_obs, dones [B,1] f32) or on a fresh sample of the replay ring.  Returns the loss (device scalar).
+        With `fused_train` a fresh sample is drawn and trained on inside one HIP launch (`train_fused`); an explicit batch stays eager."""
+        if experiences is None and self._uses_fused():
+            return self.train_fused()
+        self._enter_train_path("torch")
         obs, actions, rewards, next_obs, dones = experiences if experiences is not None else self.memory.sample()
         with torch.no_grad():
             next_q = self.q_net_target(next_obs).max(dim=1)[0].reshape(-1, 1)
@@ -96,9 +141,7 @@ class DQNAgent:
             obs = train_env.reset_done()
             self.num_timesteps += n
             if (it + 1) % tgt_every == 0:                                       # dqn.py:175-176, tau = 1 -> hard copy
-                with torch.no_grad():
-                    for tp, lp in zip(self.q_net_target.parameters(), self.q_net.parameters()):
-                        tp.mul_(1 - self.tau).add_(lp, alpha=self.tau)
+                self.sync_target()
             if self.num_timesteps > self.learning_starts and (it + 1) % self.train_freq == 0 and len(self.memory) >= self.batch_size:
                 for _ in range(self.gradient_steps):
                     losses.append(self.train())
@@ -106,6 +149,15 @@ class DQNAgent:
                 callback(self, it)
         return dict(vector_steps=total_vector_steps, n_updates=self.n_updates,
                     mean_loss=float(torch.stack(losses).mean()) if losses else float("nan"))
+
+    @torch.no_grad()
+    def sync_target(self):
+        """Polyak update of the target network (tau = 1: the hard copy, one copy of the flat buffer on the fused path)."""
+        if self.tau == 1.0 and self._fused is not None and self._fused.owns(self):
+            self._fused.sync_target()
+            return
+        for tp, lp in zip(self.q_net_target.parameters(), self.q_net.parameters()):
+            tp.mul_(1 - self.tau).add_(lp, alpha=self.tau)
 
     # ---- checkpoints: the `policy.pth` of an sb3 zip (q_net.* and q_net_target.* keys) -----------------------------
     def state_dict(self):

@@ -4,7 +4,7 @@ The reference's DQN agent is its modified stable-baselines3 `ObsEncoderPolicy`: 
 whole 26 -> (16 | 16 | 176) -> 64 -> 64 -> 9 observation network WITHOUT activations on the three encoders
 (thirdparty/stable_baselines3/common/torch_layers.py:96-135), followed by sb3's default 9 -> 64 -> 64 -> 9 Q head
 (dqn/policies.py:48-58, torch_layers.py:137-174).  Only the greedy policy is needed on the batched path (the
-experiment sweep and evaluation); DQN training stays with sb3.
+experiment sweep and evaluation); training is `dqn.agent.DQNAgent` (eager, or the fused HIP step of csrc/dqn_train.hip).
 
 Module / parameter names mirror sb3's (`q_net.features_extractor.*`, `q_net.q_net.{0,2,4}.*`) so that the
 `policy.pth` inside an sb3 checkpoint zip loads unchanged.
@@ -105,6 +105,13 @@ class DQNPolicy(nn.Module):
         if rc:
             raise _capi.MarineNavHipError(f"mn_dqn_act failed ({rc})")
         return q, a
+
+    def weights_changed(self):
+        """The weights were written outside PyTorch's version counters (the fused gradient step, dqn/fused_train.py): repack the
+        act kernel's weight image before its next launch."""
+        st = getattr(self, "_fused_state", None)
+        if st is not None:
+            st["sig"] = None
 
     def _fusable(self, obs):
         return (self.use_fused_act and obs.is_cuda and not torch.is_grad_enabled() and len(self.q_net.q_net) == 5

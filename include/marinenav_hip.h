@@ -477,6 +477,27 @@ int mn_iqn_train_set_cu_limit(int32_t n_cu);
 int64_t mn_dqn_image_floats(void);
 int mn_dqn_act(const float *obs_dev, const float *const *weights, float *image_dev, int32_t repack, float *qvals_dev, int32_t *actions_dev,
                int32_t n, void *stream);
+/* ---- Fused gradient step of the DQN baseline (csrc/dqn_train.hip): ONE launch = one optimizer step of DQNAgent.train (sb3 DQN.train, dqn/dqn.py:188-230):
+ * target forward on next_states, max over the 9 actions, y = r + (1 - done) gamma max; local forward on states, gather Q[a], smooth_l1_loss (beta 1,
+ * mean); backward through the 9 layers; clip_grad_norm_(max_norm); torch.optim.Adam (step counter t = *step_dev + 1, advanced by the launch).
+ *   ring_*            the replay ring in mn_replay_append's layout: states / next_states [cap][26] f32, actions [cap] i64, rewards / dones [cap] f32
+ *   rng_state_dev     u64[2] = {seed, call counter}: the batch is mn_iqn_sample's draw (batch DISTINCT rows of [0, ring_size), same keyed
+ *                     permutation), the counter is advanced by exactly one; NULL: the rows are idx_dev [batch] i64
+ *   idx_out           [batch] i64, receives the rows (NULL: not written)
+ *   params_local      flat [27 650] f32 in DQNPolicy.q_net.named_parameters() order (features_extractor.{velocity,goal,sensor}_encoder,
+ *                     hidden_layer, hidden_layer_2, output_layer, q_net.{0,2,4}; weight then bias, nn.Linear [out][in]), updated in place;
+ *                     params_target the same layout (read only)
+ *   workspace         mn_dqn_train_workspace_floats(batch) floats, 16-byte aligned, ZERO-initialised once by the caller (it holds the
+ *                     workgroups' ticket, which every launch leaves at 0); one workspace per concurrently running step
+ *   grad_out [27 650] the clipped gradient; loss_out [1] the loss; exp_avg / exp_avg_sq [27 650] Adam's moments
+ * batch 1..256, exact float32, deterministic (no float atomics, fixed summation order, independent of workgroup placement).
+ * mn_dqn_train_workspace_floats: < 0 for a batch outside 1..256. */
+int64_t mn_dqn_train_workspace_floats(int32_t batch);
+int mn_dqn_train_step(const float *ring_states, const float *ring_next_states, const int64_t *ring_actions, const float *ring_rewards,
+                      const float *ring_dones, int64_t ring_size, uint64_t *rng_state_dev, const int64_t *idx_dev, int64_t *idx_out,
+                      float *params_local, const float *params_target, float *workspace, float *grad_out, float *loss_out, float *exp_avg,
+                      float *exp_avg_sq, int32_t *step_dev, int32_t batch, float gamma, double lr, double beta1, double beta2, double eps,
+                      double max_norm, void *stream);
 
 typedef struct mn_xchg mn_xchg;
 int mn_xchg_create(int32_t rank, int32_t world, mn_xchg **out);
