@@ -40,14 +40,8 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "iqn_act_common.h"
 
-constexpr int K_TAUS = 32;      // model.py:118
-constexpr int N_COS = 64;       // model.py:130
-constexpr int F = 208;          // 16 + 16 + 176 feature width
-constexpr int H = 64;           // hidden width
-constexpr int A_OUT = 9;        // actions
-constexpr int T1 = F / 16;      // 13 feature tiles
 // LDS layout (floats)
 constexpr int OFF_W1 = 0;                         // [13 t][4 m4][64 lanes][4]
 constexpr int OFF_W2 = OFF_W1 + T1 * 4 * 64 * 4;  // [4 mt][13 t][64][4]
@@ -57,8 +51,6 @@ constexpr int OFF_B1 = OFF_W4 + 4 * 64 * 4;       // [208]
 constexpr int OFF_B2 = OFF_B1 + F;                // [64]
 constexpr int OFF_B3 = OFF_B2 + H;                // [64]
 constexpr int OFF_B4 = OFF_B3 + H;                // [16]
-constexpr int OBS = MN_OBS_DIM;                   // 26
-constexpr int OBS4 = 7;                           // 26 inputs padded to 7 float4
 constexpr int OFF_WE = OFF_B4 + 16;               // [7 i4][208 f][4]: block-diagonal encoder weights
 constexpr int OFF_BE = OFF_WE + OBS4 * F * 4;     // [208] encoder biases
 constexpr int OFF_FB = OFF_BE + F;                // [8 waves][208] per-wave feature buffer
@@ -71,20 +63,6 @@ __device__ __forceinline__ f32x4 relu4(f32x4 v) {
     r.x = v.x > 0.f ? v.x : 0.f; r.y = v.y > 0.f ? v.y : 0.f; r.z = v.z > 0.f ? v.z : 0.f; r.w = v.w > 0.f ? v.w : 0.f;
     return r;
 }
-
-// sum over the 16 lanes of a row (lanes sharing l >> 4)
-__device__ __forceinline__ float row_sum16(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));   // quad xor 1
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));   // quad xor 2
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));  // row_half_mirror
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));  // row_mirror
-    return v;
-}
-
-struct IqnWeights {   // device pointers, nn.Linear layout [out][in]
-    const float *ve_w, *ve_b, *ge_w, *ge_b, *se_w, *se_b;   // velocity / goal / sensor encoders
-    const float *W1, *b1, *W2, *b2, *W3, *b3, *W4, *b4;     // cos_embedding, hidden_layer, hidden_layer_2, output_layer
-};
 
 // block-diagonal encoder weight: feature f (0..207) x observation input i (0..25)  (model.py:126-128,170-173)
 __device__ __forceinline__ float enc_weight(const IqnWeights &w, int f, int i) {
@@ -131,45 +109,7 @@ __global__ __launch_bounds__(256) void iqn_pack_kernel(IqnWeights w, float *__re
     if (i < OFF_FB) packed[i] = pack_element(w, i);
 }
 
-// Counter-based uniform draws: draw number `idx` of call `ctr` is a double murmur3-fmix32 of the index under two 32-bit
-// keys derived from (seed, ctr) -- no generator state per element, any element can be produced by any thread.
-__device__ __forceinline__ uint32_t fmix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13; x *= 0xc2b2ae35u; x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ float u01(uint32_t idx, uint32_t k0, uint32_t k1) {      // 24-bit uniform in [0, 1), like torch.rand
-    return (float)(fmix32(fmix32(idx ^ k0) + k1) >> 8) * (1.0f / 16777216.0f);
-}
-
 constexpr int PACK_BLOCKS = (OFF_FB + 255) / 256;
-
-// The random numbers of one act call: blocks [pack_blocks, gridDim.x) fill draws[0 .. 32 n) with tau = U[0,1) * cvar
-// (model.py:149-153; per-row cvar if cvar_row) and draws[32 n .. 33 n) with the exploration uniforms of IQNAgent.act
-// (agent.py:199).
-__device__ __forceinline__ void draw_block(const uint64_t *__restrict__ rng_state, float *__restrict__ draws, int n,
-                                           const float *__restrict__ cvar_row, float cvar, int pack_blocks) {
-    const uint64_t base = mix64(rng_state[0] + 0x9E3779B97F4A7C15ull * (rng_state[1] + 1));
-    const uint32_t k0 = (uint32_t)base, k1 = (uint32_t)(base >> 32);
-    const long total4 = ((long)n * (K_TAUS + 1) + 3) / 4;          // float4 groups
-    const long stride = (long)((int)gridDim.x - pack_blocks) * 256;
-    for (long q = (long)((int)blockIdx.x - pack_blocks) * 256 + threadIdx.x; q < total4; q += stride) {
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const long idx = 4 * q + j;
-            float u = u01((uint32_t)idx, k0, k1);
-            if (idx < (long)n * K_TAUS) u *= cvar_row ? cvar_row[idx / K_TAUS] : cvar;
-            v[j] = u;
-        }
-        if (4 * q + 3 < (long)n * (K_TAUS + 1)) *reinterpret_cast<float4 *>(draws + 4 * q) = make_float4(v[0], v[1], v[2], v[3]);
-        else
-            for (int j = 0; j < 4 && 4 * q + j < (long)n * (K_TAUS + 1); ++j) draws[4 * q + j] = v[j];
-    }
-}
 
 // The same weight image PLUS the random numbers of the call in one launch: blocks [0, PACK_BLOCKS) pack, the others
 // fill draws[0 .. 32 n) with tau = U[0,1) * cvar (model.py:149-153; per-row cvar if cvar_row) and draws[32 n .. 33 n)
@@ -518,6 +458,7 @@ struct mn_iqn_ctx {
     uint64_t late_bound_ticks = sp::LATE_BOUND_TICKS;    // mn_iqn_set_late_bound_ms
     std::vector<hipEvent_t> ev;
     int prof_max = 0, prof_n = 0;
+    uint32_t *rollout_words = nullptr;      // mn_rollout_iqn: its launch's ticket and longest episode (zero between launches)
 };
 
 extern "C" int mn_iqn_set_grid(mn_iqn_ctx *c, int32_t max_workgroups) {
@@ -586,6 +527,7 @@ extern "C" int mn_iqn_destroy(mn_iqn_ctx *c) {
     (void)hipFree(c->timg);
     (void)hipFree(c->taux);
     (void)hipFree(c->late_status);
+    (void)hipFree(c->rollout_words);
     if (c->late_status_host) (void)hipHostFree((void *)c->late_status_host);
     if (moved) (void)hipSetDevice(cur);
     delete c;
@@ -826,6 +768,23 @@ extern "C" int mn_iqn_refresh(mn_iqn_ctx *c, const float *const *weights, void *
         c->dirty = false;
     }
     return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
+}
+
+// What mn_rollout_iqn (mn_capi.hip) needs of a context: the split-f16 weight image, rebuilt first if stale (as mn_iqn_refresh), and two device
+// words for its launch.  MN_ERR_INVALID for the forms the rollout does not reproduce: the exact-f32 variant, launch-shared taus.
+int mn_iqn_rollout_image(mn_iqn_ctx *c, const float *const *weights, hipStream_t s, const uint32_t **image, uint32_t **words) {
+    if (!c || !weights || !image || !words || c->variant != 2 || c->tau_mode != 0) return MN_ERR_INVALID;
+    if (!c->rollout_words) {
+        uint32_t *w = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&w), 2 * sizeof(uint32_t)) != hipSuccess) return MN_ERR_ALLOC;
+        if (hipMemset(w, 0, 2 * sizeof(uint32_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipFree(w); return MN_ERR_HIP; }
+        c->rollout_words = w;
+    }
+    const int rc = mn_iqn_refresh(c, weights, (void *)s);
+    if (rc) return rc;
+    *image = c->packed_sp;
+    *words = c->rollout_words;
+    return MN_OK;
 }
 
 extern "C" int mn_iqn_act(mn_iqn_ctx *c, const float *obs_dev, const float *taus_dev, const float *const *weights,

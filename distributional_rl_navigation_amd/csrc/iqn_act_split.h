@@ -827,6 +827,47 @@ __device__ __forceinline__ void tail(const u32x4 *__restrict__ lds4, const f32x4
     });
 }
 
+// The per-environment pieces of the acting form below as functions, for the IQN episode rollout (mn_rollout_iqn.hip), which runs the same
+// arithmetic on one environment per wavefront.  iqn_qvals_split_kernel keeps these lines written out: calling the functions from it moves
+// its register allocation and schedule (same results, different code object).
+// Observation encoders of one environment (ov = its 26 inputs, zero padded), its scales S_l, and S 2^-k1 features -> this wave's LDS buffer
+// (the shared layer-1 constant carries no 2^k1).
+template <bool SHARED>
+__device__ __forceinline__ EnvScale encode_env(float *__restrict__ lds, const f32x4 *__restrict__ ldsv, int enc_w, int enc_f, int fb_f, int lane,
+                                               const float (&ov)[28], float c1, float a2, float d2, float a3, float d3) {
+    EncState st;
+    static_for<N_ENC_SUB>([&](auto I_) { enc_substep<decltype(I_)::value>(lds, ldsv, enc_w, enc_f, lane, ov, st); });
+    const EnvScale sc = env_scale(st.bnd, a2, d2, a3, d3);
+    store_features(lds, fb_f, lane, st, SHARED ? sc.S1 : sc.S1 * c1);
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    return sc;
+}
+
+// Layer 3 epilogue, tau mean, f32 output layer (as in the exact kernel; the sums carry the factor S3): Q(s, action = col) in lane (g, col),
+// valid for col < 9.  c3e brings the layer-3 accumulators (S2 2^k3) to S3.
+__device__ __forceinline__ float q_mean(const float *__restrict__ lds, const f32x4 *__restrict__ ldsv, const LdsBase &lb, const f32x4 (&acc3)[4][NT],
+                                        float c3e, const EnvScale &sc, int col) {
+    float hs[16];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+        const f32x4 sb = ldsv[lb.fl + ((OFF_B3 - OFF_B1) >> 2) + 4 * mt] * sc.S3;
+        const f32x4 h0 = relu4s(fma4(acc3[mt][0], c3e, sb)), h1 = relu4s(fma4(acc3[mt][1], c3e, sb));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) hs[4 * mt + r] = h0[r] + h1[r];
+    }
+    row_sum16_x16(hs);                          // sum over the 32 taus of h3[16 mt + 4 g + r], in every lane of row group g
+    float part = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+        const f32x4 a = ldsv[lb.w_hi + ((OFF_W4 >> 2) - 4096) + mt * 64];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) part = fmaf(a[r], hs[4 * mt + r], part);
+    }
+    part = sum_rows4(part);                     // the four row groups' shares of action `col`
+    return part * (sc.invS3 * (1.0f / K_TAUS)) + lds[OFF_B4 + col];
+}
+
 // QUANT = false: acting / training (tau mean before the linear output layer, f32 VALU mat-vec).
 // QUANT = true : IQNAgent.act_eval (agent.py:217-236): the output layer runs per tau on the matrix pipe (12 more MFMAs on a padded
 //                16-row tile), the [n][32][9] quantile values are written out and Q is their mean.

@@ -90,6 +90,31 @@ class UnderActGuard:
         self._end_preflight()
 
 
+def evaluation_from_traces(reward, done, info, action, discount, energy_tab, dt, N):
+    """The bookkeeping of IQNAgent.evaluation_vec's loop on the traces of one mn_rollout_iqn launch (numpy [T][n], T = the steps the loop ran):
+    the same float64 operations in the same step order -- return += (discount ** t) * reward, energy += energy_tab[action] while alive --, so the
+    lists are equal to the loop's bit for bit.  Returns (action_data, reward_data, success_data, time_data, energy_data)."""
+    T, n = reward.shape
+    alive = np.ones(n, dtype=bool)
+    ret = np.zeros(n, dtype=np.float64)
+    length = np.zeros(n, dtype=np.int64)
+    energy = np.zeros(n, dtype=np.float64)
+    last_info = np.zeros(n, dtype=np.uint8)
+    etab = np.asarray(energy_tab, dtype=np.float32).astype(np.float64)
+    for t in range(T):
+        ret += np.where(alive, (discount ** t) * reward[t].astype(np.float64), 0.0)
+        length += alive
+        energy += np.where(alive, etab[np.clip(action[t], 0, len(etab) - 1)], 0.0)
+        last_info = np.where(alive, info[t], last_info)
+        alive = alive & ~done[t].astype(bool)
+    action_data = [[int(x) for x in action[:length[i], i]] for i in range(n)]
+    reward_data = [float(x) for x in ret]
+    success_data = [bool(x) for x in (last_info == 4)]
+    time_data = [float(dt * N * l) for l in length]
+    energy_data = [float(x) for x in energy]
+    return action_data, reward_data, success_data, time_data, energy_data
+
+
 class IQNAgent(ReferenceLoopMixin):
     def __init__(self, state_size, action_size, layer_size=64, n_step=1, BATCH_SIZE=32, BUFFER_SIZE=1_000_000,
                  LR=1e-4, TAU=1.0, GAMMA=0.99, UPDATE_EVERY=4, learning_starts=10000, target_update_interval=10000,
@@ -457,13 +482,14 @@ class IQNAgent(ReferenceLoopMixin):
     # ---- batched loop on the HIP vector env ----------------------------------------------------------
     def learn_vec(self, total_vector_steps, train_env, eval_env=None, eval_config=None, eval_freq=None,
                   eval_log_path=None, total_timesteps=None, world_size=1, cvar=1.0, verbose=True,
-                  train_every=None, on_step=None, report_timestep_scale=1.0, eval_adaptive=True, reset_under_act=True):
+                  train_every=None, on_step=None, report_timestep_scale=1.0, eval_adaptive=True, reset_under_act=True, eval_one_launch=False):
         """Vectorised agent.py:94-173.  One iteration = one vector step of `train_env` (n_envs env
         steps): act_batch -> mn_step -> replay.add_batch -> mn_reset_done -> (every UPDATE_EVERY vector
         steps) sample + train.  `current_timestep` counts env steps over all ranks, so eps, the
         learning_starts gate and the curriculum keep the reference's meaning of "timesteps";
         `learning_timestep` counts vector steps after learning_starts (UPDATE_EVERY,
-        target_update_interval and eval_freq are applied to it)."""
+        target_update_interval and eval_freq are applied to it).  `eval_one_launch`: the evaluations as one mn_rollout_iqn launch each
+        (evaluation_vec(one_launch=True): the same results)."""
         n = train_env.n_envs
         per_iter = n * world_size
         # evaluation npz `timesteps` are reported as current_timestep * report_timestep_scale (train_iqn: reference-
@@ -500,9 +526,9 @@ class IQNAgent(ReferenceLoopMixin):
                     ep_ret.masked_fill_(d, 0.0); ep_len.masked_fill_(d, 0.0)
                 if evaluate_now:
                     self.check_learner()      # (a device synchronisation; the evaluation below is one anyway)
-                    res = self.evaluation_vec(eval_env, eval_config, greedy=True, eval_log_path=eval_log_path)
+                    res = self.evaluation_vec(eval_env, eval_config, greedy=True, eval_log_path=eval_log_path, one_launch=eval_one_launch)
                     if eval_adaptive:
-                        self.evaluation_vec(eval_env, eval_config, greedy=False, eval_log_path=eval_log_path)
+                        self.evaluation_vec(eval_env, eval_config, greedy=False, eval_log_path=eval_log_path, one_launch=eval_one_launch)
                     # agent.py:140-148 keeps the LATEST network at every evaluation point; the batched run also keeps the BEST greedy evaluation so far beside it
                     # (`best_*`: ~1 run in 12 ends on a checkpoint far below its own best -- profiles/r05_learning_curve.txt)
                     score = (int(sum(res["successes"])), float(np.mean(res["rewards"])))
@@ -578,10 +604,24 @@ class IQNAgent(ReferenceLoopMixin):
         self.current_timestep += per_iter
         return obs, reward, done, info, loss
 
+    def _rollout_evaluation(self, eval_env, greedy, max_steps):
+        """The evaluation episodes of `evaluation_vec` as ONE mn_rollout_iqn launch (iqn/fused_act.rollout_iqn) -- the traces, or None where the
+        loop's acting form has no one-launch twin (CPU, PyTorch acting, torch.rand taus, the exact-f32 variant, launch-shared taus)."""
+        if not (self.device.type == "cuda" and self.use_fused_act and self.use_library_rng and hasattr(eval_env, "h")):
+            return None
+        from .fused_act import ActRng, rollout_iqn
+        if self._act_rng is None:
+            self._act_rng = ActRng(self.gen.initial_seed(), self.device)
+        return rollout_iqn(self.qnetwork_local, eval_env, max_steps, self._act_rng, cvar=1.0, adaptive=not greedy, shared_taus=self.shared_taus,
+                           trace=("reward", "done", "info", "action"))
+
     @torch.no_grad()
-    def evaluation_vec(self, eval_env, eval_config, greedy=True, eval_log_path=None, max_steps=1000):
+    def evaluation_vec(self, eval_env, eval_config, greedy=True, eval_log_path=None, max_steps=1000, one_launch=False):
         """agent.py:319-398 with all evaluation worlds stepped side by side on the GPU.
-        `eval_env` is a VecMarineNavEnv with n_envs == len(eval_config); the npz schema is unchanged."""
+        `eval_env` is a VecMarineNavEnv with n_envs == len(eval_config); the npz schema is unchanged.
+        `one_launch`: every episode in one mn_rollout_iqn launch instead of a Python iteration per step -- the same results, bit for bit (the
+        returned dict, the logged entries, the npz, the act draws' counter); where that launch cannot reproduce the loop's acting form it falls
+        back to the loop."""
         from ..marinenav_env.vec_env import VecMarineNavEnv
         cfgs = list(eval_config.values())
         n = len(cfgs)
@@ -599,6 +639,15 @@ class IQNAgent(ReferenceLoopMixin):
         last_info = torch.zeros(n, dtype=torch.uint8, device=self.device)
         acts = torch.full((max_steps, n), -1, dtype=torch.int32, device=self.device)
         self.qnetwork_local.eval()
+        tr = self._rollout_evaluation(eval_env, greedy, max_steps) if one_launch else None
+        if tr is not None:
+            self.qnetwork_local.train()
+            T = tr["steps_run"]
+            data = evaluation_from_traces(tr["reward"][:T].cpu().numpy(), tr["done"][:T].cpu().numpy(), tr["info"][:T].cpu().numpy(),
+                                          tr["action"][:T].cpu().numpy(), eval_env.discount, energy_tab.cpu().numpy(), r0["dt"], r0["N"])
+            self._log_evaluation(greedy, *data, eval_log_path)
+            action_data, reward_data, success_data, time_data, energy_data = data
+            return dict(rewards=reward_data, successes=success_data, times=time_data, energies=energy_data, actions=action_data)
         for t in range(max_steps):
             cv = 1.0 if greedy else self.adjust_cvar_batch(obs)
             a = self.act_batch(obs, 0.0, cv)

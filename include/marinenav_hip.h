@@ -371,6 +371,22 @@ int mn_iqn_act(mn_iqn_ctx *c, const float *obs_dev, const float *taus_dev, const
 int mn_iqn_act_rng(mn_iqn_ctx *c, const float *obs_dev, const float *const *weights, uint64_t *rng_state_dev,
                    float *draws_dev, const float *cvar_row_dev, float cvar, float eps, int32_t *actions_dev,
                    float *qvals_dev, float *quantiles_dev, int32_t n, int32_t num_taus, void *stream);
+/* IQN EPISODES in ONE launch: mn_rollout_policy with the learned policy (IQNAgent.evaluation_vec, agent.py:319-398).  Every env of `h` runs its
+ * CURRENT episode -- starting from the observation in obs_dev -- for up to n_steps steps; per step it acts exactly as one mn_iqn_act_rng call of
+ * context `ctx` on the n current rows at eps = 0 would for its row (taus of call counter rng_state_dev[1] + t, x the scalar `cvar` or, with
+ * `adaptive`, x IQNAgent.adjust_cvar_batch of the row; the split-f16 network; argmax, first maximum wins), then steps like mn_step.  An env that
+ * finishes is NOT reset: it idles, its traces read reward 0 / done 1 / its terminal info code / action -1 from then on, obs_dev keeps its
+ * terminal observation and its terminal pose and counters are stored.  Bit-identical to a loop of (mn_iqn_act_rng, mn_step) run while any env
+ * is alive, the act call counter included: afterwards rng_state_dev[1] has grown by steps_run = the longest episode of the launch (at most
+ * n_steps), also written to *steps_run_dev (device i32, may be NULL).  The context's weight image is rebuilt first if stale (mn_iqn_refresh).
+ * Traces (device, any may be NULL) as mn_rollout_policy ([n_steps][n] ...), plus cvar_trace_dev [n_steps][n] f32 (the cvar each step's taus were
+ * drawn with) and q_trace_dev [n_steps][n][9] f32 (Q(s, .) of each step); obs / cvar / Q entries of steps after an env finished are not written.
+ * MN_ERR_INVALID for the exact-f32 variant (mn_iqn_set_variant 0), a launch-shared tau mode, n_steps < 1 or a NULL h / ctx / weights /
+ * rng_state_dev / obs_dev.  One launch at a time per context (it keeps two device words for the counter update). */
+int mn_rollout_iqn(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weights, int32_t n_steps, uint64_t *rng_state_dev, float cvar,
+                   int32_t adaptive, float *obs_dev, float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev,
+                   uint8_t *info_trace_dev, int32_t *action_trace_dev, float *cvar_trace_dev, float *q_trace_dev, int32_t *steps_run_dev,
+                   void *stream);
 
 /* ---- replay ring ------------------------------------------------------------------------------
  * ReplayBuffer.add (thirdparty/IQN/replay_buffer.py:26-34) for n transitions in one launch: batch row i
