@@ -18,21 +18,14 @@
 // at a time and carries it through all four layers in registers; nothing but observations, taus and
 // the 9 Q-values / the action touches HBM.
 //
-// MFMA mapping: exact-f32 v_mfma_f32_16x16x4_f32 (the reference is float32; no reduced precision).
-// Every layer is computed TRANSPOSED, H^T = W . X^T: the weights are the A operand (16 output
-// features x 4 k), the activations the B operand (4 k x 16 tau rows) and the C tile is
-// [16 features x 16 taus] with lane l holding column (l & 15) and rows 4*(l >> 4) + r.  Because the
-// k order of a dot product is free, MFMA step (t, r) of the NEXT layer is defined to consume input
-// features {16t + 4g + r : g = 0..3} -- which is exactly register r of C tile t in lane group g.  So a
-// layer's accumulator registers ARE the next layer's B operands: no LDS round trip, no shuffles.
-// The weights are permuted into that order once per call (iqn_pack_kernel) and copied to LDS per workgroup
-// (155 KiB of the 160 KiB incl. the encoders: one 512-thread workgroup per CU, 2 waves per SIMD so one wave's bias /
-// ReLU / cos VALU work runs under the other's MFMAs); each ds_read_b128 feeds 4 k-steps x 2 tau
-// tiles = 8 MFMAs.  Layers 1 and 2 are fused over the 13 feature tiles of the 208-wide activation,
-// so the live state is 32 accumulator + 32 cos registers per lane.
+// The kernels live in three headers, one per family: iqn_act_exact.h (exact-f32 MFMA, variant 0), iqn_act_split.h (the same network on the
+// f16 matrix pipe at float32 accuracy, variant 2: the default) and iqn_act_tiled.h (launch-shared taus with the environments in the MFMA
+// columns).  This file is the host side: the kernel forms, the per-caller context, the one launch routine and the C ABI.  (The MFMA clock probe
+// at the end, mfma_probe.h, is a measurement aid that shares the translation unit, nothing more.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <utility>
+#include <vector>
 
 #include "marinenav_hip.h"
 
@@ -41,399 +34,45 @@
 namespace {
 
 #include "iqn_act_common.h"
-
-// LDS layout (floats)
-constexpr int OFF_W1 = 0;                         // [13 t][4 m4][64 lanes][4]
-constexpr int OFF_W2 = OFF_W1 + T1 * 4 * 64 * 4;  // [4 mt][13 t][64][4]
-constexpr int OFF_W3 = OFF_W2 + 4 * T1 * 64 * 4;  // [4 mt][4 t2][64][4]
-constexpr int OFF_W4 = OFF_W3 + 4 * 4 * 64 * 4;   // [4 t2][64][4]
-constexpr int OFF_B1 = OFF_W4 + 4 * 64 * 4;       // [208]
-constexpr int OFF_B2 = OFF_B1 + F;                // [64]
-constexpr int OFF_B3 = OFF_B2 + H;                // [64]
-constexpr int OFF_B4 = OFF_B3 + H;                // [16]
-constexpr int OFF_WE = OFF_B4 + 16;               // [7 i4][208 f][4]: block-diagonal encoder weights
-constexpr int OFF_BE = OFF_WE + OBS4 * F * 4;     // [208] encoder biases
-constexpr int OFF_FB = OFF_BE + F;                // [8 waves][208] per-wave feature buffer
-constexpr int LDS_FLOATS = OFF_FB + 8 * F;
-
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-__device__ __forceinline__ f32x4 relu4(f32x4 v) {
-    f32x4 r;
-    r.x = v.x > 0.f ? v.x : 0.f; r.y = v.y > 0.f ? v.y : 0.f; r.z = v.z > 0.f ? v.z : 0.f; r.w = v.w > 0.f ? v.w : 0.f;
-    return r;
-}
-
-// block-diagonal encoder weight: feature f (0..207) x observation input i (0..25)  (model.py:126-128,170-173)
-__device__ __forceinline__ float enc_weight(const IqnWeights &w, int f, int i) {
-    if (f < 16) return (i < 2) ? w.ve_w[f * 2 + i] : 0.f;
-    if (f < 32) return (i >= 2 && i < 4) ? w.ge_w[(f - 16) * 2 + (i - 2)] : 0.f;
-    return (i >= 4 && i < OBS) ? w.se_w[(f - 32) * 22 + (i - 4)] : 0.f;
-}
-
-// Value of element i of the LDS weight image (floats [0, OFF_FB)): weights permuted into MFMA A-fragment
-// order (nn.Linear stores [out][in]), biases, block-diagonal encoder.
-__device__ __forceinline__ float pack_element(const IqnWeights &w, int i) {
-    if (i < OFF_B1) {
-        const int j = i & 3, l = (i >> 2) & 63, g = l >> 4, row = l & 15;
-        if (i < OFF_W2) {            // W1p[t][m4][l][j] = W1[16t + row][4*(4*m4 + j) + g]
-            const int q = i >> 8, m4 = q & 3, t = q >> 2;
-            return w.W1[(16 * t + row) * N_COS + 4 * (4 * m4 + j) + g];
-        } else if (i < OFF_W3) {     // W2p[mt][t][l][r] = W2[16mt + row][16t + 4g + r]
-            const int q = (i - OFF_W2) >> 8, t = q % T1, mt = q / T1;
-            return w.W2[(16 * mt + row) * F + 16 * t + 4 * g + j];
-        } else if (i < OFF_W4) {     // W3p[mt][t2][l][r] = W3[16mt + row][16t2 + 4g + r]
-            const int q = (i - OFF_W3) >> 8, t2 = q & 3, mt = q >> 2;
-            return w.W3[(16 * mt + row) * H + 16 * t2 + 4 * g + j];
-        }                            // W4p[t2][l][r] = W4[row][16t2 + 4g + r] (rows >= 9 are zero)
-        const int t2 = (i - OFF_W4) >> 8;
-        return row < A_OUT ? w.W4[row * H + 16 * t2 + 4 * g + j] : 0.f;
-    }
-    if (i < OFF_B2) return w.b1[i - OFF_B1];
-    if (i < OFF_B3) return w.b2[i - OFF_B2];
-    if (i < OFF_B4) return w.b3[i - OFF_B3];
-    if (i < OFF_WE) return (i - OFF_B4) < A_OUT ? w.b4[i - OFF_B4] : 0.f;
-    if (i < OFF_BE) {                // WEp[i4][f][c] = Wenc[f][4*i4 + c] (block-diagonal 208 x 26, zero elsewhere / padding)
-        const int k = i - OFF_WE, c = k & 3, f = (k >> 2) % F, i4 = (k >> 2) / F;
-        const int inp = 4 * i4 + c;
-        return inp < OBS ? enc_weight(w, f, inp) : 0.f;
-    }
-    const int f = i - OFF_BE;
-    return f < 16 ? w.ve_b[f] : (f < 32 ? w.ge_b[f - 16] : w.se_b[f - 32]);
-}
-
-// Builds the 149 KiB LDS image once per call in global memory, so that each of the 256 workgroups of the
-// act kernel fills its LDS with a straight 16-byte coalesced copy instead of a 38 K-element gather.
-__global__ __launch_bounds__(256) void iqn_pack_kernel(IqnWeights w, float *__restrict__ packed) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < OFF_FB) packed[i] = pack_element(w, i);
-}
-
-constexpr int PACK_BLOCKS = (OFF_FB + 255) / 256;
-
-// The same weight image PLUS the random numbers of the call in one launch: blocks [0, PACK_BLOCKS) pack, the others
-// fill draws[0 .. 32 n) with tau = U[0,1) * cvar (model.py:149-153; per-row cvar if cvar_row) and draws[32 n .. 33 n)
-// with the exploration uniforms of IQNAgent.act (agent.py:199).  rng_state = {seed, call counter}; the counter is
-// advanced by the act kernel that follows in the stream.
-__global__ __launch_bounds__(256) void iqn_prep_kernel(IqnWeights w, float *__restrict__ packed, const uint64_t *__restrict__ rng_state,
-                                                       float *__restrict__ draws, int n, const float *__restrict__ cvar_row,
-                                                       float cvar, int pack_blocks) {
-    // pack_blocks = PACK_BLOCKS when the cached weight image is stale (mn_iqn_weights_changed), else 0
-    if ((int)blockIdx.x < pack_blocks) {
-        const int i = blockIdx.x * blockDim.x + threadIdx.x;
-        if (i < OFF_FB) packed[i] = pack_element(w, i);
-        return;
-    }
-    draw_block(rng_state, draws, n, cvar_row, cvar, pack_blocks);
-}
-
-// QUANT = false: the training / acting hot path (tau-mean before the linear output layer, 960 MFMAs per env).
-// QUANT = true : IQNAgent.act_eval (agent.py:217-236): the output layer runs per tau on the matrix pipe (+32 MFMAs on a
-//                padded 16-row tile), the [n][32][9] quantile values are written out and Q is their mean.
-template <bool QUANT>
-__global__ __launch_bounds__(512, 2) void iqn_qvals_kernel(const float *__restrict__ obs, const float *__restrict__ taus,
-                                                           const float *__restrict__ packed, float *__restrict__ qvals,
-                                                           const float *__restrict__ explore_u, float eps,
-                                                           int32_t *__restrict__ actions, int n,
-                                                           uint64_t *__restrict__ rng_state, float *__restrict__ quantiles) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x;
-    if (rng_state && blockIdx.x == 0 && tid == 0) rng_state[1] += 1;   // the draws of this call were made by iqn_prep_kernel
-    {
-        const f32x4 *src = reinterpret_cast<const f32x4 *>(packed);
-        f32x4 *dst = reinterpret_cast<f32x4 *>(lds);
-        for (int i = tid; i < OFF_FB / 4; i += blockDim.x) dst[i] = src[i];
-    }
-    __syncthreads();
-
-    const int lane = tid & 63, g = lane >> 4, col = lane & 15;
-    const int wave = tid >> 6, waves_per_block = blockDim.x >> 6;
-    const f32x4 *ldsv = reinterpret_cast<const f32x4 *>(lds);
-
-    // cos(tau * pi * k) = cos(2 pi * (tau * k / 2)), k = 4m + g: the phase in REVOLUTIONS is tau * (k/2),
-    // one exact-ish multiply; v_fract + v_cos_f32 replace libm's ~35-instruction range reduction.  The
-    // reference rounds tau * float32(pi k) before its cos (model.py:130,155), so the two already
-    // differ by ~1e-5 rad of input rounding at k = 63; that noise dominates either cos error.
-    float hk[16];
-#pragma unroll
-    for (int m = 0; m < 16; ++m) hk[m] = 0.5f * (float)(4 * m + g);
-
-    // one environment (32 tau rows = NT = 2 column tiles) per wave iteration
-    constexpr int NT = 2;
-    for (int e = blockIdx.x * waves_per_block + wave; e < n; e += gridDim.x * waves_per_block) {
-        float tau[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) tau[nt] = taus[(size_t)e * K_TAUS + 16 * nt + col];
-        // layer-1 B operands: cos(tau * pis[k]) for k = 4m + g  (model.py:155)
-        float cb[16][NT];
-#pragma unroll
-        for (int m = 0; m < 16; ++m)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) cb[m][nt] = __builtin_amdgcn_cosf(__builtin_amdgcn_fractf(tau[nt] * hk[m]));
-
-        // ---- observation encoders (model.py:170-173): lane l computes features l, l+64, l+128, l+192 from
-        // the 26 inputs (wave-uniform -> scalar loads) and parks them in this wave's LDS buffer, from
-        // where every lane later reads the float4 {16t + 4g + r} it needs for the Hadamard product
-        {
-            const float *orow = obs + (size_t)__builtin_amdgcn_readfirstlane(e) * OBS;
-            float ov[OBS4 * 4];
-#pragma unroll
-            for (int i = 0; i < OBS4 * 4; ++i) ov[i] = i < OBS ? orow[i] : 0.f;
-            float *fb = lds + OFF_FB + wave * F;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int f = lane + 64 * j;
-                if (f < F) {
-                    float a = lds[OFF_BE + f];
-#pragma unroll
-                    for (int i4 = 0; i4 < OBS4; ++i4) {
-                        const f32x4 wv = ldsv[(OFF_WE >> 2) + i4 * F + f];
-                        a += wv[0] * ov[4 * i4] + wv[1] * ov[4 * i4 + 1] + wv[2] * ov[4 * i4 + 2] + wv[3] * ov[4 * i4 + 3];
-                    }
-                    fb[f] = a;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-        const f32x4 *fbv = reinterpret_cast<const f32x4 *>(lds + OFF_FB + wave * F) + g;   // + 4*t per tile
-
-        f32x4 acc2[4][NT];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc2[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-        // ---- layers 1 + 2 fused over the 13 feature tiles, software-pipelined: the layer-1 MFMAs of
-        // tile t+1 are issued BEFORE the bias / ReLU / Hadamard epilogue of tile t, so the wave's own VALU
-        // work sits in the shadow of its own MFMAs (in-order issue would otherwise drain the matrix pipe
-        // at every tile boundary) -------------------------------------------------------------------
-        f32x4 acc1[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc1[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int m4 = 0; m4 < 4; ++m4) {
-            const f32x4 a = ldsv[(OFF_W1 >> 2) + m4 * 64 + lane];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc1[nt] = mfma(a[j], cb[4 * m4 + j][nt], acc1[nt]);
-        }
-#pragma unroll
-        for (int t = 0; t < T1; ++t) {
-            f32x4 nxt[NT];
-            if (t + 1 < T1) {
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) nxt[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int m4 = 0; m4 < 4; ++m4) {
-                    const f32x4 a = ldsv[(OFF_W1 >> 2) + ((t + 1) * 4 + m4) * 64 + lane];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) nxt[nt] = mfma(a[j], cb[4 * m4 + j][nt], nxt[nt]);
-                }
-            }
-            const f32x4 fv = fbv[4 * t];                             // features[e][16t + 4g + r]
-            const f32x4 bias = ldsv[(OFF_B1 >> 2) + 4 * t + g];      // b1[16t + 4g + r]
-            f32x4 h1[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) h1[nt] = relu4(acc1[nt] + bias) * fv;
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                const f32x4 a = ldsv[(OFF_W2 >> 2) + (mt * T1 + t) * 64 + lane];
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) acc2[mt][nt] = mfma(a[r], h1[nt][r], acc2[mt][nt]);
-            }
-            if (t + 1 < T1) {
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc1[nt] = nxt[nt];
-            }
-        }
-        // ---- layer 2 epilogue, layer 3 ---------------------------------------------------------------
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            const f32x4 bias = ldsv[(OFF_B2 >> 2) + 4 * mt + g];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc2[mt][nt] = relu4(acc2[mt][nt] + bias);
-        }
-        f32x4 acc3[4][NT];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc3[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int t2 = 0; t2 < 4; ++t2) {
-                const f32x4 a = ldsv[(OFF_W3 >> 2) + (mt * 4 + t2) * 64 + lane];
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) acc3[mt][nt] = mfma(a[r], acc2[t2][nt][r], acc3[mt][nt]);
-            }
-            const f32x4 bias = ldsv[(OFF_B3 >> 2) + 4 * mt + g];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc3[mt][nt] = relu4(acc3[mt][nt] + bias);
-        }
-        // ---- layer 4 + mean over the 32 taus (model.py:185,190).  The output layer is linear, so
-        // mean_tau(W4 h3(tau) + b4) = W4 mean_tau(h3(tau)) + b4: the tau mean is taken FIRST (DPP row sums of the
-        // layer-3 accumulators) and the 9 x 64 output layer becomes one small VALU mat-vec per environment
-        // instead of 32 MFMAs on a padded 16-row tile (3 % of the kernel's matrix work).
-        // After row_sum16 every lane of row group g holds sum_tau h3[16mt + 4g + r]; lane (g, col) then forms the
-        // part of action `col` that comes from its 16 features (W4p[mt][lane][r] = W4[col][16mt + 4g + r], zero rows
-        // for col >= 9) and the four row groups are added with two cross-row shuffles.
-        float qv;
-        if constexpr (!QUANT) {
-            float part = 0.f;
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                const f32x4 a = ldsv[(OFF_W4 >> 2) + mt * 64 + lane];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) part = fmaf(a[r], row_sum16(acc3[mt][0][r] + acc3[mt][1][r]), part);
-            }
-            part += __shfl_xor(part, 16);
-            part += __shfl_xor(part, 32);
-            qv = part * (1.0f / K_TAUS) + lds[OFF_B4 + col];     // Q(s, action = col), valid for col < 9
-        } else {
-            // quantile values Z(tau, a) = W4 h3(tau) + b4 (model.py:185): C tile [16 padded actions x 16 taus] per tau tile;
-            // lane (g, col) holds actions 4g + r of tau 16 nt + col
-            f32x4 acc4[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc4[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int t2 = 0; t2 < 4; ++t2) {
-                const f32x4 a = ldsv[(OFF_W4 >> 2) + t2 * 64 + lane];
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) acc4[nt] = mfma(a[r], acc3[t2][nt][r], acc4[nt]);
-            }
-            const f32x4 b4 = ldsv[(OFF_B4 >> 2) + g];
-            float mine = 0.f;      // lane `a` (< 9) ends up with Q(s, a) = mean over the 32 taus
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int a_idx = 4 * g + r;
-                float sum = 0.f;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const float z = acc4[nt][r] + b4[r];
-                    if (a_idx < A_OUT) quantiles[((size_t)e * K_TAUS + 16 * nt + col) * A_OUT + a_idx] = z;
-                    sum += z;
-                }
-                sum = row_sum16(sum);                    // over the 16 tau columns of the row group
-#pragma unroll
-                for (int gg = 0; gg < 4; ++gg) {         // hand action 4 gg + r to lane (4 gg + r)
-                    const float v = __shfl(sum, 16 * gg);
-                    if (lane == 4 * gg + r) mine = v;
-                }
-            }
-            qv = mine * (1.0f / K_TAUS);
-        }
-        if (qvals && lane < A_OUT) qvals[(size_t)e * A_OUT + lane] = qv;
-        // ---- IQNAgent.act epilogue (agent.py:199-203): argmax, epsilon-greedy ------------------------
-        if (actions) {
-            // lane a holds action a; gather the 9 values (first maximum wins, like np.argmax)
-            float best = -INFINITY;
-            int arg = 0;
-#pragma unroll
-            for (int a = 0; a < A_OUT; ++a) {
-                const float v = __shfl(qv, a);
-                if (v > best) { best = v; arg = a; }
-            }
-            if (lane == 0) {
-                int act = arg;
-                if (explore_u && eps > 0.f) {
-                    const float u = explore_u[e];            // greedy iff u > eps (agent.py:200)
-                    if (!(u > eps)) { act = (int)(u / eps * (float)A_OUT); act = act > A_OUT - 1 ? A_OUT - 1 : act; }
-                }
-                actions[e] = act;
-            }
-        }
-    }
-}
-
-
+#include "iqn_act_exact.h"
 #include "iqn_act_split.h"
 #include "iqn_act_tiled.h"
 
-// ---- what clock does THIS GPU sustain under f16 matrix load?  (mn_probe_mfma_clock; round 4)
-// The same act binary runs 10-12 % slower on some boxes of the pool (304-318 us vs 352-367 us per 65 536-env launch) while the
-// exact-f32 kernel does not move.  This probe separates a slow box from a slow kernel: a pure stream of v_mfma_f32_16x16x32_f16 -- the act
-// kernel's matrix instruction -- from two waves per SIMD on every CU.  The instruction occupies the SIMD's matrix pipe for 16 cycles
-// (4 passes), so with the pipe saturated   effective clock = 16 x (matrix instructions per SIMD) / elapsed time.
-// Wave 0 of every workgroup also brackets its loop with s_memtime (shader-clock ticks) and s_memrealtime (constant 100 MHz).
-__global__ __launch_bounds__(512) void mfma_clock_probe_kernel(int iters, unsigned long long *__restrict__ stamps, float *__restrict__ sink) {
-    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-    const int lane = threadIdx.x & 63;
-    h8 a, b;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { a[i] = (_Float16)(0.001f * (lane + i)); b[i] = (_Float16)(0.002f * (lane - i)); }
-    f32x4 acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    __syncthreads();
-    const unsigned long long c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-    for (int it = 0; it < iters; ++it) {
-#pragma unroll
-        for (int u = 0; u < 16; ++u) acc[u & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc[u & 3], 0, 0, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    float s = acc[0][0] + acc[1][1] + acc[2][2] + acc[3][3];
-    const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-    if (s == 12345.678f) sink[0] = s;      // keeps the accumulators alive
-    if (threadIdx.x == 0) { stamps[2 * blockIdx.x] = c1 - c0; stamps[2 * blockIdx.x + 1] = r1 - r0; }
+// A kernel form = (kernel, dynamic LDS, workgroup size); the member of its family is set.  mn_iqn_create raises the LDS limit of every entry and
+// launch_act launches the entry form_of picks with that entry's size, so the registered and the launched size of a form are one number.
+using ExactKernel = decltype(&iqn_qvals_kernel<false>);
+using SplitKernel = decltype(&sp::iqn_qvals_split_kernel<false>);
+using TiledKernel = decltype(&sp::iqn_qvals_tiled_kernel);
+struct Form {
+    ExactKernel exact;
+    SplitKernel split;
+    TiledKernel tiled;
+    int lds_floats, threads;
+    const void *kernel() const { return exact ? (const void *)exact : split ? (const void *)split : (const void *)tiled; }
+    size_t lds_bytes() const { return lds_floats * sizeof(float); }
+};
+enum { F_EXACT, F_EXACT_QUANT, F_SPLIT, F_SPLIT_LATE, F_SPLIT_QUANT, F_SHARED, F_SHARED_QUANT, F_TILED, N_FORMS };
+const Form FORMS[N_FORMS] = {
+    {iqn_qvals_kernel<false>, nullptr, nullptr, LDS_FLOATS, 512},
+    {iqn_qvals_kernel<true>, nullptr, nullptr, LDS_FLOATS, 512},      // act_eval: the [n][32][9] quantile values as well
+    {nullptr, sp::iqn_qvals_split_kernel<false>, nullptr, sp::LDS_ACT_FLOATS, 512},
+    {nullptr, sp::iqn_qvals_split_kernel<false, false, sp::WAVES, true>, nullptr, sp::LDS_ACT_FLOATS, 512},      // late rows (mn_iqn_set_late_rows)
+    {nullptr, sp::iqn_qvals_split_kernel<true>, nullptr, sp::LDS_FLOATS, 512},
+    // launch-shared taus (12 waves per workgroup -- three per SIMD, the kernel needs 153 registers -- measured: 202-204 us against 203, no gain)
+    {nullptr, sp::iqn_qvals_split_kernel<false, true, 8>, nullptr, sp::OFF_FB, 512},
+    {nullptr, sp::iqn_qvals_split_kernel<true, true, 8>, nullptr, sp::OFF_FB, 512},
+    {nullptr, nullptr, sp::iqn_qvals_tiled_kernel, sp::TL_FLOATS, 512},      // ... with the environments in the MFMA columns (iqn_act_tiled.h)
+};
+
+// NULL checks + fill of the 14 weight pointers of the C ABI
+bool load_weights(const float *const *p, IqnWeights *w) {
+    if (!p) return false;
+    for (int i = 0; i < 14; ++i) if (!p[i]) return false;
+    *w = {p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], p[11], p[12], p[13]};
+    return true;
 }
 
 }  // namespace
-
-// C-ABI ----------------------------------------------------------------------------------------------
-#include <vector>
-
-extern "C" int mn_probe_mfma_clock(double target_ms, double *out, void *stream) {
-    if (!out || !(target_ms > 0.0) || target_ms > 2000.0) return MN_ERR_INVALID;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return MN_ERR_NO_DEVICE;
-    const int n_cu = prop.multiProcessorCount;
-    unsigned long long *stamps = nullptr;
-    float *sink = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&stamps), 2 * n_cu * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&sink), sizeof(float)) != hipSuccess) { (void)hipFree(stamps); return MN_ERR_ALLOC; }
-    hipStream_t s = (hipStream_t)stream;
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    int rc = MN_OK;
-    int iters = 2000;
-    float ms = 0.f;
-    for (int pass = 0; pass < 2 && rc == MN_OK; ++pass) {      // pass 0 calibrates the loop count, pass 1 is the measurement
-        (void)hipEventRecord(e0, s);
-        hipLaunchKernelGGL(mfma_clock_probe_kernel, dim3(n_cu), dim3(512), 0, s, iters, stamps, sink);
-        (void)hipEventRecord(e1, s);
-        if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess || !(ms > 0.f)) { rc = MN_ERR_HIP; break; }
-        if (pass == 0) {
-            double scaled = iters * target_ms / ms;
-            iters = scaled > 5e7 ? 50000000 : (scaled < 100 ? 100 : (int)scaled);
-        }
-    }
-    if (rc == MN_OK) {
-        std::vector<unsigned long long> h(2 * n_cu);
-        if (hipMemcpy(h.data(), stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) rc = MN_ERR_HIP;
-        else {
-            double ct = 0, rt = 0;
-            for (int i = 0; i < n_cu; ++i) { ct += (double)h[2 * i]; rt += (double)h[2 * i + 1]; }
-            const double per_simd = 2.0 * iters * 16.0;      // two waves per SIMD, 16 matrix instructions per loop iteration
-            out[0] = ms;
-            out[1] = 16.0 * per_simd / (ms * 1e-3) / 1e9;     // GHz the matrix pipe ran at, if saturated
-            out[2] = rt > 0 ? ct / rt * 0.1 : 0.0;            // GHz by the wave's own counters: shader ticks per 100 MHz tick
-            out[3] = per_simd * 4.0 * n_cu * 16384.0 / (ms * 1e-3) / 1e12;      // sustained f16 TFLOP/s of the whole chip (2 x 16 x 16 x 32 FLOP each)
-            out[4] = (double)n_cu;
-        }
-    }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(stamps); (void)hipFree(sink);
-    return rc;
-}
 
 // Per-caller state of the act path: the permuted LDS weight image (cached between calls until the caller says the
 // weights changed), the profiling events.  One context per agent / per stream: two contexts never share a buffer, so
@@ -447,6 +86,10 @@ struct mn_iqn_ctx {
     float *h1_sp = nullptr;        // the launch's layer-1 constant [32 taus x 208] of the shared-tau kernels (mn_iqn_set_tau_mode) + 32 block maxima
     uint32_t *timg = nullptr;      // tiled shared-tau kernel (iqn_act_tiled.h): T = W2 h1 as hi / lo f16 pairs, and its auxiliary float block
     float *taux = nullptr;
+    // the buffers above with their element counts: the one list that create, its failure path and destroy walk
+    template <class Fn> void each_buffer(Fn f) {
+        f(packed, OFF_FB); f(packed_sp, sp::OFF_FB); f(consts_sp, sp::N_CONST_BUF); f(h1_sp, sp::H1_FLOATS + 32); f(timg, sp::T_WORDS); f(taux, sp::TA_FLOATS);
+    }
     int tau_mode = 0;              // 0 = every environment its own 32 taus (the reference's per-call draw), 1 = one set of 32 per launch
     bool dirty = true, dirty_sp = true;
     int variant = MN_IQN_VARIANT_DEFAULT;   // mn_iqn_set_variant
@@ -474,39 +117,15 @@ extern "C" int mn_iqn_create(mn_iqn_ctx **out) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return MN_ERR_HIP;
     // per-device function attribute; setting it again for another context is harmless and has no shared host state
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(iqn_qvals_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            LDS_FLOATS * (int)sizeof(float)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(iqn_qvals_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            LDS_FLOATS * (int)sizeof(float)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sp::iqn_qvals_split_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            sp::LDS_FLOATS * (int)sizeof(float)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sp::iqn_qvals_split_kernel<false, false, sp::WAVES, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            sp::LDS_FLOATS * (int)sizeof(float)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sp::iqn_qvals_split_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            sp::LDS_FLOATS * (int)sizeof(float)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sp::iqn_qvals_tiled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            sp::TL_FLOATS * (int)sizeof(float)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sp::iqn_qvals_split_kernel<false, true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            sp::OFF_FB * (int)sizeof(float)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sp::iqn_qvals_split_kernel<true, true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            sp::OFF_FB * (int)sizeof(float)) != hipSuccess)
-        return MN_ERR_HIP;
+    for (const Form &f : FORMS)
+        if (hipFuncSetAttribute(f.kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_bytes()) != hipSuccess) return MN_ERR_HIP;
     mn_iqn_ctx *c = new mn_iqn_ctx();
     c->device = dev;
     c->n_cu = prop.multiProcessorCount;
-    if (hipMalloc(reinterpret_cast<void **>(&c->packed), OFF_FB * sizeof(float)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&c->packed_sp), sp::OFF_FB * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&c->consts_sp), sp::N_CONST_BUF * sizeof(float)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&c->h1_sp), (sp::H1_FLOATS + 32) * sizeof(float)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&c->timg), sp::T_WORDS * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&c->taux), sp::TA_FLOATS * sizeof(float)) != hipSuccess ||
-        hipMemset(c->consts_sp, 0, sp::N_CONST_BUF * sizeof(float)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        (void)hipFree(c->packed);
-        (void)hipFree(c->packed_sp);
-        (void)hipFree(c->consts_sp);
-        (void)hipFree(c->h1_sp);
-        (void)hipFree(c->timg);
-        (void)hipFree(c->taux);
+    bool ok = true;
+    c->each_buffer([&](auto *&p, size_t count) { ok = ok && hipMalloc(reinterpret_cast<void **>(&p), count * sizeof(*p)) == hipSuccess; });
+    if (!ok || hipMemset(c->consts_sp, 0, sp::N_CONST_BUF * sizeof(float)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        c->each_buffer([](auto *p, size_t) { (void)hipFree(p); });
         delete c;
         return MN_ERR_ALLOC;
     }
@@ -520,12 +139,7 @@ extern "C" int mn_iqn_destroy(mn_iqn_ctx *c) {
     const bool moved = hipGetDevice(&cur) == hipSuccess && cur != c->device;
     if (moved) (void)hipSetDevice(c->device);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
-    (void)hipFree(c->packed);
-    (void)hipFree(c->packed_sp);
-    (void)hipFree(c->consts_sp);
-    (void)hipFree(c->h1_sp);
-    (void)hipFree(c->timg);
-    (void)hipFree(c->taux);
+    c->each_buffer([](auto *p, size_t) { (void)hipFree(p); });
     (void)hipFree(c->late_status);
     (void)hipFree(c->rollout_words);
     if (c->late_status_host) (void)hipHostFree((void *)c->late_status_host);
@@ -581,13 +195,22 @@ extern "C" int mn_iqn_profile_end(mn_iqn_ctx *c, void *stream, double *mean_ms, 
     return MN_OK;
 }
 
+// Workgroups of the wave-per-environment forms: eight environments per workgroup pass, capped by mn_iqn_set_grid or at one persistent workgroup per CU
+static int act_grid(const mn_iqn_ctx *c, int n) {
+    const int blocks = (n + 7) / 8, cap = c->max_blocks > 0 ? c->max_blocks : c->n_cu;
+    return blocks < cap ? blocks : cap;
+}
+
+// Blocks of 256 threads that make a launch's `items` draws beside the pack blocks of a prep kernel
+static int draw_blocks(const mn_iqn_ctx *c, long items) {
+    const long blocks = (items + 255) / 256;
+    return blocks < 8L * c->n_cu ? (int)blocks : 8 * c->n_cu;
+}
+
 // The acting kernel that takes late rows: split-f16, per-environment taus, no quantile capture, at most 64 rows per wavefront.
 static bool late_rows_supported(const mn_iqn_ctx *c, int n, bool quantiles) {
     if (c->variant != 2 || c->tau_mode != 0 || quantiles || n <= 0) return false;
-    int blocks = (n + 7) / 8;
-    const int cap = c->max_blocks > 0 ? c->max_blocks : c->n_cu;
-    if (blocks > cap) blocks = cap;
-    return (long)n <= 64L * 8L * blocks;
+    return (long)n <= 64L * 8L * act_grid(c, n);
 }
 
 // Rows of the next act launch whose observation is still being written by a reset launch on another stream (mn_reset_done_async):
@@ -636,142 +259,111 @@ extern "C" int mn_iqn_set_late_bound_ms(mn_iqn_ctx *c, double ms) {
     return MN_OK;
 }
 
+// The form a launch of `n` rows runs in (variants, mn_iqn_set_variant: 0 = exact-f32 16x16x4 kernel, 2 = split-f16 kernel; tau modes, mn_iqn_set_tau_mode:
+// shared taus run with the environments in the MFMA columns from sp::TILED_MIN_ENVS rows, in mode 3 always, and never with quantiles)
+static const Form &form_of(const mn_iqn_ctx *c, int n, bool quantiles, bool late) {
+    if (c->tau_mode != 0) {
+        if (!quantiles && ((c->tau_mode == 1 && n >= sp::TILED_MIN_ENVS) || c->tau_mode == 3)) return FORMS[F_TILED];
+        return FORMS[quantiles ? F_SHARED_QUANT : F_SHARED];
+    }
+    if (c->variant != 2) return FORMS[quantiles ? F_EXACT_QUANT : F_EXACT];
+    return FORMS[quantiles ? F_SPLIT_QUANT : late ? F_SPLIT_LATE : F_SPLIT];
+}
+
+// Begins the rebuild of the variant's weight image if it is stale (mn_iqn_weights_changed): returns the block count of its pack, 0 for a cached image, with
+// the split image's constants enqueued.  The caller enqueues the pack next -- pack_image, or a prep kernel that packs in its first blocks.
+static int begin_pack(mn_iqn_ctx *c, const IqnWeights &w, hipStream_t s) {
+    bool &stale = c->variant == 2 ? c->dirty_sp : c->dirty;
+    if (!stale) return 0;
+    stale = false;
+    if (c->variant != 2) return PACK_BLOCKS;
+    hipLaunchKernelGGL(sp::iqn_split_consts_kernel, dim3(sp::CONST_BLOCKS), dim3(256), 0, s, w, c->consts_sp);
+    return sp::PACK_BLOCKS;
+}
+
+static void pack_image(mn_iqn_ctx *c, const IqnWeights &w, hipStream_t s) {
+    if (c->variant == 2) hipLaunchKernelGGL(sp::iqn_split_pack_kernel, dim3(sp::PACK_BLOCKS), dim3(256), 0, s, w, (const float *)c->consts_sp, c->packed_sp);
+    else hipLaunchKernelGGL(iqn_pack_kernel, dim3(PACK_BLOCKS), dim3(256), 0, s, w, c->packed);
+}
+
 static int launch_act(mn_iqn_ctx *c, const float *obs_dev, const float *taus_dev, const float *const *weights, float *qvals_dev,
                       const float *explore_u_dev, float eps, int32_t *actions_dev, float *quantiles_dev, int32_t n,
                       int32_t num_taus, uint64_t *rng_state_dev, float *draws_dev, const float *cvar_row_dev, float cvar,
                       void *stream) {
-    if (!c || !obs_dev || !weights || (!qvals_dev && !actions_dev && !quantiles_dev)) return MN_ERR_INVALID;
+    // ---- prologue: arguments, the launch's form, its armed late rows
+    IqnWeights w;
+    if (!c || !obs_dev || !load_weights(weights, &w) || (!qvals_dev && !actions_dev && !quantiles_dev)) return MN_ERR_INVALID;
     if (rng_state_dev ? !draws_dev : !taus_dev) return MN_ERR_INVALID;
     if (rng_state_dev && (long)n * (K_TAUS + 1) >= (1L << 32)) return MN_ERR_INVALID;   // 32-bit draw index
-    for (int i = 0; i < 14; ++i) if (!weights[i]) return MN_ERR_INVALID;
     if (n <= 0 || num_taus != K_TAUS) return MN_ERR_INVALID;
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != c->device) return MN_ERR_INVALID;   // context lives on another device
-    const IqnWeights w = {weights[0], weights[1], weights[2], weights[3], weights[4], weights[5], weights[6],
-                          weights[7], weights[8], weights[9], weights[10], weights[11], weights[12], weights[13]};
-    int blocks = (n + 7) / 8;
-    const int cap = c->max_blocks > 0 ? c->max_blocks : c->n_cu;
-    if (blocks > cap) blocks = cap;
     hipStream_t s = (hipStream_t)stream;
     // late rows (mn_iqn_set_late_rows) belong to THIS launch only; a form that cannot honour them must never see them (the caller joined the reset instead)
     const sp::LateRows late = c->late;
     c->late = sp::LateRows{};
     if (late.mask && !late_rows_supported(c, n, quantiles_dev != nullptr)) return MN_ERR_INVALID;
+    // Launch-shared taus: ONE set of 32 quantile fractions for every environment of the launch (iqn_act_split.h, stage_sh).  Only the
+    // split-f16 kernel has this form; per-row CVaR (adaptive policies) needs per-environment taus.
+    const bool shared = c->tau_mode != 0, rng = rng_state_dev != nullptr;
+    if (shared && (c->variant != 2 || cvar_row_dev)) return MN_ERR_INVALID;
+    const Form &f = form_of(c, n, quantiles_dev != nullptr, late.mask != nullptr);
     const bool prof = c->prof_n < c->prof_max;
     if (prof) (void)hipEventRecord(c->ev[2 * c->prof_n], s);
-    // variants (mn_iqn_set_variant): 0 = exact-f32 16x16x4 kernel, 2 = split-f16 kernel (iqn_act_split.h); each has a quantile-capture form (act_eval)
-    const bool use_sp = c->variant == 2;
-    if (c->tau_mode != 0) {
-        // Launch-shared taus: ONE set of 32 quantile fractions for every environment of the launch (iqn_act_split.h, stage_sh).  Only the
-        // split-f16 kernel has this form; per-row CVaR (adaptive policies) needs per-environment taus.
-        if (c->variant != 2 || cvar_row_dev) return MN_ERR_INVALID;
-        const int pack_blocks = c->dirty_sp ? sp::PACK_BLOCKS : 0;
-        if (pack_blocks) hipLaunchKernelGGL(sp::iqn_split_consts_kernel, dim3(sp::CONST_BLOCKS), dim3(256), 0, s, w, c->consts_sp);
-        int rng_blocks = 0;
-        if (rng_state_dev) {
-            rng_blocks = (int)(((long)n + K_TAUS + 255) / 256);
-            if (rng_blocks > 8 * c->n_cu) rng_blocks = 8 * c->n_cu;
-        }
+
+    // ---- prepare: the weight image if it is stale and the launch's draws, in one launch where both are due
+    const int pack_blocks = begin_pack(c, w, s);
+    if (shared) {      // (packs, draws the 32 taus and the n exploration uniforms, builds the layer-1 constant)
+        const int rng_blocks = rng ? draw_blocks(c, (long)n + K_TAUS) : 0;
         hipLaunchKernelGGL(sp::iqn_shared_prep_kernel, dim3(pack_blocks + sp::H1_BLOCKS + rng_blocks), dim3(256), 0, s, w, (const float *)c->consts_sp,
-                           c->packed_sp, (const uint64_t *)rng_state_dev, draws_dev, n, rng_state_dev ? nullptr : taus_dev, cvar, pack_blocks, c->h1_sp);
-        if (rng_state_dev) explore_u_dev = eps > 0.f ? draws_dev + K_TAUS : nullptr;
-        c->dirty_sp = false;
-        if (!quantiles_dev && ((c->tau_mode == 1 && n >= sp::TILED_MIN_ENVS) || c->tau_mode == 3)) {
-            // large batch: the MFMA columns are environments (iqn_act_tiled.h): T = W2 h1 built once, 32 environments per wavefront
+                           c->packed_sp, (const uint64_t *)rng_state_dev, draws_dev, n, rng ? nullptr : taus_dev, cvar, pack_blocks, c->h1_sp);
+        if (rng) explore_u_dev = eps > 0.f ? draws_dev + K_TAUS : nullptr;
+        taus_dev = nullptr;
+        if (f.tiled)      // large batch: the MFMA columns are environments (iqn_act_tiled.h): T = W2 h1 built once, 32 environments per wavefront
             hipLaunchKernelGGL(sp::iqn_tiled_prep_kernel, dim3(sp::T_PREP_BLOCKS + sp::TA_PREP_BLOCKS), dim3(256), 0, s, w, (const float *)c->consts_sp,
                                (const float *)c->h1_sp, c->timg, c->taux);
-            hipLaunchKernelGGL(sp::iqn_qvals_tiled_kernel, dim3((n + 255) / 256), dim3(512), sp::TL_FLOATS * sizeof(float), s, obs_dev,
-                               (const uint32_t *)c->packed_sp, (const uint32_t *)c->timg, (const float *)c->taux, qvals_dev, explore_u_dev, eps,
-                               actions_dev, n, rng_state_dev);
-            if (prof) { (void)hipEventRecord(c->ev[2 * c->prof_n + 1], s); ++c->prof_n; }
-            return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
-        }
-        if (quantiles_dev)
-            hipLaunchKernelGGL((sp::iqn_qvals_split_kernel<true, true, 8>), dim3(blocks), dim3(512), sp::OFF_FB * sizeof(float), s, obs_dev, (const float *)nullptr,
-                               (const uint32_t *)c->packed_sp, qvals_dev, explore_u_dev, eps, actions_dev, n, rng_state_dev, quantiles_dev, (const float *)c->h1_sp);
-        else      // (12 waves per workgroup -- three per SIMD, the kernel needs 153 registers -- measured: 202-204 us against 203, no gain)
-            hipLaunchKernelGGL((sp::iqn_qvals_split_kernel<false, true, 8>), dim3(blocks), dim3(512), sp::OFF_FB * sizeof(float), s, obs_dev, (const float *)nullptr,
-                               (const uint32_t *)c->packed_sp, qvals_dev, explore_u_dev, eps, actions_dev, n, rng_state_dev, (float *)nullptr, (const float *)c->h1_sp);
-        if (prof) { (void)hipEventRecord(c->ev[2 * c->prof_n + 1], s); ++c->prof_n; }
-        return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
-    }
-    if (use_sp) {
-        bool &dirty_s = c->dirty_sp;
-        uint32_t *image = c->packed_sp;
-        const int pack_blocks = dirty_s ? sp::PACK_BLOCKS : 0;
-        if (pack_blocks) hipLaunchKernelGGL(sp::iqn_split_consts_kernel, dim3(sp::CONST_BLOCKS), dim3(256), 0, s, w, c->consts_sp);
-        if (rng_state_dev) {
-            long groups = ((long)n * (K_TAUS + 1) + 3) / 4;
-            int rng_blocks = (int)((groups + 255) / 256);
-            if (rng_blocks > 8 * c->n_cu) rng_blocks = 8 * c->n_cu;
+    } else if (rng) {      // (n x 32 taus and n exploration uniforms, as float4 groups)
+        const int rng_blocks = draw_blocks(c, ((long)n * (K_TAUS + 1) + 3) / 4);
+        if (f.split)
             hipLaunchKernelGGL(sp::iqn_split_prep_kernel, dim3(pack_blocks + rng_blocks), dim3(256), 0, s, w, (const float *)c->consts_sp,
-                               image, (const uint64_t *)rng_state_dev, draws_dev, n, cvar_row_dev, cvar, pack_blocks);
-            taus_dev = draws_dev;
-            explore_u_dev = eps > 0.f ? draws_dev + (size_t)n * K_TAUS : nullptr;
-        } else if (pack_blocks) {
-            hipLaunchKernelGGL(sp::iqn_split_pack_kernel, dim3(sp::PACK_BLOCKS), dim3(256), 0, s, w, (const float *)c->consts_sp, image);
-        }
-        dirty_s = false;
-        if (quantiles_dev)
-            hipLaunchKernelGGL(sp::iqn_qvals_split_kernel<true>, dim3(blocks), dim3(512), sp::LDS_FLOATS * sizeof(float), s, obs_dev, taus_dev,
-                               (const uint32_t *)image, qvals_dev, explore_u_dev, eps, actions_dev, n, rng_state_dev, quantiles_dev, (const float *)nullptr);
-        else if (late.mask)
-            hipLaunchKernelGGL((sp::iqn_qvals_split_kernel<false, false, sp::WAVES, true>), dim3(blocks), dim3(512), sp::LDS_ACT_FLOATS * sizeof(float), s, obs_dev, taus_dev,
-                               (const uint32_t *)image, qvals_dev, explore_u_dev, eps, actions_dev, n, rng_state_dev, (float *)nullptr, (const float *)nullptr, late);
+                               c->packed_sp, (const uint64_t *)rng_state_dev, draws_dev, n, cvar_row_dev, cvar, pack_blocks);
         else
-            hipLaunchKernelGGL(sp::iqn_qvals_split_kernel<false>, dim3(blocks), dim3(512), sp::LDS_ACT_FLOATS * sizeof(float), s, obs_dev, taus_dev,
-                               (const uint32_t *)image, qvals_dev, explore_u_dev, eps, actions_dev, n, rng_state_dev, (float *)nullptr, (const float *)nullptr, sp::LateRows{});
-        if (prof) { (void)hipEventRecord(c->ev[2 * c->prof_n + 1], s); ++c->prof_n; }
-        return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
-    }
-    bool &dirty = c->dirty;
-    float *packed = c->packed;
-    const int pack_blocks = dirty ? PACK_BLOCKS : 0;
-    if (rng_state_dev) {
-        long groups = ((long)n * (K_TAUS + 1) + 3) / 4;
-        int rng_blocks = (int)((groups + 255) / 256);
-        if (rng_blocks > 8 * c->n_cu) rng_blocks = 8 * c->n_cu;
-        hipLaunchKernelGGL(iqn_prep_kernel, dim3(pack_blocks + rng_blocks), dim3(256), 0, s, w, packed,
-                           (const uint64_t *)rng_state_dev, draws_dev, n, cvar_row_dev, cvar, pack_blocks);
+            hipLaunchKernelGGL(iqn_prep_kernel, dim3(pack_blocks + rng_blocks), dim3(256), 0, s, w, c->packed,
+                               (const uint64_t *)rng_state_dev, draws_dev, n, cvar_row_dev, cvar, pack_blocks);
         taus_dev = draws_dev;
         explore_u_dev = eps > 0.f ? draws_dev + (size_t)n * K_TAUS : nullptr;
     } else if (pack_blocks) {
-        hipLaunchKernelGGL(iqn_pack_kernel, dim3(PACK_BLOCKS), dim3(256), 0, s, w, packed);
+        pack_image(c, w, s);
     }
-    dirty = false;
-    if (quantiles_dev)
-        hipLaunchKernelGGL(iqn_qvals_kernel<true>, dim3(blocks), dim3(512), LDS_FLOATS * sizeof(float), s, obs_dev, taus_dev,
-                           packed, qvals_dev, explore_u_dev, eps, actions_dev, n, rng_state_dev, quantiles_dev);
+
+    // ---- launch
+    const dim3 grid(act_grid(c, n)), block(f.threads);
+    if (f.tiled)
+        hipLaunchKernelGGL(f.tiled, dim3((n + 255) / 256), block, f.lds_bytes(), s, obs_dev, (const uint32_t *)c->packed_sp, (const uint32_t *)c->timg,
+                           (const float *)c->taux, qvals_dev, explore_u_dev, eps, actions_dev, n, rng_state_dev);
+    else if (f.split)
+        hipLaunchKernelGGL(f.split, grid, block, f.lds_bytes(), s, obs_dev, taus_dev, (const uint32_t *)c->packed_sp, qvals_dev, explore_u_dev, eps,
+                           actions_dev, n, rng_state_dev, quantiles_dev, shared ? (const float *)c->h1_sp : nullptr, late);
     else
-        hipLaunchKernelGGL(iqn_qvals_kernel<false>, dim3(blocks), dim3(512), LDS_FLOATS * sizeof(float), s, obs_dev, taus_dev,
-                           packed, qvals_dev, explore_u_dev, eps, actions_dev, n, rng_state_dev, nullptr);
+        hipLaunchKernelGGL(f.exact, grid, block, f.lds_bytes(), s, obs_dev, taus_dev, (const float *)c->packed, qvals_dev, explore_u_dev, eps,
+                           actions_dev, n, rng_state_dev, quantiles_dev);
+
+    // ---- epilogue
     if (prof) { (void)hipEventRecord(c->ev[2 * c->prof_n + 1], s); ++c->prof_n; }
     return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
 }
 
 extern "C" int mn_iqn_refresh(mn_iqn_ctx *c, const float *const *weights, void *stream) {
-    if (!c || !weights) return MN_ERR_INVALID;
-    for (int i = 0; i < 14; ++i) if (!weights[i]) return MN_ERR_INVALID;
+    IqnWeights w;
+    if (!c || !load_weights(weights, &w)) return MN_ERR_INVALID;
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != c->device) return MN_ERR_INVALID;
-    const IqnWeights w = {weights[0], weights[1], weights[2], weights[3], weights[4], weights[5], weights[6],
-                          weights[7], weights[8], weights[9], weights[10], weights[11], weights[12], weights[13]};
-    hipStream_t s = (hipStream_t)stream;
-    if (c->variant == 2) {
-        if (c->dirty_sp) {
-            hipLaunchKernelGGL(sp::iqn_split_consts_kernel, dim3(sp::CONST_BLOCKS), dim3(256), 0, s, w, c->consts_sp);
-            hipLaunchKernelGGL(sp::iqn_split_pack_kernel, dim3(sp::PACK_BLOCKS), dim3(256), 0, s, w, (const float *)c->consts_sp, c->packed_sp);
-            c->dirty_sp = false;
-        }
-    } else if (c->dirty) {
-        hipLaunchKernelGGL(iqn_pack_kernel, dim3(PACK_BLOCKS), dim3(256), 0, s, w, c->packed);
-        c->dirty = false;
-    }
+    if (begin_pack(c, w, (hipStream_t)stream)) pack_image(c, w, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
 }
 
-// What mn_rollout_iqn (mn_capi.hip) needs of a context: the split-f16 weight image, rebuilt first if stale (as mn_iqn_refresh), and two device
-// words for its launch.  MN_ERR_INVALID for the forms the rollout does not reproduce: the exact-f32 variant, launch-shared taus.
+// What mn_rollout_iqn (mn_capi.hip) needs of a context: the split-f16 weight image, rebuilt first if stale (as mn_iqn_refresh, which also checks
+// `weights`), and two device words for its launch.  MN_ERR_INVALID for the forms the rollout does not reproduce: the exact-f32 variant, launch-shared taus.
 int mn_iqn_rollout_image(mn_iqn_ctx *c, const float *const *weights, hipStream_t s, const uint32_t **image, uint32_t **words) {
     if (!c || !weights || !image || !words || c->variant != 2 || c->tau_mode != 0) return MN_ERR_INVALID;
     if (!c->rollout_words) {
@@ -801,3 +393,5 @@ extern "C" int mn_iqn_act_rng(mn_iqn_ctx *c, const float *obs_dev, const float *
     return launch_act(c, obs_dev, nullptr, weights, qvals_dev, nullptr, eps, actions_dev, quantiles_dev, n, num_taus,
                       rng_state_dev, draws_dev, cvar_row_dev, cvar, stream);
 }
+
+#include "mfma_probe.h"

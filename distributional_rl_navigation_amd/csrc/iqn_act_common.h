@@ -1,5 +1,6 @@
-// iqn_act_common.h -- what the IQN act kernels (iqn_act.hip) and the IQN episode rollout (mn_rollout_iqn.hip) share: the network's
-// widths, the weight pointers, the tau-row sum and the counter-based draws of an act call.  Included inside each file's anonymous namespace.
+// iqn_act_common.h -- what the IQN act kernels (iqn_act_exact.h, iqn_act_split.h, iqn_act_tiled.h) and the IQN episode rollout share: the network's
+// widths, the weight pointers, the tau-row sum and the counter-based draws of an act call.  Included by iqn_act.hip and mn_rollout_iqn.hip inside
+// their anonymous namespaces, in front of the kernel headers.
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

@@ -1,5 +1,6 @@
 // iqn_act_split.h -- the IQN action-value network of iqn_act.hip on the f16 matrix pipe at float32 accuracy.
-// Included by iqn_act.hip inside its anonymous namespace (uses IqnWeights, row_sum16, draw_block, the layer constants).
+// Included by iqn_act.hip and mn_rollout_iqn.hip inside their anonymous namespaces, after iqn_act_common.h (uses IqnWeights, row_sum16, draw_block, the
+// layer constants).
 //
 // Why: the exact-f32 MFMA (v_mfma_f32_16x16x4_f32) runs at the f32 VECTOR rate, 1/16 of the f16 rate, and the act kernel
 // built on it sits at 84 % of that peak -- the only way to go substantially faster is to leave that
@@ -81,7 +82,8 @@ constexpr int OFF_W4H = OFF_BE + F;                     // [2 kb][piece][64 l] x
 constexpr int OFF_FB = OFF_W4H + 2 * 2 * 64 * 4;        // [waves][208] per-wave scaled features
 constexpr int WAVES = 8;                                // one 512-thread workgroup per CU, two waves per SIMD
 constexpr int LDS_FLOATS = OFF_FB + WAVES * F;
-constexpr int LDS_ACT_FLOATS = OFF_W4H + WAVES * F;       // acting form (no quantile output): the feature buffers take the place of the output layer's MFMA operands
+constexpr int ACT_IMG_FLOATS = OFF_W4H;                 // the image of the acting forms (no quantile output) ends in front of the output layer's MFMA operands ...
+constexpr int LDS_ACT_FLOATS = ACT_IMG_FLOATS + WAVES * F;      // ... and their feature buffers take that place
 static_assert(LDS_FLOATS * 4 <= 160 * 1024, "LDS image of the split-f16 act kernel must fit the CU's 160 KB");
 static_assert(OFF_WS % 4 == 0 && OFF_WVG % 4 == 0 && OFF_BE % 4 == 0 && OFF_FB % 4 == 0 && OFF_CST % 4 == 0 && OFF_W4H % 4 == 0, "16-byte aligned blocks");
 constexpr int PACK_BLOCKS = (OFF_FB + 255) / 256;       // one thread per 32-bit word of the image

@@ -1,5 +1,5 @@
 // iqn_act_tiled.h -- launch-shared taus, second form: the MFMA columns are ENVIRONMENTS (round 4).
-// Included by iqn_act.hip inside its anonymous namespace, after iqn_act_split.h (uses namespace sp's helpers and image offsets).
+// Included by iqn_act.hip inside its anonymous namespace, after iqn_act_common.h and iqn_act_split.h (uses namespace sp's helpers and image offsets).
 //
 // With one set of 32 taus per launch (mn_iqn_set_tau_mode), layer 1 is a constant h1[tau][j] of the launch and layer 2 of environment e
 // at quantile tau is

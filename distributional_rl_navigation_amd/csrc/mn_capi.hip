@@ -391,8 +391,7 @@ extern "C" int mn_rollout_iqn(mn_handle *h, mn_iqn_ctx *ctx, const float *const 
                               int32_t adaptive, float *obs_dev, float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev,
                               uint8_t *info_trace_dev, int32_t *action_trace_dev, float *cvar_trace_dev, float *q_trace_dev, int32_t *steps_run_dev,
                               void *stream) {
-    if (!h || !ctx || !weights || !rng_state_dev || !obs_dev || n_steps < 1) return MN_ERR_INVALID;
-    for (int i = 0; i < 14; ++i) if (!weights[i]) return MN_ERR_INVALID;
+    if (!h || !ctx || !weights || !rng_state_dev || !obs_dev || n_steps < 1) return MN_ERR_INVALID;      // (the 14 pointers of `weights`: mn_iqn_rollout_image)
     if ((long)h->A.n * 32 >= (1L << 32)) return MN_ERR_INVALID;      // 32-bit draw index, as mn_iqn_act_rng
     MN_ON_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;

@@ -8,7 +8,7 @@
 // (mn_iqn_act_rng, mn_step) on the same state, the act call counter included: it ends at counter0 + steps_run, steps_run = the longest
 // episode of the launch (the loop acts once per step while any env is alive).
 //
-// One wavefront per workgroup (the step's sonar work-list is workgroup LDS), and the acting weight image (151 KB) fills the CU's LDS, so
+// One wavefront per workgroup (the step's sonar work-list is workgroup LDS), and the acting weight image (sp::ACT_IMG_FLOATS) fills the CU's LDS, so
 // a workgroup has its CU to itself.  All eight 8-lane groups of the wave load the same environment so that every value the step
 // computes is valid; group 0 alone is `active` (writes rows, traces, the pose).
 //
@@ -62,9 +62,8 @@ struct IqnTrace {
     float *q;          // [T][n][9]  Q(s, .) the action was chosen from (not written once finished)
 };
 
-constexpr int ROW_OFF = sp::OFF_W4H + F;                              // observation row, behind the feature buffer
+constexpr int ROW_OFF = sp::ACT_IMG_FLOATS + F;                       // observation row, behind the acting image and the wave's feature buffer
 constexpr int LDS_ROLL_FLOATS = ROW_OFF + 32;
-static_assert(sp::OFF_W4H == 37840, "acting weight image of the split-f16 kernel");
 static_assert(ROW_OFF % 4 == 0, "16-byte aligned row");
 
 template <typename M, bool PARITY, int L>
