@@ -100,6 +100,8 @@ SIGNATURES = [
     ("mn_rollout_policy", C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mn_planner_act", C.c_int, [_vp, _i32, _i32, _pd, _pd, _vp, _vp]),
     ("mn_rollout_iqn", C.c_int, [_vp, _vp, C.POINTER(C.c_void_p), _i32, _vp, C.c_float, _i32] + [_vp] * 10),
+    ("mn_rollout_iqn_rows", C.c_int, [_vp, _vp, C.POINTER(C.c_void_p), _i32, _vp, C.c_float, _i32] + [_vp] * 12),
+    ("mn_rollout_dqn", C.c_int, [_vp, C.POINTER(C.c_void_p), _vp, _i32, _i32] + [_vp] * 8),
     ("mn_dqn_image_floats", C.c_int64, []),
     ("mn_dqn_act", C.c_int, [_vp, C.POINTER(C.c_void_p), _vp, _i32, _vp, _vp, _i32, _vp]),
     ("mn_dqn_train_workspace_floats", C.c_int64, [_i32]),

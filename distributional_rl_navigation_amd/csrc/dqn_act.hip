@@ -17,25 +17,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "marinenav_hip.h"
+#include "mn_internal.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int OBS = MN_OBS_DIM;      // 26
-constexpr int F = 208, H = 64, A = 9;
-// stages: the encoders (one block-diagonal matrix) + hidden_layer + hidden_layer_2 + output_layer + q_net.0 + q_net.2 + q_net.4, each as
-// (M tiles of 16 outputs, K tiles of 16 inputs).  LDS image (floats): per stage [mt][kt][64 lanes][4 r] weights, then the biases padded
-// to multiples of 16
-constexpr int N_LAYERS = 7;
-constexpr int LM[N_LAYERS] = {13, 4, 4, 1, 4, 4, 1}, LK[N_LAYERS] = {2, 13, 4, 4, 1, 4, 4};
-constexpr int lw_off(int l) { int o = 0; for (int i = 0; i < l; ++i) o += LM[i] * LK[i] * 256; return o; }
-constexpr int OFF_BIAS = lw_off(N_LAYERS);
-constexpr int lb_off(int l) { int o = OFF_BIAS; for (int i = 0; i < l; ++i) o += LM[i] * 16; return o; }
-constexpr int IMAGE_FLOATS = lb_off(N_LAYERS);
-static_assert(IMAGE_FLOATS * 4 <= 160 * 1024, "the DQN weight image must fit the CU's LDS");
-static_assert(IMAGE_FLOATS % 4 == 0, "16-byte copy");
+#include "dqn_net.h"
 
 struct DqnWeights {      // device pointers, nn.Linear layout [out][in]; sb3 names in the comment
     const float *ve_w, *ve_b, *ge_w, *ge_b, *se_w, *se_b;      // q_net.features_extractor.{velocity,goal,sensor}_encoder
@@ -86,25 +72,6 @@ __global__ __launch_bounds__(256) void dqn_pack_kernel(DqnWeights w, float *__re
     image[i] = layer_weight(w, l, 16 * mt + (lane & 15), 16 * t + 4 * (lane >> 4) + r);
 }
 
-// out[mt] = act(W_l in + b_l) for one 16-env tile: in[t][r] = input feature 16 t + 4 g + r of env col
-template <int L, bool RELU, int MT, int KT>
-__device__ __forceinline__ void dense(const float *__restrict__ lds, int lane, const f32x4 (&in)[KT], f32x4 (&out)[MT]) {
-    const f32x4 *w4 = reinterpret_cast<const f32x4 *>(lds + lw_off(L)) + lane;
-    const f32x4 *b4 = reinterpret_cast<const f32x4 *>(lds + lb_off(L)) + (lane >> 4);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        f32x4 acc = b4[4 * mt];      // bias[16 mt + 4 g + r]: the accumulator's initial value
-#pragma unroll
-        for (int t = 0; t < KT; ++t) {
-            const f32x4 a = w4[(mt * KT + t) * 64];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], in[t][r], acc, 0, 0, 0);
-        }
-        if (RELU) { acc.x = fmaxf(acc.x, 0.f); acc.y = fmaxf(acc.y, 0.f); acc.z = fmaxf(acc.z, 0.f); acc.w = fmaxf(acc.w, 0.f); }
-        out[mt] = acc;
-    }
-}
-
 __global__ __launch_bounds__(512) void dqn_qvals_kernel(const float *__restrict__ obs, const float *__restrict__ image, float *__restrict__ qvals,
                                                         int32_t *__restrict__ actions, int n) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -129,33 +96,13 @@ __global__ __launch_bounds__(512) void dqn_qvals_kernel(const float *__restrict_
                 const int k = 16 * t + 4 * g + r;
                 x0[t][r] = (live && k < OBS) ? row[k < OBS ? k : 0] : 0.f;
             }
-        f32x4 f[13], h1[4], h2[4], o[1], q1[4], q2[4], q[1];
-        dense<0, false, 13, 2>(lds, lane, x0, f);        // the three encoders, no activation (torch_layers.py:125-128)
-        dense<1, true, 4, 13>(lds, lane, f, h1);         // hidden_layer + ReLU
-        dense<2, true, 4, 4>(lds, lane, h1, h2);         // hidden_layer_2 + ReLU
-        dense<3, false, 1, 4>(lds, lane, h2, o);         // output_layer: the extractor's 9 "features" (rows 9..15 are zero)
-        dense<4, true, 4, 1>(lds, lane, o, q1);          // q_net.0 + ReLU
-        dense<5, true, 4, 4>(lds, lane, q1, q2);         // q_net.2 + ReLU
-        dense<6, false, 1, 4>(lds, lane, q2, q);         // q_net.4: Q(s, a), lane (g, col) holds actions 4 g + r of env col
+        const f32x4 q = dqn_forward(lds, lane, x0);
         if (qvals && live)
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (4 * g + r < A) qvals[(size_t)e * A + 4 * g + r] = q[0][r];
-        if (actions) {      // first maximum over the 9 actions: in-lane over r, then across the four lane groups
-            float best = -INFINITY;
-            int arg = 0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int a_idx = 4 * g + r;
-                const float v = a_idx < A ? q[0][r] : -INFINITY;
-                if (v > best) { best = v; arg = a_idx; }
-            }
-#pragma unroll
-            for (int off = 16; off < 64; off <<= 1) {
-                const float ob = __shfl_xor(best, off);
-                const int oa = __shfl_xor(arg, off);
-                if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-            }
+                if (4 * g + r < A) qvals[(size_t)e * A + 4 * g + r] = q[r];
+        if (actions) {
+            const int arg = dqn_argmax(q, g);
             if (live && g == 0) actions[e] = arg;
         }
     }
@@ -164,6 +111,13 @@ __global__ __launch_bounds__(512) void dqn_qvals_kernel(const float *__restrict_
 }  // namespace
 
 extern "C" int64_t mn_dqn_image_floats(void) { return IMAGE_FLOATS; }
+
+// the weight image of `weights[18]` (all non-NULL), for mn_dqn_act and mn_rollout_dqn
+void mn_launch_dqn_pack(const float *const *weights, float *image_dev, hipStream_t s) {
+    const DqnWeights w = {weights[0], weights[1], weights[2], weights[3], weights[4], weights[5], weights[6], weights[7], weights[8],
+                          weights[9], weights[10], weights[11], weights[12], weights[13], weights[14], weights[15], weights[16], weights[17]};
+    hipLaunchKernelGGL(dqn_pack_kernel, dim3((IMAGE_FLOATS + 255) / 256), dim3(256), 0, s, w, image_dev);
+}
 
 extern "C" int mn_dqn_act(const float *obs_dev, const float *const *weights, float *image_dev, int32_t repack, float *qvals_dev,
                           int32_t *actions_dev, int32_t n, void *stream) {
@@ -178,10 +132,8 @@ extern "C" int mn_dqn_act(const float *obs_dev, const float *const *weights, flo
                                 IMAGE_FLOATS * (int)sizeof(float)) != hipSuccess) return MN_ERR_HIP;
         attr_set[dev] = true;
     }
-    const DqnWeights w = {weights[0], weights[1], weights[2], weights[3], weights[4], weights[5], weights[6], weights[7], weights[8],
-                          weights[9], weights[10], weights[11], weights[12], weights[13], weights[14], weights[15], weights[16], weights[17]};
     hipStream_t s = (hipStream_t)stream;
-    if (repack) hipLaunchKernelGGL(dqn_pack_kernel, dim3((IMAGE_FLOATS + 255) / 256), dim3(256), 0, s, w, image_dev);
+    if (repack) mn_launch_dqn_pack(weights, image_dev, s);
     const int n_tiles = (n + 15) / 16;
     int blocks = (n_tiles + 7) / 8;
     if (blocks > prop.multiProcessorCount) blocks = prop.multiProcessorCount;

@@ -387,10 +387,10 @@ extern "C" int mn_rollout_policy(mn_handle *h, int32_t n_steps, int32_t policy, 
     return MN_OK;
 }
 
-extern "C" int mn_rollout_iqn(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weights, int32_t n_steps, uint64_t *rng_state_dev, float cvar,
-                              int32_t adaptive, float *obs_dev, float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev,
-                              uint8_t *info_trace_dev, int32_t *action_trace_dev, float *cvar_trace_dev, float *q_trace_dev, int32_t *steps_run_dev,
-                              void *stream) {
+extern "C" int mn_rollout_iqn_rows(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weights, int32_t n_steps, uint64_t *rng_state_dev, float cvar,
+                                   int32_t adaptive, const float *cvar_row_dev, const uint8_t *adaptive_row_dev, float *obs_dev, float *obs_trace_dev,
+                                   float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev, float *cvar_trace_dev,
+                                   float *q_trace_dev, int32_t *steps_run_dev, void *stream) {
     if (!h || !ctx || !weights || !rng_state_dev || !obs_dev || n_steps < 1) return MN_ERR_INVALID;      // (the 14 pointers of `weights`: mn_iqn_rollout_image)
     if ((long)h->A.n * 32 >= (1L << 32)) return MN_ERR_INVALID;      // 32-bit draw index, as mn_iqn_act_rng
     MN_ON_DEVICE(h);
@@ -401,8 +401,36 @@ extern "C" int mn_rollout_iqn(mn_handle *h, mn_iqn_ctx *ctx, const float *const 
     if (rc) return rc;
     const bool prof = h->prof_n < h->prof_max;
     if (prof) (void)hipEventRecord(h->ev[2 * h->prof_n], s);
-    mn_launch_rollout_iqn(h->A, h->P, h->params.precision, n_steps, image, rng_state_dev, cvar, adaptive ? 1 : 0, obs_dev, obs_trace_dev, reward_trace_dev,
-                          done_trace_dev, info_trace_dev, action_trace_dev, cvar_trace_dev, q_trace_dev, words, steps_run_dev, s);
+    mn_launch_rollout_iqn_rows(h->A, h->P, h->params.precision, n_steps, image, rng_state_dev, cvar, adaptive ? 1 : 0, cvar_row_dev, adaptive_row_dev, obs_dev,
+                               obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev, action_trace_dev, cvar_trace_dev, q_trace_dev, words,
+                               steps_run_dev, s);
+    if (prof) { (void)hipEventRecord(h->ev[2 * h->prof_n + 1], s); h->prof_n++; }
+    MN_HIP(h, hipGetLastError());
+    h->step_parity = 0;
+    h->last_parity = 0;
+    return MN_OK;
+}
+
+extern "C" int mn_rollout_iqn(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weights, int32_t n_steps, uint64_t *rng_state_dev, float cvar,
+                              int32_t adaptive, float *obs_dev, float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev,
+                              uint8_t *info_trace_dev, int32_t *action_trace_dev, float *cvar_trace_dev, float *q_trace_dev, int32_t *steps_run_dev,
+                              void *stream) {
+    return mn_rollout_iqn_rows(h, ctx, weights, n_steps, rng_state_dev, cvar, adaptive, nullptr, nullptr, obs_dev, obs_trace_dev, reward_trace_dev,
+                               done_trace_dev, info_trace_dev, action_trace_dev, cvar_trace_dev, q_trace_dev, steps_run_dev, stream);
+}
+
+extern "C" int mn_rollout_dqn(mn_handle *h, const float *const *weights, float *image_dev, int32_t repack, int32_t n_steps, float *obs_dev,
+                              float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev,
+                              float *q_trace_dev, void *stream) {
+    if (!h || !weights || !image_dev || !obs_dev || n_steps < 1) return MN_ERR_INVALID;
+    for (int i = 0; i < 18; ++i) if (!weights[i]) return MN_ERR_INVALID;
+    MN_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (repack) mn_launch_dqn_pack(weights, image_dev, s);
+    const bool prof = h->prof_n < h->prof_max;
+    if (prof) (void)hipEventRecord(h->ev[2 * h->prof_n], s);
+    mn_launch_rollout_dqn(h->A, h->P, h->params.precision, n_steps, image_dev, obs_dev, obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev,
+                          action_trace_dev, q_trace_dev, s);
     if (prof) { (void)hipEventRecord(h->ev[2 * h->prof_n + 1], s); h->prof_n++; }
     MN_HIP(h, hipGetLastError());
     h->step_parity = 0;

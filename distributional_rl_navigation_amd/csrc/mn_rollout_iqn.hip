@@ -7,6 +7,8 @@
 // the taus, argmax with the first maximum winning -- then the same MnLane::step as mn_rollout_policy_kernel.  Bit-identical to a loop of
 // (mn_iqn_act_rng, mn_step) on the same state, the act call counter included: it ends at counter0 + steps_run, steps_run = the longest
 // episode of the launch (the loop acts once per step while any env is alive).
+// The cvar and the adaptive flag are the launch's scalars or, for the experiment sweep's five IQN policies side by side in one handle, per env
+// (mn_rollout_iqn_rows): the taus are keyed by the env index, so that launch draws what the sweep's one act call on all rows draws.
 //
 // One wavefront per workgroup (the step's sonar work-list is workgroup LDS), and the acting weight image (sp::ACT_IMG_FLOATS) fills the CU's LDS, so
 // a workgroup has its CU to itself.  All eight 8-lane groups of the wave load the same environment so that every value the step
@@ -68,8 +70,9 @@ static_assert(ROW_OFF % 4 == 0, "16-byte aligned row");
 
 template <typename M, bool PARITY, int L>
 __global__ __launch_bounds__(MN_WAVE, 1) void mn_rollout_iqn_kernel(MnArrays A, MnDev P, int n_steps, const uint32_t *__restrict__ packed,
-                                                                    uint64_t *rng_state, float cvar, int adaptive, float *__restrict__ obs_io,
-                                                                    IqnTrace T, uint32_t *__restrict__ words, int32_t *__restrict__ steps_out) {
+                                                                    uint64_t *rng_state, float cvar, int adaptive, const float *__restrict__ cvar_row,
+                                                                    const uint8_t *__restrict__ adaptive_row, float *__restrict__ obs_io, IqnTrace T,
+                                                                    uint32_t *__restrict__ words, int32_t *__restrict__ steps_out) {
     using namespace sp;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     using Lane = MnLane<M, PARITY, L>;
@@ -78,6 +81,9 @@ __global__ __launch_bounds__(MN_WAVE, 1) void mn_rollout_iqn_kernel(MnArrays A, 
     const size_t n = (size_t)A.n;
     if (e == 0 && lane < 2 * MN_QSHARDS) A.queue_count[lane * MN_QSTRIDE] = 0u;   // nothing is left for a later mn_reset_done
     const uint64_t seed = rng_state[0], ctr0 = rng_state[1];
+    // per-env cvar / adaptive flag (one env per wavefront: wave-uniform loads, outside the step loop); NULL = the launch's scalar
+    if (cvar_row) cvar = cvar_row[e];
+    if (adaptive_row) adaptive = adaptive_row[e];
 
     {   // the acting weight image (iqn_qvals_split_kernel's IMG for QUANT = false)
         const u32x4 *src = reinterpret_cast<const u32x4 *>(packed);
@@ -201,19 +207,20 @@ __global__ __launch_bounds__(MN_WAVE, 1) void mn_rollout_iqn_kernel(MnArrays A, 
 
 }  // namespace
 
-void mn_launch_rollout_iqn(const MnArrays &A, const MnDev &P, int precision, int n_steps, const uint32_t *image, uint64_t *rng_state, float cvar,
-                           int adaptive, float *obs_io, float *obs_trace, float *reward_trace, uint8_t *done_trace, uint8_t *info_trace,
-                           int32_t *action_trace, float *cvar_trace, float *q_trace, uint32_t *words, int32_t *steps_run, hipStream_t s) {
+void mn_launch_rollout_iqn_rows(const MnArrays &A, const MnDev &P, int precision, int n_steps, const uint32_t *image, uint64_t *rng_state, float cvar,
+                                int adaptive, const float *cvar_row, const uint8_t *adaptive_row, float *obs_io, float *obs_trace, float *reward_trace,
+                                uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *cvar_trace, float *q_trace, uint32_t *words,
+                                int32_t *steps_run, hipStream_t s) {
     const IqnTrace T = {obs_trace, reward_trace, done_trace, info_trace, action_trace, cvar_trace, q_trace};
     constexpr int LL = 8;      // the lane groups of mn_rollout_policy_kernel
     const size_t lds_bytes = LDS_ROLL_FLOATS * sizeof(float);
     if (precision == MN_PRECISION_F64) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mn_rollout_iqn_kernel<double, true, LL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         hipLaunchKernelGGL((mn_rollout_iqn_kernel<double, true, LL>), dim3((unsigned)A.n), dim3(MN_WAVE), lds_bytes, s, A, P, n_steps, image, rng_state, cvar,
-                           adaptive, obs_io, T, words, steps_run);
+                           adaptive, cvar_row, adaptive_row, obs_io, T, words, steps_run);
     } else {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mn_rollout_iqn_kernel<float, false, LL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         hipLaunchKernelGGL((mn_rollout_iqn_kernel<float, false, LL>), dim3((unsigned)A.n), dim3(MN_WAVE), lds_bytes, s, A, P, n_steps, image, rng_state, cvar,
-                           adaptive, obs_io, T, words, steps_run);
+                           adaptive, cvar_row, adaptive_row, obs_io, T, words, steps_run);
     }
 }

@@ -77,9 +77,9 @@ class DQNPolicy(nn.Module):
 
     use_fused_act = True      # GPU tensors: the whole network + argmax as ONE HIP launch (csrc/dqn_act.hip); False = eager PyTorch
 
-    def _fused(self, obs, want_q, want_a):
-        """C-ABI mn_dqn_act on a contiguous float32 device batch; the permuted weight image is rebuilt when a parameter was written
-        (PyTorch version counters) or re-allocated."""
+    def _image(self, device):
+        """The permuted weight image of the HIP kernels on `device` and whether it must be rebuilt in front of the next launch: when a parameter
+        was written (PyTorch version counters), re-allocated, or `weights_changed()` was called.  Returns (state dict, repack)."""
         import ctypes as C
         from .. import _capi
         L = _capi.lib()
@@ -88,8 +88,8 @@ class DQNPolicy(nn.Module):
         ps = [t for m in mods for t in (m.weight, m.bias)]
         sig = tuple((t.data_ptr(), t._version) for t in ps)
         st = getattr(self, "_fused_state", None)
-        if st is None or st["image"].device != obs.device:
-            st = dict(image=torch.empty(L.mn_dqn_image_floats(), dtype=torch.float32, device=obs.device), sig=None, ptrs=(C.c_void_p * 18)())
+        if st is None or st["image"].device != device:
+            st = dict(image=torch.empty(L.mn_dqn_image_floats(), dtype=torch.float32, device=device), sig=None, ptrs=(C.c_void_p * 18)())
             object.__setattr__(self, "_fused_state", st)
         repack = sig != st["sig"]
         if repack:
@@ -97,6 +97,15 @@ class DQNPolicy(nn.Module):
                 assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32
                 st["ptrs"][i] = t.data_ptr()
             st["sig"] = sig
+        return st, repack
+
+    def _fused(self, obs, want_q, want_a):
+        """C-ABI mn_dqn_act on a contiguous float32 device batch; the permuted weight image is rebuilt when a parameter was written
+        (PyTorch version counters) or re-allocated."""
+        import ctypes as C
+        from .. import _capi
+        L = _capi.lib()
+        st, repack = self._image(obs.device)
         n = obs.shape[0]
         q = torch.empty(n, self.action_size, dtype=torch.float32, device=obs.device) if want_q else None
         a = torch.empty(n, dtype=torch.int32, device=obs.device) if want_a else None
@@ -116,6 +125,35 @@ class DQNPolicy(nn.Module):
     def _fusable(self, obs):
         return (self.use_fused_act and obs.is_cuda and not torch.is_grad_enabled() and len(self.q_net.q_net) == 5
                 and self.q_net.q_net[0].out_features == 64 and self.q_net.q_net[2].out_features == 64 and obs.shape[0] > 0)
+
+    @torch.no_grad()
+    def rollout(self, env, n_steps, trace=("reward", "done", "info", "action")):
+        """Every env's CURRENT episode of `env` (a VecMarineNavEnv) under this greedy policy for up to `n_steps` steps in ONE launch (C-ABI
+        mn_rollout_dqn): per step what `act_batch(env.obs)` chooses, then the env step -- bit-identical to that loop.  No resets: a finished env idles
+        (reward 0, done 1, terminal info, action -1 in the traces; its obs / Q entries stay 0 / NaN); an env still alive afterwards continues with the
+        next call.  Returns the requested traces ([n_steps][n]; "obs" [n_steps][n][26], "q" [n_steps][n][9]) and `final_obs`, or None where the fused
+        act kernel would not run either (CPU, another net_arch, use_fused_act = False): the caller runs the loop instead."""
+        import ctypes as C
+        from .. import _capi
+        if not (hasattr(env, "h") and self._fusable(env.obs)):
+            return None
+        T, n, dev = int(n_steps), env.n_envs, env.device
+        st, repack = self._image(dev)
+        mk = dict(obs=lambda: torch.zeros(T, n, self.state_size, dtype=torch.float32, device=dev),
+                  reward=lambda: torch.empty(T, n, dtype=torch.float32, device=dev),
+                  done=lambda: torch.empty(T, n, dtype=torch.uint8, device=dev),
+                  info=lambda: torch.empty(T, n, dtype=torch.uint8, device=dev),
+                  action=lambda: torch.empty(T, n, dtype=torch.int32, device=dev),
+                  q=lambda: torch.full((T, n, self.action_size), float("nan"), dtype=torch.float32, device=dev))
+        tr = {k: mk[k]() for k in trace}
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        rc = _capi.lib().mn_rollout_dqn(env.h, st["ptrs"], p(st["image"]), int(repack), T, p(env.obs), p(tr.get("obs")), p(tr.get("reward")),
+                                        p(tr.get("done")), p(tr.get("info")), p(tr.get("action")), p(tr.get("q")), env._stream())
+        if rc:
+            raise _capi.MarineNavHipError(f"mn_rollout_dqn failed ({rc})")
+        out = dict(tr)
+        out["final_obs"] = env.obs
+        return out
 
     @torch.no_grad()
     def q_values(self, obs):

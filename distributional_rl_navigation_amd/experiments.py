@@ -68,49 +68,89 @@ def _episode_record(world, params, name, actions, traj, cvars=None, quantiles=No
 
 
 @torch.no_grad()
-def _classical_episodes(worlds, name, device, max_steps, seed):
-    """All of `worlds` under the classical baseline `name` ("APF" / "BA"), one episode each, as ONE launch: the policy runs inside the
-    rollout kernel (VecMarineNavEnv.rollout_policy -> mn_rollout_policy).  Same result record as the launch-per-step path."""
-    num = len(worlds)
-    env = VecMarineNavEnv(num, device=device, precision="f64")
-    _configure(env)
-    env.load_worlds(worlds)
+def _records_from_traces(tr, env, names, num, elapsed_ms):
+    """Result records of the policies `names` (policy p owns rows [p * num, (p + 1) * num) of `env`) from the traces of ONE episode-rollout launch
+    that took `elapsed_ms`: the bookkeeping of run_experiment's per-step loop on the traces (same operations, same order, for the steps that loop
+    would have run).  `computation_times`: the launch's device time divided by the actions it chose, one entry per step of every episode."""
     dev = env.device
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    tr = env.rollout_policy(max_steps, name)
-    e1.record()
+    n = env.n_envs
     reward, done, info, acts = tr["reward"], tr["done"].bool(), tr["info"], tr["action"]
-    T = reward.shape[0]
     a_tab = torch.tensor(env.params.a[:], device=dev); w_tab = torch.tensor(env.params.w[:], device=dev)
     energy_tab = ((a_tab / a_tab.max()).abs().view(3, 1) + (w_tab / w_tab.max()).abs().view(1, 3)).reshape(-1)
-    alive = torch.ones(num, dtype=torch.bool, device=dev)
-    ret = torch.zeros(num, dtype=torch.float64, device=dev); energy = torch.zeros_like(ret)
-    length = torch.zeros(num, dtype=torch.int64, device=dev)
-    last_info = torch.zeros(num, dtype=torch.uint8, device=dev)
-    for t in range(T):      # the bookkeeping of the per-step loop below, on the traces (same operations, same order)
+    alive = torch.ones(n, dtype=torch.bool, device=dev)
+    ret = torch.zeros(n, dtype=torch.float64, device=dev); energy = torch.zeros_like(ret)
+    length = torch.zeros(n, dtype=torch.int64, device=dev)
+    last_info = torch.zeros(n, dtype=torch.uint8, device=dev)
+    # the loop stops after the step that ends the last episode
+    steps = int(torch.where(done.any(dim=0), done.int().argmax(dim=0) + 1, torch.full((n,), done.shape[0], device=dev)).max())
+    for t in range(steps):
         ret += torch.where(alive, (env.discount ** t) * reward[t].double(), torch.zeros_like(ret))
         length += alive.long()
         energy += torch.where(alive, energy_tab[acts[t].clamp_min(0).long()].double(), torch.zeros_like(energy))
         last_info = torch.where(alive, info[t], last_info)
         alive = alive & ~done[t]
-        if not bool(alive.any()):
-            break
     torch.cuda.synchronize(dev)
     length_h, info_h, acts_h = length.cpu().numpy(), last_info.cpu().numpy(), acts.cpu().numpy()
+    ret_h, energy_h = ret.cpu().numpy(), energy.cpu().numpy()
     dtN = env.params.dt * env.params.N
-    per_action = e0.elapsed_time(e1) * 1e-3 / max(1, int(length_h.sum()))
-    rec = dict(success=[bool(v) for v in info_h == 4], out_of_area=[bool(v) for v in info_h == 1],
-               time=[float(dtN * l) for l in length_h], energy=[float(v) for v in energy.cpu().numpy()],
-               reward=[float(v) for v in ret.cpu().numpy()],
-               actions=[[int(x) for x in acts_h[:length_h[i], i]] for i in range(num)],
-               computation_times=[per_action] * int(length_h.sum()))
+    per_action = elapsed_ms * 1e-3 / max(1, int(length_h.sum()))
+    out = {}
+    for p, name in enumerate(names):
+        sl = slice(p * num, (p + 1) * num)
+        out[name] = dict(success=[bool(v) for v in info_h[sl] == 4], out_of_area=[bool(v) for v in info_h[sl] == 1],
+                         time=[float(dtN * l) for l in length_h[sl]], energy=[float(v) for v in energy_h[sl]],
+                         reward=[float(v) for v in ret_h[sl]],
+                         actions=[[int(x) for x in acts_h[:length_h[i], i]] for i in range(p * num, (p + 1) * num)],
+                         computation_times=[per_action] * int(length_h[sl].sum()))
+    return out
+
+
+def _rollout_episodes(worlds, names, device, launch):
+    """One env holding `worlds` once per policy of `names`, all of its episodes as ONE launch: `launch(env)` returns the traces (reward, done, info,
+    action) or None where the library has no one-launch form of the policy.  Returns {name: record} or None."""
+    env = VecMarineNavEnv(len(worlds) * len(names), device=device, precision="f64")
+    _configure(env)
+    env.load_worlds(worlds * len(names))
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    tr = launch(env)
+    e1.record()
+    rec = None
+    if tr is not None:
+        torch.cuda.synchronize(env.device)
+        rec = _records_from_traces(tr, env, names, len(worlds), e0.elapsed_time(e1))
     env.close()
     return rec
 
 
+def _classical_episodes(worlds, name, device, max_steps, seed):
+    """All of `worlds` under the classical baseline `name` ("APF" / "BA"), one episode each, as ONE launch: the policy runs inside the
+    rollout kernel (VecMarineNavEnv.rollout_policy -> mn_rollout_policy).  Same result record as the launch-per-step path."""
+    return _rollout_episodes(worlds, (name,), device, lambda env: env.rollout_policy(max_steps, name))[name]
+
+
+@torch.no_grad()
+def _iqn_episodes(worlds, names, agent, device, max_steps):
+    """The IQN policies `names` on `worlds` as ONE mn_rollout_iqn_rows launch: policy p owns rows [p * num, (p + 1) * num), the rows of the per-step
+    loop's IQN act call, so every row draws the taus it draws there.  None where that loop's acting form has no one-launch twin (PyTorch acting,
+    torch.rand taus, the exact-f32 variant)."""
+    if not (agent.device.type == "cuda" and agent.use_fused_act and agent.use_library_rng):
+        return None
+    from .iqn.fused_act import ActRng, rollout_iqn
+    if agent._act_rng is None:
+        agent._act_rng = ActRng(agent.gen.initial_seed(), agent.device)
+    num = len(worlds)
+    cvar_rows = torch.tensor([_CVAR.get(name, 1.0) for name in names], dtype=torch.float32).repeat_interleave(num)
+    adaptive_rows = torch.tensor([name == "adaptive_IQN" for name in names]).repeat_interleave(num)
+    agent.qnetwork_local.eval()
+    rec = _rollout_episodes(worlds, names, device, lambda env: rollout_iqn(agent.qnetwork_local, env, max_steps, agent._act_rng, cvar_rows=cvar_rows,
+                                                                           adaptive_rows=adaptive_rows, trace=("reward", "done", "info", "action")))
+    agent.qnetwork_local.train()
+    return rec
+
+
 def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, device="cuda:0", max_steps=1000, dqn=None,
-                   capture=False, classical_rollout=True):
+                   capture=False, classical_rollout=True, one_launch=False):
     """run_experiments.py:213-282 for the IQN policies, the classical APF / BA baselines and (when `dqn`, a
     `dqn.DQNPolicy`, is given and "DQN" is in `policies`) the greedy DQN baseline.  Returns {policy: dict(success, time, energy,
     out_of_area, reward, actions)} with one entry per world.  With `capture` each policy also gets the reference's `ep_data`
@@ -119,7 +159,14 @@ def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, d
     `exp_data` JSON the reference dumps.  `computation_times` (run_experiments.py:30,37-44,254-255: the wall-clock seconds of every
     act call, flattened over a policy's episodes) is the batched equivalent: the device time of the step's act launch(es) for that
     policy group (HIP events) divided by the rows the launch served, one entry per step of every episode -- the amortised cost of one
-    action, which is what `avg_compute_t` (run_experiments.py:274) averages."""
+    action, which is what `avg_compute_t` (run_experiments.py:274) averages.
+    `one_launch` (opt-in, ignored with `capture`): the learned policies run whole episodes inside one kernel too -- the requested IQN policies as ONE
+    mn_rollout_iqn_rows launch on one env of len(IQN policies) x num rows in the order of `policies` (per-row cvar and adaptive flag; the rows are the
+    per-step loop's, so the taus are the same), DQN as one mn_rollout_dqn launch on its own env: with APF / BA the whole sweep is four launches.
+    Results are bit-identical to the loop's; `computation_times` are built as for APF / BA (the launch's device time divided by the actions it
+    chose).  Where the library has no one-launch form of a policy (an agent on the exact-f32 act variant or on torch.rand taus, a DQN policy with
+    use_fused_act = False) that policy runs in the loop.  One difference: the agent's act-call counter ends at + the longest IQN episode, where the
+    loop ends at + the longest episode of any policy in the loop."""
     worlds = generate_worlds(num, n_obs, n_cores, seed, device)
     # APF / BA: the policy is a device function inside the episode rollout kernel -- one launch per policy for all worlds -- unless the
     # per-sub-step trajectory is wanted (`capture`), which the launch-per-step path below records
@@ -127,9 +174,18 @@ def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, d
     rolled = {}
     if classical_rollout and not capture:
         rolled = {name: _classical_episodes(worlds, name, device, max_steps, seed) for name in requested if name in ("APF", "BA")}
-        policies = tuple(p for p in requested if p not in rolled)
-        if not policies:
-            return {name: rolled[name] for name in requested}, worlds
+    if one_launch and not capture:
+        iqn_names = tuple(p for p in requested if p == "adaptive_IQN" or p in _CVAR)
+        if iqn_names:
+            rolled.update(_iqn_episodes(worlds, iqn_names, agent, device, max_steps) or {})
+        if "DQN" in requested:
+            if dqn is None:
+                raise ValueError("policy 'DQN' needs run_experiment(..., dqn=DQNPolicy.load(...))")
+            rolled.update(_rollout_episodes(worlds, ("DQN",), device,
+                                            lambda env: dqn.rollout(env, max_steps, trace=("reward", "done", "info", "action"))) or {})
+    policies = tuple(p for p in requested if p not in rolled)
+    if not policies:
+        return {name: rolled[name] for name in requested}, worlds
     n = num * len(policies)
     env = VecMarineNavEnv(n, device=device, precision="f64")
     _configure(env)

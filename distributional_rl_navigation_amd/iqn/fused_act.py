@@ -296,16 +296,24 @@ def fused_act(net, states, eps=0.0, cvar=1.0, taus=None, generator=None, want_qv
 
 @torch.no_grad()
 def rollout_iqn(net, env, n_steps, rng, cvar=1.0, adaptive=False, shared_taus=False,
-                trace=("reward", "done", "info", "action", "cvar", "q")):
+                trace=("reward", "done", "info", "action", "cvar", "q"), cvar_rows=None, adaptive_rows=None):
     """Every env's CURRENT episode of `env` (a VecMarineNavEnv) under the IQN policy of `net` for up to `n_steps` steps in ONE launch (C-ABI
     mn_rollout_iqn): per step what `fused_act(net, env.obs, 0.0, cvar, rng=rng, shared_taus=shared_taus)` would choose -- `cvar` a float, or with
     `adaptive` IQNAgent.adjust_cvar_batch of each row -- then the env step.  No resets: a finished env idles (reward 0, done 1, terminal info,
     action -1 in the traces; its cvar / Q / obs entries stay NaN / 0).  `rng` (an ActRng) advances as that loop would advance it.
+    `cvar_rows` ([n] float tensor) / `adaptive_rows` ([n] bool tensor): per-env cvar and adaptive flag (C-ABI mn_rollout_iqn_rows) -- what a loop of
+    `fused_act(net, env.obs, 0.0, torch.where(adaptive_rows, adjust_cvar_batch(env.obs), cvar_rows), rng=rng)` would choose; a per-row cvar tensor
+    keeps fused_act on per-row taus whatever `shared_taus` says, and so does this call.
     Returns the requested traces ([n_steps][n], Q [n_steps][n][9]), `final_obs` and `steps_run` (the longest episode), or None when the
     library refuses the form (the exact-f32 variant, launch-shared taus: the caller runs the loop instead)."""
     T, n, dev = int(n_steps), env.n_envs, env.device
     ctx = act_context(net)
-    ctx.set_tau_mode(1 if (shared_taus and not adaptive and ctx.variant == 2) else 0)      # the form fused_act would pick for the loop
+    per_row = cvar_rows is not None or adaptive_rows is not None
+    ctx.set_tau_mode(1 if (shared_taus and not adaptive and not per_row and ctx.variant == 2) else 0)      # the form fused_act would pick for the loop
+    cv_rows = cvar_rows.to(device=dev, dtype=torch.float32).contiguous() if cvar_rows is not None else None
+    ad_rows = adaptive_rows.to(device=dev, dtype=torch.uint8).contiguous() if adaptive_rows is not None else None
+    assert cv_rows is None or cv_rows.numel() == n
+    assert ad_rows is None or ad_rows.numel() == n
     mk = dict(obs=lambda: torch.zeros(T, n, 26, dtype=torch.float32, device=dev),
               reward=lambda: torch.empty(T, n, dtype=torch.float32, device=dev),
               done=lambda: torch.empty(T, n, dtype=torch.uint8, device=dev),
@@ -316,12 +324,13 @@ def rollout_iqn(net, env, n_steps, rng, cvar=1.0, adaptive=False, shared_taus=Fa
     tr = {k: mk[k]() for k in trace}
     p = lambda k: _p(tr[k]) if k in tr else None
     steps = torch.zeros(1, dtype=torch.int32, device=dev)
-    rc = _capi.lib().mn_rollout_iqn(env.h, ctx.h, ctx.weights(net), T, _p(rng.state), C.c_float(float(cvar)), int(bool(adaptive)), _p(env.obs),
-                                    p("obs"), p("reward"), p("done"), p("info"), p("action"), p("cvar"), p("q"), _p(steps), env._stream())
+    rc = _capi.lib().mn_rollout_iqn_rows(env.h, ctx.h, ctx.weights(net), T, _p(rng.state), C.c_float(float(cvar)), int(bool(adaptive)), _p(cv_rows),
+                                         _p(ad_rows), _p(env.obs), p("obs"), p("reward"), p("done"), p("info"), p("action"), p("cvar"), p("q"),
+                                         _p(steps), env._stream())
     if rc == -1:      # MN_ERR_INVALID: a form the rollout does not reproduce
         return None
     if rc:
-        raise _capi.MarineNavHipError(f"mn_rollout_iqn failed ({rc})")
+        raise _capi.MarineNavHipError(f"mn_rollout_iqn_rows failed ({rc})")
     out = dict(tr)
     out["final_obs"] = env.obs
     out["steps_run"] = int(steps.item())

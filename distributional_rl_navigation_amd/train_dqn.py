@@ -2,7 +2,7 @@
 path, with the interface of train_iqn.
 
     python -m distributional_rl_navigation_amd.train_dqn -C config_DQN.json [--n-envs 4096] [--batch 256] [--replay N]
-        [--grad-steps G] [--total-grad-steps N] [--n-evals K] [--torch-train] [--dry-run]
+        [--grad-steps G] [--total-grad-steps N] [--n-evals K] [--torch-train] [--eval-one-launch] [--dry-run]
 
 Same JSON schema as train_iqn (agent, seed (list -> grid), total_timesteps, eval_freq, save_dir); the trials run one after another
 on one device.  Cadence: `train_iqn.plan_cadence` with the reference DQN's values (one batch-32 gradient step per env step, target
@@ -50,8 +50,24 @@ def exploration_rate(it, plan):
     return EPS_INITIAL + progress * (EPS_FINAL - EPS_INITIAL) / EXPLORATION_FRACTION
 
 
-def evaluate(agent, eval_env, eval_config, max_steps=1000):
-    """The greedy DQN on the evaluation worlds, stepped side by side on the GPU (as IQNAgent.evaluation_vec)."""
+def evaluation_from_rollout(tr, discount, energy_tab, dt, N):
+    """`evaluate`'s result dict from the traces of one DQNPolicy.rollout launch (numpy [T][n] reward / done / info / action): the loop's bookkeeping
+    (iqn.agent.evaluation_from_traces: the same float64 operations in the same step order) on the steps the loop would have run -- it stops after the
+    step that ends the last episode."""
+    from .iqn.agent import evaluation_from_traces
+    done = tr["done"].astype(bool)
+    ended = done.any(axis=0)
+    steps = int(np.where(ended, done.argmax(axis=0) + 1, done.shape[0]).max())
+    actions, rewards, successes, times, energies = evaluation_from_traces(tr["reward"][:steps], tr["done"][:steps], tr["info"][:steps],
+                                                                          tr["action"][:steps], discount, energy_tab, dt, N)
+    return dict(rewards=np.array(rewards, dtype=np.float64), successes=np.array(successes, dtype=bool), times=np.array(times, dtype=np.float64),
+                energies=np.array(energies, dtype=np.float64), actions=actions)
+
+
+def evaluate(agent, eval_env, eval_config, max_steps=1000, one_launch=False):
+    """The greedy DQN on the evaluation worlds, stepped side by side on the GPU (as IQNAgent.evaluation_vec).
+    `one_launch`: every episode in one mn_rollout_dqn launch (DQNPolicy.rollout) instead of a Python iteration per step -- the same dict, bit for
+    bit; where the policy does not act through the fused kernel the loop runs."""
     import torch
     from .marinenav_env.vec_env import VecMarineNavEnv
     cfgs = list(eval_config.values())
@@ -66,6 +82,10 @@ def evaluate(agent, eval_env, eval_config, max_steps=1000):
     length = torch.zeros(n, dtype=torch.int64, device=dev)
     energy = torch.zeros(n, dtype=torch.float64, device=dev)
     last_info = torch.zeros(n, dtype=torch.uint8, device=dev)
+    tr = agent.policy.rollout(eval_env, max_steps, trace=("reward", "done", "info", "action")) if one_launch else None
+    if tr is not None:
+        return evaluation_from_rollout({k: tr[k].cpu().numpy() for k in ("reward", "done", "info", "action")}, eval_env.discount,
+                                       energy_tab.cpu().numpy(), r0["dt"], r0["N"])
     acts = torch.full((max_steps, n), -1, dtype=torch.int32, device=dev)
     for t in range(max_steps):
         a = agent.policy.act_batch(obs)
@@ -94,8 +114,9 @@ def save_zip(agent, path):
 
 
 def run_trial(device, params, n_envs, batch=256, replay=100_000, grad_steps=None, total_grad_steps=None, n_evals=None, torch_train=False,
-              verbose=True):
-    """train_sb3_model.py on the vector env for one trial of the config grid; returns the trial directory."""
+              verbose=True, eval_one_launch=False):
+    """train_sb3_model.py on the vector env for one trial of the config grid; returns the trial directory.
+    `eval_one_launch`: each evaluation as one mn_rollout_dqn launch instead of one Python iteration per env step (same results)."""
     import torch
     from .dqn.agent import DQNAgent
     from .marinenav_env.vec_env import VecMarineNavEnv
@@ -140,7 +161,7 @@ def run_trial(device, params, n_envs, batch=256, replay=100_000, grad_steps=None
         if (it + 1) % plan["eval_every_vector_steps"] == 0 or it + 1 == plan["vector_steps"]:
             if len(log["timesteps"]) >= plan["n_evals"]:
                 continue
-            ev = evaluate(agent, eval_env, eval_config)
+            ev = evaluate(agent, eval_env, eval_config, one_launch=eval_one_launch)
             log["timesteps"].append(int(round((it + 1) * n_envs * report_scale)))
             for k in ("rewards", "times", "energies", "successes", "actions"):
                 log[k].append(ev[k])
@@ -176,6 +197,8 @@ def main(argv=None):
                     help="learner budget (default: the reference's sample count, total_timesteps x 32 / batch)")
     ap.add_argument("--n-evals", type=int, default=None, help="evaluation points over the run (default: min(30, total_timesteps / eval_freq))")
     ap.add_argument("--torch-train", action="store_true", help="eager PyTorch gradient step instead of the fused HIP kernel")
+    ap.add_argument("--eval-one-launch", action="store_true",
+                    help="run each evaluation's episodes in one HIP launch (mn_rollout_dqn) instead of one Python iteration per env step; same results")
     ap.add_argument("--dry-run", action="store_true", help="print the plan of every trial as JSON and exit (no GPU needed)")
     args = ap.parse_args(argv)
     params = json.load(args.config_file)
@@ -187,7 +210,7 @@ def main(argv=None):
         for p in trials:
             plan = make_plan(p, args.n_envs, args.batch, args.grad_steps, args.total_grad_steps, args.n_evals)
             print(json.dumps(dict(seed=p["seed"], n_envs=args.n_envs, batch=args.batch, replay=args.replay, fused=not args.torch_train,
-                                  eps_start=exploration_rate(0, plan), eps_end=exploration_rate(int(np.ceil(plan["exploration_vector_steps"])), plan),
+                                  eval_one_launch=args.eval_one_launch, eps_start=exploration_rate(0, plan), eps_end=exploration_rate(int(np.ceil(plan["exploration_vector_steps"])), plan),
                                   plan=plan)))
         return
     import torch
@@ -196,7 +219,7 @@ def main(argv=None):
     for p in trials:
         t0 = time.time()
         d = run_trial(device, p, args.n_envs, batch=args.batch, replay=args.replay, grad_steps=args.grad_steps,
-                      total_grad_steps=args.total_grad_steps, n_evals=args.n_evals, torch_train=args.torch_train)
+                      total_grad_steps=args.total_grad_steps, n_evals=args.n_evals, torch_train=args.torch_train, eval_one_launch=args.eval_one_launch)
         print(f"[train_dqn] seed {p['seed']}: {time.time() - t0:.1f} s -> {d}", flush=True)
 
 

@@ -387,6 +387,15 @@ int mn_rollout_iqn(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weights, i
                    int32_t adaptive, float *obs_dev, float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev,
                    uint8_t *info_trace_dev, int32_t *action_trace_dev, float *cvar_trace_dev, float *q_trace_dev, int32_t *steps_run_dev,
                    void *stream);
+/* The same launch with PER-ENV cvar and adaptive flag (the experiment sweep: adaptive IQN and IQN at cvar 0.25 / 0.5 / 0.75 / 1.0 side by side in one
+ * handle, taus keyed by the env index like one mn_iqn_act_rng call with cvar_row_dev on all rows): cvar_row_dev [n] f32 and adaptive_row_dev [n] u8
+ * on the device, either may be NULL = the scalar `cvar` / `adaptive` for every env.  Env i acts with adjust_cvar of its row where its flag is set, with
+ * cvar_row_dev[i] otherwise.  Refusals, traces, counter update and `one launch at a time per context` as mn_rollout_iqn, which is this call with two
+ * NULLs.  No allocation after the context's first rollout, no host synchronisation, caller's stream. */
+int mn_rollout_iqn_rows(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weights, int32_t n_steps, uint64_t *rng_state_dev, float cvar,
+                        int32_t adaptive, const float *cvar_row_dev, const uint8_t *adaptive_row_dev, float *obs_dev, float *obs_trace_dev,
+                        float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev, float *cvar_trace_dev,
+                        float *q_trace_dev, int32_t *steps_run_dev, void *stream);
 
 /* ---- replay ring ------------------------------------------------------------------------------
  * ReplayBuffer.add (thirdparty/IQN/replay_buffer.py:26-34) for n transitions in one launch: batch row i
@@ -493,6 +502,17 @@ int mn_iqn_train_set_cu_limit(int32_t n_cu);
 int64_t mn_dqn_image_floats(void);
 int mn_dqn_act(const float *obs_dev, const float *const *weights, float *image_dev, int32_t repack, float *qvals_dev, int32_t *actions_dev,
                int32_t n, void *stream);
+/* DQN EPISODES in ONE launch: mn_rollout_policy with the greedy DQN policy (train_dqn.evaluate, the DQN rows of run_experiments.py:213-282).  Every env
+ * of `h` runs its CURRENT episode -- starting from the observation in obs_dev -- for up to n_steps steps; per step it acts exactly as mn_dqn_act would
+ * for its row (same network code, same weight image, argmax with the first maximum), then steps like mn_step.  An env that finishes is NOT reset: it
+ * idles, its traces read reward 0 / done 1 / its terminal info code / action -1 from then on, obs_dev keeps its terminal observation and its terminal
+ * pose and counters are stored; an env still alive after n_steps stores its state, so a second call continues the episode.  Bit-identical to a loop of
+ * (mn_dqn_act, mn_step).  weights[18], image_dev, repack as mn_dqn_act.  Traces (device, any may be NULL) as mn_rollout_policy ([n_steps][n] ...), plus
+ * q_trace_dev [n_steps][n][9] f32 (Q(s, .) of each step); obs / Q entries of steps after an env finished are not written.  MN_ERR_INVALID for a NULL
+ * h / weights / one of the 18 pointers / image_dev / obs_dev, or n_steps < 1.  No allocation, no host synchronisation, caller's stream. */
+int mn_rollout_dqn(mn_handle *h, const float *const *weights, float *image_dev, int32_t repack, int32_t n_steps, float *obs_dev,
+                   float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev,
+                   float *q_trace_dev, void *stream);
 /* ---- Fused gradient step of the DQN baseline (csrc/dqn_train.hip): ONE launch = one optimizer step of DQNAgent.train (sb3 DQN.train, dqn/dqn.py:188-230):
  * target forward on next_states, max over the 9 actions, y = r + (1 - done) gamma max; local forward on states, gather Q[a], smooth_l1_loss (beta 1,
  * mean); backward through the 9 layers; clip_grad_norm_(max_norm); torch.optim.Adam (step counter t = *step_dev + 1, advanced by the launch).
