@@ -211,12 +211,26 @@ def test_fused_train_step_equals_pytorch(torch, B):
         exp = _random_batch(torch, B, g)
         tt, tl = torch.rand(B, 8, device=dev, generator=g), torch.rand(B, 8, device=dev, generator=g)
         b.qnetwork_local.load_state_dict(a.qnetwork_local.state_dict())     # same starting weights for this step
+        # which branch of the clip each batch covers, from the eager gradient norm BEFORE the clip.  Measured on the MI355X (device generator, these seeds):
+        # 5.06 / 5.26 at B = 2 and 0.97 / 1.22 at B = 32 (steps 0 / 1): both paths scale; 0.392 at B = 256, step 0: NEITHER scales (coef = 1) -- the batch
+        # of 256 is an unclipped step, which the `clipped` assertion below never noticed (it holds on either branch).  Each batch is pinned to its branch here;
+        # a clipped step at 256 and both sides of the threshold, against float64, are tests/test_iqn_train_f64_gpu.py's
+        a.optimizer.zero_grad(set_to_none=False)
+        a.compute_loss(exp, tt, tl).backward()
+        pre_clip = float(torch.linalg.vector_norm(torch.cat([p.grad.reshape(-1) for p in a.qnetwork_local.parameters()])))
+        print(f"B {B} step {step}: eager gradient norm before the clip {pre_clip:.4f}")
+        if B < 256:
+            assert pre_clip > 0.5, pre_clip
+        elif step == 0:
+            assert pre_clip < 0.45, pre_clip
         la, lb = float(a.train(exp, tt, tl)), float(b.train(exp, tt, tl))
         assert abs(la - lb) <= 1e-6 * abs(la), (la, lb)
         ga = torch.cat([p.grad.reshape(-1) for p in a.qnetwork_local.parameters()])
         gb = torch.cat([p.grad.reshape(-1) for p in b.qnetwork_local.parameters()])
         assert float((ga - gb).abs().max()) <= 1e-6 * float(ga.abs().max()), step
         assert abs(float(torch.linalg.vector_norm(gb)) - min(0.5, float(torch.linalg.vector_norm(gb)))) < 1e-6   # clipped
+        # ... and to the norm the branch of the eager norm dictates: 0.5 norm / (norm + 1e-6) above the threshold, the norm itself below it
+        assert abs(float(torch.linalg.vector_norm(gb)) - pre_clip * min(1.0, 0.5 / (pre_clip + 1e-6))) <= 2e-6, (step, pre_clip)
         if step == 0:      # identical Adam state only on the first step (b's weights are re-synchronised, its moments are its own)
             pa = torch.cat([p.detach().reshape(-1) for p in a.qnetwork_local.parameters()])
             pb = torch.cat([p.detach().reshape(-1) for p in b.qnetwork_local.parameters()])
