@@ -351,40 +351,48 @@ extern "C" int mn_step_append(mn_handle *h, const int32_t *actions_dev, const fl
     return step_common(h, actions_dev, obs_dev, reward_dev, done_dev, info_dev, &R, stream);
 }
 
+// What the episode entry points share around their one launch: the device guard, whatever has to be enqueued in front of the launch (`prepare`: the
+// weight image of a learned policy; its error code is the entry point's), the profiling event pair, the launch error and the parity reset -- the
+// episode kernels zero both done-queue counters: a following mn_reset_done has nothing to do, the next mn_step starts clean.
+template <class Prepare, class Launch>
+static int launch_episodes(mn_handle *h, hipStream_t s, Prepare prepare, Launch launch) {
+    MN_ON_DEVICE(h);
+    const int rc = prepare();
+    if (rc) return rc;
+    const bool prof = h->prof_n < h->prof_max;
+    if (prof) (void)hipEventRecord(h->ev[2 * h->prof_n], s);
+    launch();
+    if (prof) { (void)hipEventRecord(h->ev[2 * h->prof_n + 1], s); h->prof_n++; }
+    MN_HIP(h, hipGetLastError());
+    h->step_parity = 0;
+    h->last_parity = 0;
+    return MN_OK;
+}
+template <class Launch>
+static int launch_episodes(mn_handle *h, hipStream_t s, Launch launch) {
+    return launch_episodes(h, s, [] { return MN_OK; }, launch);
+}
+
 extern "C" int mn_rollout(mn_handle *h, int32_t n_steps, const int32_t *actions_dev, uint64_t action_seed,
                           uint64_t first_step_index, uint64_t first_env_index, float *obs_dev, float *obs_trace_dev,
                           float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev,
                           int32_t *action_trace_dev, void *stream) {
     if (!h || !obs_dev || n_steps < 1) return MN_ERR_INVALID;
-    MN_ON_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
-    const bool prof = h->prof_n < h->prof_max;
-    if (prof) (void)hipEventRecord(h->ev[2 * h->prof_n], s);
-    mn_launch_rollout(h->A, h->P, h->params.precision, h->params.rollout_lanes, n_steps, actions_dev, action_seed, first_step_index,
-                      first_env_index, obs_dev, obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev,
-                      action_trace_dev, s);
-    if (prof) { (void)hipEventRecord(h->ev[2 * h->prof_n + 1], s); h->prof_n++; }
-    MN_HIP(h, hipGetLastError());
-    // the kernel zeroed both done-queue counters: a following mn_reset_done has nothing to do, the next mn_step starts clean
-    h->step_parity = 0;
-    h->last_parity = 0;
-    return MN_OK;
+    return launch_episodes(h, s, [&] {
+        mn_launch_rollout(h->A, h->P, h->params.precision, h->params.rollout_lanes, n_steps, actions_dev, action_seed, first_step_index,
+                          first_env_index, obs_dev, obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev, action_trace_dev, s);
+    });
 }
 
 extern "C" int mn_rollout_policy(mn_handle *h, int32_t n_steps, int32_t policy, float *obs_dev, float *obs_trace_dev, float *reward_trace_dev,
                                  uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev, void *stream) {
     if (!h || !obs_dev || n_steps < 1 || (policy != MN_POLICY_APF && policy != MN_POLICY_BA)) return MN_ERR_INVALID;
-    MN_ON_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
-    const bool prof = h->prof_n < h->prof_max;
-    if (prof) (void)hipEventRecord(h->ev[2 * h->prof_n], s);
-    mn_launch_rollout_policy(h->A, h->P, h->params.precision, n_steps, policy, obs_dev, obs_trace_dev, reward_trace_dev, done_trace_dev,
-                             info_trace_dev, action_trace_dev, s);
-    if (prof) { (void)hipEventRecord(h->ev[2 * h->prof_n + 1], s); h->prof_n++; }
-    MN_HIP(h, hipGetLastError());
-    h->step_parity = 0;
-    h->last_parity = 0;
-    return MN_OK;
+    return launch_episodes(h, s, [&] {
+        mn_launch_rollout_policy(h->A, h->P, h->params.precision, n_steps, policy, obs_dev, obs_trace_dev, reward_trace_dev, done_trace_dev,
+                                 info_trace_dev, action_trace_dev, s);
+    });
 }
 
 extern "C" int mn_rollout_iqn_rows(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weights, int32_t n_steps, uint64_t *rng_state_dev, float cvar,
@@ -393,22 +401,14 @@ extern "C" int mn_rollout_iqn_rows(mn_handle *h, mn_iqn_ctx *ctx, const float *c
                                    float *q_trace_dev, int32_t *steps_run_dev, void *stream) {
     if (!h || !ctx || !weights || !rng_state_dev || !obs_dev || n_steps < 1) return MN_ERR_INVALID;      // (the 14 pointers of `weights`: mn_iqn_rollout_image)
     if ((long)h->A.n * 32 >= (1L << 32)) return MN_ERR_INVALID;      // 32-bit draw index, as mn_iqn_act_rng
-    MN_ON_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
     const uint32_t *image = nullptr;
     uint32_t *words = nullptr;
-    const int rc = mn_iqn_rollout_image(ctx, weights, s, &image, &words);
-    if (rc) return rc;
-    const bool prof = h->prof_n < h->prof_max;
-    if (prof) (void)hipEventRecord(h->ev[2 * h->prof_n], s);
-    mn_launch_rollout_iqn_rows(h->A, h->P, h->params.precision, n_steps, image, rng_state_dev, cvar, adaptive ? 1 : 0, cvar_row_dev, adaptive_row_dev, obs_dev,
-                               obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev, action_trace_dev, cvar_trace_dev, q_trace_dev, words,
-                               steps_run_dev, s);
-    if (prof) { (void)hipEventRecord(h->ev[2 * h->prof_n + 1], s); h->prof_n++; }
-    MN_HIP(h, hipGetLastError());
-    h->step_parity = 0;
-    h->last_parity = 0;
-    return MN_OK;
+    return launch_episodes(h, s, [&] { return mn_iqn_rollout_image(ctx, weights, s, &image, &words); }, [&] {
+        mn_launch_rollout_iqn_rows(h->A, h->P, h->params.precision, n_steps, image, rng_state_dev, cvar, adaptive ? 1 : 0, cvar_row_dev, adaptive_row_dev, obs_dev,
+                                   obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev, action_trace_dev, cvar_trace_dev, q_trace_dev, words,
+                                   steps_run_dev, s);
+    });
 }
 
 extern "C" int mn_rollout_iqn(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weights, int32_t n_steps, uint64_t *rng_state_dev, float cvar,
@@ -424,18 +424,11 @@ extern "C" int mn_rollout_dqn(mn_handle *h, const float *const *weights, float *
                               float *q_trace_dev, void *stream) {
     if (!h || !weights || !image_dev || !obs_dev || n_steps < 1) return MN_ERR_INVALID;
     for (int i = 0; i < 18; ++i) if (!weights[i]) return MN_ERR_INVALID;
-    MN_ON_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
-    if (repack) mn_launch_dqn_pack(weights, image_dev, s);
-    const bool prof = h->prof_n < h->prof_max;
-    if (prof) (void)hipEventRecord(h->ev[2 * h->prof_n], s);
-    mn_launch_rollout_dqn(h->A, h->P, h->params.precision, n_steps, image_dev, obs_dev, obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev,
-                          action_trace_dev, q_trace_dev, s);
-    if (prof) { (void)hipEventRecord(h->ev[2 * h->prof_n + 1], s); h->prof_n++; }
-    MN_HIP(h, hipGetLastError());
-    h->step_parity = 0;
-    h->last_parity = 0;
-    return MN_OK;
+    return launch_episodes(h, s, [&] { if (repack) mn_launch_dqn_pack(weights, image_dev, s); return MN_OK; }, [&] {
+        mn_launch_rollout_dqn(h->A, h->P, h->params.precision, n_steps, image_dev, obs_dev, obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev,
+                              action_trace_dev, q_trace_dev, s);
+    });
 }
 
 extern "C" int mn_planner_act(const float *obs_dev, int32_t n, int32_t policy, const double *a, const double *w, int32_t *actions_dev, void *stream) {

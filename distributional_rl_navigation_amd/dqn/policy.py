@@ -135,17 +135,12 @@ class DQNPolicy(nn.Module):
         act kernel would not run either (CPU, another net_arch, use_fused_act = False): the caller runs the loop instead."""
         import ctypes as C
         from .. import _capi
+        from ..episodes import trace_buffers
         if not (hasattr(env, "h") and self._fusable(env.obs)):
             return None
         T, n, dev = int(n_steps), env.n_envs, env.device
         st, repack = self._image(dev)
-        mk = dict(obs=lambda: torch.zeros(T, n, self.state_size, dtype=torch.float32, device=dev),
-                  reward=lambda: torch.empty(T, n, dtype=torch.float32, device=dev),
-                  done=lambda: torch.empty(T, n, dtype=torch.uint8, device=dev),
-                  info=lambda: torch.empty(T, n, dtype=torch.uint8, device=dev),
-                  action=lambda: torch.empty(T, n, dtype=torch.int32, device=dev),
-                  q=lambda: torch.full((T, n, self.action_size), float("nan"), dtype=torch.float32, device=dev))
-        tr = {k: mk[k]() for k in trace}
+        tr = trace_buffers(T, n, dev, trace, obs_dim=self.state_size, n_actions=self.action_size)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         rc = _capi.lib().mn_rollout_dqn(env.h, st["ptrs"], p(st["image"]), int(repack), T, p(env.obs), p(tr.get("obs")), p(tr.get("reward")),
                                         p(tr.get("done")), p(tr.get("info")), p(tr.get("action")), p(tr.get("q")), env._stream())

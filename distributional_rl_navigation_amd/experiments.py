@@ -6,9 +6,9 @@ time on the CPU (`exp_setup_5`: fixed start (5,5) / goal (45,45), `set_boundary 
 Here the worlds are generated once from the same RNG stream (bit-identical to the reference's), replicated
 per policy into ONE vector env and all 500 x 5 episodes are stepped side by side on the GPU.
 """
-import numpy as np
 import torch
 
+from .episodes import EPISODE_TRACES, energy_table, host_traces, loop_episodes, tally
 from .marinenav_env.vec_env import VecMarineNavEnv
 from .planners import planner_act_batch
 
@@ -67,41 +67,24 @@ def _episode_record(world, params, name, actions, traj, cvars=None, quantiles=No
     return ep
 
 
-@torch.no_grad()
-def _records_from_traces(tr, env, names, num, elapsed_ms):
-    """Result records of the policies `names` (policy p owns rows [p * num, (p + 1) * num) of `env`) from the traces of ONE episode-rollout launch
-    that took `elapsed_ms`: the bookkeeping of run_experiment's per-step loop on the traces (same operations, same order, for the steps that loop
-    would have run).  `computation_times`: the launch's device time divided by the actions it chose, one entry per step of every episode."""
-    dev = env.device
-    n = env.n_envs
-    reward, done, info, acts = tr["reward"], tr["done"].bool(), tr["info"], tr["action"]
-    a_tab = torch.tensor(env.params.a[:], device=dev); w_tab = torch.tensor(env.params.w[:], device=dev)
-    energy_tab = ((a_tab / a_tab.max()).abs().view(3, 1) + (w_tab / w_tab.max()).abs().view(1, 3)).reshape(-1)
-    alive = torch.ones(n, dtype=torch.bool, device=dev)
-    ret = torch.zeros(n, dtype=torch.float64, device=dev); energy = torch.zeros_like(ret)
-    length = torch.zeros(n, dtype=torch.int64, device=dev)
-    last_info = torch.zeros(n, dtype=torch.uint8, device=dev)
-    # the loop stops after the step that ends the last episode
-    steps = int(torch.where(done.any(dim=0), done.int().argmax(dim=0) + 1, torch.full((n,), done.shape[0], device=dev)).max())
-    for t in range(steps):
-        ret += torch.where(alive, (env.discount ** t) * reward[t].double(), torch.zeros_like(ret))
-        length += alive.long()
-        energy += torch.where(alive, energy_tab[acts[t].clamp_min(0).long()].double(), torch.zeros_like(energy))
-        last_info = torch.where(alive, info[t], last_info)
-        alive = alive & ~done[t]
-    torch.cuda.synchronize(dev)
-    length_h, info_h, acts_h = length.cpu().numpy(), last_info.cpu().numpy(), acts.cpu().numpy()
-    ret_h, energy_h = ret.cpu().numpy(), energy.cpu().numpy()
-    dtN = env.params.dt * env.params.N
-    per_action = elapsed_ms * 1e-3 / max(1, int(length_h.sum()))
+def _records_from_traces(tr, params, names, num, launch_s=None, step_s=None):
+    """Result records of the policies `names` (policy p owns rows [p * num, (p + 1) * num)) from the numpy traces of their episodes, whichever way
+    they were produced: `episodes.tally`'s numbers, sliced per policy.  `computation_times`, one entry per step of every episode, either way:
+    `launch_s`, the device seconds of ONE launch that ran all the episodes, divided by the actions it chose; or `step_s`, per policy the per-step
+    list of its act launch's device seconds per row served -- step t counts once for every env alive before it, i.e. with length > t."""
+    tl = tally(tr["reward"], tr["done"], tr["info"], tr["action"], params.discount, energy_table(params.a[:], params.w[:]))
+    length, info = tl["length"], tl["last_info"]
+    dtN = params.dt * params.N
     out = {}
     for p, name in enumerate(names):
         sl = slice(p * num, (p + 1) * num)
-        out[name] = dict(success=[bool(v) for v in info_h[sl] == 4], out_of_area=[bool(v) for v in info_h[sl] == 1],
-                         time=[float(dtN * l) for l in length_h[sl]], energy=[float(v) for v in energy_h[sl]],
-                         reward=[float(v) for v in ret_h[sl]],
-                         actions=[[int(x) for x in acts_h[:length_h[i], i]] for i in range(p * num, (p + 1) * num)],
-                         computation_times=[per_action] * int(length_h[sl].sum()))
+        if step_s is None:
+            times = [launch_s / max(1, int(length.sum()))] * int(length[sl].sum())
+        else:
+            times = [float(s_) for t, s_ in enumerate(step_s.get(name, [])) for _ in range(int((length[sl] > t).sum()))]
+        out[name] = dict(success=[bool(v) for v in info[sl] == 4], out_of_area=[bool(v) for v in info[sl] == 1],
+                         time=[float(dtN * l) for l in length[sl]], energy=[float(v) for v in tl["energy"][sl]],
+                         reward=[float(v) for v in tl["ret"][sl]], actions=tl["actions"][sl], computation_times=times)
     return out
 
 
@@ -118,7 +101,7 @@ def _rollout_episodes(worlds, names, device, launch):
     rec = None
     if tr is not None:
         torch.cuda.synchronize(env.device)
-        rec = _records_from_traces(tr, env, names, len(worlds), e0.elapsed_time(e1))
+        rec = _records_from_traces(host_traces(tr), env.params, names, len(worlds), launch_s=e0.elapsed_time(e1) * 1e-3)
     env.close()
     return rec
 
@@ -144,7 +127,7 @@ def _iqn_episodes(worlds, names, agent, device, max_steps):
     adaptive_rows = torch.tensor([name == "adaptive_IQN" for name in names]).repeat_interleave(num)
     agent.qnetwork_local.eval()
     rec = _rollout_episodes(worlds, names, device, lambda env: rollout_iqn(agent.qnetwork_local, env, max_steps, agent._act_rng, cvar_rows=cvar_rows,
-                                                                           adaptive_rows=adaptive_rows, trace=("reward", "done", "info", "action")))
+                                                                           adaptive_rows=adaptive_rows, trace=EPISODE_TRACES))
     agent.qnetwork_local.train()
     return rec
 
@@ -182,7 +165,7 @@ def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, d
             if dqn is None:
                 raise ValueError("policy 'DQN' needs run_experiment(..., dqn=DQNPolicy.load(...))")
             rolled.update(_rollout_episodes(worlds, ("DQN",), device,
-                                            lambda env: dqn.rollout(env, max_steps, trace=("reward", "done", "info", "action"))) or {})
+                                            lambda env: dqn.rollout(env, max_steps, trace=EPISODE_TRACES)) or {})
     policies = tuple(p for p in requested if p not in rolled)
     if not policies:
         return {name: rolled[name] for name in requested}, worlds
@@ -208,16 +191,8 @@ def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, d
         else:
             fixed[rows] = _CVAR[name]
     iqn_idx = torch.nonzero(iqn_rows).view(-1)
-    a_tab = torch.tensor(env.params.a[:], device=dev); w_tab = torch.tensor(env.params.w[:], device=dev)
-    energy_tab = ((a_tab / a_tab.max()).abs().view(3, 1) + (w_tab / w_tab.max()).abs().view(1, 3)).reshape(-1)
-    alive = torch.ones(n, dtype=torch.bool, device=dev)
-    ret = torch.zeros(n, dtype=torch.float64, device=dev); energy = torch.zeros_like(ret)
-    length = torch.zeros(n, dtype=torch.int64, device=dev)
-    last_info = torch.zeros(n, dtype=torch.uint8, device=dev)
-    acts = torch.full((max_steps, n), -1, dtype=torch.int32, device=dev)
     cap_cv, cap_q, cap_t, cap_traj = [], [], [], []
     act_events = {}                                                # group -> [(start, end)] per step; groups: "IQN" (one launch for all IQN policies), planners
-    alive_hist = []                                                # per step: live envs per policy (before the step)
 
     def timed(group, fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -226,13 +201,9 @@ def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, d
         e1.record()
         act_events.setdefault(group, []).append((e0, e1))
         return r
-    if capture:
-        env.enable_trajectory()
-    if agent is not None:
-        agent.qnetwork_local.eval()
-    for t in range(max_steps):
+
+    def act(t, obs):
         a = torch.zeros(n, dtype=torch.int32, device=dev)
-        alive_hist.append(alive.view(len(policies), num).sum(dim=1))
         if iqn_idx.numel():
             o = obs[iqn_idx].contiguous()
 
@@ -250,50 +221,36 @@ def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, d
                 a[rows] = timed(name, lambda: dqn.act_batch(obs[rows]))
                 continue
             a[rows] = timed(name, lambda: planner_act_batch(obs[rows], name, env.params.a[:], env.params.w[:]))      # one HIP launch (mn_planner_act)
-        obs, reward, done, info = env.step(a)
-        if capture:
-            cap_traj.append(env.get_trajectory())
-        ret += torch.where(alive, (env.discount ** t) * reward.double(), torch.zeros_like(ret))
-        length += alive.long()
-        energy += torch.where(alive, energy_tab[a.long()].double(), torch.zeros_like(energy))
-        acts[t] = torch.where(alive, a, torch.full_like(a, -1))
-        last_info = torch.where(alive, info, last_info)
-        alive = alive & ~done.bool()
-        if not bool(alive.any()):
-            break
+        return a
+    if capture:
+        env.enable_trajectory()
+    if agent is not None:
+        agent.qnetwork_local.eval()
+    tr = loop_episodes(env, obs, act, max_steps, after_step=(lambda t: cap_traj.append(env.get_trajectory())) if capture else None)
     if agent is not None:
         agent.qnetwork_local.train()
-    length_h = length.cpu().numpy(); info_h = last_info.cpu().numpy(); acts_h = acts.cpu().numpy()
-    ret_h = ret.cpu().numpy(); energy_h = energy.cpu().numpy()
-    dtN = env.params.dt * env.params.N
     torch.cuda.synchronize(dev)
     group_rows = {"IQN": max(1, int(iqn_idx.numel()))}
     step_s = {g: [e0.elapsed_time(e1) * 1e-3 / group_rows.get(g, num) for e0, e1 in evs] for g, evs in act_events.items()}
-    alive_h = torch.stack(alive_hist).cpu().numpy() if alive_hist else np.zeros((0, len(policies)), dtype=np.int64)
-    out = {}
-    for p, name in enumerate(policies):
-        sl = slice(p * num, (p + 1) * num)
-        out[name] = dict(success=[bool(v) for v in info_h[sl] == 4], out_of_area=[bool(v) for v in info_h[sl] == 1],
-                         time=[float(dtN * l) for l in length_h[sl]], energy=[float(v) for v in energy_h[sl]],
-                         reward=[float(v) for v in ret_h[sl]],
-                         actions=[[int(x) for x in acts_h[:length_h[i], i]] for i in range(p * num, (p + 1) * num)])
-        ts = step_s.get(name if name in classical else "IQN", [])
-        # one entry per act call of the reference = per live episode and step: the step's amortised per-row device time
-        out[name]["computation_times"] = [float(ts[t_]) for t_ in range(len(ts)) for _ in range(int(alive_h[t_, p]))]
-        if capture:
-            iqn_pos = {int(g_): k for k, g_ in enumerate(iqn_idx.cpu().numpy())}     # env row -> row of the IQN captures
+    # one entry per act call of the reference = per live episode and step: the step's amortised per-row device time
+    out = _records_from_traces(host_traces(tr), env.params, policies, num,
+                               step_s={name: step_s.get(name if name in classical else "IQN", []) for name in policies})
+    if capture:
+        iqn_pos = {int(g_): k for k, g_ in enumerate(iqn_idx.cpu().numpy())}     # env row -> row of the IQN captures
+        for p, name in enumerate(policies):
             eps_ = []
             for i in range(p * num, (p + 1) * num):
-                L = int(length_h[i])
+                acts_i = out[name]["actions"][i - p * num]
+                L = len(acts_i)
                 traj = [q for t_ in range(L) for q in cap_traj[t_][i]]
                 if i in iqn_pos:
                     k = iqn_pos[i]
-                    eps_.append(_episode_record(worlds[i - p * num], env.params, name, acts_h[:L, i], traj,
+                    eps_.append(_episode_record(worlds[i - p * num], env.params, name, acts_i, traj,
                                                 cvars=[cap_cv[t_][k] for t_ in range(L)],
                                                 quantiles=[cap_q[t_][k:k + 1] for t_ in range(L)],
                                                 taus=[cap_t[t_][k:k + 1] for t_ in range(L)], seed=seed))
                 else:
-                    eps_.append(_episode_record(worlds[i - p * num], env.params, name, acts_h[:L, i], traj, seed=seed))
+                    eps_.append(_episode_record(worlds[i - p * num], env.params, name, acts_i, traj, seed=seed))
             out[name]["ep_data"] = eps_
     env.close()
     out.update(rolled)

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 import torch.optim as optim
 
+from ..episodes import EPISODE_TRACES, energy_table, host_traces, loop_episodes, tally
 from .cadence import cadence_tick
 from .compat import ReferenceLoopMixin
 from .model import ObsEncoder
@@ -91,28 +92,11 @@ class UnderActGuard:
 
 
 def evaluation_from_traces(reward, done, info, action, discount, energy_tab, dt, N):
-    """The bookkeeping of IQNAgent.evaluation_vec's loop on the traces of one mn_rollout_iqn launch (numpy [T][n], T = the steps the loop ran):
-    the same float64 operations in the same step order -- return += (discount ** t) * reward, energy += energy_tab[action] while alive --, so the
-    lists are equal to the loop's bit for bit.  Returns (action_data, reward_data, success_data, time_data, energy_data)."""
-    T, n = reward.shape
-    alive = np.ones(n, dtype=bool)
-    ret = np.zeros(n, dtype=np.float64)
-    length = np.zeros(n, dtype=np.int64)
-    energy = np.zeros(n, dtype=np.float64)
-    last_info = np.zeros(n, dtype=np.uint8)
-    etab = np.asarray(energy_tab, dtype=np.float32).astype(np.float64)
-    for t in range(T):
-        ret += np.where(alive, (discount ** t) * reward[t].astype(np.float64), 0.0)
-        length += alive
-        energy += np.where(alive, etab[np.clip(action[t], 0, len(etab) - 1)], 0.0)
-        last_info = np.where(alive, info[t], last_info)
-        alive = alive & ~done[t].astype(bool)
-    action_data = [[int(x) for x in action[:length[i], i]] for i in range(n)]
-    reward_data = [float(x) for x in ret]
-    success_data = [bool(x) for x in (last_info == 4)]
-    time_data = [float(dt * N * l) for l in length]
-    energy_data = [float(x) for x in energy]
-    return action_data, reward_data, success_data, time_data, energy_data
+    """The evaluation lists of IQNAgent.evaluation_vec from the traces (numpy [T][n]) of its episodes, whichever way they were produced:
+    `episodes.tally`'s numbers as (action_data, reward_data, success_data, time_data, energy_data)."""
+    tl = tally(reward, done, info, action, discount, energy_tab)
+    return (tl["actions"], [float(x) for x in tl["ret"]], [bool(x) for x in (tl["last_info"] == 4)], [float(dt * N * l) for l in tl["length"]],
+            [float(x) for x in tl["energy"]])
 
 
 class IQNAgent(ReferenceLoopMixin):
@@ -613,7 +597,7 @@ class IQNAgent(ReferenceLoopMixin):
         if self._act_rng is None:
             self._act_rng = ActRng(self.gen.initial_seed(), self.device)
         return rollout_iqn(self.qnetwork_local, eval_env, max_steps, self._act_rng, cvar=1.0, adaptive=not greedy, shared_taus=self.shared_taus,
-                           trace=("reward", "done", "info", "action"))
+                           trace=EPISODE_TRACES)
 
     @torch.no_grad()
     def evaluation_vec(self, eval_env, eval_config, greedy=True, eval_log_path=None, max_steps=1000, one_launch=False):
@@ -624,50 +608,18 @@ class IQNAgent(ReferenceLoopMixin):
         back to the loop."""
         from ..marinenav_env.vec_env import VecMarineNavEnv
         cfgs = list(eval_config.values())
-        n = len(cfgs)
-        assert eval_env.n_envs == n
+        assert eval_env.n_envs == len(cfgs)
         r0 = cfgs[0]["robot"]
         eval_env.set_attrs(N=r0["N"], dt=r0["dt"])
         obs = eval_env.load_worlds([VecMarineNavEnv.world_from_eval_config(c) for c in cfgs]).clone()
-        a_tab = torch.tensor(r0["a"], device=self.device); w_tab = torch.tensor(r0["w"], device=self.device)
-        e_a = (a_tab / a_tab.max()).abs(); e_w = (w_tab / w_tab.max()).abs()
-        energy_tab = (e_a.view(3, 1) + e_w.view(1, 3)).reshape(-1)      # robot.py:72-77
-        alive = torch.ones(n, dtype=torch.bool, device=self.device)
-        ret = torch.zeros(n, dtype=torch.float64, device=self.device)
-        length = torch.zeros(n, dtype=torch.int64, device=self.device)
-        energy = torch.zeros(n, dtype=torch.float64, device=self.device)
-        last_info = torch.zeros(n, dtype=torch.uint8, device=self.device)
-        acts = torch.full((max_steps, n), -1, dtype=torch.int32, device=self.device)
         self.qnetwork_local.eval()
         tr = self._rollout_evaluation(eval_env, greedy, max_steps) if one_launch else None
-        if tr is not None:
-            self.qnetwork_local.train()
-            T = tr["steps_run"]
-            data = evaluation_from_traces(tr["reward"][:T].cpu().numpy(), tr["done"][:T].cpu().numpy(), tr["info"][:T].cpu().numpy(),
-                                          tr["action"][:T].cpu().numpy(), eval_env.discount, energy_tab.cpu().numpy(), r0["dt"], r0["N"])
-            self._log_evaluation(greedy, *data, eval_log_path)
-            action_data, reward_data, success_data, time_data, energy_data = data
-            return dict(rewards=reward_data, successes=success_data, times=time_data, energies=energy_data, actions=action_data)
-        for t in range(max_steps):
-            cv = 1.0 if greedy else self.adjust_cvar_batch(obs)
-            a = self.act_batch(obs, 0.0, cv)
-            obs, reward, done, info = eval_env.step(a)
-            ret += torch.where(alive, (eval_env.discount ** t) * reward.double(), torch.zeros_like(ret))
-            length += alive.long()
-            energy += torch.where(alive, energy_tab[a.long()].double(), torch.zeros_like(energy))
-            acts[t] = torch.where(alive, a, torch.full_like(a, -1))
-            last_info = torch.where(alive, info, last_info)
-            alive = alive & ~done.bool()
-            if not bool(alive.any()):
-                break
+        if tr is None:
+            tr = loop_episodes(eval_env, obs, lambda t, o: self.act_batch(o, 0.0, 1.0 if greedy else self.adjust_cvar_batch(o)), max_steps)
         self.qnetwork_local.train()
-        acts_h = acts.cpu().numpy(); length_h = length.cpu().numpy()
-        action_data = [[int(x) for x in acts_h[:length_h[i], i]] for i in range(n)]
-        reward_data = [float(x) for x in ret.cpu().numpy()]
-        success_data = [bool(x) for x in (last_info == 4).cpu().numpy()]
-        time_data = [float(r0["dt"] * r0["N"] * l) for l in length_h]
-        energy_data = [float(x) for x in energy.cpu().numpy()]
-        self._log_evaluation(greedy, action_data, reward_data, success_data, time_data, energy_data, eval_log_path)
+        data = evaluation_from_traces(**host_traces(tr), discount=eval_env.discount, energy_tab=energy_table(r0["a"], r0["w"]), dt=r0["dt"], N=r0["N"])
+        self._log_evaluation(greedy, *data, eval_log_path)
+        action_data, reward_data, success_data, time_data, energy_data = data
         return dict(rewards=reward_data, successes=success_data, times=time_data, energies=energy_data, actions=action_data)
 
     def _log_evaluation(self, greedy, action_data, reward_data, success_data, time_data, energy_data, eval_log_path,

@@ -11,6 +11,7 @@ import weakref
 import torch
 
 from .. import _capi
+from ..episodes import trace_buffers
 
 _ORDER = ("velocity_encoder", "goal_encoder", "sensor_encoder", "cos_embedding", "hidden_layer", "hidden_layer_2", "output_layer")
 
@@ -314,14 +315,7 @@ def rollout_iqn(net, env, n_steps, rng, cvar=1.0, adaptive=False, shared_taus=Fa
     ad_rows = adaptive_rows.to(device=dev, dtype=torch.uint8).contiguous() if adaptive_rows is not None else None
     assert cv_rows is None or cv_rows.numel() == n
     assert ad_rows is None or ad_rows.numel() == n
-    mk = dict(obs=lambda: torch.zeros(T, n, 26, dtype=torch.float32, device=dev),
-              reward=lambda: torch.empty(T, n, dtype=torch.float32, device=dev),
-              done=lambda: torch.empty(T, n, dtype=torch.uint8, device=dev),
-              info=lambda: torch.empty(T, n, dtype=torch.uint8, device=dev),
-              action=lambda: torch.empty(T, n, dtype=torch.int32, device=dev),
-              cvar=lambda: torch.full((T, n), float("nan"), dtype=torch.float32, device=dev),
-              q=lambda: torch.full((T, n, net.action_size), float("nan"), dtype=torch.float32, device=dev))
-    tr = {k: mk[k]() for k in trace}
+    tr = trace_buffers(T, n, dev, trace, n_actions=net.action_size)
     p = lambda k: _p(tr[k]) if k in tr else None
     steps = torch.zeros(1, dtype=torch.int32, device=dev)
     rc = _capi.lib().mn_rollout_iqn_rows(env.h, ctx.h, ctx.weights(net), T, _p(rng.state), C.c_float(float(cvar)), int(bool(adaptive)), _p(cv_rows),

@@ -11,6 +11,7 @@ import torch
 
 from .. import _capi
 from .._capi import MAX_CORES, MAX_OBS, OBS_DIM, INFO_STRINGS
+from ..episodes import trace_buffers
 
 _ATTR_TO_PARAM = {
     # MarineNavEnv attribute (marinenav_env.py:40-73) -> mn_params field
@@ -216,12 +217,7 @@ class VecMarineNavEnv:
         key = (T, tuple(sorted(trace)))
         bufs = getattr(self, "_rollout_bufs", None)
         if bufs is None or bufs[0] != key:
-            mk = dict(obs=lambda: torch.empty(T, n, OBS_DIM, dtype=torch.float32, device=dev),
-                      reward=lambda: torch.empty(T, n, dtype=torch.float32, device=dev),
-                      done=lambda: torch.empty(T, n, dtype=torch.uint8, device=dev),
-                      info=lambda: torch.empty(T, n, dtype=torch.uint8, device=dev),
-                      action=lambda: torch.empty(T, n, dtype=torch.int32, device=dev))
-            bufs = self._rollout_bufs = (key, {k: mk[k]() for k in trace})
+            bufs = self._rollout_bufs = (key, trace_buffers(T, n, dev, trace, fill=False))      # (with auto-reset every row is written)
         tr = bufs[1]
         a = None
         if actions is not None:
@@ -243,12 +239,7 @@ class VecMarineNavEnv:
         No resets: a finished env idles (reward 0, done 1, terminal info, action -1 in the traces).  Step for step identical to the
         loop (planners.planner_act_batch, step).  Returns the requested traces + `final_obs` (terminal observations where finished)."""
         T, n, dev = int(n_steps), self.n_envs, self.device
-        mk = dict(obs=lambda: torch.zeros(T, n, OBS_DIM, dtype=torch.float32, device=dev),
-                  reward=lambda: torch.empty(T, n, dtype=torch.float32, device=dev),
-                  done=lambda: torch.empty(T, n, dtype=torch.uint8, device=dev),
-                  info=lambda: torch.empty(T, n, dtype=torch.uint8, device=dev),
-                  action=lambda: torch.empty(T, n, dtype=torch.int32, device=dev))
-        tr = {k: mk[k]() for k in trace}
+        tr = trace_buffers(T, n, dev, trace)
         p = lambda k: _ptr(tr[k]) if k in tr else None
         self._check(self.L.mn_rollout_policy(self.h, T, int(self.POLICIES[policy]), _ptr(self.obs), p("obs"), p("reward"), p("done"), p("info"),
                                              p("action"), self._stream()))

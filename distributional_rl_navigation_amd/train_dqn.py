@@ -51,57 +51,28 @@ def exploration_rate(it, plan):
 
 
 def evaluation_from_rollout(tr, discount, energy_tab, dt, N):
-    """`evaluate`'s result dict from the traces of one DQNPolicy.rollout launch (numpy [T][n] reward / done / info / action): the loop's bookkeeping
-    (iqn.agent.evaluation_from_traces: the same float64 operations in the same step order) on the steps the loop would have run -- it stops after the
-    step that ends the last episode."""
-    from .iqn.agent import evaluation_from_traces
-    done = tr["done"].astype(bool)
-    ended = done.any(axis=0)
-    steps = int(np.where(ended, done.argmax(axis=0) + 1, done.shape[0]).max())
-    actions, rewards, successes, times, energies = evaluation_from_traces(tr["reward"][:steps], tr["done"][:steps], tr["info"][:steps],
-                                                                          tr["action"][:steps], discount, energy_tab, dt, N)
-    return dict(rewards=np.array(rewards, dtype=np.float64), successes=np.array(successes, dtype=bool), times=np.array(times, dtype=np.float64),
-                energies=np.array(energies, dtype=np.float64), actions=actions)
+    """`evaluate`'s result dict from the traces (numpy [T][n] reward / done / info / action) of its episodes, whichever way they were produced:
+    `episodes.tally`'s numbers as arrays."""
+    from .episodes import tally
+    tl = tally(tr["reward"], tr["done"], tr["info"], tr["action"], discount, energy_tab)
+    return dict(rewards=tl["ret"], successes=tl["last_info"] == 4, times=np.array([dt * N * l for l in tl["length"]], dtype=np.float64),
+                energies=tl["energy"], actions=tl["actions"])
 
 
 def evaluate(agent, eval_env, eval_config, max_steps=1000, one_launch=False):
     """The greedy DQN on the evaluation worlds, stepped side by side on the GPU (as IQNAgent.evaluation_vec).
     `one_launch`: every episode in one mn_rollout_dqn launch (DQNPolicy.rollout) instead of a Python iteration per step -- the same dict, bit for
     bit; where the policy does not act through the fused kernel the loop runs."""
-    import torch
+    from .episodes import EPISODE_TRACES, energy_table, host_traces, loop_episodes
     from .marinenav_env.vec_env import VecMarineNavEnv
     cfgs = list(eval_config.values())
-    n, dev = len(cfgs), agent.device
     r0 = cfgs[0]["robot"]
     eval_env.set_attrs(N=r0["N"], dt=r0["dt"])
     obs = eval_env.load_worlds([VecMarineNavEnv.world_from_eval_config(c) for c in cfgs]).clone()
-    a_tab = torch.tensor(r0["a"], device=dev); w_tab = torch.tensor(r0["w"], device=dev)
-    energy_tab = ((a_tab / a_tab.max()).abs().view(3, 1) + (w_tab / w_tab.max()).abs().view(1, 3)).reshape(-1)      # robot.py:72-77
-    alive = torch.ones(n, dtype=torch.bool, device=dev)
-    ret = torch.zeros(n, dtype=torch.float64, device=dev)
-    length = torch.zeros(n, dtype=torch.int64, device=dev)
-    energy = torch.zeros(n, dtype=torch.float64, device=dev)
-    last_info = torch.zeros(n, dtype=torch.uint8, device=dev)
-    tr = agent.policy.rollout(eval_env, max_steps, trace=("reward", "done", "info", "action")) if one_launch else None
-    if tr is not None:
-        return evaluation_from_rollout({k: tr[k].cpu().numpy() for k in ("reward", "done", "info", "action")}, eval_env.discount,
-                                       energy_tab.cpu().numpy(), r0["dt"], r0["N"])
-    acts = torch.full((max_steps, n), -1, dtype=torch.int32, device=dev)
-    for t in range(max_steps):
-        a = agent.policy.act_batch(obs)
-        obs, reward, done, info = eval_env.step(a)
-        ret += torch.where(alive, (eval_env.discount ** t) * reward.double(), torch.zeros_like(ret))
-        length += alive.long()
-        energy += torch.where(alive, energy_tab[a.long()].double(), torch.zeros_like(energy))
-        acts[t] = torch.where(alive, a, torch.full_like(a, -1))
-        last_info = torch.where(alive, info, last_info)
-        alive = alive & ~done.bool()
-        if not bool(alive.any()):
-            break
-    acts_h, length_h = acts.cpu().numpy(), length.cpu().numpy()
-    return dict(rewards=ret.cpu().numpy(), successes=(last_info == 4).cpu().numpy(),
-                times=np.array([r0["dt"] * r0["N"] * l for l in length_h], dtype=np.float64), energies=energy.cpu().numpy(),
-                actions=[[int(x) for x in acts_h[:length_h[i], i]] for i in range(n)])
+    tr = agent.policy.rollout(eval_env, max_steps, trace=EPISODE_TRACES) if one_launch else None
+    if tr is None:
+        tr = loop_episodes(eval_env, obs, lambda t, o: agent.policy.act_batch(o), max_steps)
+    return evaluation_from_rollout(host_traces(tr), eval_env.discount, energy_table(r0["a"], r0["w"]), r0["dt"], r0["N"])
 
 
 def save_zip(agent, path):

@@ -26,7 +26,7 @@ def _time_eval(agent, env, cfg, greedy, one, reps):
         torch.cuda.synchronize()
         ts.append(time.perf_counter() - t0)
         res = r if res is None else res
-    return sorted(ts)[len(ts) // 2], r
+    return (sorted(ts)[len(ts) // 2], min(ts), max(ts)), r
 
 
 def main():
@@ -41,8 +41,9 @@ def main():
     from distributional_rl_navigation_amd.marinenav_env.vec_env import VecMarineNavEnv
     with open(os.path.join(G, "eval_config_seed3.json")) as f:
         cfg = json.load(f)
-    print(f"device: {torch.cuda.get_device_name(0)}; 30 evaluation worlds, f64 env; median of {args.reps} evaluations")
-    print(f"{'network':<22}{'policy':<10}{'steps':>6}{'loop ms':>10}{'one launch ms':>15}{'speed-up':>10}{'us/step (one)':>15}  same")
+    print(f"device: {torch.cuda.get_device_name(0)}; 30 evaluation worlds, f64 env; {args.reps} evaluations each: median [min .. max]")
+    print(f"{'network':<22}{'policy':<10}{'steps':>6}{'loop ms':>28}{'one launch ms':>28}{'speed-up':>10}{'us/step (one)':>15}  same")
+    ms = lambda t: f"{t[0] * 1e3:.2f} [{t[1] * 1e3:.2f} .. {t[2] * 1e3:.2f}]"
     for name in ("shipped checkpoint", "untrained (seed 7)"):
         for greedy in (True, False):
             out = {}
@@ -59,8 +60,8 @@ def main():
                     out[one] = _time_eval(agent, env, cfg, greedy, one, args.reps)
                 env.close()
             steps = max(len(a) for a in out[True][1]["actions"])
-            lo, hi = out[False][0] * 1e3, out[True][0] * 1e3
-            print(f"{name:<22}{'greedy' if greedy else 'adaptive':<10}{steps:>6}{lo:>10.1f}{hi:>15.2f}{lo / hi:>9.1f}x{hi * 1e3 / steps:>15.2f}  "
+            lo, hi = out[False][0][0] * 1e3, out[True][0][0] * 1e3
+            print(f"{name:<22}{'greedy' if greedy else 'adaptive':<10}{steps:>6}{ms(out[False][0]):>28}{ms(out[True][0]):>28}{lo / hi:>9.1f}x{hi * 1e3 / steps:>15.2f}  "
                   f"{out[False][1] == out[True][1]}")
     if args.train:
         import subprocess
