@@ -79,6 +79,7 @@ SIGNATURES = [
     ("mn_get_reward64", C.c_int, [_vp, _i32, _i32, _pd]),
     ("mn_enable_trajectory", C.c_int, [_vp, _i32]),
     ("mn_get_trajectory", C.c_int, [_vp, _i32, _i32, _i32, _pd]),
+    ("mn_set_trajectory_trace", C.c_int, [_vp, _vp, _i32, _i32]),
     ("mn_peek_next_double", C.c_int, [_vp, _i32, _i32, _pd]),
     ("mn_last_done_count", C.c_int, [_vp, _vp, _pi32]),
     ("mn_profile_begin", C.c_int, [_vp, _i32]),
@@ -101,6 +102,7 @@ SIGNATURES = [
     ("mn_planner_act", C.c_int, [_vp, _i32, _i32, _pd, _pd, _vp, _vp]),
     ("mn_rollout_iqn", C.c_int, [_vp, _vp, C.POINTER(C.c_void_p), _i32, _vp, C.c_float, _i32] + [_vp] * 10),
     ("mn_rollout_iqn_rows", C.c_int, [_vp, _vp, C.POINTER(C.c_void_p), _i32, _vp, C.c_float, _i32] + [_vp] * 12),
+    ("mn_rollout_iqn_eval", C.c_int, [_vp, _vp, C.POINTER(C.c_void_p), _i32, _vp, C.c_float, _i32] + [_vp] * 14),
     ("mn_rollout_dqn", C.c_int, [_vp, C.POINTER(C.c_void_p), _vp, _i32, _i32] + [_vp] * 8),
     ("mn_dqn_image_floats", C.c_int64, []),
     ("mn_dqn_act", C.c_int, [_vp, C.POINTER(C.c_void_p), _vp, _i32, _vp, _vp, _i32, _vp]),

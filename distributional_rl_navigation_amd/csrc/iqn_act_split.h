@@ -829,8 +829,8 @@ __device__ __forceinline__ void tail(const u32x4 *__restrict__ lds4, const f32x4
     });
 }
 
-// The per-environment pieces of the acting form below as functions, for the IQN episode rollout (mn_rollout_iqn.hip), which runs the same
-// arithmetic on one environment per wavefront.  iqn_qvals_split_kernel keeps these lines written out: calling the functions from it moves
+// The per-environment pieces of the acting form below as functions, for the IQN episode rollout (mn_rollout_iqn_body.h), which runs the same
+// arithmetic on one environment per wavefront.  iqn_qvals_split_kernel keeps the acting form's lines written out: calling the functions from it moves
 // its register allocation and schedule (same results, different code object).
 // Observation encoders of one environment (ov = its 26 inputs, zero padded), its scales S_l, and S 2^-k1 features -> this wave's LDS buffer
 // (the shared layer-1 constant carries no 2^k1).
@@ -868,6 +868,58 @@ __device__ __forceinline__ float q_mean(const float *__restrict__ lds, const f32
     }
     part = sum_rows4(part);                     // the four row groups' shares of action `col`
     return part * (sc.invS3 * (1.0f / K_TAUS)) + lds[OFF_B4 + col];
+}
+
+// act_eval's output (QUANT = true), shared by iqn_qvals_split_kernel and the IQN episode launch that records what it chose from
+// (mn_rollout_iqn_eval.hip): quantile values Z(tau, a) = W4 h3(tau) + b4 (model.py:185) -- layer 3 epilogue + split, then the output layer as
+// 12 MFMAs on a padded 16-row tile (operands at OFF_W4H); lane (g, col) ends up with actions 4 g + r of tau 16 nt + col (scaled by S 2^k4) and writes
+// them to `quant` ([32][9] of this environment; NULL: not written).  Returns Q(s, a) = the mean over the 32 taus in lane a (< 9).
+__device__ __forceinline__ float q_quantiles(const float *__restrict__ lds, const f32x4 *__restrict__ ldsv, const LdsBase &lb, const f32x4 (&acc3)[4][NT],
+                                             float c3e, const EnvScale &sc, int lane, float *__restrict__ quant) {
+    const int g = lane >> 4, col = lane & 15;
+    f16x8 b4h[2][NT], b4l[2][NT];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+        const f32x4 sb0 = ldsv[lb.fl + ((OFF_B3 - OFF_B1) >> 2) + 4 * (2 * kb)] * sc.S3, sb1 = ldsv[lb.fl + ((OFF_B3 - OFF_B1) >> 2) + 4 * (2 * kb + 1)] * sc.S3;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+            split_tiles(relu4s(fma4(acc3[2 * kb][nt], c3e, sb0)), relu4s(fma4(acc3[2 * kb + 1][nt], c3e, sb1)), b4h[kb][nt], b4l[kb][nt]);
+    }
+    f32x4 acc4[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) acc4[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const u32x4 *w4 = reinterpret_cast<const u32x4 *>(lds + OFF_W4H);
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+        const f16x8 ah = __builtin_bit_cast(f16x8, w4[(kb * 2) * 64 + lane]), al = __builtin_bit_cast(f16x8, w4[(kb * 2 + 1) * 64 + lane]);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            acc4[nt] = mf(al, b4h[kb][nt], acc4[nt]);
+            acc4[nt] = mf(ah, b4l[kb][nt], acc4[nt]);
+            acc4[nt] = mf(ah, b4h[kb][nt], acc4[nt]);
+        }
+    }
+    const float unscale = sc.invS3 * lds[OFF_CST + 8];    // 1 / (S3 2^k4)
+    const f32x4 b4 = ldsv[(OFF_B4 >> 2) + g];
+    float mine = 0.f;      // lane `a` (< 9) ends up with Q(s, a) = mean over the 32 taus
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int a_idx = 4 * g + r;
+        float sum = 0.f;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const float z = fmaf(acc4[nt][r], unscale, b4[r]);
+            if (quant && a_idx < A_OUT) quant[(16 * nt + col) * A_OUT + a_idx] = z;
+            sum += z;
+        }
+        sum = row_sum16(sum);                    // over the 16 tau columns of the row group
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {         // hand action 4 gg + r to lane (4 gg + r)
+            const float v = __shfl(sum, 16 * gg);
+            if (lane == 4 * gg + r) mine = v;
+        }
+    }
+    return mine * (1.0f / K_TAUS);
 }
 
 // QUANT = false: acting / training (tau mean before the linear output layer, f32 VALU mat-vec).
@@ -1109,51 +1161,8 @@ __global__ __launch_bounds__(64 * NW) void iqn_qvals_split_kernel(const float *_
             part = sum_rows4(part);                     // the four row groups' shares of action `col`
             qv = part * (sc.invS3 * (1.0f / K_TAUS)) + lds[OFF_B4 + col];     // Q(s, action = col), valid for col < 9
         } else {
-            // ---- quantile values Z(tau, a) = W4 h3(tau) + b4 (model.py:185): layer 3 epilogue + split, then the output layer as 12 MFMAs
-            // on a padded 16-row tile; lane (g, col) ends up with actions 4 g + r of tau 16 nt + col (scaled by S 2^k4)
-            f16x8 b4h[2][NT], b4l[2][NT];
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-                const f32x4 sb0 = ldsv[lb.fl + ((OFF_B3 - OFF_B1) >> 2) + 4 * (2 * kb)] * sc.S3, sb1 = ldsv[lb.fl + ((OFF_B3 - OFF_B1) >> 2) + 4 * (2 * kb + 1)] * sc.S3;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    split_tiles(relu4s(fma4(acc3[2 * kb][nt], c3e, sb0)), relu4s(fma4(acc3[2 * kb + 1][nt], c3e, sb1)), b4h[kb][nt], b4l[kb][nt]);
-            }
-            f32x4 acc4[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc4[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            const u32x4 *w4 = reinterpret_cast<const u32x4 *>(lds + OFF_W4H);
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-                const f16x8 ah = __builtin_bit_cast(f16x8, w4[(kb * 2) * 64 + lane]), al = __builtin_bit_cast(f16x8, w4[(kb * 2 + 1) * 64 + lane]);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    acc4[nt] = mf(al, b4h[kb][nt], acc4[nt]);
-                    acc4[nt] = mf(ah, b4l[kb][nt], acc4[nt]);
-                    acc4[nt] = mf(ah, b4h[kb][nt], acc4[nt]);
-                }
-            }
-            const float unscale = sc.invS3 * lds[OFF_CST + 8];    // 1 / (S3 2^k4)
-            const f32x4 b4 = ldsv[(OFF_B4 >> 2) + g];
-            float mine = 0.f;      // lane `a` (< 9) ends up with Q(s, a) = mean over the 32 taus
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int a_idx = 4 * g + r;
-                float sum = 0.f;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const float z = fmaf(acc4[nt][r], unscale, b4[r]);
-                    if (a_idx < A_OUT) quantiles[((size_t)e * K_TAUS + 16 * nt + col) * A_OUT + a_idx] = z;
-                    sum += z;
-                }
-                sum = row_sum16(sum);                    // over the 16 tau columns of the row group
-#pragma unroll
-                for (int gg = 0; gg < 4; ++gg) {         // hand action 4 gg + r to lane (4 gg + r)
-                    const float v = __shfl(sum, 16 * gg);
-                    if (lane == 4 * gg + r) mine = v;
-                }
-            }
-            qv = mine * (1.0f / K_TAUS);
+            // ---- quantile values Z(tau, a), written out, and their tau mean (q_quantiles)
+            qv = q_quantiles(lds, ldsv, lb, acc3, c3e, sc, lane, quantiles + (size_t)e * K_TAUS * A_OUT);
         }
         if (qvals && lane < A_OUT) qvals[(size_t)e * A_OUT + lane] = qv;
         // ---- IQNAgent.act epilogue (agent.py:199-203): argmax, epsilon-greedy ------------------------

@@ -22,6 +22,8 @@ struct mn_handle {
     int32_t *list_scratch = nullptr;
     double *peek_scratch = nullptr;
     double *obs64_buf = nullptr, *rew64_buf = nullptr;      // mn_enable_obs64: A.obs64 / A.rew64 point here while enabled
+    double *traj_trace = nullptr;                           // mn_set_trajectory_trace: the caller's [traj_trace_steps][n][N][2] buffer, until the next episode launch takes it
+    int32_t traj_trace_steps = 0, traj_trace_sub = 0;
     int device = -1;      // HIP device the handle's memory lives on (the caller's current device at mn_create)
     // profiling
     std::vector<hipEvent_t> ev;
@@ -373,11 +375,40 @@ static int launch_episodes(mn_handle *h, hipStream_t s, Launch launch) {
     return launch_episodes(h, s, [] { return MN_OK; }, launch);
 }
 
+// The sub-step trajectory trace an episode entry point launches with: the attachment of mn_set_trajectory_trace, detached here whatever the outcome
+// (*out = NULL: none).  One that is too short for the launch, or whose sub-step count is no longer the handle's N, is refused.
+static int take_traj_trace(mn_handle *h, int32_t n_steps, double **out) {
+    double *t = h->traj_trace;
+    const int32_t steps = h->traj_trace_steps, sub = h->traj_trace_sub;
+    h->traj_trace = nullptr;
+    h->traj_trace_steps = 0;
+    *out = nullptr;
+    if (!t) return MN_OK;
+    if (h->params.precision != MN_PRECISION_F64) return fail(h, MN_ERR_INVALID, "sub-step trajectories are recorded only with MN_PRECISION_F64");
+    if (n_steps > steps) return fail(h, MN_ERR_INVALID, "the attached trajectory trace has fewer steps than the launch");
+    if (sub != h->P.N) return fail(h, MN_ERR_INVALID, "the attached trajectory trace was sized for another robot N");
+    *out = t;
+    return MN_OK;
+}
+
+extern "C" int mn_set_trajectory_trace(mn_handle *h, double *traj_trace_dev, int32_t n_steps, int32_t n_substeps) {
+    if (!h) return MN_ERR_INVALID;
+    if (!traj_trace_dev) { h->traj_trace = nullptr; h->traj_trace_steps = 0; return MN_OK; }      // detach
+    if (h->params.precision != MN_PRECISION_F64) return fail(h, MN_ERR_INVALID, "sub-step trajectories are recorded only with MN_PRECISION_F64");
+    if (n_steps < 1) return fail(h, MN_ERR_INVALID, "mn_set_trajectory_trace: n_steps < 1");
+    if (n_substeps != h->P.N) return fail(h, MN_ERR_INVALID, "mn_set_trajectory_trace: n_substeps must be the handle's robot N");
+    h->traj_trace = traj_trace_dev;
+    h->traj_trace_steps = n_steps;
+    h->traj_trace_sub = n_substeps;
+    return MN_OK;
+}
+
 extern "C" int mn_rollout(mn_handle *h, int32_t n_steps, const int32_t *actions_dev, uint64_t action_seed,
                           uint64_t first_step_index, uint64_t first_env_index, float *obs_dev, float *obs_trace_dev,
                           float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev,
                           int32_t *action_trace_dev, void *stream) {
     if (!h || !obs_dev || n_steps < 1) return MN_ERR_INVALID;
+    if (h->traj_trace) return fail(h, MN_ERR_INVALID, "mn_rollout records no trajectory trace: detach it (mn_set_trajectory_trace(h, NULL, 0, 0))");
     hipStream_t s = (hipStream_t)stream;
     return launch_episodes(h, s, [&] {
         mn_launch_rollout(h->A, h->P, h->params.precision, h->params.rollout_lanes, n_steps, actions_dev, action_seed, first_step_index,
@@ -387,11 +418,41 @@ extern "C" int mn_rollout(mn_handle *h, int32_t n_steps, const int32_t *actions_
 
 extern "C" int mn_rollout_policy(mn_handle *h, int32_t n_steps, int32_t policy, float *obs_dev, float *obs_trace_dev, float *reward_trace_dev,
                                  uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev, void *stream) {
-    if (!h || !obs_dev || n_steps < 1 || (policy != MN_POLICY_APF && policy != MN_POLICY_BA)) return MN_ERR_INVALID;
+    if (!h) return MN_ERR_INVALID;
+    double *traj = nullptr;
+    const int trc = take_traj_trace(h, n_steps, &traj);      // first: the attachment is consumed even by a call refused below
+    if (!obs_dev || n_steps < 1 || (policy != MN_POLICY_APF && policy != MN_POLICY_BA)) return MN_ERR_INVALID;
+    if (trc) return trc;
     hipStream_t s = (hipStream_t)stream;
     return launch_episodes(h, s, [&] {
         mn_launch_rollout_policy(h->A, h->P, h->params.precision, n_steps, policy, obs_dev, obs_trace_dev, reward_trace_dev, done_trace_dev,
-                                 info_trace_dev, action_trace_dev, s);
+                                 info_trace_dev, action_trace_dev, traj, s);
+    });
+}
+
+// mn_rollout_iqn_rows and mn_rollout_iqn_eval: one routine, the acting kernel or -- `eval` -- act_eval's with its two traces
+static int rollout_iqn(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weights, int32_t n_steps, uint64_t *rng_state_dev, float cvar, int32_t adaptive,
+                       const float *cvar_row_dev, const uint8_t *adaptive_row_dev, float *obs_dev, float *obs_trace_dev, float *reward_trace_dev,
+                       uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev, float *cvar_trace_dev, float *q_trace_dev, bool eval,
+                       float *quantiles_trace_dev, float *taus_trace_dev, int32_t *steps_run_dev, void *stream) {
+    if (!h) return MN_ERR_INVALID;
+    double *traj = nullptr;
+    const int trc = take_traj_trace(h, n_steps, &traj);      // first: the attachment is consumed even by a call refused below
+    if (!ctx || !weights || !rng_state_dev || !obs_dev || n_steps < 1) return MN_ERR_INVALID;      // (the 14 pointers of `weights`: mn_iqn_rollout_image)
+    if ((long)h->A.n * 32 >= (1L << 32)) return MN_ERR_INVALID;      // 32-bit draw index, as mn_iqn_act_rng
+    if (trc) return trc;
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t *image = nullptr;
+    uint32_t *words = nullptr;
+    return launch_episodes(h, s, [&] { return mn_iqn_rollout_image(ctx, weights, s, &image, &words); }, [&] {
+        if (eval)
+            mn_launch_rollout_iqn_eval(h->A, h->P, h->params.precision, n_steps, image, rng_state_dev, cvar, adaptive ? 1 : 0, cvar_row_dev, adaptive_row_dev, obs_dev,
+                                       obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev, action_trace_dev, cvar_trace_dev, q_trace_dev, traj,
+                                       quantiles_trace_dev, taus_trace_dev, words, steps_run_dev, s);
+        else
+            mn_launch_rollout_iqn_rows(h->A, h->P, h->params.precision, n_steps, image, rng_state_dev, cvar, adaptive ? 1 : 0, cvar_row_dev, adaptive_row_dev, obs_dev,
+                                       obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev, action_trace_dev, cvar_trace_dev, q_trace_dev, traj, words,
+                                       steps_run_dev, s);
     });
 }
 
@@ -399,16 +460,17 @@ extern "C" int mn_rollout_iqn_rows(mn_handle *h, mn_iqn_ctx *ctx, const float *c
                                    int32_t adaptive, const float *cvar_row_dev, const uint8_t *adaptive_row_dev, float *obs_dev, float *obs_trace_dev,
                                    float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev, float *cvar_trace_dev,
                                    float *q_trace_dev, int32_t *steps_run_dev, void *stream) {
-    if (!h || !ctx || !weights || !rng_state_dev || !obs_dev || n_steps < 1) return MN_ERR_INVALID;      // (the 14 pointers of `weights`: mn_iqn_rollout_image)
-    if ((long)h->A.n * 32 >= (1L << 32)) return MN_ERR_INVALID;      // 32-bit draw index, as mn_iqn_act_rng
-    hipStream_t s = (hipStream_t)stream;
-    const uint32_t *image = nullptr;
-    uint32_t *words = nullptr;
-    return launch_episodes(h, s, [&] { return mn_iqn_rollout_image(ctx, weights, s, &image, &words); }, [&] {
-        mn_launch_rollout_iqn_rows(h->A, h->P, h->params.precision, n_steps, image, rng_state_dev, cvar, adaptive ? 1 : 0, cvar_row_dev, adaptive_row_dev, obs_dev,
-                                   obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev, action_trace_dev, cvar_trace_dev, q_trace_dev, words,
-                                   steps_run_dev, s);
-    });
+    return rollout_iqn(h, ctx, weights, n_steps, rng_state_dev, cvar, adaptive, cvar_row_dev, adaptive_row_dev, obs_dev, obs_trace_dev, reward_trace_dev,
+                       done_trace_dev, info_trace_dev, action_trace_dev, cvar_trace_dev, q_trace_dev, false, nullptr, nullptr, steps_run_dev, stream);
+}
+
+extern "C" int mn_rollout_iqn_eval(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weights, int32_t n_steps, uint64_t *rng_state_dev, float cvar,
+                                   int32_t adaptive, const float *cvar_row_dev, const uint8_t *adaptive_row_dev, float *obs_dev, float *obs_trace_dev,
+                                   float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev, float *cvar_trace_dev,
+                                   float *q_trace_dev, float *quantiles_trace_dev, float *taus_trace_dev, int32_t *steps_run_dev, void *stream) {
+    return rollout_iqn(h, ctx, weights, n_steps, rng_state_dev, cvar, adaptive, cvar_row_dev, adaptive_row_dev, obs_dev, obs_trace_dev, reward_trace_dev,
+                       done_trace_dev, info_trace_dev, action_trace_dev, cvar_trace_dev, q_trace_dev, true, quantiles_trace_dev, taus_trace_dev, steps_run_dev,
+                       stream);
 }
 
 extern "C" int mn_rollout_iqn(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weights, int32_t n_steps, uint64_t *rng_state_dev, float cvar,
@@ -422,12 +484,16 @@ extern "C" int mn_rollout_iqn(mn_handle *h, mn_iqn_ctx *ctx, const float *const 
 extern "C" int mn_rollout_dqn(mn_handle *h, const float *const *weights, float *image_dev, int32_t repack, int32_t n_steps, float *obs_dev,
                               float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev,
                               float *q_trace_dev, void *stream) {
-    if (!h || !weights || !image_dev || !obs_dev || n_steps < 1) return MN_ERR_INVALID;
+    if (!h) return MN_ERR_INVALID;
+    double *traj = nullptr;
+    const int trc = take_traj_trace(h, n_steps, &traj);      // first: the attachment is consumed even by a call refused below
+    if (!weights || !image_dev || !obs_dev || n_steps < 1) return MN_ERR_INVALID;
     for (int i = 0; i < 18; ++i) if (!weights[i]) return MN_ERR_INVALID;
+    if (trc) return trc;
     hipStream_t s = (hipStream_t)stream;
     return launch_episodes(h, s, [&] { if (repack) mn_launch_dqn_pack(weights, image_dev, s); return MN_OK; }, [&] {
         mn_launch_rollout_dqn(h->A, h->P, h->params.precision, n_steps, image_dev, obs_dev, obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev,
-                              action_trace_dev, q_trace_dev, s);
+                              action_trace_dev, q_trace_dev, traj, s);
     });
 }
 

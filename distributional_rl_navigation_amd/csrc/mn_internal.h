@@ -102,19 +102,25 @@ void mn_launch_rollout(const MnArrays &A, const MnDev &P, int precision, int lan
 void mn_launch_random_actions(uint64_t seed, uint64_t step, uint64_t env0, int n, int32_t *out, hipStream_t s);
 // episodes under a device-side policy (MN_POLICY_APF / MN_POLICY_BA, mn_planners.h), and one policy step for a vector of observations
 void mn_launch_rollout_policy(const MnArrays &A, const MnDev &P, int precision, int n_steps, int policy, float *obs_io, float *obs_trace,
-                              float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, hipStream_t s);
+                              float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, double *traj_trace, hipStream_t s);
 void mn_launch_planner_act(const float *obs, int n, int policy, const double *a, const double *w, int32_t *actions, hipStream_t s);
 // IQN evaluation episodes in one launch (mn_rollout_iqn.hip); `image` / `words` from mn_iqn_rollout_image (iqn_act.hip)
 // cvar_row / adaptive_row: per-env cvar / adaptive flags ([n] device arrays; NULL = the scalar)
+// traj_trace (here and in the policy / DQN launches): [n_steps][n][P.N][2] sub-step positions (mn_set_trajectory_trace), or NULL
 void mn_launch_rollout_iqn_rows(const MnArrays &A, const MnDev &P, int precision, int n_steps, const uint32_t *image, uint64_t *rng_state, float cvar,
                                 int adaptive, const float *cvar_row, const uint8_t *adaptive_row, float *obs_io, float *obs_trace, float *reward_trace,
-                                uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *cvar_trace, float *q_trace, uint32_t *words,
-                                int32_t *steps_run, hipStream_t s);
+                                uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *cvar_trace, float *q_trace, double *traj_trace,
+                                uint32_t *words, int32_t *steps_run, hipStream_t s);
+// the same episodes acting as act_eval does, with the quantile / tau traces (mn_rollout_iqn_eval.hip)
+void mn_launch_rollout_iqn_eval(const MnArrays &A, const MnDev &P, int precision, int n_steps, const uint32_t *image, uint64_t *rng_state, float cvar,
+                                int adaptive, const float *cvar_row, const uint8_t *adaptive_row, float *obs_io, float *obs_trace, float *reward_trace,
+                                uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *cvar_trace, float *q_trace, double *traj_trace,
+                                float *quantiles_trace, float *taus_trace, uint32_t *words, int32_t *steps_run, hipStream_t s);
 int mn_iqn_rollout_image(mn_iqn_ctx *c, const float *const *weights, hipStream_t s, const uint32_t **image, uint32_t **words);
 // DQN evaluation episodes in one launch (mn_rollout_dqn.hip); `image` = the weight image mn_launch_dqn_pack (dqn_act.hip) builds from weights[18]
 void mn_launch_dqn_pack(const float *const *weights, float *image_dev, hipStream_t s);
 void mn_launch_rollout_dqn(const MnArrays &A, const MnDev &P, int precision, int n_steps, const float *image, float *obs_io, float *obs_trace,
-                           float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *q_trace, hipStream_t s);
+                           float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *q_trace, double *traj_trace, hipStream_t s);
 // mode 0: full reset (RNG); mode 1: pose-only (keeps the loaded world, no RNG)
 // (mn_launch_reset: `sharded` = count_dev / list_dev are the handle's done-queue of one step -- MN_QSHARDS counters and lists; otherwise one counter, one list)
 void mn_launch_reset_under_act(const MnArrays &A, const MnDev &P, int precision, const uint32_t *count_dev, const int32_t *list_dev, float *obs,

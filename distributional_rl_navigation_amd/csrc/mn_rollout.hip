@@ -128,7 +128,8 @@ __global__ __launch_bounds__(MN_WAVE, MN_ROLLOUT_MIN_WAVES(L)) void mn_rollout_k
 // done 1, the terminal info code, action -1), its terminal pose and counters are stored.  Per step the same MnLane::step as everywhere else:
 // bit-identical to a loop of (policy launch, mn_step) on the same worlds.
 template <typename M, bool PARITY, int L>
-__global__ __launch_bounds__(MN_WAVE, 1) void mn_rollout_policy_kernel(MnArrays A, MnDev P, int n_steps, int policy, float *__restrict__ obs_io, MnTrace T) {
+__global__ __launch_bounds__(MN_WAVE, 1) void mn_rollout_policy_kernel(MnArrays A, MnDev P, int n_steps, int policy, float *__restrict__ obs_io, MnTrace T,
+                                                                       double *__restrict__ traj_trace) {
     __shared__ float rows[MN_WAVE / L][28];
     using Lane = MnLane<M, PARITY, L>;
     const int tid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -152,6 +153,9 @@ __global__ __launch_bounds__(MN_WAVE, 1) void mn_rollout_policy_kernel(MnArrays 
         action = __shfl(action, (int)(threadIdx.x & (MN_WAVE - 1)) - q);      // from the group's lane 0
         __syncthreads();      // every lane has its action before the step overwrites the row
         float *trow = T.obs ? T.obs + ((size_t)t * n + (ln.active ? e : 0)) * MN_OBS_DIM : nullptr;
+        // traj_trace [T][n][N][2] (mn_set_trajectory_trace): the step body records env e's N sub-step positions at [e][s] of this step's slice while the env is alive
+        if constexpr (PARITY)
+            if (traj_trace) { A.traj = alive ? traj_trace + (size_t)t * n * (size_t)P.N * 2 : nullptr; A.traj_n = P.N; }
         const MnStepOut o = ln.template step<false>(A, P, action, rows[slot], (PARITY && A.obs64 && alive) ? A.obs64 + (size_t)e * MN_OBS_DIM : nullptr, none,
                                                     nullptr, nullptr, (alive && trow) ? trow : nullptr);
         if (ln.active && q == 0) {
@@ -248,12 +252,12 @@ extern "C" int mn_debug_rollout_phases(unsigned long long *out_host, int reset) 
 #endif
 
 void mn_launch_rollout_policy(const MnArrays &A, const MnDev &P, int precision, int n_steps, int policy, float *obs_io, float *obs_trace,
-                              float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, hipStream_t s) {
+                              float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, double *traj_trace, hipStream_t s) {
     const MnTrace T = {obs_trace, reward_trace, done_trace, info_trace, action_trace};
     constexpr int LL = 8;      // eight lanes per env: the sweeps this serves are a few hundred to a few thousand envs, latency-bound per wave
     const dim3 grid((unsigned)((size_t)A.npad * LL / MN_WAVE));
-    if (precision == MN_PRECISION_F64) hipLaunchKernelGGL((mn_rollout_policy_kernel<double, true, LL>), grid, dim3(MN_WAVE), 0, s, A, P, n_steps, policy, obs_io, T);
-    else hipLaunchKernelGGL((mn_rollout_policy_kernel<float, false, LL>), grid, dim3(MN_WAVE), 0, s, A, P, n_steps, policy, obs_io, T);
+    if (precision == MN_PRECISION_F64) hipLaunchKernelGGL((mn_rollout_policy_kernel<double, true, LL>), grid, dim3(MN_WAVE), 0, s, A, P, n_steps, policy, obs_io, T, traj_trace);
+    else hipLaunchKernelGGL((mn_rollout_policy_kernel<float, false, LL>), grid, dim3(MN_WAVE), 0, s, A, P, n_steps, policy, obs_io, T, traj_trace);
 }
 
 void mn_launch_planner_act(const float *obs, int n, int policy, const double *a, const double *w, int32_t *actions, hipStream_t s) {

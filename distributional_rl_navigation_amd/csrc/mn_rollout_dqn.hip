@@ -26,6 +26,7 @@ struct DqnTrace {
     uint8_t *info;     // [T][n]     the terminal code once finished
     int32_t *action;   // [T][n]     -1 once finished
     float *q;          // [T][n][9]  Q(s, .) the action was chosen from (not written once finished)
+    double *traj;      // [T][n][N][2] the step's sub-step positions (mn_set_trajectory_trace; float64 handles; not written once finished)
 };
 
 template <typename M, bool PARITY, int L>
@@ -77,6 +78,8 @@ __global__ __launch_bounds__(MN_WAVE, 1) void mn_rollout_dqn_kernel(MnArrays A, 
         __syncthreads();      // every lane has read the rows before the step overwrites them
         // ---- step
         float *trow = T.obs ? T.obs + ((size_t)t * n + (ln.active ? e : 0)) * MN_OBS_DIM : nullptr;
+        if constexpr (PARITY)      // the step body records env e's N sub-step positions at [e][s] of this step's slice while the env is alive
+            if (T.traj) { A.traj = alive ? T.traj + (size_t)t * n * (size_t)P.N * 2 : nullptr; A.traj_n = P.N; }
         const MnStepOut o = ln.template step<false>(A, P, action, rows[slot], (PARITY && A.obs64 && alive) ? A.obs64 + (size_t)e * MN_OBS_DIM : nullptr, none,
                                                     nullptr, nullptr, (alive && trow) ? trow : nullptr);
         if (ln.active && q == 0) {
@@ -117,8 +120,8 @@ __global__ __launch_bounds__(MN_WAVE, 1) void mn_rollout_dqn_kernel(MnArrays A, 
 }  // namespace
 
 void mn_launch_rollout_dqn(const MnArrays &A, const MnDev &P, int precision, int n_steps, const float *image, float *obs_io, float *obs_trace,
-                           float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *q_trace, hipStream_t s) {
-    const DqnTrace T = {obs_trace, reward_trace, done_trace, info_trace, action_trace, q_trace};
+                           float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *q_trace, double *traj_trace, hipStream_t s) {
+    const DqnTrace T = {obs_trace, reward_trace, done_trace, info_trace, action_trace, q_trace, traj_trace};
     constexpr int LL = 8;
     const dim3 grid((unsigned)((A.n + MN_WAVE / LL - 1) / (MN_WAVE / LL)));      // (npad is a multiple of 256: the last wave's idle lane groups load padding)
     const size_t lds_bytes = IMAGE_FLOATS * sizeof(float);

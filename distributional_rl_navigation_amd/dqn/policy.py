@@ -131,7 +131,8 @@ class DQNPolicy(nn.Module):
         """Every env's CURRENT episode of `env` (a VecMarineNavEnv) under this greedy policy for up to `n_steps` steps in ONE launch (C-ABI
         mn_rollout_dqn): per step what `act_batch(env.obs)` chooses, then the env step -- bit-identical to that loop.  No resets: a finished env idles
         (reward 0, done 1, terminal info, action -1 in the traces; its obs / Q entries stay 0 / NaN); an env still alive afterwards continues with the
-        next call.  Returns the requested traces ([n_steps][n]; "obs" [n_steps][n][26], "q" [n_steps][n][9]) and `final_obs`, or None where the fused
+        next call.  Returns the requested traces ([n_steps][n]; "obs" [n_steps][n][26], "q" [n_steps][n][9], "traj" [n_steps][n][N][2] float64: the sub-step
+        positions of every step while the env is alive, f64 envs) and `final_obs`, or None where the fused
         act kernel would not run either (CPU, another net_arch, use_fused_act = False): the caller runs the loop instead."""
         import ctypes as C
         from .. import _capi
@@ -140,8 +141,9 @@ class DQNPolicy(nn.Module):
             return None
         T, n, dev = int(n_steps), env.n_envs, env.device
         st, repack = self._image(dev)
-        tr = trace_buffers(T, n, dev, trace, obs_dim=self.state_size, n_actions=self.action_size)
+        tr = trace_buffers(T, n, dev, trace, obs_dim=self.state_size, n_actions=self.action_size, n_substeps=int(env.params.N))
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        env.set_trajectory_trace(tr.get("traj"))
         rc = _capi.lib().mn_rollout_dqn(env.h, st["ptrs"], p(st["image"]), int(repack), T, p(env.obs), p(tr.get("obs")), p(tr.get("reward")),
                                         p(tr.get("done")), p(tr.get("info")), p(tr.get("action")), p(tr.get("q")), env._stream())
         if rc:

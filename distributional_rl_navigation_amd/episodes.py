@@ -2,7 +2,7 @@
 
 Evaluation episodes are produced either by one HIP launch (VecMarineNavEnv.rollout_policy, iqn.fused_act.rollout_iqn, DQNPolicy.rollout) or by
 the per-step Python loop (`loop_episodes`).  Both give the same `[T][n]` traces -- reward, done, info, action, with a finished env idling at
-reward 0, done 1, its terminal info code and action -1 -- and `tally` turns traces into the discounted return, energy, length, last info code and
+reward 0, done 1, its terminal info code and action -1; for captured episodes also traj and, for IQN, cvar / quantiles / taus (`capture_lists`) -- and `tally` turns traces into the discounted return, energy, length, last info code and
 action list of every env.  The consumers (IQNAgent.evaluation_vec, train_dqn.evaluate, experiments.run_experiment) only format what it returns.
 Plain numpy and torch: nothing here needs the HIP library, so all of it runs on a machine without a GPU.
 """
@@ -18,13 +18,19 @@ _TRACES = dict(obs=(("obs_dim",), torch.float32, 0.0),
                info=((), torch.uint8, None),
                action=((), torch.int32, None),
                cvar=((), torch.float32, float("nan")),
-               q=(("n_actions",), torch.float32, float("nan")))
+               q=(("n_actions",), torch.float32, float("nan")),
+               # what an IQN action was chosen from (act_eval's quantile values and taus: rollout_iqn(want_quantiles=True)) and the sub-step positions of a step
+               quantiles=(("n_taus", "n_actions"), torch.float32, float("nan")),
+               taus=(("n_taus",), torch.float32, float("nan")),
+               traj=(("n_substeps", "xy"), torch.float64, float("nan")))
 
 
-def trace_buffers(T, n, device, names, fill=True, obs_dim=26, n_actions=9):
-    """The `[T][n]` trace tensors `names` of one episode producer.  The entries a finished env never writes start as obs 0, cvar / q NaN; with
-    `fill=False` nothing is initialised (VecMarineNavEnv.rollout resets its envs and writes every row)."""
-    dims = dict(obs_dim=obs_dim, n_actions=n_actions)
+def trace_buffers(T, n, device, names, fill=True, obs_dim=26, n_actions=9, n_taus=32, n_substeps=None):
+    """The `[T][n]` trace tensors `names` of one episode producer.  The entries a finished env never writes start as obs 0, cvar / q / quantiles /
+    taus / traj NaN; with `fill=False` nothing is initialised (VecMarineNavEnv.rollout resets its envs and writes every row).  "traj"
+    ([T][n][n_substeps][2] float64) needs `n_substeps`, the robot's N."""
+    dims = dict(obs_dim=obs_dim, n_actions=n_actions, n_taus=n_taus, n_substeps=n_substeps, xy=2)
+    assert "traj" not in names or n_substeps, "the traj trace needs n_substeps"
     out = {}
     for k in names:
         tail, dtype, init = _TRACES[k]
@@ -68,6 +74,23 @@ def tally(reward, done, info, action, discount, energy_tab):
     return dict(ret=ret, energy=energy, length=length, last_info=last_info, actions=[by_env[i, :length[i]].tolist() for i in range(n)])
 
 
+def capture_lists(tr, length):
+    """What the reference's robot accumulates over an episode, per env, from the numpy traces `tr` of n episodes and `tally`'s `length` [n]: a list of
+    n dicts with `action_history` (L actions) and `trajectory` (N x L sub-step positions [x, y], from "traj" [T][n][N][2]) and -- when `tr` has
+    "quantiles" -- the IQN policies' `actions_cvars` (L), `actions_quantiles` (L x [1][32][9]) and `actions_taus` (L x [1][32][1]), L = the env's
+    length.  Plain Python numbers throughout (JSON); rows behind an env's end are not looked at."""
+    iqn = "quantiles" in tr
+    out = []
+    for i, L in enumerate(int(l) for l in length):
+        d = {"action_history": tr["action"][:L, i].tolist(), "trajectory": tr["traj"][:L, i].reshape(-1, 2).tolist()}
+        if iqn:
+            d["actions_cvars"] = tr["cvar"][:L, i].tolist()
+            d["actions_quantiles"] = tr["quantiles"][:L, i][:, None].tolist()            # each [1][32][9], as act_eval returns
+            d["actions_taus"] = tr["taus"][:L, i][:, None, :, None].tolist()             # each [1][32][1]
+        out.append(d)
+    return out
+
+
 @torch.no_grad()
 def loop_episodes(env, obs, act, max_steps, after_step=None):
     """The per-step twin of the episode launches: from the observations `obs` [n][26], up to `max_steps` times `a = act(t, obs)` (int32 [n]) and
@@ -98,9 +121,9 @@ def loop_episodes(env, obs, act, max_steps, after_step=None):
     return out
 
 
-def host_traces(tr):
-    """The four bookkeeping traces of an episode producer's result as numpy arrays: `done` first, then of the others only the `steps_run(done)`
-    rows that `tally` looks at (a launch writes all T rows however early its last episode ends)."""
+def host_traces(tr, also=()):
+    """The four bookkeeping traces of an episode producer's result (and those named in `also`) as numpy arrays: `done` first, then of the others only
+    the `steps_run(done)` rows that `tally` looks at (a launch writes all T rows however early its last episode ends)."""
     done = tr["done"].cpu().numpy()
     T = steps_run(done)
-    return dict({k: tr[k][:T].cpu().numpy() for k in EPISODE_TRACES if k != "done"}, done=done[:T])
+    return dict({k: tr[k][:T].cpu().numpy() for k in EPISODE_TRACES + tuple(also) if k != "done"}, done=done[:T])

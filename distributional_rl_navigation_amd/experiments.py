@@ -6,15 +6,33 @@ time on the CPU (`exp_setup_5`: fixed start (5,5) / goal (45,45), `set_boundary 
 Here the worlds are generated once from the same RNG stream (bit-identical to the reference's), replicated
 per policy into ONE vector env and all 500 x 5 episodes are stepped side by side on the GPU.
 """
+import contextlib
+import time
+
+import numpy as np
 import torch
 
-from .episodes import EPISODE_TRACES, energy_table, host_traces, loop_episodes, tally
+from .episodes import EPISODE_TRACES, capture_lists, energy_table, host_traces, loop_episodes, tally
 from .marinenav_env.vec_env import VecMarineNavEnv
 from .planners import planner_act_batch
 
 POLICIES = ("adaptive_IQN", "IQN_0.25", "IQN_0.5", "IQN_0.75", "IQN_1.0", "APF", "BA")   # run_experiments.py:216 (minus DQN)
 ALL_POLICIES = POLICIES[:5] + ("DQN",) + POLICIES[5:]                                        # run_experiments.py:216, needs `dqn=`
 _CVAR = {"IQN_0.25": 0.25, "IQN_0.5": 0.5, "IQN_0.75": 0.75, "IQN_1.0": 1.0}
+
+
+@contextlib.contextmanager
+def _producing(timings, device):
+    """run_experiment(timings=...): the wall seconds of a trace-producing phase -- from its first launch until its traces are complete on the device --
+    are added to timings["traces_s"]."""
+    if timings is None:
+        yield
+        return
+    torch.cuda.synchronize(device)
+    t0 = time.perf_counter()
+    yield
+    torch.cuda.synchronize(device)
+    timings["traces_s"] = timings.get("traces_s", 0.0) + time.perf_counter() - t0
 
 
 def _configure(env):
@@ -37,10 +55,14 @@ def generate_worlds(num, n_obs, n_cores, seed=15, device="cuda:0"):
     return worlds
 
 
-def _episode_record(world, params, name, actions, traj, cvars=None, quantiles=None, taus=None, seed=15):
+CAPTURE_TRACES = ("traj",)                                   # what `capture` adds to EPISODE_TRACES for every policy ...
+IQN_CAPTURE_TRACES = ("cvar", "quantiles", "taus")           # ... and for the IQN policies (act_eval's outputs)
+
+
+def _episode_record(world, params, lists, seed=15):
     """One `ep_data` entry of the reference's exp_data JSON: MarineNavEnv.episode_data() (marinenav_env.py:557-622) of
     the finished episode plus, for the IQN policies, robot.actions_cvars / actions_quantiles / actions_taus
-    (run_experiments.py:62-69)."""
+    (run_experiments.py:62-69).  `lists`: the episode's entry of `episodes.capture_lists`."""
     p = params
     ep = {"env": {}, "robot": {}}
     e = ep["env"]
@@ -58,20 +80,25 @@ def _episode_record(world, params, name, actions, traj, cvars=None, quantiles=No
     ep["robot"] = {"dt": p.dt, "N": p.N, "length": 1.0, "width": 0.5, "r": p.robot_r, "max_speed": p.max_speed,
                    "a": [p.a[0], p.a[1], p.a[2]], "w": [p.w[0], p.w[1], p.w[2]],
                    "init_theta": float(world["init_theta"]), "init_speed": float(world["init_speed"]),
-                   "sonar": {"range": p.sonar_range, "angle": p.sonar_angle, "num_beams": p.num_beams},
-                   "action_history": [int(a) for a in actions], "trajectory": [[float(q[0]), float(q[1])] for q in traj]}
-    if cvars is not None:
-        ep["robot"]["actions_cvars"] = [float(v) for v in cvars]
-        ep["robot"]["actions_quantiles"] = [q.tolist() for q in quantiles]       # each [1][32][9], as act_eval returns
-        ep["robot"]["actions_taus"] = [t.tolist() for t in taus]                 # each [1][32][1]
+                   "sonar": {"range": p.sonar_range, "angle": p.sonar_angle, "num_beams": p.num_beams}}
+    ep["robot"].update(lists)
     return ep
 
 
-def _records_from_traces(tr, params, names, num, launch_s=None, step_s=None):
+def ep_data_from_traces(tr, length, worlds, params, seed=15):
+    """The `ep_data` list of ONE policy from the numpy traces of its episodes -- `tr`: action [T][num], traj [T][num][N][2] and, for an IQN policy,
+    cvar [T][num], quantiles [T][num][32][9], taus [T][num][32]; `length` [num]: `tally`'s -- whichever way they were produced (the per-step loop
+    stacks what it collects per step into the same arrays the episode launches trace).  Episode i ran in worlds[i]."""
+    return [_episode_record(w, params, lists, seed) for w, lists in zip(worlds, capture_lists(tr, length))]
+
+
+def _records_from_traces(tr, params, names, num, launch_s=None, step_s=None, capture=None):
     """Result records of the policies `names` (policy p owns rows [p * num, (p + 1) * num)) from the numpy traces of their episodes, whichever way
     they were produced: `episodes.tally`'s numbers, sliced per policy.  `computation_times`, one entry per step of every episode, either way:
     `launch_s`, the device seconds of ONE launch that ran all the episodes, divided by the actions it chose; or `step_s`, per policy the per-step
-    list of its act launch's device seconds per row served -- step t counts once for every env alive before it, i.e. with length > t."""
+    list of its act launch's device seconds per row served -- step t counts once for every env alive before it, i.e. with length > t.
+    `capture` = (worlds, seed, iqn_tr, iqn_first): every record also gets its `ep_data` (ep_data_from_traces) from the traj trace in `tr` and, for an IQN
+    policy -- a name in `iqn_first`, its first row in the cvar / quantiles / taus traces `iqn_tr` ([T][IQN rows]) --, from those."""
     tl = tally(tr["reward"], tr["done"], tr["info"], tr["action"], params.discount, energy_table(params.a[:], params.w[:]))
     length, info = tl["length"], tl["last_info"]
     dtN = params.dt * params.N
@@ -85,37 +112,52 @@ def _records_from_traces(tr, params, names, num, launch_s=None, step_s=None):
         out[name] = dict(success=[bool(v) for v in info[sl] == 4], out_of_area=[bool(v) for v in info[sl] == 1],
                          time=[float(dtN * l) for l in length[sl]], energy=[float(v) for v in tl["energy"][sl]],
                          reward=[float(v) for v in tl["ret"][sl]], actions=tl["actions"][sl], computation_times=times)
+        if capture is not None:
+            worlds, seed, iqn_tr, iqn_first = capture
+            ptr = {k: tr[k][:, sl] for k in ("action", "traj")}
+            if name in iqn_first:
+                isl = slice(iqn_first[name], iqn_first[name] + num)
+                ptr.update({k: iqn_tr[k][:, isl] for k in IQN_CAPTURE_TRACES})
+            out[name]["ep_data"] = ep_data_from_traces(ptr, length[sl], worlds, params, seed)
     return out
 
 
-def _rollout_episodes(worlds, names, device, launch):
+def _rollout_episodes(worlds, names, device, launch, capture=None, iqn=False, timings=None):
     """One env holding `worlds` once per policy of `names`, all of its episodes as ONE launch: `launch(env)` returns the traces (reward, done, info,
-    action) or None where the library has no one-launch form of the policy.  Returns {name: record} or None."""
+    action; with `capture` = the sweep's seed also traj and, `iqn`, cvar / quantiles / taus, which become the records' `ep_data`) or None where the
+    library has no one-launch form of the policy.  Only the rows of the steps run are copied to the host.  Returns {name: record} or None."""
     env = VecMarineNavEnv(len(worlds) * len(names), device=device, precision="f64")
     _configure(env)
     env.load_worlds(worlds * len(names))
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    tr = launch(env)
-    e1.record()
+    with _producing(timings, env.device):
+        e0.record()
+        tr = launch(env)
+        e1.record()
     rec = None
     if tr is not None:
         torch.cuda.synchronize(env.device)
-        rec = _records_from_traces(host_traces(tr), env.params, names, len(worlds), launch_s=e0.elapsed_time(e1) * 1e-3)
+        also = () if capture is None else CAPTURE_TRACES + (IQN_CAPTURE_TRACES if iqn else ())
+        host = host_traces(tr, also)
+        cap = None if capture is None else (worlds, capture, host, {name: p * len(worlds) for p, name in enumerate(names)} if iqn else {})
+        rec = _records_from_traces(host, env.params, names, len(worlds), launch_s=e0.elapsed_time(e1) * 1e-3, capture=cap)
     env.close()
     return rec
 
 
-def _classical_episodes(worlds, name, device, max_steps, seed):
+def _classical_episodes(worlds, name, device, max_steps, seed, capture=False, timings=None):
     """All of `worlds` under the classical baseline `name` ("APF" / "BA"), one episode each, as ONE launch: the policy runs inside the
     rollout kernel (VecMarineNavEnv.rollout_policy -> mn_rollout_policy).  Same result record as the launch-per-step path."""
-    return _rollout_episodes(worlds, (name,), device, lambda env: env.rollout_policy(max_steps, name))[name]
+    trace = EPISODE_TRACES + (CAPTURE_TRACES if capture else ())
+    return _rollout_episodes(worlds, (name,), device, lambda env: env.rollout_policy(max_steps, name, trace=trace), capture=seed if capture else None,
+                             timings=timings)[name]
 
 
 @torch.no_grad()
-def _iqn_episodes(worlds, names, agent, device, max_steps):
+def _iqn_episodes(worlds, names, agent, device, max_steps, capture=None, timings=None):
     """The IQN policies `names` on `worlds` as ONE mn_rollout_iqn_rows launch: policy p owns rows [p * num, (p + 1) * num), the rows of the per-step
-    loop's IQN act call, so every row draws the taus it draws there.  None where that loop's acting form has no one-launch twin (PyTorch acting,
+    loop's IQN act call, so every row draws the taus it draws there.  With `capture` (the sweep's seed) the launch is mn_rollout_iqn_eval: it acts as
+    the capture loop's act_eval_batch does and traces what that returns.  None where that loop's acting form has no one-launch twin (PyTorch acting,
     torch.rand taus, the exact-f32 variant)."""
     if not (agent.device.type == "cuda" and agent.use_fused_act and agent.use_library_rng):
         return None
@@ -126,14 +168,17 @@ def _iqn_episodes(worlds, names, agent, device, max_steps):
     cvar_rows = torch.tensor([_CVAR.get(name, 1.0) for name in names], dtype=torch.float32).repeat_interleave(num)
     adaptive_rows = torch.tensor([name == "adaptive_IQN" for name in names]).repeat_interleave(num)
     agent.qnetwork_local.eval()
+    cap = capture is not None
+    trace = EPISODE_TRACES + ((CAPTURE_TRACES + ("cvar",)) if cap else ())
     rec = _rollout_episodes(worlds, names, device, lambda env: rollout_iqn(agent.qnetwork_local, env, max_steps, agent._act_rng, cvar_rows=cvar_rows,
-                                                                           adaptive_rows=adaptive_rows, trace=EPISODE_TRACES))
+                                                                           adaptive_rows=adaptive_rows, trace=trace, want_quantiles=cap),
+                            capture=capture, iqn=cap, timings=timings)
     agent.qnetwork_local.train()
     return rec
 
 
 def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, device="cuda:0", max_steps=1000, dqn=None,
-                   capture=False, classical_rollout=True, one_launch=False):
+                   capture=False, classical_rollout=True, one_launch=False, timings=None):
     """run_experiments.py:213-282 for the IQN policies, the classical APF / BA baselines and (when `dqn`, a
     `dqn.DQNPolicy`, is given and "DQN" is in `policies`) the greedy DQN baseline.  Returns {policy: dict(success, time, energy,
     out_of_area, reward, actions)} with one entry per world.  With `capture` each policy also gets the reference's `ep_data`
@@ -143,29 +188,39 @@ def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, d
     act call, flattened over a policy's episodes) is the batched equivalent: the device time of the step's act launch(es) for that
     policy group (HIP events) divided by the rows the launch served, one entry per step of every episode -- the amortised cost of one
     action, which is what `avg_compute_t` (run_experiments.py:274) averages.
-    `one_launch` (opt-in, ignored with `capture`): the learned policies run whole episodes inside one kernel too -- the requested IQN policies as ONE
+    `one_launch` (opt-in): the learned policies run whole episodes inside one kernel too -- the requested IQN policies as ONE
     mn_rollout_iqn_rows launch on one env of len(IQN policies) x num rows in the order of `policies` (per-row cvar and adaptive flag; the rows are the
     per-step loop's, so the taus are the same), DQN as one mn_rollout_dqn launch on its own env: with APF / BA the whole sweep is four launches.
     Results are bit-identical to the loop's; `computation_times` are built as for APF / BA (the launch's device time divided by the actions it
     chose).  Where the library has no one-launch form of a policy (an agent on the exact-f32 act variant or on torch.rand taus, a DQN policy with
     use_fused_act = False) that policy runs in the loop.  One difference: the agent's act-call counter ends at + the longest IQN episode, where the
-    loop ends at + the longest episode of any policy in the loop."""
+    loop ends at + the longest episode of any policy in the loop.
+    `capture` with `one_launch`: the same four launches also produce the `ep_data` -- every launch traces the sub-step positions of every step
+    (mn_set_trajectory_trace), the IQN launch is mn_rollout_iqn_eval, which acts as act_eval does and traces the quantile values and taus of every
+    action -- and both ways build `ep_data` with the same function from such traces (ep_data_from_traces), so the records are equal, `ep_data`
+    included.  Trace memory on the device: max_steps x rows x (288 + 32) x 4 B for the IQN group -- about 3.2 GB for 500 worlds x 5 policies x
+    1 000 steps -- and max_steps x rows x N x 16 B per launch for the trajectories, about 0.2 GB for that sweep's 2 500 IQN rows at N = 5; only the
+    rows of the steps run are copied to the host.  `capture` without `one_launch` runs the loop for every policy, APF / BA included.
+    `timings` (a dict, for measurements): timings["traces_s"] += the wall seconds of every trace-producing phase, launches and loop alike -- from its
+    first launch until its traces are complete on the device (synchronised; the loop's per-step host copies are part of how it produces them) --, i.e.
+    without the world generation, the env set-up and the host-side assembly of the records that both ways share."""
     worlds = generate_worlds(num, n_obs, n_cores, seed, device)
-    # APF / BA: the policy is a device function inside the episode rollout kernel -- one launch per policy for all worlds -- unless the
-    # per-sub-step trajectory is wanted (`capture`), which the launch-per-step path below records
+    # APF / BA: the policy is a device function inside the episode rollout kernel -- one launch per policy for all worlds.  With `capture` the
+    # launches run only on request (`one_launch`): otherwise the launch-per-step path below records the per-sub-step trajectory, as it always has
     requested = tuple(policies)
     rolled = {}
-    if classical_rollout and not capture:
-        rolled = {name: _classical_episodes(worlds, name, device, max_steps, seed) for name in requested if name in ("APF", "BA")}
-    if one_launch and not capture:
+    if classical_rollout and (one_launch or not capture):
+        rolled = {name: _classical_episodes(worlds, name, device, max_steps, seed, capture, timings) for name in requested if name in ("APF", "BA")}
+    if one_launch:
         iqn_names = tuple(p for p in requested if p == "adaptive_IQN" or p in _CVAR)
         if iqn_names:
-            rolled.update(_iqn_episodes(worlds, iqn_names, agent, device, max_steps) or {})
+            rolled.update(_iqn_episodes(worlds, iqn_names, agent, device, max_steps, seed if capture else None, timings) or {})
         if "DQN" in requested:
             if dqn is None:
                 raise ValueError("policy 'DQN' needs run_experiment(..., dqn=DQNPolicy.load(...))")
-            rolled.update(_rollout_episodes(worlds, ("DQN",), device,
-                                            lambda env: dqn.rollout(env, max_steps, trace=EPISODE_TRACES)) or {})
+            trace = EPISODE_TRACES + (CAPTURE_TRACES if capture else ())
+            rolled.update(_rollout_episodes(worlds, ("DQN",), device, lambda env: dqn.rollout(env, max_steps, trace=trace),
+                                            capture=seed if capture else None, timings=timings) or {})
     policies = tuple(p for p in requested if p not in rolled)
     if not policies:
         return {name: rolled[name] for name in requested}, worlds
@@ -191,7 +246,7 @@ def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, d
         else:
             fixed[rows] = _CVAR[name]
     iqn_idx = torch.nonzero(iqn_rows).view(-1)
-    cap_cv, cap_q, cap_t, cap_traj = [], [], [], []
+    cap = {}                                                       # capture: name -> numpy [max_steps][rows]..., row t filled by step t (allocated at step 0; untouched pages cost nothing)
     act_events = {}                                                # group -> [(start, end)] per step; groups: "IQN" (one launch for all IQN policies), planners
 
     def timed(group, fn):
@@ -201,6 +256,11 @@ def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, d
         e1.record()
         act_events.setdefault(group, []).append((e0, e1))
         return r
+
+    def record(t, k, x):
+        if k not in cap:
+            cap[k] = np.empty((max_steps,) + x.shape, dtype=x.dtype)
+        cap[k][t] = x
 
     def act(t, obs):
         a = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -215,7 +275,7 @@ def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, d
             cv, a_iqn, quant, taus = timed("IQN", iqn_act)
             a[iqn_idx] = a_iqn
             if capture:
-                cap_cv.append(cv.cpu().numpy()); cap_q.append(quant.cpu().numpy()); cap_t.append(taus.cpu().numpy())
+                record(t, "cvar", cv.cpu().numpy()); record(t, "quantiles", quant.cpu().numpy()); record(t, "taus", taus.cpu().numpy()[:, :, 0])
         for name, rows in classical.items():                                 # APF.py:17-78 / BA.py:14-72
             if name == "DQN":                                                # run_experiments.py:86 (greedy predict)
                 a[rows] = timed(name, lambda: dqn.act_batch(obs[rows]))
@@ -226,32 +286,23 @@ def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, d
         env.enable_trajectory()
     if agent is not None:
         agent.qnetwork_local.eval()
-    tr = loop_episodes(env, obs, act, max_steps, after_step=(lambda t: cap_traj.append(env.get_trajectory())) if capture else None)
+    with _producing(timings, dev):
+        tr = loop_episodes(env, obs, act, max_steps, after_step=(lambda t: record(t, "traj", env.get_trajectory())) if capture else None)
     if agent is not None:
         agent.qnetwork_local.train()
     torch.cuda.synchronize(dev)
     group_rows = {"IQN": max(1, int(iqn_idx.numel()))}
     step_s = {g: [e0.elapsed_time(e1) * 1e-3 / group_rows.get(g, num) for e0, e1 in evs] for g, evs in act_events.items()}
     # one entry per act call of the reference = per live episode and step: the step's amortised per-row device time
-    out = _records_from_traces(host_traces(tr), env.params, policies, num,
-                               step_s={name: step_s.get(name if name in classical else "IQN", []) for name in policies})
-    if capture:
-        iqn_pos = {int(g_): k for k, g_ in enumerate(iqn_idx.cpu().numpy())}     # env row -> row of the IQN captures
-        for p, name in enumerate(policies):
-            eps_ = []
-            for i in range(p * num, (p + 1) * num):
-                acts_i = out[name]["actions"][i - p * num]
-                L = len(acts_i)
-                traj = [q for t_ in range(L) for q in cap_traj[t_][i]]
-                if i in iqn_pos:
-                    k = iqn_pos[i]
-                    eps_.append(_episode_record(worlds[i - p * num], env.params, name, acts_i, traj,
-                                                cvars=[cap_cv[t_][k] for t_ in range(L)],
-                                                quantiles=[cap_q[t_][k:k + 1] for t_ in range(L)],
-                                                taus=[cap_t[t_][k:k + 1] for t_ in range(L)], seed=seed))
-                else:
-                    eps_.append(_episode_record(worlds[i - p * num], env.params, name, acts_i, traj, seed=seed))
-            out[name]["ep_data"] = eps_
+    host = host_traces(tr)
+    capd = None
+    if capture:      # the loop's captures as the launches' traces: [T][rows]..., T = the steps run
+        T = host["done"].shape[0]
+        host["traj"] = cap["traj"][:T]
+        iqn_first = {name: k * num for k, name in enumerate(p_ for p_ in policies if p_ not in classical)}      # (iqn_idx is ascending: policy order)
+        capd = (worlds, seed, {k: cap[k][:T] for k in IQN_CAPTURE_TRACES if k in cap}, iqn_first)
+    out = _records_from_traces(host, env.params, policies, num,
+                               step_s={name: step_s.get(name if name in classical else "IQN", []) for name in policies}, capture=capd)
     env.close()
     out.update(rolled)
     return {name: out[name] for name in requested}, worlds

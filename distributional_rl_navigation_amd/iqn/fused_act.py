@@ -297,7 +297,7 @@ def fused_act(net, states, eps=0.0, cvar=1.0, taus=None, generator=None, want_qv
 
 @torch.no_grad()
 def rollout_iqn(net, env, n_steps, rng, cvar=1.0, adaptive=False, shared_taus=False,
-                trace=("reward", "done", "info", "action", "cvar", "q"), cvar_rows=None, adaptive_rows=None):
+                trace=("reward", "done", "info", "action", "cvar", "q"), cvar_rows=None, adaptive_rows=None, want_quantiles=False):
     """Every env's CURRENT episode of `env` (a VecMarineNavEnv) under the IQN policy of `net` for up to `n_steps` steps in ONE launch (C-ABI
     mn_rollout_iqn): per step what `fused_act(net, env.obs, 0.0, cvar, rng=rng, shared_taus=shared_taus)` would choose -- `cvar` a float, or with
     `adaptive` IQNAgent.adjust_cvar_batch of each row -- then the env step.  No resets: a finished env idles (reward 0, done 1, terminal info,
@@ -305,6 +305,10 @@ def rollout_iqn(net, env, n_steps, rng, cvar=1.0, adaptive=False, shared_taus=Fa
     `cvar_rows` ([n] float tensor) / `adaptive_rows` ([n] bool tensor): per-env cvar and adaptive flag (C-ABI mn_rollout_iqn_rows) -- what a loop of
     `fused_act(net, env.obs, 0.0, torch.where(adaptive_rows, adjust_cvar_batch(env.obs), cvar_rows), rng=rng)` would choose; a per-row cvar tensor
     keeps fused_act on per-row taus whatever `shared_taus` says, and so does this call.
+    `want_quantiles`: the batched IQNAgent.act_eval instead (C-ABI mn_rollout_iqn_eval) -- per step what `fused_act(..., want_quantiles=True)` chooses (Q =
+    the mean of the per-tau outputs; can differ from the acting form in the last bit) -- with the traces "quantiles" [n_steps][n][32][9] and "taus"
+    [n_steps][n][32] of what it chose from (NaN behind an env's end).  "traj" among the traces (f64 envs): [n_steps][n][N][2], every step's sub-step
+    positions while the env is alive -- the loop's `env.get_trajectory()`.
     Returns the requested traces ([n_steps][n], Q [n_steps][n][9]), `final_obs` and `steps_run` (the longest episode), or None when the
     library refuses the form (the exact-f32 variant, launch-shared taus: the caller runs the loop instead)."""
     T, n, dev = int(n_steps), env.n_envs, env.device
@@ -315,16 +319,24 @@ def rollout_iqn(net, env, n_steps, rng, cvar=1.0, adaptive=False, shared_taus=Fa
     ad_rows = adaptive_rows.to(device=dev, dtype=torch.uint8).contiguous() if adaptive_rows is not None else None
     assert cv_rows is None or cv_rows.numel() == n
     assert ad_rows is None or ad_rows.numel() == n
-    tr = trace_buffers(T, n, dev, trace, n_actions=net.action_size)
+    if want_quantiles:
+        trace = tuple(trace) + tuple(k for k in ("quantiles", "taus") if k not in trace)
+    else:
+        assert "quantiles" not in trace and "taus" not in trace, "the quantile / tau traces need want_quantiles=True"
+    tr = trace_buffers(T, n, dev, trace, n_actions=net.action_size, n_taus=net.K, n_substeps=int(env.params.N))
     p = lambda k: _p(tr[k]) if k in tr else None
     steps = torch.zeros(1, dtype=torch.int32, device=dev)
-    rc = _capi.lib().mn_rollout_iqn_rows(env.h, ctx.h, ctx.weights(net), T, _p(rng.state), C.c_float(float(cvar)), int(bool(adaptive)), _p(cv_rows),
-                                         _p(ad_rows), _p(env.obs), p("obs"), p("reward"), p("done"), p("info"), p("action"), p("cvar"), p("q"),
-                                         _p(steps), env._stream())
+    args = (env.h, ctx.h, ctx.weights(net), T, _p(rng.state), C.c_float(float(cvar)), int(bool(adaptive)), _p(cv_rows), _p(ad_rows), _p(env.obs),
+            p("obs"), p("reward"), p("done"), p("info"), p("action"), p("cvar"), p("q"))
+    env.set_trajectory_trace(tr.get("traj"))      # last before the launch, which consumes it whatever it returns
+    if want_quantiles:
+        rc = _capi.lib().mn_rollout_iqn_eval(*args, p("quantiles"), p("taus"), _p(steps), env._stream())
+    else:
+        rc = _capi.lib().mn_rollout_iqn_rows(*args, _p(steps), env._stream())
     if rc == -1:      # MN_ERR_INVALID: a form the rollout does not reproduce
         return None
     if rc:
-        raise _capi.MarineNavHipError(f"mn_rollout_iqn_rows failed ({rc})")
+        raise _capi.MarineNavHipError(f"mn_rollout_iqn_{'eval' if want_quantiles else 'rows'} failed ({rc})")
     out = dict(tr)
     out["final_obs"] = env.obs
     out["steps_run"] = int(steps.item())

@@ -237,11 +237,14 @@ class VecMarineNavEnv:
         """Every env's CURRENT episode under the classical baseline `policy` ("APF" = APF.py:17-78, "BA" = BA.py:14-155) for up to
         `n_steps` steps in ONE launch (C-ABI mn_rollout_policy): the policy is evaluated on the device on each step's observation row.
         No resets: a finished env idles (reward 0, done 1, terminal info, action -1 in the traces).  Step for step identical to the
-        loop (planners.planner_act_batch, step).  Returns the requested traces + `final_obs` (terminal observations where finished)."""
+        loop (planners.planner_act_batch, step).  Returns the requested traces + `final_obs` (terminal observations where finished).  "traj" among the
+        traces (f64 envs): [n_steps][n][N][2], every step's sub-step positions while the env is alive (NaN behind its end) -- the loop's `get_trajectory()`."""
         T, n, dev = int(n_steps), self.n_envs, self.device
-        tr = trace_buffers(T, n, dev, trace)
+        code = int(self.POLICIES[policy])      # (a wrong name raises before anything is attached)
+        tr = trace_buffers(T, n, dev, trace, n_substeps=int(self.params.N))
         p = lambda k: _ptr(tr[k]) if k in tr else None
-        self._check(self.L.mn_rollout_policy(self.h, T, int(self.POLICIES[policy]), _ptr(self.obs), p("obs"), p("reward"), p("done"), p("info"),
+        self.set_trajectory_trace(tr.get("traj"))
+        self._check(self.L.mn_rollout_policy(self.h, T, code, _ptr(self.obs), p("obs"), p("reward"), p("done"), p("info"),
                                              p("action"), self._stream()))
         out = dict(tr)
         out["final_obs"] = self.obs
@@ -417,6 +420,15 @@ class VecMarineNavEnv:
     def enable_trajectory(self, max_substeps=None):
         """Record the per-sub-step positions of every step (robot.trajectory, marinenav_env.py:211-212); f64 handles."""
         self._check(self.L.mn_enable_trajectory(self.h, int(self.params.N if max_substeps is None else max_substeps)))
+
+    def set_trajectory_trace(self, traj):
+        """Attach `traj` ([T][n][N][2] float64 on the device; C-ABI mn_set_trajectory_trace) to the NEXT episode launch of this env (rollout_policy,
+        iqn.fused_act.rollout_iqn, DQNPolicy.rollout), which records every step's sub-step positions into it and detaches it; None detaches.  f64 envs."""
+        if traj is None:
+            self._check(self.L.mn_set_trajectory_trace(self.h, None, 0, 0))
+            return
+        assert traj.is_contiguous() and traj.dtype == torch.float64 and traj.shape[1:] == (self.n_envs, int(self.params.N), 2)
+        self._check(self.L.mn_set_trajectory_trace(self.h, _ptr(traj), int(traj.shape[0]), int(self.params.N)))
 
     def get_trajectory(self, first_env=0, count=None):
         """[count, N, 2] positions after each of the N sub-steps of the last step()."""

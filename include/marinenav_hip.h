@@ -259,6 +259,15 @@ int mn_get_reward64(mn_handle *h, int32_t first_env, int32_t count, double *out)
  * of the LAST step.  MN_PRECISION_F64 handles only (the facade / evaluation path); off by default. */
 int mn_enable_trajectory(mn_handle *h, int32_t max_substeps);
 int mn_get_trajectory(mn_handle *h, int32_t first_env, int32_t count, int32_t n_substeps, double *out);
+/* The same positions of WHOLE EPISODES: a device trace traj_trace_dev [n_steps][n][n_substeps][2] f64 for the next episode launch of `h` --
+ * mn_rollout_policy, mn_rollout_iqn, mn_rollout_iqn_rows, mn_rollout_iqn_eval or mn_rollout_dqn --, which records into row [t][i] the N positions
+ * mn_step would record for env i at step t (what mn_get_trajectory returns after that step of the per-step loop, bit for bit) while env i is alive; rows
+ * of steps after an env has finished are not written.  A handle-level attachment, like mn_enable_trajectory, and independent of it: the launch that
+ * takes it detaches it, whether it succeeds or not -- a call refused for any of its arguments included (only a NULL handle has nothing to detach) --
+ * and a launch of more than n_steps steps, or after the robot's N has changed, is refused with MN_ERR_INVALID; mn_rollout records none and refuses to run while one is attached; traj_trace_dev = NULL detaches.  With nothing attached every
+ * launch does exactly what it did before, and attaching changes no other output.  n_substeps must be the handle's robot N.  MN_PRECISION_F64 handles
+ * only: a mixed-precision handle is refused with MN_ERR_INVALID and a message (mn_last_error).  The buffer must stay valid until the launch has run. */
+int mn_set_trajectory_trace(mn_handle *h, double *traj_trace_dev, int32_t n_steps, int32_t n_substeps);
 
 /* Next double each env's RandomState would return, without consuming it (test hook pinning the
  * RNG stream position; cf. np.random.RandomState.random_sample). */
@@ -396,6 +405,19 @@ int mn_rollout_iqn_rows(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weigh
                         int32_t adaptive, const float *cvar_row_dev, const uint8_t *adaptive_row_dev, float *obs_dev, float *obs_trace_dev,
                         float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev, float *cvar_trace_dev,
                         float *q_trace_dev, int32_t *steps_run_dev, void *stream);
+/* mn_rollout_iqn_rows acting as IQNAgent.act_eval does, and recording what each action was chosen from (the experiment sweep's captured episodes,
+ * run_experiments.py:26-69): per step each env acts exactly as one mn_iqn_act_rng call WITH quantiles_dev != NULL at eps = 0 would for its row -- the
+ * output layer runs per tau on the matrix pipe, Q is the mean of those 32 values, the first maximum wins; mn_rollout_iqn_rows takes the tau mean in
+ * front of the output layer, as the call without quantiles_dev does, and the two can differ in the last bit.  Two more traces (device, may be NULL):
+ *   quantiles_trace_dev [n_steps][n][32][9] f32 : the quantile values Z(tau, a) of the step (act_eval's `quantiles` of the row)
+ *   taus_trace_dev      [n_steps][n][32]    f32 : the taus they belong to (act_eval's `taus`: the call's draws x the row's cvar)
+ * whose entries of steps after an env has finished are not written.  q_trace_dev holds the means.  Everything else -- the other traces, the
+ * refusals, the counter update, steps_run_dev, `one launch at a time per context` -- as mn_rollout_iqn_rows.  A kernel of its own: its LDS holds the
+ * full weight image incl. the output layer's matrix operands (4 KB more than the acting episode kernel's). */
+int mn_rollout_iqn_eval(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weights, int32_t n_steps, uint64_t *rng_state_dev, float cvar,
+                        int32_t adaptive, const float *cvar_row_dev, const uint8_t *adaptive_row_dev, float *obs_dev, float *obs_trace_dev,
+                        float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev, float *cvar_trace_dev,
+                        float *q_trace_dev, float *quantiles_trace_dev, float *taus_trace_dev, int32_t *steps_run_dev, void *stream);
 
 /* ---- replay ring ------------------------------------------------------------------------------
  * ReplayBuffer.add (thirdparty/IQN/replay_buffer.py:26-34) for n transitions in one launch: batch row i
