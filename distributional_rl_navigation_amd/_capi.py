@@ -103,6 +103,9 @@ SIGNATURES = [
     ("mn_rollout_iqn", C.c_int, [_vp, _vp, C.POINTER(C.c_void_p), _i32, _vp, C.c_float, _i32] + [_vp] * 10),
     ("mn_rollout_iqn_rows", C.c_int, [_vp, _vp, C.POINTER(C.c_void_p), _i32, _vp, C.c_float, _i32] + [_vp] * 12),
     ("mn_rollout_iqn_eval", C.c_int, [_vp, _vp, C.POINTER(C.c_void_p), _i32, _vp, C.c_float, _i32] + [_vp] * 14),
+    ("mn_iqn_image_floats", _i32, []),
+    ("mn_iqn_export_image", C.c_int, [_vp, C.POINTER(C.c_void_p), _vp, _vp]),
+    ("mn_rollout_iqn_groups", C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32] + [_vp] * 14),
     ("mn_rollout_dqn", C.c_int, [_vp, C.POINTER(C.c_void_p), _vp, _i32, _i32] + [_vp] * 8),
     ("mn_dqn_image_floats", C.c_int64, []),
     ("mn_dqn_act", C.c_int, [_vp, C.POINTER(C.c_void_p), _vp, _i32, _vp, _vp, _i32, _vp]),

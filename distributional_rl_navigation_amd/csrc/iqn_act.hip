@@ -379,6 +379,18 @@ int mn_iqn_rollout_image(mn_iqn_ctx *c, const float *const *weights, hipStream_t
     return MN_OK;
 }
 
+extern "C" int32_t mn_iqn_image_floats(void) { return sp::ACT_IMG_FLOATS; }
+
+// A copy of the acting image for mn_rollout_iqn_groups: the same image, under the same refusals, as mn_iqn_rollout_image hands to mn_rollout_iqn
+extern "C" int mn_iqn_export_image(mn_iqn_ctx *c, const float *const *weights, uint32_t *image_out_dev, void *stream) {
+    if (!c || !weights || !image_out_dev || c->variant != 2 || c->tau_mode != 0) return MN_ERR_INVALID;
+    const int rc = mn_iqn_refresh(c, weights, stream);
+    if (rc) return rc;
+    if (hipMemcpyAsync(image_out_dev, c->packed_sp, sp::ACT_IMG_FLOATS * sizeof(uint32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+        return MN_ERR_HIP;
+    return MN_OK;
+}
+
 extern "C" int mn_iqn_act(mn_iqn_ctx *c, const float *obs_dev, const float *taus_dev, const float *const *weights,
                           float *qvals_dev, const float *explore_u_dev, float eps, int32_t *actions_dev,
                           float *quantiles_dev, int32_t n, int32_t num_taus, void *stream) {

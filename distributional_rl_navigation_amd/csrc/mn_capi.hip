@@ -481,6 +481,29 @@ extern "C" int mn_rollout_iqn(mn_handle *h, mn_iqn_ctx *ctx, const float *const 
                                done_trace_dev, info_trace_dev, action_trace_dev, cvar_trace_dev, q_trace_dev, steps_run_dev, stream);
 }
 
+extern "C" int mn_rollout_iqn_groups(mn_handle *h, const uint32_t *images_dev, int64_t image_stride, int32_t n_groups, int32_t rows_per_group,
+                                     int32_t n_steps, uint64_t *rng_states_dev, const float *cvar_row_dev, const uint8_t *adaptive_row_dev, float *obs_dev,
+                                     float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev,
+                                     float *cvar_trace_dev, float *q_trace_dev, uint32_t *group_words_dev, int32_t *steps_run_dev, void *stream) {
+    if (!h) return MN_ERR_INVALID;
+    if (h->traj_trace) {      // as mn_rollout: the attachment is consumed, the call refused
+        h->traj_trace = nullptr;
+        h->traj_trace_steps = 0;
+        return fail(h, MN_ERR_INVALID, "mn_rollout_iqn_groups records no trajectory trace");
+    }
+    if (!images_dev || !rng_states_dev || !obs_dev || !group_words_dev || n_steps < 1) return MN_ERR_INVALID;
+    if (n_groups < 1 || rows_per_group < 1 || (int64_t)n_groups * rows_per_group != (int64_t)h->A.n)
+        return fail(h, MN_ERR_INVALID, "mn_rollout_iqn_groups: n_groups * rows_per_group must be the handle's n_envs");
+    if (image_stride < mn_iqn_image_floats() || image_stride % 4 != 0)
+        return fail(h, MN_ERR_INVALID, "mn_rollout_iqn_groups: image_stride below mn_iqn_image_floats() or no multiple of 4");
+    hipStream_t s = (hipStream_t)stream;
+    return launch_episodes(h, s, [&] {
+        mn_launch_rollout_iqn_groups(h->A, h->P, h->params.precision, n_steps, images_dev, image_stride, rows_per_group, rng_states_dev, cvar_row_dev,
+                                     adaptive_row_dev, obs_dev, obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev, action_trace_dev,
+                                     cvar_trace_dev, q_trace_dev, group_words_dev, steps_run_dev, s);
+    });
+}
+
 extern "C" int mn_rollout_dqn(mn_handle *h, const float *const *weights, float *image_dev, int32_t repack, int32_t n_steps, float *obs_dev,
                               float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev,
                               float *q_trace_dev, void *stream) {

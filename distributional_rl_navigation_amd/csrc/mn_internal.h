@@ -116,6 +116,11 @@ void mn_launch_rollout_iqn_eval(const MnArrays &A, const MnDev &P, int precision
                                 int adaptive, const float *cvar_row, const uint8_t *adaptive_row, float *obs_io, float *obs_trace, float *reward_trace,
                                 uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *cvar_trace, float *q_trace, double *traj_trace,
                                 float *quantiles_trace, float *taus_trace, uint32_t *words, int32_t *steps_run, hipStream_t s);
+// the acting episodes with a weight image and a tau stream per group of rows (mn_rollout_iqn_groups.hip); image_stride in 32-bit words
+void mn_launch_rollout_iqn_groups(const MnArrays &A, const MnDev &P, int precision, int n_steps, const uint32_t *images, int64_t image_stride,
+                                  int rows_per_group, uint64_t *rng_states, const float *cvar_row, const uint8_t *adaptive_row, float *obs_io,
+                                  float *obs_trace, float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *cvar_trace,
+                                  float *q_trace, uint32_t *group_words, int32_t *steps_run, hipStream_t s);
 int mn_iqn_rollout_image(mn_iqn_ctx *c, const float *const *weights, hipStream_t s, const uint32_t **image, uint32_t **words);
 // DQN evaluation episodes in one launch (mn_rollout_dqn.hip); `image` = the weight image mn_launch_dqn_pack (dqn_act.hip) builds from weights[18]
 void mn_launch_dqn_pack(const float *const *weights, float *image_dev, hipStream_t s);

@@ -26,7 +26,8 @@ __global__ __launch_bounds__(MN_WAVE, 1) void mn_rollout_iqn_kernel(MnArrays A, 
                                                                     const uint8_t *__restrict__ adaptive_row, float *__restrict__ obs_io, IqnTrace T,
                                                                     uint32_t *__restrict__ words, int32_t *__restrict__ steps_out) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    iqn_episode<M, PARITY, L, false>(lds, A, P, n_steps, packed, rng_state, cvar, adaptive, cvar_row, adaptive_row, obs_io, T, words, steps_out);
+    iqn_episode<M, PARITY, L, false>(lds, A, P, n_steps, packed, rng_state, cvar, adaptive, cvar_row, adaptive_row, obs_io, T, words, steps_out,
+                                     IqnGroups{});      // one group: the whole launch
 }
 
 }  // namespace

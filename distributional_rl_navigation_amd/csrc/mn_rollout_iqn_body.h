@@ -1,7 +1,8 @@
 // mn_rollout_iqn_body.h -- one IQN evaluation episode per wavefront: the body of the IQN episode launches.
-// Included ONCE by mn_rollout_iqn.hip (QUANT = false: the acting form, mn_rollout_iqn / mn_rollout_iqn_rows) and by mn_rollout_iqn_eval.hip
-// (QUANT = true: act_eval's form, which also records the quantile values and taus each action was chosen from, mn_rollout_iqn_eval); each wraps
-// iqn_episode<> in its own __global__ kernel.  Both files are built with -ffp-contract=fast-honor-pragmas (Makefile).
+// Included ONCE by mn_rollout_iqn.hip (QUANT = false: the acting form, mn_rollout_iqn / mn_rollout_iqn_rows), by mn_rollout_iqn_eval.hip
+// (QUANT = true: act_eval's form, which also records the quantile values and taus each action was chosen from, mn_rollout_iqn_eval) and by
+// mn_rollout_iqn_groups.hip (the acting form with GROUPED = true: every group of rows its own weight image and tau stream, mn_rollout_iqn_groups);
+// each wraps iqn_episode<> in its own __global__ kernel.  All three files are built with -ffp-contract=fast-honor-pragmas (Makefile).
 //
 // Floating-point contraction: the network is built like iqn_act.o (contraction allowed -- fast-honor-pragmas without a pragma compiles the
 // per-row act kernels to the same code as -ffp-contract=fast), the step body and adjust_cvar under `#pragma clang fp contract(off)`, like
@@ -67,13 +68,23 @@ template <bool QUANT> struct IqnLds {
     static_assert(FLOATS * 4 <= 160 * 1024, "fits the CU's 160 KB");
 };
 
+// Which rows of a launch act together (GROUPED = true): row e belongs to group e / rows and is row e % rows of it.  A group has its own weight image
+// (packed + group * stride), its own {seed, counter} (rng_state + 2 * group), its own ticket and maximum (words + 2 * group) and its own steps_out entry,
+// and keys its tau draws by the row's index INSIDE the group: it draws, and leaves in its counter, what a launch of its own on `rows` rows does.
+// GROUPED = false: one group, the whole launch -- the descriptor is not read.
+struct IqnGroups {
+    int rows;          // rows per group
+    int64_t stride;    // 32-bit words from one group's weight image to the next (a multiple of 4: the image is staged 16 bytes at a time)
+};
+
 // QUANT = false: Q as the acting form of iqn_qvals_split_kernel computes it (tau mean before the f32 output layer: mn_iqn_act_rng without quantiles_dev).
 // QUANT = true : as its QUANT = true form (per-tau output layer on the matrix pipe, Q = the mean of those values: mn_iqn_act_rng with quantiles_dev,
 //                IQNAgent.act_eval) -- the two can differ in the last bit -- and T.quantiles / T.taus are recorded.
-template <typename M, bool PARITY, int L, bool QUANT>
+template <typename M, bool PARITY, int L, bool QUANT, bool GROUPED = false>
 __device__ __forceinline__ void iqn_episode(float *lds, MnArrays A, const MnDev &P, int n_steps, const uint32_t *__restrict__ packed, uint64_t *rng_state,
                                             float cvar, int adaptive, const float *__restrict__ cvar_row, const uint8_t *__restrict__ adaptive_row,
-                                            float *__restrict__ obs_io, const IqnTrace &T, uint32_t *__restrict__ words, int32_t *__restrict__ steps_out) {
+                                            float *__restrict__ obs_io, const IqnTrace &T, uint32_t *__restrict__ words, int32_t *__restrict__ steps_out,
+                                            const IqnGroups &G) {
     using namespace sp;
     using Lds = IqnLds<QUANT>;
     using Lane = MnLane<M, PARITY, L>;
@@ -81,6 +92,15 @@ __device__ __forceinline__ void iqn_episode(float *lds, MnArrays A, const MnDev 
     const int e = blockIdx.x;
     const size_t n = (size_t)A.n;
     if (e == 0 && lane < 2 * MN_QSHARDS) A.queue_count[lane * MN_QSTRIDE] = 0u;   // nothing is left for a later mn_reset_done
+    int draw_row = e;                     // the row index the tau draws are keyed with
+    if constexpr (GROUPED) {
+        const int grp = e / G.rows;
+        draw_row = e - grp * G.rows;
+        packed += (size_t)grp * (size_t)G.stride;
+        rng_state += 2 * (size_t)grp;
+        words += 2 * (size_t)grp;
+        if (steps_out) steps_out += grp;
+    }
     const uint64_t seed = rng_state[0], ctr0 = rng_state[1];
     // per-env cvar / adaptive flag (one env per wavefront: wave-uniform loads, outside the step loop); NULL = the launch's scalar
     if (cvar_row) cvar = cvar_row[e];
@@ -118,7 +138,7 @@ __device__ __forceinline__ void iqn_episode(float *lds, MnArrays A, const MnDev 
         draw_keys(seed, ctr0 + (uint64_t)t, k0, k1);
         float tau[NT];
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) tau[nt] = tau_draw(e, 16 * nt + col, k0, k1, cv);
+        for (int nt = 0; nt < NT; ++nt) tau[nt] = tau_draw(draw_row, 16 * nt + col, k0, k1, cv);
         f16x8 cbh[2][NT], cbl[2][NT];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
@@ -202,12 +222,14 @@ __device__ __forceinline__ void iqn_episode(float *lds, MnArrays A, const MnDev 
             if (T.info) T.info[k] = (uint8_t)last_info;
             if (T.action) T.action[k] = -1;
         }
-    // the act call counter: + the longest episode of the launch.  Every workgroup has read counter0 before it takes its ticket, the last one
-    // writes (ticket words[0] and maximum words[1] are zero between launches)
+    // the act call counter: + the longest episode of the launch (GROUPED: of the group, in the group's own counter and words).  Every workgroup has read
+    // counter0 before it takes its ticket, the last one writes (ticket words[0] and maximum words[1] are zero between launches).  Nobody waits for a ticket:
+    // a grouped launch has far more workgroups than CUs, and a group's rows need not be resident together
     if (lane == 0) {
         __hip_atomic_fetch_max(words + 1, (uint32_t)steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const uint32_t old = __hip_atomic_fetch_add(words, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == gridDim.x - 1) {
+        const uint32_t last = GROUPED ? (uint32_t)G.rows - 1 : gridDim.x - 1;      // the ticket of the group's last arriver
+        if (old == last) {
             const uint32_t s = __hip_atomic_load(words + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             rng_state[1] = ctr0 + s;
             if (steps_out) *steps_out = (int32_t)s;

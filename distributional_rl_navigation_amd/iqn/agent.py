@@ -466,14 +466,19 @@ class IQNAgent(ReferenceLoopMixin):
     # ---- batched loop on the HIP vector env ----------------------------------------------------------
     def learn_vec(self, total_vector_steps, train_env, eval_env=None, eval_config=None, eval_freq=None,
                   eval_log_path=None, total_timesteps=None, world_size=1, cvar=1.0, verbose=True,
-                  train_every=None, on_step=None, report_timestep_scale=1.0, eval_adaptive=True, reset_under_act=True, eval_one_launch=False):
+                  train_every=None, on_step=None, report_timestep_scale=1.0, eval_adaptive=True, reset_under_act=True, eval_one_launch=False,
+                  eval_deferred=False):
         """Vectorised agent.py:94-173.  One iteration = one vector step of `train_env` (n_envs env
         steps): act_batch -> mn_step -> replay.add_batch -> mn_reset_done -> (every UPDATE_EVERY vector
         steps) sample + train.  `current_timestep` counts env steps over all ranks, so eps, the
         learning_starts gate and the curriculum keep the reference's meaning of "timesteps";
         `learning_timestep` counts vector steps after learning_starts (UPDATE_EVERY,
         target_update_interval and eval_freq are applied to it).  `eval_one_launch`: the evaluations as one mn_rollout_iqn launch each
-        (evaluation_vec(one_launch=True): the same results)."""
+        (evaluation_vec(one_launch=True): the same results).  `eval_deferred` (True, or a dict of DeferredEvaluations arguments such as max_pending /
+        max_steps): an evaluation point only KEEPS the policy of the moment (two device copies, no synchronisation); the episodes of all pending points run
+        later as one mn_rollout_iqn_groups launch, each point on a tau stream of its own, and are logged as the inline form logs them
+        (iqn/deferred_eval.py: what is on disk between flushes, and why the number of points then leaves the training run untouched).  Where that launch
+        cannot reproduce the acting form (CPU, PyTorch acting, torch.rand taus, the exact-f32 variant, launch-shared taus) the points stay inline."""
         n = train_env.n_envs
         per_iter = n * world_size
         # evaluation npz `timesteps` are reported as current_timestep * report_timestep_scale (train_iqn: reference-
@@ -491,6 +496,7 @@ class IQNAgent(ReferenceLoopMixin):
         was_under_act, self.reset_under_act = self.reset_under_act, bool(reset_under_act)
         guard = UnderActGuard(self, train_env)
         self.under_act_fallback = None
+        deferred = self._deferred_evaluations(eval_deferred, eval_env, eval_config, eval_adaptive, eval_log_path) if eval_deferred and eval_env is not None else None
         try:
             for it in range(total_vector_steps):
                 eps = self.linear_eps(total_timesteps)
@@ -508,7 +514,9 @@ class IQNAgent(ReferenceLoopMixin):
                     stats["collisions"] += int((info == 3).sum())
                     stats["timeouts"] += int((info == 2).sum())
                     ep_ret.masked_fill_(d, 0.0); ep_len.masked_fill_(d, 0.0)
-                if evaluate_now:
+                if evaluate_now and deferred is not None:
+                    deferred.snapshot(vector_step=it)
+                elif evaluate_now:
                     self.check_learner()      # (a device synchronisation; the evaluation below is one anyway)
                     res = self.evaluation_vec(eval_env, eval_config, greedy=True, eval_log_path=eval_log_path, one_launch=eval_one_launch)
                     if eval_adaptive:
@@ -526,17 +534,35 @@ class IQNAgent(ReferenceLoopMixin):
                         self.qnetwork_local.save(eval_log_path)
                 if on_step is not None:
                     on_step(it, stats)
+            if deferred is not None:
+                deferred.flush()
             # the end-of-run look at the bounded waits happens while `reset_under_act` still says how this loop ran (every rank, evaluation env or not)
             if hasattr(train_env, "join_reset"):
                 train_env.join_reset()
             self.check_learner()
         finally:
+            if deferred is not None:
+                deferred.close()
             guard.close()
             self.under_act_fallback = guard.fallback
             self.reset_under_act = was_under_act
             if hasattr(train_env, "join_reset"):
                 train_env.join_reset()
         return stats
+
+    def _deferred_evaluations(self, options, eval_env, eval_config, adaptive, eval_log_path):
+        """learn_vec's DeferredEvaluations (iqn/deferred_eval.py), or None -- with one log line -- where the grouped launch has no twin of this agent's
+        acting form.  `options`: True, or a dict of further DeferredEvaluations arguments."""
+        from .fused_act import act_context
+        ok = self.device.type == "cuda" and self.use_fused_act and self.use_library_rng and not self.shared_taus and hasattr(eval_env, "h")
+        if ok and act_context(self.qnetwork_local).variant != 2:
+            ok = False
+        if not ok:
+            print("[learn_vec] eval_deferred: the grouped episode launch does not reproduce this acting form; evaluating inline")
+            return None
+        from .deferred_eval import DeferredEvaluations
+        kw = dict(options) if isinstance(options, dict) else {}
+        return DeferredEvaluations(self, eval_config, adaptive=adaptive, eval_log_path=eval_log_path, precision=eval_env.precision, verbose=kw.pop("verbose", True), **kw)
 
     def check_learner(self):
         """Raise if a bounded wait of the fused gradient step ran out since the last look (`FusedTrainer.check_timeouts`): the step(s) concerned updated
@@ -623,8 +649,9 @@ class IQNAgent(ReferenceLoopMixin):
         return dict(rewards=reward_data, successes=success_data, times=time_data, energies=energy_data, actions=action_data)
 
     def _log_evaluation(self, greedy, action_data, reward_data, success_data, time_data, energy_data, eval_log_path,
-                        verbose=True):
-        """agent.py:367-398: summary print + append + npz with the reference's keys."""
+                        verbose=True, timestep=None):
+        """agent.py:367-398: summary print + append + npz with the reference's keys.  `timestep`: the reported timestep the evaluated policy was taken
+        at, where that is not now (iqn/deferred_eval.py)."""
         policy = "greedy" if greedy else "adaptive"
         if verbose:
             idx = np.where(np.array(success_data) == 1)[0]
@@ -636,7 +663,7 @@ class IQNAgent(ReferenceLoopMixin):
             print(f"Avg time: {avg_t:.2f}")
             print(f"Avg energy: {avg_e:.2f}")
             print(f"++++++++ Evaluation info ({policy} IQN) ++++++++\n")
-        self.eval_timesteps[policy].append(int(round(self.current_timestep * getattr(self, "_report_scale", 1.0))))
+        self.eval_timesteps[policy].append(int(round(self.current_timestep * getattr(self, "_report_scale", 1.0))) if timestep is None else int(timestep))
         self.eval_actions[policy].append(action_data)
         self.eval_rewards[policy].append(reward_data)
         self.eval_successes[policy].append(success_data)

@@ -11,7 +11,7 @@ import weakref
 import torch
 
 from .. import _capi
-from ..episodes import trace_buffers
+from ..episodes import EPISODE_TRACES, trace_buffers
 
 _ORDER = ("velocity_encoder", "goal_encoder", "sensor_encoder", "cos_embedding", "hidden_layer", "hidden_layer_2", "output_layer")
 
@@ -340,6 +340,58 @@ def rollout_iqn(net, env, n_steps, rng, cvar=1.0, adaptive=False, shared_taus=Fa
     out = dict(tr)
     out["final_obs"] = env.obs
     out["steps_run"] = int(steps.item())
+    return out
+
+
+def image_floats():
+    """32-bit words of one acting weight image (C-ABI mn_iqn_image_floats): the row length of `rollout_iqn_groups`' `images`."""
+    return int(_capi.lib().mn_iqn_image_floats())
+
+
+@torch.no_grad()
+def export_image(net, out):
+    """A copy of `net`'s acting weight image -- what `rollout_iqn` would act with now -- in `out`, an [image_floats()] uint32 (or int32) tensor on the
+    net's device (C-ABI mn_iqn_export_image): rebuilt first if the weights changed, then one device copy on the current stream, no host synchronisation.
+    Raises for the forms the episode launches do not reproduce (the exact-f32 variant, launch-shared taus)."""
+    ctx = act_context(net)
+    assert out.is_cuda and out.device == ctx.device and out.is_contiguous() and out.element_size() == 4 and out.numel() == image_floats()
+    rc = _capi.lib().mn_iqn_export_image(ctx.h, ctx.weights(net), _p(out), _capi.stream_ptr(ctx.device))
+    if rc:
+        raise _capi.MarineNavHipError(f"mn_iqn_export_image failed ({rc})")
+    return out
+
+
+@torch.no_grad()
+def rollout_iqn_groups(images, env, n_steps, rng_states, rows_per_group, cvar_rows=None, adaptive_rows=None, trace=EPISODE_TRACES):
+    """`rollout_iqn` for MANY networks in ONE launch (C-ABI mn_rollout_iqn_groups): rows [g * rows_per_group, (g + 1) * rows_per_group) of `env` act
+    with `images[g]` (a [G][>= image_floats()] 4-byte tensor of `export_image` rows) and `rng_states[g]` ([G][2] int64: {seed, counter}, the state of
+    an ActRng; each counter advances by its group's longest episode), their taus keyed by the row's index inside the group.  Group g gets, bit for bit, what
+    `rollout_iqn(net_g, env_g, n_steps, ActRng(seed_g), cvar_rows=..., adaptive_rows=...)` gets on an env of its own with the group's worlds.
+    `cvar_rows` / `adaptive_rows`: [n] over ALL rows (None: cvar 1 / not adaptive).  Returns the requested traces ([n_steps][n] ...), `final_obs`
+    and `steps_run`, an int32 [G] DEVICE tensor (nothing here synchronises with the host)."""
+    T, n, dev, R = int(n_steps), env.n_envs, env.device, int(rows_per_group)
+    assert images.is_cuda and images.dim() == 2 and images.element_size() == 4 and images.stride(1) == 1
+    assert rng_states.is_cuda and rng_states.dtype == torch.int64 and rng_states.is_contiguous() and rng_states.shape == (images.shape[0], 2)
+    G = images.shape[0]
+    cv_rows = cvar_rows.to(device=dev, dtype=torch.float32).contiguous() if cvar_rows is not None else None
+    ad_rows = adaptive_rows.to(device=dev, dtype=torch.uint8).contiguous() if adaptive_rows is not None else None
+    assert cv_rows is None or cv_rows.numel() == n
+    assert ad_rows is None or ad_rows.numel() == n
+    assert "quantiles" not in trace and "taus" not in trace and "traj" not in trace, "the grouped launch records no quantile / tau / trajectory traces"
+    tr = trace_buffers(T, n, dev, trace)
+    p = lambda k: _p(tr[k]) if k in tr else None
+    steps = torch.zeros(G, dtype=torch.int32, device=dev)
+    words = env.__dict__.get("_group_words")      # the launch's tickets: zeroed once, left zero by every launch
+    if words is None or words.shape[0] < G:
+        words = env._group_words = torch.zeros(G, 2, dtype=torch.int32, device=dev)
+    rc = _capi.lib().mn_rollout_iqn_groups(env.h, _p(images), images.stride(0), G, R, T, _p(rng_states), _p(cv_rows), _p(ad_rows), _p(env.obs), p("obs"),
+                                           p("reward"), p("done"), p("info"), p("action"), p("cvar"), p("q"), _p(words), _p(steps), env._stream())
+    if rc:
+        raise _capi.MarineNavHipError(f"mn_rollout_iqn_groups failed ({rc}): {_capi.lib().mn_last_error(env.h).decode()}")
+    out = dict(tr)
+    out["final_obs"] = env.obs
+    out["steps_run"] = steps
+    out["group_words"] = words[:G]
     return out
 
 

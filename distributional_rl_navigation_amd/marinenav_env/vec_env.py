@@ -319,10 +319,11 @@ class VecMarineNavEnv:
         return out.value
 
     # ---- worlds ------------------------------------------------------------------------------
-    def load_worlds(self, worlds, first_env=0):
+    def load_worlds(self, worlds, first_env=0, repeat=1):
         """reset_with_eval_config (marinenav_env.py:467-555) for consecutive envs.  `worlds` is a
         list of dicts with keys cores [n,4]=(x,y,clockwise,Gamma), obstacles [n,3]=(x,y,r), start,
-        goal, init_theta, init_speed.  Returns the first observations of those envs."""
+        goal, init_theta, init_speed.  Returns the first observations of those envs.  `repeat` > 1: the list that many times in a row (what
+        `worlds * repeat` loads, without walking the list again for every copy)."""
         cnt = len(worlds)
         ncs = np.zeros(cnt, np.int32); nos = np.zeros(cnt, np.int32)
         cxy = np.zeros((cnt, MAX_CORES, 2)); cw = np.zeros((cnt, MAX_CORES), np.int32); gm = np.zeros((cnt, MAX_CORES))
@@ -337,6 +338,10 @@ class VecMarineNavEnv:
             cxy[i, :len(c)] = c[:, :2]; cw[i, :len(c)] = c[:, 2] != 0; gm[i, :len(c)] = c[:, 3]
             oxy[i, :len(o)] = o[:, :2]; orr[i, :len(o)] = o[:, 2]
             st[i] = w["start"]; gl[i] = w["goal"]; th[i] = w["init_theta"]; sp[i] = w["init_speed"]
+        if repeat > 1:
+            cnt *= int(repeat)
+            ncs, nos, cxy, cw, gm, oxy, orr, st, gl, th, sp = (np.ascontiguousarray(np.concatenate([x] * int(repeat)))
+                                                               for x in (ncs, nos, cxy, cw, gm, oxy, orr, st, gl, th, sp))
         d = C.c_double
         self._check(self.L.mn_load_worlds(self.h, int(first_env), cnt, _np_ptr(ncs, C.c_int32), _np_ptr(cxy, d),
                                           _np_ptr(cw, C.c_int32), _np_ptr(gm, d), _np_ptr(nos, C.c_int32), _np_ptr(oxy, d),

@@ -106,7 +106,7 @@ def plan_cadence(total_timesteps, eval_freq, n_envs_total, batch, ref_batch=32, 
 def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=256, replay=100_000, verbose=True,
               grad_steps=None, torch_train=False, total_grad_steps=None, n_evals=None, cvar=1.0, precision="f64",
               exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1,
-              eval_one_launch=False):
+              eval_one_launch=False, eval_deferred=False):
     """train_IQN_model.py:74-121 on the vector env.  `params` is one trial of the reference's config grid
     (seed, total_timesteps, eval_freq, save_dir); see `plan_cadence` for how its env-step cadences map to vector steps.
     `precision`: the env kernels' arithmetic.  "f64" (default: every float32 output within 1e-5 of the reference, no
@@ -117,7 +117,9 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=256, 
     `target_sync_mult`, `final_eps`: study knobs (scripts/learning_curve.py) -- the target network is copied every target_sync_mult x the planned number of gradient
     steps; the exploration floor (agent.py: 0.05); `n_step`: the agent's n-step returns (agent.py:12-29; the reference's scripts use 1; > 1 takes the step + append launch pair
     instead of the fused mn_step_append).  `eval_adaptive` = False skips the adaptive-CVaR evaluation at the evaluation points (the reference runs both).
-    `eval_one_launch`: each evaluation as one mn_rollout_iqn launch instead of one Python iteration per env step (same results)."""
+    `eval_one_launch`: each evaluation as one mn_rollout_iqn launch instead of one Python iteration per env step (same results).
+    `eval_deferred`: an evaluation point keeps the policy of the moment and the episodes of all pending points run as one mn_rollout_iqn_groups launch
+    (iqn/deferred_eval.py) -- with `n_evals=300` the reference's evaluation density."""
     import torch
     from .iqn.agent import IQNAgent
     from .marinenav_env.vec_env import VecMarineNavEnv
@@ -166,7 +168,7 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=256, 
                     eval_freq=plan["eval_every_vector_steps"], eval_log_path=exp_dir if writer else None,
                     total_timesteps=plan["vector_steps"] * total, world_size=world, cvar=cvar, verbose=False,
                     report_timestep_scale=params["total_timesteps"] / (plan["vector_steps"] * total), eval_adaptive=eval_adaptive,
-                    eval_one_launch=eval_one_launch)
+                    eval_one_launch=eval_one_launch, eval_deferred=eval_deferred)
     if writer:
         agent.qnetwork_local.save(exp_dir)
     train_env.close()
@@ -225,6 +227,9 @@ def main(argv=None):
     ap.add_argument("--shared-taus", action="store_true", help="acting: one set of 32 taus per act launch instead of per env (opt-in, ~11 %% shorter runs)")
     ap.add_argument("--eval-one-launch", action="store_true",
                     help="evaluations: every episode in one mn_rollout_iqn launch instead of one Python iteration per step (same results)")
+    ap.add_argument("--eval-deferred", action="store_true",
+                    help="evaluations: a point only keeps the policy of the moment; all pending points run later as ONE mn_rollout_iqn_groups launch on tau streams of "
+                         "their own (iqn/deferred_eval.py).  With --n-evals 300: the reference's evaluation density")
     args = ap.parse_args(argv)
     params = json.load(args.config_file)
     import torch
@@ -244,7 +249,7 @@ def main(argv=None):
         p["training_time"] = stamp
     kw = dict(batch=args.batch, replay=args.replay, grad_steps=args.grad_steps, torch_train=args.torch_train,
               total_grad_steps=args.total_grad_steps, n_evals=args.n_evals, cvar=args.cvar, precision=args.precision,
-              exchange=args.exchange, shared_taus=args.shared_taus, eval_one_launch=args.eval_one_launch)
+              exchange=args.exchange, shared_taus=args.shared_taus, eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred)
     if args.num_procs > 1:
         # train_IQN_model.py:173-179: a Pool of workers, one trial each.  `spawn`: every worker gets its own HIP context
         if world > 1:

@@ -419,6 +419,29 @@ int mn_rollout_iqn_eval(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weigh
                         float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev, float *cvar_trace_dev,
                         float *q_trace_dev, float *quantiles_trace_dev, float *taus_trace_dev, int32_t *steps_run_dev, void *stream);
 
+/* Size of the acting weight image in 32-bit words: what mn_iqn_export_image writes and one group of mn_rollout_iqn_groups reads. */
+int32_t mn_iqn_image_floats(void);
+/* Copies the context's acting weight image -- rebuilt first if stale, as mn_iqn_refresh does -- into image_out_dev[mn_iqn_image_floats()] (device,
+ * 16-byte aligned), device to device on `stream`: a snapshot of the policy that mn_rollout_iqn_groups can act with later, whatever happens to the
+ * weights meanwhile.  MN_ERR_INVALID for the forms mn_rollout_iqn refuses (the exact-f32 variant, a launch-shared tau mode) or a NULL argument. */
+int mn_iqn_export_image(mn_iqn_ctx *c, const float *const *weights, uint32_t *image_out_dev, void *stream);
+/* IQN episodes of MANY sets of weights in ONE launch: mn_rollout_iqn_rows with a weight image and a tau stream per GROUP of rows.  Row e of `h`
+ * belongs to group e / rows_per_group and is row e % rows_per_group of it.  Group g acts with the image at images_dev + g * image_stride (32-bit
+ * words; images of mn_iqn_export_image) and with rng_states_dev[g] = {seed, call counter}, its tau draws keyed by the row's index inside the group:
+ * the group computes -- traces, final rows and poses, and its counter, which grows by steps_run_dev[g] = the longest episode of the group -- bit for
+ * bit what mn_rollout_iqn_rows computes on a handle of rows_per_group rows holding those worlds.  cvar_row_dev / adaptive_row_dev are indexed by e
+ * (NULL: cvar 1 / not adaptive).  Episode semantics and traces ([n_steps][n] ..., any may be NULL) as mn_rollout_iqn_rows.
+ * group_words_dev [n_groups][2] u32 is the launch's scratch: zeroed ONCE by the caller, left zero by every launch; one launch at a time per
+ * buffer.  steps_run_dev [n_groups] i32 may be NULL.  The launch has n workgroups, usually far more than the device runs at once; none waits for
+ * another.  No allocation, no host synchronisation, caller's stream.
+ * MN_ERR_INVALID, without launching, if n_groups * rows_per_group is not the handle's n_envs, if image_stride is below mn_iqn_image_floats() or no
+ * multiple of 4, for a NULL h / images_dev / rng_states_dev / obs_dev / group_words_dev, or n_steps < 1.  It records no sub-step trajectories: an
+ * attached trace (mn_set_trajectory_trace) is detached and the call refused. */
+int mn_rollout_iqn_groups(mn_handle *h, const uint32_t *images_dev, int64_t image_stride, int32_t n_groups, int32_t rows_per_group, int32_t n_steps,
+                          uint64_t *rng_states_dev, const float *cvar_row_dev, const uint8_t *adaptive_row_dev, float *obs_dev, float *obs_trace_dev,
+                          float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev, float *cvar_trace_dev,
+                          float *q_trace_dev, uint32_t *group_words_dev, int32_t *steps_run_dev, void *stream);
+
 /* ---- replay ring ------------------------------------------------------------------------------
  * ReplayBuffer.add (thirdparty/IQN/replay_buffer.py:26-34) for n transitions in one launch: batch row i
  * goes to ring slot (ptr + i) mod capacity (FIFO eviction like deque(maxlen); if n > capacity only the
