@@ -108,6 +108,8 @@ SIGNATURES = [
     ("mn_rollout_iqn_groups", C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32] + [_vp] * 14),
     ("mn_rollout_dqn", C.c_int, [_vp, C.POINTER(C.c_void_p), _vp, _i32, _i32] + [_vp] * 8),
     ("mn_dqn_image_floats", C.c_int64, []),
+    ("mn_dqn_export_image", C.c_int, [C.POINTER(C.c_void_p), _vp, _vp]),
+    ("mn_rollout_dqn_groups", C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32] + [_vp] * 8),
     ("mn_dqn_act", C.c_int, [_vp, C.POINTER(C.c_void_p), _vp, _i32, _vp, _vp, _i32, _vp]),
     ("mn_dqn_train_workspace_floats", C.c_int64, [_i32]),
     ("mn_dqn_train_step", C.c_int, [_vp] * 5 + [_i64] + [_vp] * 11 + [_i32, C.c_float] + [_dbl] * 5 + [_vp]),

@@ -520,6 +520,34 @@ extern "C" int mn_rollout_dqn(mn_handle *h, const float *const *weights, float *
     });
 }
 
+extern "C" int mn_dqn_export_image(const float *const *weights, float *image_out_dev, void *stream) {
+    if (!weights || !image_out_dev || (uintptr_t)image_out_dev % 16 != 0) return MN_ERR_INVALID;
+    for (int i = 0; i < 18; ++i) if (!weights[i]) return MN_ERR_INVALID;
+    mn_launch_dqn_pack(weights, image_out_dev, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
+}
+
+extern "C" int mn_rollout_dqn_groups(mn_handle *h, const float *images_dev, int64_t image_stride, int32_t n_groups, int32_t rows_per_group, int32_t n_steps,
+                                     float *obs_dev, float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev,
+                                     int32_t *action_trace_dev, float *q_trace_dev, void *stream) {
+    if (!h) return MN_ERR_INVALID;
+    if (h->traj_trace) {      // as mn_rollout_iqn_groups: the attachment is consumed, the call refused
+        h->traj_trace = nullptr;
+        h->traj_trace_steps = 0;
+        return fail(h, MN_ERR_INVALID, "mn_rollout_dqn_groups records no trajectory trace");
+    }
+    if (!images_dev || !obs_dev || n_steps < 1) return MN_ERR_INVALID;
+    if (n_groups < 1 || rows_per_group < 1 || (int64_t)n_groups * rows_per_group != (int64_t)h->A.n)
+        return fail(h, MN_ERR_INVALID, "mn_rollout_dqn_groups: n_groups * rows_per_group must be the handle's n_envs");
+    if (image_stride < mn_dqn_image_floats() || image_stride % 4 != 0 || (uintptr_t)images_dev % 16 != 0)
+        return fail(h, MN_ERR_INVALID, "mn_rollout_dqn_groups: image_stride below mn_dqn_image_floats() or no multiple of 4, or images_dev not 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return launch_episodes(h, s, [&] {
+        mn_launch_rollout_dqn_groups(h->A, h->P, h->params.precision, n_steps, images_dev, image_stride, n_groups, rows_per_group, obs_dev, obs_trace_dev,
+                                     reward_trace_dev, done_trace_dev, info_trace_dev, action_trace_dev, q_trace_dev, s);
+    });
+}
+
 extern "C" int mn_planner_act(const float *obs_dev, int32_t n, int32_t policy, const double *a, const double *w, int32_t *actions_dev, void *stream) {
     if (!obs_dev || !actions_dev || !a || !w || n <= 0 || (policy != MN_POLICY_APF && policy != MN_POLICY_BA)) return MN_ERR_INVALID;
     mn_launch_planner_act(obs_dev, n, policy, a, w, actions_dev, (hipStream_t)stream);

@@ -126,6 +126,10 @@ int mn_iqn_rollout_image(mn_iqn_ctx *c, const float *const *weights, hipStream_t
 void mn_launch_dqn_pack(const float *const *weights, float *image_dev, hipStream_t s);
 void mn_launch_rollout_dqn(const MnArrays &A, const MnDev &P, int precision, int n_steps, const float *image, float *obs_io, float *obs_trace,
                            float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *q_trace, double *traj_trace, hipStream_t s);
+// the same episodes with a weight image per group of rows (mn_rollout_dqn_groups.hip); image_stride in floats
+void mn_launch_rollout_dqn_groups(const MnArrays &A, const MnDev &P, int precision, int n_steps, const float *images, int64_t image_stride, int n_groups,
+                                  int rows_per_group, float *obs_io, float *obs_trace, float *reward_trace, uint8_t *done_trace, uint8_t *info_trace,
+                                  int32_t *action_trace, float *q_trace, hipStream_t s);
 // mode 0: full reset (RNG); mode 1: pose-only (keeps the loaded world, no RNG)
 // (mn_launch_reset: `sharded` = count_dev / list_dev are the handle's done-queue of one step -- MN_QSHARDS counters and lists; otherwise one counter, one list)
 void mn_launch_reset_under_act(const MnArrays &A, const MnDev &P, int precision, const uint32_t *count_dev, const int32_t *list_dev, float *obs,

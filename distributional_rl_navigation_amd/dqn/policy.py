@@ -17,6 +17,37 @@ import torch
 import torch.nn as nn
 
 
+def image_floats():
+    """Floats of one weight image (C-ABI mn_dqn_image_floats): the row length of `rollout_dqn_groups`' `images`."""
+    from .. import _capi
+    return int(_capi.lib().mn_dqn_image_floats())
+
+
+@torch.no_grad()
+def rollout_dqn_groups(images, env, n_steps, rows_per_group, trace=("reward", "done", "info", "action")):
+    """`DQNPolicy.rollout` for MANY networks in ONE launch (C-ABI mn_rollout_dqn_groups): rows [g * rows_per_group, (g + 1) * rows_per_group) of `env`
+    act with `images[g]` (a [G][>= image_floats()] float32 tensor of `DQNPolicy.export_image` rows).  Group g gets, bit for bit, what
+    `policy_g.rollout(env_g, n_steps)` gets on an env of its own with the group's worlds.  Returns the requested traces ([n_steps][n] ...; "obs"
+    [n_steps][n][26], "q" [n_steps][n][9]; no "traj") and `final_obs`.  Nothing here synchronises with the host; the longest episode of a group is
+    `episodes.steps_run` of its columns of the done trace."""
+    import ctypes as C
+    from .. import _capi
+    from ..episodes import trace_buffers
+    T, n, dev, R = int(n_steps), env.n_envs, env.device, int(rows_per_group)
+    assert images.is_cuda and images.dim() == 2 and images.dtype == torch.float32 and images.stride(1) == 1
+    assert "traj" not in trace, "the grouped launch records no trajectory trace"
+    G = images.shape[0]
+    tr = trace_buffers(T, n, dev, trace)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    rc = _capi.lib().mn_rollout_dqn_groups(env.h, p(images), images.stride(0), G, R, T, p(env.obs), p(tr.get("obs")), p(tr.get("reward")), p(tr.get("done")),
+                                           p(tr.get("info")), p(tr.get("action")), p(tr.get("q")), env._stream())
+    if rc:
+        raise _capi.MarineNavHipError(f"mn_rollout_dqn_groups failed ({rc}): {_capi.lib().mn_last_error(env.h).decode()}")
+    out = dict(tr)
+    out["final_obs"] = env.obs
+    return out
+
+
 class _Extractor(nn.Module):
     def __init__(self, state_size=26, action_size=9):
         super().__init__()
@@ -114,6 +145,23 @@ class DQNPolicy(nn.Module):
         if rc:
             raise _capi.MarineNavHipError(f"mn_dqn_act failed ({rc})")
         return q, a
+
+    @torch.no_grad()
+    def export_image(self, out):
+        """The weight image the HIP kernels would act with NOW, packed into `out` -- an [image_floats()] float32 tensor on the policy's device, 16-byte
+        aligned -- on the current stream (C-ABI mn_dqn_export_image): a snapshot `rollout_dqn_groups` can act with later, whatever happens to the
+        weights meanwhile.  The weights are read through the pointer table `_image()` maintains, i.e. from the parameters' current storage: correct
+        after a fused gradient step too.  No host synchronisation."""
+        import ctypes as C
+        from .. import _capi
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == image_floats()
+        st, repack = self._image(out.device)
+        if repack:
+            st["sig"] = None      # only the pointer table was brought up to date: the policy's own image is still to be rebuilt by its next launch
+        rc = _capi.lib().mn_dqn_export_image(st["ptrs"], C.c_void_p(out.data_ptr()), _capi.stream_ptr(out.device))
+        if rc:
+            raise _capi.MarineNavHipError(f"mn_dqn_export_image failed ({rc})")
+        return out
 
     def weights_changed(self):
         """The weights were written outside PyTorch's version counters (the fused gradient step, dqn/fused_train.py): repack the

@@ -2,7 +2,7 @@
 path, with the interface of train_iqn.
 
     python -m distributional_rl_navigation_amd.train_dqn -C config_DQN.json [--n-envs 4096] [--batch 256] [--replay N]
-        [--grad-steps G] [--total-grad-steps N] [--n-evals K] [--torch-train] [--eval-one-launch] [--dry-run]
+        [--grad-steps G] [--total-grad-steps N] [--n-evals K] [--torch-train] [--eval-one-launch] [--eval-deferred] [--dry-run]
 
 Same JSON schema as train_iqn (agent, seed (list -> grid), total_timesteps, eval_freq, save_dir); the trials run one after another
 on one device.  Cadence: `train_iqn.plan_cadence` with the reference DQN's values (one batch-32 gradient step per env step, target
@@ -16,6 +16,10 @@ Per trial, in save_dir/training_<time>/seed_<s>/, what the sb3 fork's EvalCallba
 plan), training_schedule.json, evaluations.npz (timesteps, rewards, times, energies, successes, actions on the 30 evaluation worlds
 of create_eval_configs), latest_model.zip after every evaluation and best_model.zip on a new best mean reward (a zip holding
 policy.pth with q_net.* and q_net_target.*).
+
+`--eval-deferred`: an evaluation point only keeps the policy of the moment (a weight image and the parameters, device copies on the training
+stream); the episodes of all pending points run later as ONE mn_rollout_dqn_groups launch (dqn/deferred_eval.py) and are logged as above -- the same
+files, bit for bit, without a host round trip per point: `--n-evals 300` logs the reference's evaluation density.
 """
 import argparse
 import io
@@ -75,19 +79,38 @@ def evaluate(agent, eval_env, eval_config, max_steps=1000, one_launch=False):
     return evaluation_from_rollout(host_traces(tr), eval_env.discount, energy_table(r0["a"], r0["w"]), r0["dt"], r0["N"])
 
 
-def save_zip(agent, path):
-    """An sb3-style checkpoint zip holding policy.pth (q_net.* and q_net_target.*): what DQNPolicy.load / DQNAgent.load read."""
+def save_state_zip(state_dict, path):
+    """An sb3-style checkpoint zip holding `state_dict` as policy.pth."""
     import torch
     buf = io.BytesIO()
-    torch.save({k: v.cpu() for k, v in agent.state_dict().items()}, buf)
+    torch.save({k: v.cpu() for k, v in state_dict.items()}, buf)
     with zipfile.ZipFile(path, "w") as z:
         z.writestr("policy.pth", buf.getvalue())
 
 
+def save_zip(agent, path):
+    """An sb3-style checkpoint zip holding policy.pth (q_net.* and q_net_target.*): what DQNPolicy.load / DQNAgent.load read."""
+    save_state_zip(agent.state_dict(), path)
+
+
+def write_evaluations(exp_dir, log):
+    """evaluations.npz of the sb3 fork's EvalCallback from the lists of `log` (timesteps, rewards, times, energies, successes, actions)."""
+    actions = np.empty(len(log["actions"]), dtype=object)
+    actions[:] = log["actions"]
+    np.savez(os.path.join(exp_dir, "evaluations.npz"), timesteps=np.array(log["timesteps"], dtype=np.int64),
+             rewards=np.array(log["rewards"], dtype=np.float64), times=np.array(log["times"], dtype=np.float64),
+             energies=np.array(log["energies"], dtype=np.float64), successes=np.array(log["successes"], dtype=bool),
+             actions=actions)
+
+
 def run_trial(device, params, n_envs, batch=256, replay=100_000, grad_steps=None, total_grad_steps=None, n_evals=None, torch_train=False,
-              verbose=True, eval_one_launch=False):
-    """train_sb3_model.py on the vector env for one trial of the config grid; returns the trial directory.
-    `eval_one_launch`: each evaluation as one mn_rollout_dqn launch instead of one Python iteration per env step (same results)."""
+              verbose=True, eval_one_launch=False, eval_deferred=False, eval_config=None, max_eval_steps=1000, return_agent=False):
+    """train_sb3_model.py on the vector env for one trial of the config grid; returns the trial directory (`return_agent`: and the agent).
+    `eval_one_launch`: each evaluation as one mn_rollout_dqn launch instead of one Python iteration per env step (same results).
+    `eval_deferred` (True, or a dict of DeferredEvaluations arguments such as max_pending): an evaluation point keeps the policy of the moment and the
+    episodes of all pending points run as one mn_rollout_dqn_groups launch (dqn/deferred_eval.py) -- the same files as the inline form; where the policy
+    does not act through the fused kernel (CPU, another net_arch) one line says so and the evaluations stay inline.
+    `eval_config`: the evaluation worlds (default: the 30 of create_eval_configs); `max_eval_steps`: the step limit of an evaluation episode."""
     import torch
     from .dqn.agent import DQNAgent
     from .marinenav_env.vec_env import VecMarineNavEnv
@@ -106,7 +129,8 @@ def run_trial(device, params, n_envs, batch=256, replay=100_000, grad_steps=None
 
     train_env = VecMarineNavEnv(n_envs, seed=params["seed"], schedule=TRAINING_SCHEDULE, timestep_scale=plan["timestep_scale"], device=device,
                                 precision="f64")
-    eval_config = create_eval_configs(device)
+    if eval_config is None:
+        eval_config = create_eval_configs(device)
     eval_env = VecMarineNavEnv(len(eval_config), device=device, precision="f64")
     agent = DQNAgent(26, 9, buffer_size=replay, batch_size=batch, learning_starts=0, device=device, seed=params["seed"] + 100,
                      fused_train=not torch_train)
@@ -115,6 +139,16 @@ def run_trial(device, params, n_envs, batch=256, replay=100_000, grad_steps=None
     log = dict(timesteps=[], rewards=[], times=[], energies=[], successes=[], actions=[])
     best = -np.inf
     t0 = time.time()
+    deferred = None
+    if eval_deferred:
+        from .dqn.deferred_eval import DeferredEvaluations, can_defer
+        if can_defer(agent):
+            deferred = DeferredEvaluations(agent, eval_config, exp_dir, **dict(dict(max_steps=max_eval_steps, verbose=verbose, label=f"seed {params['seed']} ",
+                                                                                    n_evals=plan["n_evals"], t0=t0),
+                                                                               **(eval_deferred if isinstance(eval_deferred, dict) else {})))
+        else:
+            print("[train_dqn] eval_deferred: the policy does not act through the fused kernel here (CPU or another net_arch); evaluations stay inline", flush=True)
+    n_points = 0
     obs = train_env.reset()
     grad_steps_done = 0
     for it in range(plan["vector_steps"]):
@@ -130,18 +164,17 @@ def run_trial(device, params, n_envs, batch=256, replay=100_000, grad_steps=None
                 if grad_steps_done % sync_every == 0:
                     agent.sync_target()
         if (it + 1) % plan["eval_every_vector_steps"] == 0 or it + 1 == plan["vector_steps"]:
-            if len(log["timesteps"]) >= plan["n_evals"]:
+            if n_points >= plan["n_evals"]:
                 continue
-            ev = evaluate(agent, eval_env, eval_config, one_launch=eval_one_launch)
+            n_points += 1
+            if deferred is not None:      # keep the policy of this moment; its episodes run with the other pending points'
+                deferred.snapshot(int(round((it + 1) * n_envs * report_scale)))
+                continue
+            ev = evaluate(agent, eval_env, eval_config, max_steps=max_eval_steps, one_launch=eval_one_launch)
             log["timesteps"].append(int(round((it + 1) * n_envs * report_scale)))
             for k in ("rewards", "times", "energies", "successes", "actions"):
                 log[k].append(ev[k])
-            actions = np.empty(len(log["actions"]), dtype=object)
-            actions[:] = log["actions"]
-            np.savez(os.path.join(exp_dir, "evaluations.npz"), timesteps=np.array(log["timesteps"], dtype=np.int64),
-                     rewards=np.array(log["rewards"], dtype=np.float64), times=np.array(log["times"], dtype=np.float64),
-                     energies=np.array(log["energies"], dtype=np.float64), successes=np.array(log["successes"], dtype=bool),
-                     actions=actions)
+            write_evaluations(exp_dir, log)
             save_zip(agent, os.path.join(exp_dir, "latest_model.zip"))
             mean_r = float(np.mean(ev["rewards"]))
             if mean_r > best:
@@ -149,11 +182,14 @@ def run_trial(device, params, n_envs, batch=256, replay=100_000, grad_steps=None
                 save_zip(agent, os.path.join(exp_dir, "best_model.zip"))
             if verbose:
                 print(f"[train_dqn] seed {params['seed']} eval {len(log['timesteps'])}/{plan['n_evals']} at {log['timesteps'][-1]} steps: "
-                      f"{int(np.sum(ev['successes']))}/30 successes, mean return {mean_r:.2f} ({time.time() - t0:.1f} s)", flush=True)
+                      f"{int(np.sum(ev['successes']))}/{len(eval_config)} successes, mean return {mean_r:.2f} ({time.time() - t0:.1f} s)", flush=True)
+    if deferred is not None:
+        deferred.flush()
+        deferred.close()
     torch.cuda.synchronize()
     train_env.close()
     eval_env.close()
-    return exp_dir
+    return (exp_dir, agent) if return_agent else exp_dir
 
 
 def main(argv=None):
@@ -170,6 +206,9 @@ def main(argv=None):
     ap.add_argument("--torch-train", action="store_true", help="eager PyTorch gradient step instead of the fused HIP kernel")
     ap.add_argument("--eval-one-launch", action="store_true",
                     help="run each evaluation's episodes in one HIP launch (mn_rollout_dqn) instead of one Python iteration per env step; same results")
+    ap.add_argument("--eval-deferred", action="store_true",
+                    help="evaluations: a point only keeps the policy of the moment; all pending points run later as ONE mn_rollout_dqn_groups launch and are "
+                         "logged as the inline form logs them (the same files); with --n-evals 300 the reference's evaluation density")
     ap.add_argument("--dry-run", action="store_true", help="print the plan of every trial as JSON and exit (no GPU needed)")
     args = ap.parse_args(argv)
     params = json.load(args.config_file)
@@ -181,7 +220,7 @@ def main(argv=None):
         for p in trials:
             plan = make_plan(p, args.n_envs, args.batch, args.grad_steps, args.total_grad_steps, args.n_evals)
             print(json.dumps(dict(seed=p["seed"], n_envs=args.n_envs, batch=args.batch, replay=args.replay, fused=not args.torch_train,
-                                  eval_one_launch=args.eval_one_launch, eps_start=exploration_rate(0, plan), eps_end=exploration_rate(int(np.ceil(plan["exploration_vector_steps"])), plan),
+                                  eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred, eps_start=exploration_rate(0, plan), eps_end=exploration_rate(int(np.ceil(plan["exploration_vector_steps"])), plan),
                                   plan=plan)))
         return
     import torch
@@ -190,7 +229,8 @@ def main(argv=None):
     for p in trials:
         t0 = time.time()
         d = run_trial(device, p, args.n_envs, batch=args.batch, replay=args.replay, grad_steps=args.grad_steps,
-                      total_grad_steps=args.total_grad_steps, n_evals=args.n_evals, torch_train=args.torch_train, eval_one_launch=args.eval_one_launch)
+                      total_grad_steps=args.total_grad_steps, n_evals=args.n_evals, torch_train=args.torch_train, eval_one_launch=args.eval_one_launch,
+                      eval_deferred=args.eval_deferred)
         print(f"[train_dqn] seed {p['seed']}: {time.time() - t0:.1f} s -> {d}", flush=True)
 
 

@@ -558,6 +558,23 @@ int mn_dqn_act(const float *obs_dev, const float *const *weights, float *image_d
 int mn_rollout_dqn(mn_handle *h, const float *const *weights, float *image_dev, int32_t repack, int32_t n_steps, float *obs_dev,
                    float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev,
                    float *q_trace_dev, void *stream);
+/* Packs weights[18] (as mn_dqn_act) into image_out_dev[mn_dqn_image_floats()] (device, 16-byte aligned) on `stream` -- the image mn_dqn_act and
+ * mn_rollout_dqn build with repack != 0 --: a snapshot of the policy that mn_rollout_dqn_groups can act with later, whatever happens to the weights
+ * meanwhile.  MN_ERR_INVALID for a NULL argument, a NULL entry among the 18 pointers or a misaligned destination. */
+int mn_dqn_export_image(const float *const *weights, float *image_out_dev, void *stream);
+/* DQN episodes of MANY sets of weights in ONE launch: mn_rollout_dqn with a weight image per GROUP of rows.  Row e of `h` belongs to group
+ * e / rows_per_group and is row e % rows_per_group of it.  Group g acts with the image at images_dev + g * image_stride (floats; images of
+ * mn_dqn_export_image, 16-byte aligned) and computes -- traces, final rows, poses and counters -- bit for bit what mn_rollout_dqn computes on a handle
+ * of rows_per_group rows holding those worlds.  Episode semantics and traces ([n_steps][n] ..., indexed by the handle's row e, any may be NULL) as
+ * mn_rollout_dqn.  The launch has n_groups * ceil(rows_per_group / 8) workgroups, possibly more than the device runs at once; none waits for
+ * another, and nothing is counted on the device: the longest episode of a group is read from its columns of the done trace.  No allocation, no host
+ * synchronisation, caller's stream.
+ * MN_ERR_INVALID, without launching, if n_groups < 1, rows_per_group < 1 or n_groups * rows_per_group is not the handle's n_envs, if image_stride is
+ * below mn_dqn_image_floats() or no multiple of 4 (or images_dev is not 16-byte aligned), for a NULL h / images_dev / obs_dev, or n_steps < 1.  It
+ * records no sub-step trajectories: an attached trace (mn_set_trajectory_trace) is detached and the call refused. */
+int mn_rollout_dqn_groups(mn_handle *h, const float *images_dev, int64_t image_stride, int32_t n_groups, int32_t rows_per_group, int32_t n_steps,
+                          float *obs_dev, float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev,
+                          int32_t *action_trace_dev, float *q_trace_dev, void *stream);
 /* ---- Fused gradient step of the DQN baseline (csrc/dqn_train.hip): ONE launch = one optimizer step of DQNAgent.train (sb3 DQN.train, dqn/dqn.py:188-230):
  * target forward on next_states, max over the 9 actions, y = r + (1 - done) gamma max; local forward on states, gather Q[a], smooth_l1_loss (beta 1,
  * mean); backward through the 9 layers; clip_grad_norm_(max_norm); torch.optim.Adam (step counter t = *step_dev + 1, advanced by the launch).
