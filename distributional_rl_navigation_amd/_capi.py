@@ -133,6 +133,7 @@ SIGNATURES = [
     ("mn_iqn_act", C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_void_p), _vp, _vp, C.c_float, _vp, _vp, _i32, _i32, _vp]),
     ("mn_iqn_act_rng", C.c_int, [_vp, _vp, C.POINTER(C.c_void_p), _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _i32, _i32, _vp]),
     ("mn_replay_append", C.c_int, [_vp] * 10 + [_i64, _i64, _i64, _vp]),
+    ("mn_episode_log", C.c_int, [_vp, _vp, _vp, _i32, _dbl, _i64, C.c_float] + [_vp] * 9 + [_i64, _vp, _vp]),
     ("mn_iqn_train_workspace_floats", C.c_int64, [_i32]),
     ("mn_iqn_train_workspace_misplaced_word", C.c_int64, [_i32]),
     ("mn_iqn_sample", C.c_int, [_i64, _i32, _vp, _vp, _vp, _i32, _vp]),

@@ -467,7 +467,7 @@ class IQNAgent(ReferenceLoopMixin):
     def learn_vec(self, total_vector_steps, train_env, eval_env=None, eval_config=None, eval_freq=None,
                   eval_log_path=None, total_timesteps=None, world_size=1, cvar=1.0, verbose=True,
                   train_every=None, on_step=None, report_timestep_scale=1.0, eval_adaptive=True, reset_under_act=True, eval_one_launch=False,
-                  eval_deferred=False):
+                  eval_deferred=False, episode_log=None, eval_points=None, max_eval_steps=1000):
         """Vectorised agent.py:94-173.  One iteration = one vector step of `train_env` (n_envs env
         steps): act_batch -> mn_step -> replay.add_batch -> mn_reset_done -> (every UPDATE_EVERY vector
         steps) sample + train.  `current_timestep` counts env steps over all ranks, so eps, the
@@ -478,7 +478,12 @@ class IQNAgent(ReferenceLoopMixin):
         max_steps): an evaluation point only KEEPS the policy of the moment (two device copies, no synchronisation); the episodes of all pending points run
         later as one mn_rollout_iqn_groups launch, each point on a tau stream of its own, and are logged as the inline form logs them
         (iqn/deferred_eval.py: what is on disk between flushes, and why the number of points then leaves the training run untouched).  Where that launch
-        cannot reproduce the acting form (CPU, PyTorch acting, torch.rand taus, the exact-f32 variant, launch-shared taus) the points stay inline."""
+        cannot reproduce the acting form (CPU, PyTorch acting, torch.rand taus, the exact-f32 variant, launch-shared taus) the points stay inline.
+        `eval_points` ({vector step: [timesteps]}, train_iqn.plan_eval_points): evaluate after exactly these vector steps instead of on the `eval_freq`
+        cadence and log each evaluation with the timestep given (the reference-budget plan: the reference's own evaluation timesteps, the final one
+        included).  `max_eval_steps`: the step limit of an inline evaluation episode.
+        `episode_log` (episode_log.EpisodeLog): the training episodes' record -- one more launch behind every vector step, drained (without a host
+        look) at the evaluation points and wherever its arrays could fill up, closed at the end of the loop."""
         n = train_env.n_envs
         per_iter = n * world_size
         # evaluation npz `timesteps` are reported as current_timestep * report_timestep_scale (train_iqn: reference-
@@ -500,11 +505,24 @@ class IQNAgent(ReferenceLoopMixin):
         try:
             for it in range(total_vector_steps):
                 eps = self.linear_eps(total_timesteps)
-                evaluate_now = eval_env is not None and cadence_tick(self, train_every, eval_freq).evaluate      # (the state vec_step's own tick sees)
+                if eval_points is None:
+                    evaluate_now = eval_env is not None and cadence_tick(self, train_every, eval_freq).evaluate      # (the state vec_step's own tick sees)
+                    points = (None,) if evaluate_now else ()
+                else:
+                    points = tuple(eval_points.get(it, ()))
+                    evaluate_now = eval_env is not None and len(points) > 0
                 obs, reward, done, info, loss = self.vec_step(train_env, obs, eps, cvar, train_every, per_iter)
                 guard.after_step(it)
                 if loss is not None:
                     stats["loss"] = loss
+                if episode_log is not None:
+                    episode_log.step(reward, done, info, it, eps)
+                    if len(points):      # a summary row per evaluation interval, the evaluation's timestep on it
+                        episode_log.drain(int(round(self.current_timestep * self._report_scale)) if points[-1] is None else points[-1])
+                    elif episode_log.due():
+                        episode_log.drain(int(round(self.current_timestep * self._report_scale)), row=False)
+                if on_step is not None:
+                    stats["last"] = dict(reward=reward, done=done, info=info, eps=eps)
                 if verbose:
                     ep_ret += (train_env.discount ** ep_len) * reward
                     ep_len += 1
@@ -514,28 +532,19 @@ class IQNAgent(ReferenceLoopMixin):
                     stats["collisions"] += int((info == 3).sum())
                     stats["timeouts"] += int((info == 2).sum())
                     ep_ret.masked_fill_(d, 0.0); ep_len.masked_fill_(d, 0.0)
-                if evaluate_now and deferred is not None:
-                    deferred.snapshot(vector_step=it)
-                elif evaluate_now:
-                    self.check_learner()      # (a device synchronisation; the evaluation below is one anyway)
-                    res = self.evaluation_vec(eval_env, eval_config, greedy=True, eval_log_path=eval_log_path, one_launch=eval_one_launch)
-                    if eval_adaptive:
-                        self.evaluation_vec(eval_env, eval_config, greedy=False, eval_log_path=eval_log_path, one_launch=eval_one_launch)
-                    # agent.py:140-148 keeps the LATEST network at every evaluation point; the batched run also keeps the BEST greedy evaluation so far beside it
-                    # (`best_*`: ~1 run in 12 ends on a checkpoint far below its own best -- profiles/r05_learning_curve.txt)
-                    score = (int(sum(res["successes"])), float(np.mean(res["rewards"])))
-                    if self.best_eval is None or score > self.best_eval["score"]:
-                        self.best_eval = dict(score=score, timestep=self.eval_timesteps["greedy"][-1], grad_steps=self.grad_steps, vector_step=it)
-                        if eval_log_path is not None:
-                            self.qnetwork_local.save(eval_log_path, prefix="best_")
-                            with open(os.path.join(eval_log_path, "best_evaluation.json"), "w") as f:
-                                json.dump(dict(successes=score[0], n_worlds=len(res["successes"]), mean_return=score[1], **{k: v for k, v in self.best_eval.items() if k != "score"}), f)
-                    if eval_log_path is not None:
-                        self.qnetwork_local.save(eval_log_path)
+                for point in (points if evaluate_now else ()):
+                    if deferred is not None:
+                        deferred.snapshot(vector_step=it, timestep=point)
+                    else:
+                        self._evaluate_inline(it, point, eval_env, eval_config, eval_log_path, eval_adaptive, eval_one_launch, max_eval_steps)
                 if on_step is not None:
                     on_step(it, stats)
             if deferred is not None:
                 deferred.flush()
+            if episode_log is not None:
+                if episode_log.row_open:      # (what ended behind the last evaluation point)
+                    episode_log.drain(int(round(self.current_timestep * self._report_scale)))
+                episode_log.close()
             # the end-of-run look at the bounded waits happens while `reset_under_act` still says how this loop ran (every rank, evaluation env or not)
             if hasattr(train_env, "join_reset"):
                 train_env.join_reset()
@@ -549,6 +558,25 @@ class IQNAgent(ReferenceLoopMixin):
             if hasattr(train_env, "join_reset"):
                 train_env.join_reset()
         return stats
+
+    def _evaluate_inline(self, it, timestep, eval_env, eval_config, eval_log_path, eval_adaptive, one_launch, max_steps):
+        """An evaluation point of learn_vec, evaluated now: greedy and -- `eval_adaptive` -- adaptive, the `best_*` rule, the latest checkpoint.
+        `timestep`: the timestep to log (None: now)."""
+        self.check_learner()      # (a device synchronisation; the evaluation below is one anyway)
+        res = self.evaluation_vec(eval_env, eval_config, greedy=True, eval_log_path=eval_log_path, one_launch=one_launch, max_steps=max_steps, timestep=timestep)
+        if eval_adaptive:
+            self.evaluation_vec(eval_env, eval_config, greedy=False, eval_log_path=eval_log_path, one_launch=one_launch, max_steps=max_steps, timestep=timestep)
+        # agent.py:140-148 keeps the LATEST network at every evaluation point; the batched run also keeps the BEST greedy evaluation so far beside it
+        # (`best_*`: ~1 run in 12 ends on a checkpoint far below its own best -- profiles/r05_learning_curve.txt)
+        score = (int(sum(res["successes"])), float(np.mean(res["rewards"])))
+        if self.best_eval is None or score > self.best_eval["score"]:
+            self.best_eval = dict(score=score, timestep=self.eval_timesteps["greedy"][-1], grad_steps=self.grad_steps, vector_step=it)
+            if eval_log_path is not None:
+                self.qnetwork_local.save(eval_log_path, prefix="best_")
+                with open(os.path.join(eval_log_path, "best_evaluation.json"), "w") as f:
+                    json.dump(dict(successes=score[0], n_worlds=len(res["successes"]), mean_return=score[1], **{k: v for k, v in self.best_eval.items() if k != "score"}), f)
+        if eval_log_path is not None:
+            self.qnetwork_local.save(eval_log_path)
 
     def _deferred_evaluations(self, options, eval_env, eval_config, adaptive, eval_log_path):
         """learn_vec's DeferredEvaluations (iqn/deferred_eval.py), or None -- with one log line -- where the grouped launch has no twin of this agent's
@@ -626,12 +654,12 @@ class IQNAgent(ReferenceLoopMixin):
                            trace=EPISODE_TRACES)
 
     @torch.no_grad()
-    def evaluation_vec(self, eval_env, eval_config, greedy=True, eval_log_path=None, max_steps=1000, one_launch=False):
+    def evaluation_vec(self, eval_env, eval_config, greedy=True, eval_log_path=None, max_steps=1000, one_launch=False, timestep=None):
         """agent.py:319-398 with all evaluation worlds stepped side by side on the GPU.
         `eval_env` is a VecMarineNavEnv with n_envs == len(eval_config); the npz schema is unchanged.
         `one_launch`: every episode in one mn_rollout_iqn launch instead of a Python iteration per step -- the same results, bit for bit (the
         returned dict, the logged entries, the npz, the act draws' counter); where that launch cannot reproduce the loop's acting form it falls
-        back to the loop."""
+        back to the loop.  `timestep`: the timestep to log, where that is not the agent's current one."""
         from ..marinenav_env.vec_env import VecMarineNavEnv
         cfgs = list(eval_config.values())
         assert eval_env.n_envs == len(cfgs)
@@ -644,7 +672,7 @@ class IQNAgent(ReferenceLoopMixin):
             tr = loop_episodes(eval_env, obs, lambda t, o: self.act_batch(o, 0.0, 1.0 if greedy else self.adjust_cvar_batch(o)), max_steps)
         self.qnetwork_local.train()
         data = evaluation_from_traces(**host_traces(tr), discount=eval_env.discount, energy_tab=energy_table(r0["a"], r0["w"]), dt=r0["dt"], N=r0["N"])
-        self._log_evaluation(greedy, *data, eval_log_path)
+        self._log_evaluation(greedy, *data, eval_log_path, timestep=timestep)
         action_data, reward_data, success_data, time_data, energy_data = data
         return dict(rewards=reward_data, successes=success_data, times=time_data, energies=energy_data, actions=action_data)
 

@@ -145,9 +145,9 @@ class DeferredEvaluations:
 
     # ---- device half ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def snapshot(self, vector_step=None):
+    def snapshot(self, vector_step=None, timestep=None):
         """Keep the policy of this moment for a later evaluation: the acting weight image and the flat parameters go into slot `len(pending)` on the
-        current stream -- two device copies, no host synchronisation -- and the reported timestep is noted.  The snapshot that fills the last of the
+        current stream -- two device copies, no host synchronisation -- and the reported timestep is noted (`timestep`, or the agent's current one).  The snapshot that fills the last of the
         `max_pending` slots runs `flush()`."""
         from .fused_act import export_image, image_floats
         agent, net = self.agent, self.agent.qnetwork_local
@@ -158,7 +158,7 @@ class DeferredEvaluations:
         slot = len(self.pending)
         export_image(net, self._images[slot])
         torch.cat([p.detach().reshape(-1) for p in net.parameters()], out=self._params[slot])
-        self.pending.append(dict(timestep=int(round(agent.current_timestep * getattr(agent, "_report_scale", 1.0))), grad_steps=agent.grad_steps,
+        self.pending.append(dict(timestep=int(round(agent.current_timestep * getattr(agent, "_report_scale", 1.0))) if timestep is None else int(timestep), grad_steps=agent.grad_steps,
                                  vector_step=vector_step, seed=self.seed_of(self.n_taken)))
         self.n_taken += 1
         if len(self.pending) >= self.max_pending:

@@ -3,6 +3,7 @@ path, with the interface of train_iqn.
 
     python -m distributional_rl_navigation_amd.train_dqn -C config_DQN.json [--n-envs 4096] [--batch 256] [--replay N]
         [--grad-steps G] [--total-grad-steps N] [--n-evals K] [--torch-train] [--eval-one-launch] [--eval-deferred] [--dry-run]
+        [--env-budget reference] [--episode-log [full]]
 
 Same JSON schema as train_iqn (agent, seed (list -> grid), total_timesteps, eval_freq, save_dir); the trials run one after another
 on one device.  Cadence: `train_iqn.plan_cadence` with the reference DQN's values (one batch-32 gradient step per env step, target
@@ -16,6 +17,10 @@ Per trial, in save_dir/training_<time>/seed_<s>/, what the sb3 fork's EvalCallba
 plan), training_schedule.json, evaluations.npz (timesteps, rewards, times, energies, successes, actions on the 30 evaluation worlds
 of create_eval_configs), latest_model.zip after every evaluation and best_model.zip on a new best mean reward (a zip holding
 policy.pth with q_net.* and q_net_target.*).
+
+`--env-budget reference`: the reference's own experiment instead of its learner budget in big batches -- total_timesteps env steps in vector steps of
+N = 80, one batch-32 gradient step per env step from learning_starts on (2 990 000), target copy every 10 000 of them, the 1 M-row ring, evaluations logged
+at the reference's timesteps (deferred), and training_log.npz from the device-side episode log (episode_log.py; `--episode-log [full]` elsewhere).
 
 `--eval-deferred`: an evaluation point only keeps the policy of the moment (a weight image and the parameters, device copies on the training
 stream); the episodes of all pending points run later as ONE mn_rollout_dqn_groups launch (dqn/deferred_eval.py) and are logged as above -- the same
@@ -31,17 +36,24 @@ from datetime import datetime
 
 import numpy as np
 
-from .train_iqn import TRAINING_SCHEDULE, create_eval_configs, plan_cadence, trial_params
+from .train_iqn import TRAINING_SCHEDULE, create_eval_configs, make_episode_log, plan_cadence, plan_eval_points, resolve_budget_args, trial_params
 
 REF_BATCH, REF_UPDATE_EVERY, REF_TARGET_INTERVAL, REF_LEARNING_STARTS = 32, 1, 10_000, 10_000      # config_DQN.json / sb3 DQN defaults
 EXPLORATION_FRACTION, EPS_INITIAL, EPS_FINAL = 0.1, 1.0, 0.05
 
 
-def make_plan(params, n_envs, batch, grad_steps=None, total_grad_steps=None, n_evals=None):
+def make_plan(params, n_envs, batch, grad_steps=None, total_grad_steps=None, n_evals=None, budget="learner", reference=None):
+    """`train_iqn.plan_cadence` with the reference DQN's constants.  `budget="reference"`: the reference's own experiment in vector steps of `n_envs` env
+    steps -- one batch-32 gradient step per env step from the vector step that starts at learning_starts on (n_envs per vector step, total_timesteps -
+    learning_starts in all), target copy every 10 000 of them, the reference's evaluation timesteps (`train_iqn.plan_reference`)."""
     plan = plan_cadence(params["total_timesteps"], params["eval_freq"], n_envs, batch, ref_batch=REF_BATCH, ref_update_every=REF_UPDATE_EVERY,
                         ref_target_interval=REF_TARGET_INTERVAL, grad_steps_per_vector_step=grad_steps, total_grad_steps=total_grad_steps,
-                        n_evals=n_evals)
-    plan["learning_starts_vector_steps"] = -(-REF_LEARNING_STARTS // n_envs)
+                        n_evals=n_evals, budget=budget, reference=reference)
+    if budget == "reference":
+        # the loop below trains behind vector step `it` once it + 1 >= learning_starts_vector_steps: the first that trains STARTS at learning_starts
+        plan["learning_starts_vector_steps"] = plan["learning_starts"] // n_envs + 1
+    else:
+        plan["learning_starts_vector_steps"] = -(-REF_LEARNING_STARTS // n_envs)
     plan["exploration_vector_steps"] = EXPLORATION_FRACTION * plan["vector_steps"]
     return plan
 
@@ -103,20 +115,32 @@ def write_evaluations(exp_dir, log):
              actions=actions)
 
 
-def run_trial(device, params, n_envs, batch=256, replay=100_000, grad_steps=None, total_grad_steps=None, n_evals=None, torch_train=False,
-              verbose=True, eval_one_launch=False, eval_deferred=False, eval_config=None, max_eval_steps=1000, return_agent=False):
+def run_trial(device, params, n_envs, batch=None, replay=None, grad_steps=None, total_grad_steps=None, n_evals=None, torch_train=False,
+              verbose=True, eval_one_launch=False, eval_deferred=False, eval_config=None, max_eval_steps=1000, return_agent=False, env_budget="learner",
+              reference=None, episode_log=None, on_step=None):
     """train_sb3_model.py on the vector env for one trial of the config grid; returns the trial directory (`return_agent`: and the agent).
     `eval_one_launch`: each evaluation as one mn_rollout_dqn launch instead of one Python iteration per env step (same results).
     `eval_deferred` (True, or a dict of DeferredEvaluations arguments such as max_pending): an evaluation point keeps the policy of the moment and the
     episodes of all pending points run as one mn_rollout_dqn_groups launch (dqn/deferred_eval.py) -- the same files as the inline form; where the policy
     does not act through the fused kernel (CPU, another net_arch) one line says so and the evaluations stay inline.
-    `eval_config`: the evaluation worlds (default: the 30 of create_eval_configs); `max_eval_steps`: the step limit of an evaluation episode."""
+    `eval_config`: the evaluation worlds (default: the 30 of create_eval_configs); `max_eval_steps`: the step limit of an evaluation episode.
+    `env_budget`, `reference`, `episode_log`: as train_iqn.run_trial's -- "reference" is the reference's env-step budget (`make_plan`), with deferred
+    evaluations at its evaluation timesteps and the training-episode log on.  `on_step(it, dict(last=dict(reward, done, info, eps)))`: a hook behind
+    every vector step (device tensors)."""
     import torch
     from .dqn.agent import DQNAgent
     from .marinenav_env.vec_env import VecMarineNavEnv
 
     exp_dir = os.path.join(params["save_dir"], "training_" + params["training_time"], "seed_" + str(params["seed"]))
-    plan = make_plan(params, n_envs, batch, grad_steps, total_grad_steps, n_evals)
+    ref_mode = env_budget == "reference"
+    n_envs, batch, replay = resolve_budget_args(env_budget, n_envs, batch, replay)
+    plan = make_plan(params, n_envs, batch, grad_steps, total_grad_steps, n_evals, budget=env_budget, reference=reference)
+    if ref_mode:
+        if replay is not None and replay != plan["replay"]:
+            raise ValueError(f"env_budget='reference' keeps the reference's replay ring ({plan['replay']} rows); {replay} contradicts it")
+        replay = plan["replay"]
+        eval_deferred = eval_deferred or True      # (300 evaluation points: each only keeps the policy of the moment)
+    eval_points = plan_eval_points(plan, n_envs) if ref_mode else None
     os.makedirs(exp_dir, exist_ok=True)
     with open(os.path.join(exp_dir, "trial_config.json"), "w+") as f:
         json.dump(dict(params, batched=dict(plan, n_envs=n_envs, world=1, batch=batch, replay=replay)), f)
@@ -148,12 +172,18 @@ def run_trial(device, params, n_envs, batch=256, replay=100_000, grad_steps=None
                                                                                **(eval_deferred if isinstance(eval_deferred, dict) else {})))
         else:
             print("[train_dqn] eval_deferred: the policy does not act through the fused kernel here (CPU or another net_arch); evaluations stay inline", flush=True)
+    ep_log = make_episode_log(episode_log, env_budget, n_envs, plan["eval_every_vector_steps"], train_env.discount, device)
     n_points = 0
     obs = train_env.reset()
     grad_steps_done = 0
     for it in range(plan["vector_steps"]):
-        a = agent.act_batch(obs, exploration_rate(it, plan))
+        eps = exploration_rate(it, plan)
+        a = agent.act_batch(obs, eps)
         nxt, reward, done, info = train_env.step(a)
+        if ep_log is not None:
+            ep_log.step(reward, done, info, it, eps)
+        if on_step is not None:
+            on_step(it, dict(last=dict(reward=reward, done=done, info=info, eps=eps)))
         agent.memory.add_vector_step(obs, a, reward, nxt, done)
         obs = train_env.reset_done()
         agent.num_timesteps += n_envs
@@ -163,15 +193,24 @@ def run_trial(device, params, n_envs, batch=256, replay=100_000, grad_steps=None
                 grad_steps_done += 1
                 if grad_steps_done % sync_every == 0:
                     agent.sync_target()
-        if (it + 1) % plan["eval_every_vector_steps"] == 0 or it + 1 == plan["vector_steps"]:
-            if n_points >= plan["n_evals"]:
-                continue
+        if eval_points is not None:
+            points = eval_points.get(it, ())
+        elif ((it + 1) % plan["eval_every_vector_steps"] == 0 or it + 1 == plan["vector_steps"]) and n_points < plan["n_evals"]:
+            points = (int(round((it + 1) * n_envs * report_scale)),)
+        else:
+            points = ()
+        if ep_log is not None:
+            if len(points):      # a summary row per evaluation interval, the evaluation's timestep on it
+                ep_log.drain(points[-1])
+            elif ep_log.due():
+                ep_log.drain(int(round((it + 1) * n_envs * report_scale)), row=False)
+        for timestep in points:
             n_points += 1
             if deferred is not None:      # keep the policy of this moment; its episodes run with the other pending points'
-                deferred.snapshot(int(round((it + 1) * n_envs * report_scale)))
+                deferred.snapshot(timestep)
                 continue
             ev = evaluate(agent, eval_env, eval_config, max_steps=max_eval_steps, one_launch=eval_one_launch)
-            log["timesteps"].append(int(round((it + 1) * n_envs * report_scale)))
+            log["timesteps"].append(timestep)
             for k in ("rewards", "times", "energies", "successes", "actions"):
                 log[k].append(ev[k])
             write_evaluations(exp_dir, log)
@@ -186,6 +225,11 @@ def run_trial(device, params, n_envs, batch=256, replay=100_000, grad_steps=None
     if deferred is not None:
         deferred.flush()
         deferred.close()
+    if ep_log is not None:
+        if ep_log.row_open:      # (what ended behind the last evaluation point)
+            ep_log.drain(int(round(plan["vector_steps"] * n_envs * report_scale)))
+        ep_log.close()
+        ep_log.save(exp_dir)
     torch.cuda.synchronize()
     train_env.close()
     eval_env.close()
@@ -196,9 +240,16 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description="Train the DQN baseline (batched MI355X path)")
     ap.add_argument("-C", "--config-file", dest="config_file", type=open, required=True)
     ap.add_argument("-D", "--device", dest="device", type=str, default=None)
-    ap.add_argument("--n-envs", type=int, default=4096)
-    ap.add_argument("--batch", type=int, default=256)
-    ap.add_argument("--replay", type=int, default=100_000)
+    ap.add_argument("--n-envs", type=int, default=None, help="default 4096 (--env-budget reference: env steps per vector step, default 80)")
+    ap.add_argument("--batch", type=int, default=None, help="default 256 (--env-budget reference: 32, the reference's)")
+    ap.add_argument("--replay", type=int, default=None, help="replay ring rows, default 100 000 (--env-budget reference: 1 000 000, the reference's)")
+    ap.add_argument("--env-budget", default="learner", choices=["learner", "reference"],
+                    help="learner (default): the reference's learner budget in big batches -- the fast mode; reference: the reference's own experiment -- total_timesteps "
+                         "env steps, one batch-32 gradient step per env step after learning_starts, its target cadence and evaluation timesteps (deferred evaluations, "
+                         "episode log on) -- the drop-in mode; an explicit value that contradicts it is an error")
+    ap.add_argument("--episode-log", nargs="?", const=True, default=None, choices=["full"],
+                    help="training_log.npz: one summary row of the training episodes per evaluation interval, from a device-side log; `--episode-log full`: "
+                         "training_episodes.npz with every episode's record too.  Default: off (on with --env-budget reference)")
     ap.add_argument("--grad-steps", type=int, default=None, help="gradient steps per vector step (default: one per 4 096 envs)")
     ap.add_argument("--total-grad-steps", type=int, default=None,
                     help="learner budget (default: the reference's sample count, total_timesteps x 32 / batch)")
@@ -217,10 +268,17 @@ def main(argv=None):
     for p in trials:
         p["training_time"] = stamp
     if args.dry_run:
+        n_envs, batch, replay = resolve_budget_args(args.env_budget, args.n_envs, args.batch, args.replay)
         for p in trials:
-            plan = make_plan(p, args.n_envs, args.batch, args.grad_steps, args.total_grad_steps, args.n_evals)
-            print(json.dumps(dict(seed=p["seed"], n_envs=args.n_envs, batch=args.batch, replay=args.replay, fused=not args.torch_train,
-                                  eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred, eps_start=exploration_rate(0, plan), eps_end=exploration_rate(int(np.ceil(plan["exploration_vector_steps"])), plan),
+            try:
+                plan = make_plan(p, n_envs, batch, args.grad_steps, args.total_grad_steps, args.n_evals, budget=args.env_budget)
+                if args.env_budget == "reference" and replay is not None and replay != plan["replay"]:
+                    raise ValueError(f"env_budget='reference' keeps the reference's replay ring ({plan['replay']} rows); {replay} contradicts it")
+            except ValueError as e:
+                raise SystemExit(f"train_dqn: {e}")
+            extra = dict(env_budget=args.env_budget, episode_log=True if args.episode_log is None else args.episode_log) if args.env_budget == "reference" else {}
+            print(json.dumps(dict(seed=p["seed"], n_envs=n_envs, batch=batch, replay=plan.get("replay", replay), fused=not args.torch_train,
+                                  eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred or args.env_budget == "reference", **extra, eps_start=exploration_rate(0, plan), eps_end=exploration_rate(int(np.ceil(plan["exploration_vector_steps"])), plan),
                                   plan=plan)))
         return
     import torch
@@ -230,7 +288,7 @@ def main(argv=None):
         t0 = time.time()
         d = run_trial(device, p, args.n_envs, batch=args.batch, replay=args.replay, grad_steps=args.grad_steps,
                       total_grad_steps=args.total_grad_steps, n_evals=args.n_evals, torch_train=args.torch_train, eval_one_launch=args.eval_one_launch,
-                      eval_deferred=args.eval_deferred)
+                      eval_deferred=args.eval_deferred, env_budget=args.env_budget, episode_log=args.episode_log)
         print(f"[train_dqn] seed {p['seed']}: {time.time() - t0:.1f} s -> {d}", flush=True)
 
 

@@ -7,10 +7,14 @@ eval_freq, save_dir), same per-trial outputs (`trial_config.json`, `training_sch
 GPUs (independent learners per rank by default, `--shared-learner` for one IQN with an RCCL
 gradient all-reduce).
 
-    python -m distributional_rl_navigation_amd.train_iqn -C config_IQN.json [--n-envs 4096]
+    python -m distributional_rl_navigation_amd.train_iqn -C config_IQN.json [--n-envs 4096] [--env-budget reference] [--episode-log [full]] [--dry-run]
 
 Cadence.  The reference does one batch-32 gradient step per 4 env steps (replay ratio 8 sampled per generated
-transition).  With 65 536 envs a vector step IS 65 536 env steps, so that ratio is out of reach (16 384 gradient
+transition).  Two modes (`--env-budget`):
+  reference  the DROP-IN: the reference's own experiment -- total_timesteps env steps in vector steps of N = 80, N / 4 batch-32 gradient
+             steps behind each from learning_starts on, its target / evaluation cadence, its evaluation timesteps (10 000 ... 3 000 000),
+             its 1 M-row ring; deferred evaluations and the training-episode log (episode_log.py) on.  Learner-bound (`plan_reference`).
+  learner    the FAST one (default).  With 65 536 envs a vector step IS 65 536 env steps (the reference's ratio would be 16 384 gradient
 steps per vector step); the batched loop instead spends the reference's LEARNER budget (750 000 x 32 samples =
 93 750 gradient steps of batch 256) at G gradient steps per vector step (16 per 65 536 envs, one per 4 096: replay ratio
 0.06 either way) and rescales every run-fraction cadence (exploration ramp, curriculum, evaluations) -- `plan_cadence`.
@@ -67,8 +71,66 @@ def create_eval_configs(device, seed=348):
     return cfg
 
 
+REFERENCE_N_ENVS = 80      # --env-budget reference: env steps per vector step (20 IQN gradient steps each, 37 500 vector steps)
+REFERENCE_DEFAULTS = dict(learning_starts=10_000, target_update_interval=10_000, exploration_fraction=0.1, replay=1_000_000)      # agent.py:10-29 / sb3 DQN
+
+
+def reference_n_envs(total_timesteps, eval_freq, learning_starts, target_interval, update_every, thresholds=()):
+    """Every N the reference-budget plan takes: N env steps per vector step must cut the run, `learning_starts`, the evaluation and target
+    intervals and the curriculum thresholds into whole vector steps, and hold a whole number of training events (a multiple of `update_every`)."""
+    from math import gcd
+    g = 0
+    for v in (total_timesteps, eval_freq, learning_starts, target_interval) + tuple(t for t in thresholds if t):
+        g = gcd(g, int(v))
+    return [d for d in range(1, g + 1) if g % d == 0 and d % update_every == 0]
+
+
+def plan_reference(total_timesteps, eval_freq, n_envs_total, batch, ref_batch=32, ref_update_every=4, ref_target_interval=10_000, reference=None):
+    """`plan_cadence(budget="reference")`: the reference's own experiment -- its env-step budget, its replay ratio, its cadences -- cut into
+    vector steps of N = n_envs_total env steps.  Vector step k stands for the env steps [k N, (k + 1) N): it trains from the one that starts at
+    `learning_starts` on, N / update_every gradient steps of the reference's batch each, (total_timesteps - learning_starts) / update_every in
+    all (the reference's `<=` loop does one more).  An evaluation follows the vector step that starts at learning_starts + j eval_freq and is
+    logged with that env step; one more follows the last vector step, logged with total_timesteps: eval_freq, 2 eval_freq, ...,
+    total_timesteps when learning_starts = eval_freq, the reference's own list.  `reference`: overrides of REFERENCE_DEFAULTS (a run at toy size)."""
+    ref = dict(REFERENCE_DEFAULTS, target_update_interval=ref_target_interval)
+    unknown = set(reference or {}) - set(ref)
+    if unknown:
+        raise ValueError(f"reference=: unknown keys {sorted(unknown)} (known: {sorted(ref)})")
+    ref.update(reference or {})
+    N, ls, ti = int(n_envs_total), int(ref["learning_starts"]), int(ref["target_update_interval"])
+    if batch != ref_batch:
+        raise ValueError(f"budget='reference' trains with the reference's batch ({ref_batch}), not {batch}")
+    valid = reference_n_envs(total_timesteps, eval_freq, ls, ti, ref_update_every, TRAINING_SCHEDULE["timesteps"])
+    if N not in valid:
+        near = sorted(set(([max(v for v in valid if v < N)] if any(v < N for v in valid) else []) + ([min(v for v in valid if v > N)] if any(v > N for v in valid) else [])))
+        raise ValueError(f"budget='reference': {N} env steps per vector step do not divide total_timesteps ({total_timesteps}), learning_starts ({ls}), eval_freq "
+                         f"({eval_freq}), the target interval ({ti}) and the curriculum thresholds into whole vector steps of whole training events (a multiple of "
+                         f"{ref_update_every}); nearest valid values: {near} (all: {valid})")
+    if ls >= total_timesteps:
+        raise ValueError(f"budget='reference': learning_starts ({ls}) is not inside the run ({total_timesteps} timesteps)")
+    V, G = total_timesteps // N, N // ref_update_every
+    points = list(range(ls, total_timesteps, eval_freq)) + [total_timesteps]
+    total_grad = (total_timesteps - ls) // ref_update_every
+    return dict(
+        vector_steps=V, grad_steps_per_vector_step=G, total_grad_steps=total_grad, reference_grad_steps=total_timesteps // ref_update_every,
+        reference_samples=total_timesteps // ref_update_every * ref_batch, samples=total_grad * ref_batch, env_steps=total_timesteps,
+        target_sync_grad_steps=ti // ref_update_every, eval_every_vector_steps=eval_freq // N, n_evals=len(points), timestep_scale=float(N),
+        replay_ratio=G * ref_batch / N, reference_replay_ratio=ref_batch / ref_update_every,
+        budget="reference", batch=ref_batch, learning_starts=ls, learning_starts_vector_steps=ls // N, exploration_fraction=ref["exploration_fraction"],
+        exploration_timesteps=int(round(ref["exploration_fraction"] * total_timesteps)), replay=int(ref["replay"]), report_timestep_scale=1,
+        eval_timesteps=points)
+
+
+def plan_eval_points(plan, n_envs_total):
+    """{vector step: [timesteps to log]} of a reference-budget plan: the evaluations that follow that vector step."""
+    after = {}
+    for t in plan["eval_timesteps"]:
+        after.setdefault(min(t // n_envs_total, plan["vector_steps"] - 1), []).append(t)
+    return after
+
+
 def plan_cadence(total_timesteps, eval_freq, n_envs_total, batch, ref_batch=32, ref_update_every=4,
-                 ref_target_interval=10_000, grad_steps_per_vector_step=None, total_grad_steps=None, n_evals=None):
+                 ref_target_interval=10_000, grad_steps_per_vector_step=None, total_grad_steps=None, n_evals=None, budget="learner", reference=None):
     """Translate the reference's env-step cadences (config_IQN.json + agent.py defaults: 3 M timesteps, one batch-32
     gradient step every 4 env steps, target copy every 10 000 learning steps, evaluation every 10 000) into the
     batched loop's units.
@@ -79,7 +141,21 @@ def plan_cadence(total_timesteps, eval_freq, n_envs_total, batch, ref_batch=32, 
     total_grad_steps = total_timesteps / 4 * 32 / batch -- and spreads it over as many vector steps as the chosen
     gradient-steps-per-vector-step G needs.  Everything that the reference expresses as a fraction of the run
     (exploration ramp, curriculum stages, evaluation points) keeps its fraction.
-    Returns a dict; `replay_ratio` = sampled transitions per generated env step (reference: 8)."""
+    Returns a dict; `replay_ratio` = sampled transitions per generated env step (reference: 8).
+
+    `budget`: "learner" (default) is the above.  "reference" keeps the reference's ENV-STEP budget instead -- total_timesteps env steps at its own
+    replay ratio, batch and cadences (`plan_reference`; `reference`: overrides of its constants): the drop-in experiment, learner-bound."""
+    if budget == "reference":
+        given = dict(grad_steps_per_vector_step=grad_steps_per_vector_step, total_grad_steps=total_grad_steps, n_evals=n_evals)
+        plan = plan_reference(total_timesteps, eval_freq, n_envs_total, batch, ref_batch, ref_update_every, ref_target_interval, reference)
+        for k, v in given.items():
+            if v is not None and int(v) != plan[k]:
+                raise ValueError(f"budget='reference' fixes {k} = {plan[k]}; {v} contradicts it")
+        return plan
+    if budget != "learner":
+        raise ValueError(f"budget={budget!r}: 'learner' or 'reference'")
+    if reference:
+        raise ValueError("reference= overrides belong to budget='reference'")
     ref_grad_steps = total_timesteps // ref_update_every
     if total_grad_steps is None:
         total_grad_steps = max(1, int(round(ref_grad_steps * ref_batch / batch)))
@@ -103,10 +179,32 @@ def plan_cadence(total_timesteps, eval_freq, n_envs_total, batch, ref_batch=32, 
     return plan
 
 
-def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=256, replay=100_000, verbose=True,
+def resolve_budget_args(env_budget, n_envs, batch, replay, default_n_envs=4096):
+    """(n_envs, batch, replay) with the defaults of the budget filled in for what was left None: learner 4 096 envs / batch 256 / ring 100 000;
+    reference REFERENCE_N_ENVS / the reference's batch 32 / its ring (a contradicting explicit value is refused by the plan)."""
+    if env_budget == "reference":
+        return (REFERENCE_N_ENVS if n_envs is None else n_envs, 32 if batch is None else batch, replay)
+    return (default_n_envs if n_envs is None else n_envs, 256 if batch is None else batch, 100_000 if replay is None else replay)
+
+
+def make_episode_log(option, env_budget, n_envs, eval_every_vector_steps, discount, device, max_records=1 << 20):
+    """The EpisodeLog of a trial, or None.  `option`: None = the budget's default (on with "reference", off with "learner"), False, True, or "full".
+    Capacity: n_envs x the vector steps of one evaluation interval (an env ends at most one episode per vector step), at most `max_records` rows
+    (the loop then drains inside the interval as well)."""
+    if option is None:
+        option = env_budget == "reference"
+    if not option:
+        return None
+    from .episode_log import EpisodeLog
+    steps = max(1, min(int(eval_every_vector_steps) + 1, max_records // n_envs))
+    return EpisodeLog(n_envs, n_envs * steps, discount, device, full=option == "full")
+
+
+def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None, replay=None, verbose=True,
               grad_steps=None, torch_train=False, total_grad_steps=None, n_evals=None, cvar=1.0, precision="f64",
               exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1,
-              eval_one_launch=False, eval_deferred=False):
+              eval_one_launch=False, eval_deferred=False, env_budget="learner", reference=None, episode_log=None, eval_config=None, max_eval_steps=1000,
+              on_step=None, return_agent=False):
     """train_IQN_model.py:74-121 on the vector env.  `params` is one trial of the reference's config grid
     (seed, total_timesteps, eval_freq, save_dir); see `plan_cadence` for how its env-step cadences map to vector steps.
     `precision`: the env kernels' arithmetic.  "f64" (default: every float32 output within 1e-5 of the reference, no
@@ -119,7 +217,13 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=256, 
     instead of the fused mn_step_append).  `eval_adaptive` = False skips the adaptive-CVaR evaluation at the evaluation points (the reference runs both).
     `eval_one_launch`: each evaluation as one mn_rollout_iqn launch instead of one Python iteration per env step (same results).
     `eval_deferred`: an evaluation point keeps the policy of the moment and the episodes of all pending points run as one mn_rollout_iqn_groups launch
-    (iqn/deferred_eval.py) -- with `n_evals=300` the reference's evaluation density."""
+    (iqn/deferred_eval.py) -- with `n_evals=300` the reference's evaluation density.
+    `env_budget`: "learner" (the above) or "reference" -- the reference's own env-step budget, replay ratio 8, batch 32, its cadences and its evaluation
+    timesteps (`plan_reference`; `n_envs` = env steps per vector step, None = 80; `reference` = overrides of its constants for runs at toy size); implies
+    deferred evaluations at every eval_freq.  `episode_log`: None (on with "reference", off otherwise), True or "full" -- training_log.npz with one
+    summary row of the training episodes per evaluation interval, "full": training_episodes.npz with every episode's record (episode_log.py).
+    `eval_config`: the evaluation worlds (default: the 30 of create_eval_configs); `max_eval_steps`: the step limit of an evaluation episode;
+    `on_step`: learn_vec's hook; `return_agent`: return (directory, agent)."""
     import torch
     from .iqn.agent import IQNAgent
     from .marinenav_env.vec_env import VecMarineNavEnv
@@ -128,9 +232,17 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=256, 
     if world > 1 and not shared:
         exp_dir = os.path.join(exp_dir, f"rank_{rank}")
     writer = rank == 0 or not shared
+    ref_mode = env_budget == "reference"
+    if ref_mode and (world > 1 or shared):
+        raise ValueError("env_budget='reference' is the reference's single-learner experiment: one process, one GPU")
+    n_envs, batch, replay = resolve_budget_args(env_budget, n_envs, batch, replay)
     total = n_envs * world
     plan = plan_cadence(params["total_timesteps"], params["eval_freq"], total, batch,
-                        grad_steps_per_vector_step=grad_steps, total_grad_steps=total_grad_steps, n_evals=n_evals)
+                        grad_steps_per_vector_step=grad_steps, total_grad_steps=total_grad_steps, n_evals=n_evals, budget=env_budget, reference=reference)
+    if ref_mode:
+        if replay is not None and replay != plan["replay"]:
+            raise ValueError(f"env_budget='reference' keeps the reference's replay ring ({plan['replay']} rows); {replay} contradicts it")
+        replay = plan["replay"]
     if plan["total_grad_steps"] * batch < 0.1 * plan["reference_samples"]:
         raise ValueError(f"planned learner budget ({plan['total_grad_steps']} grad steps x {batch}) is more than 10x below the "
                          f"reference's ({plan['reference_grad_steps']} x 32): raise --total-grad-steps")
@@ -149,7 +261,8 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=256, 
 
     train_env = VecMarineNavEnv(n_envs, seed=params["seed"], first_index=rank * n_envs, schedule=TRAINING_SCHEDULE,
                                 timestep_scale=plan["timestep_scale"], device=device, precision=precision)
-    eval_config = create_eval_configs(device)
+    if eval_config is None:
+        eval_config = create_eval_configs(device)
     if writer:
         with open(os.path.join(exp_dir, "eval_config.json"), "w+") as f:
             json.dump(eval_config, f)
@@ -157,25 +270,34 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=256, 
 
     agent = IQNAgent(26, 9, n_step=n_step, BATCH_SIZE=batch, BUFFER_SIZE=replay, device=device,
                      seed=params["seed"] + 100 + (0 if shared else rank), distributed=shared and world > 1,
-                     UPDATE_EVERY=1, learning_starts=0, rank=rank if shared else 0, final_eps=final_eps)
+                     UPDATE_EVERY=1, learning_starts=plan["learning_starts"] if ref_mode else 0, rank=rank if shared else 0, final_eps=final_eps,
+                     **(dict(exploration_fraction=plan["exploration_fraction"]) if ref_mode else {}))
     agent.grad_steps_per_update = plan["grad_steps_per_vector_step"]
     agent.target_sync_grad_steps = max(1, int(round(plan["target_sync_grad_steps"] * target_sync_mult)))
     agent.exchange = exchange
     agent.shared_taus = bool(shared_taus)
     if torch_train:
         agent.use_fused_train = False          # PyTorch autograd + Adam instead of csrc/iqn_train.hip
+    log = make_episode_log(episode_log, env_budget, n_envs, plan["eval_every_vector_steps"], train_env.discount, device)
+    if ref_mode and not eval_deferred:
+        eval_deferred = True      # (300 evaluation points: each only keeps the policy of the moment)
+    if max_eval_steps != 1000 and eval_deferred:
+        eval_deferred = dict(dict(max_steps=max_eval_steps), **(eval_deferred if isinstance(eval_deferred, dict) else {}))
     agent.learn_vec(total_vector_steps=plan["vector_steps"], train_env=train_env, eval_env=eval_env, eval_config=eval_config,
                     eval_freq=plan["eval_every_vector_steps"], eval_log_path=exp_dir if writer else None,
                     total_timesteps=plan["vector_steps"] * total, world_size=world, cvar=cvar, verbose=False,
                     report_timestep_scale=params["total_timesteps"] / (plan["vector_steps"] * total), eval_adaptive=eval_adaptive,
-                    eval_one_launch=eval_one_launch, eval_deferred=eval_deferred)
+                    eval_one_launch=eval_one_launch, eval_deferred=eval_deferred, on_step=on_step, episode_log=log, max_eval_steps=max_eval_steps,
+                    eval_points=plan_eval_points(plan, total) if ref_mode else None)
     if writer:
         agent.qnetwork_local.save(exp_dir)
+        if log is not None:
+            log.save(exp_dir)
     train_env.close()
     if eval_env is not None:
         eval_env.close()
     torch.cuda.synchronize()
-    return exp_dir
+    return (exp_dir, agent) if return_agent else exp_dir
 
 
 def _worker_device(requested, i, n_gpu):
@@ -209,9 +331,19 @@ def main(argv=None):
     ap.add_argument("-P", "--num-procs", dest="num_procs", type=int, default=1,
                     help="train_IQN_model.py:24-30: run the trials of the config grid (seeds) in this many worker processes at a time; "
                          "worker i uses GPU i modulo the visible GPUs (several seeds on one MI355X share it).  Not combinable with torch.distributed.run")
-    ap.add_argument("--n-envs", type=int, default=4096, help="environments per GPU (default 4096: see the module docstring; 65536 = the bench's configuration)")
-    ap.add_argument("--batch", type=int, default=256)
-    ap.add_argument("--replay", type=int, default=100_000)
+    ap.add_argument("--n-envs", type=int, default=None, help="environments per GPU (default 4096: see the module docstring; 65536 = the bench's configuration; "
+                                                             "with --env-budget reference: env steps per vector step, default 80)")
+    ap.add_argument("--batch", type=int, default=None, help="default 256 (--env-budget reference: 32, the reference's)")
+    ap.add_argument("--replay", type=int, default=None, help="replay ring rows, default 100 000 (--env-budget reference: 1 000 000, the reference's)")
+    ap.add_argument("--env-budget", default="learner", choices=["learner", "reference"],
+                    help="learner (default): the reference's learner budget in big batches over many more env steps -- the fast mode; reference: the reference's own "
+                         "experiment -- total_timesteps env steps, one batch-32 gradient step per 4 of them, its target / evaluation cadence and evaluation timesteps "
+                         "(deferred evaluations, episode log on) -- the drop-in mode; an explicit value that contradicts it is an error")
+    ap.add_argument("--episode-log", nargs="?", const=True, default=None, choices=["full"],
+                    help="training_log.npz: one summary row of the training episodes per evaluation interval, from a device-side log (one small launch per vector "
+                         "step, no host synchronisation); `--episode-log full`: training_episodes.npz with every episode's record too.  Default: off (on with "
+                         "--env-budget reference)")
+    ap.add_argument("--dry-run", action="store_true", help="print the plan of every trial as JSON and exit (no GPU needed)")
     ap.add_argument("--shared-learner", action="store_true")
     ap.add_argument("--grad-steps", type=int, default=None,
                     help="gradient steps per vector step (default: 16 per 65 536 envs, i.e. learner ~ half of the GPU time)")
@@ -232,6 +364,20 @@ def main(argv=None):
                          "their own (iqn/deferred_eval.py).  With --n-evals 300: the reference's evaluation density")
     args = ap.parse_args(argv)
     params = json.load(args.config_file)
+    if args.dry_run:
+        n_envs, batch, replay = resolve_budget_args(args.env_budget, args.n_envs, args.batch, args.replay)
+        for p in trial_params(params):
+            try:
+                plan = plan_cadence(p["total_timesteps"], p["eval_freq"], n_envs, batch, grad_steps_per_vector_step=args.grad_steps,
+                                    total_grad_steps=args.total_grad_steps, n_evals=args.n_evals, budget=args.env_budget)
+                if args.env_budget == "reference" and replay is not None and replay != plan["replay"]:
+                    raise ValueError(f"env_budget='reference' keeps the reference's replay ring ({plan['replay']} rows); {replay} contradicts it")
+            except ValueError as e:
+                raise SystemExit(f"train_iqn: {e}")
+            print(json.dumps(dict(seed=p["seed"], n_envs=n_envs, batch=batch, replay=plan.get("replay", replay), env_budget=args.env_budget,
+                                  eval_deferred=args.eval_deferred or args.env_budget == "reference",
+                                  episode_log=(args.env_budget == "reference") if args.episode_log is None else args.episode_log, plan=plan)))
+        return
     import torch
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -249,7 +395,8 @@ def main(argv=None):
         p["training_time"] = stamp
     kw = dict(batch=args.batch, replay=args.replay, grad_steps=args.grad_steps, torch_train=args.torch_train,
               total_grad_steps=args.total_grad_steps, n_evals=args.n_evals, cvar=args.cvar, precision=args.precision,
-              exchange=args.exchange, shared_taus=args.shared_taus, eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred)
+              exchange=args.exchange, shared_taus=args.shared_taus, eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred,
+              env_budget=args.env_budget, episode_log=args.episode_log)
     if args.num_procs > 1:
         # train_IQN_model.py:173-179: a Pool of workers, one trial each.  `spawn`: every worker gets its own HIP context
         if world > 1:

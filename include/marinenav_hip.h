@@ -452,6 +452,23 @@ int mn_replay_append(const float *obs_dev, const int32_t *actions_dev, const flo
                      const uint8_t *done_dev, float *ring_states, float *ring_next_states, int64_t *ring_actions,
                      float *ring_rewards, float *ring_dones, int64_t n, int64_t ptr, int64_t capacity, void *stream);
 
+/* ---- training episode log ----------------------------------------------------------------------
+ * The record the reference prints at every training episode end (thirdparty/IQN/agent.py:118-119, 152-168) for the n envs of a
+ * vector step, in one launch that needs no env handle and no host look.  reward_dev [n] f32, done_dev / info_dev [n] u8 are a
+ * step's outputs.  Per env i, in float64, every operation rounding on its own:
+ *     ret += disc * (double)reward[i];   disc *= discount;   len += 1
+ * on the running state ep_ret_dev / ep_disc_dev [n] f64 and ep_len_dev [n] i32, which the caller initialises to 0 / 1 / 0.  Where
+ * done[i] is set the env writes one record -- rec_step = step_index, rec_env = i, rec_len = len, rec_info = info[i] (MN_INFO_*),
+ * rec_ret = ret, rec_eps = eps -- and its state goes back to (0, 1, 0).  The return is the RUNNING PRODUCT form above, not the
+ * reference's `discount ** ep_length` power.
+ * Records are compacted through *count_dev (u32, caller-zeroed): a wavefront claims one run of slots for its finished lanes with
+ * one atomic add.  A slot >= capacity is not written but counted: *count_dev - capacity records were dropped.  The order of the
+ * records of one call is unspecified. */
+int mn_episode_log(const float *reward_dev, const uint8_t *done_dev, const uint8_t *info_dev, int32_t n, double discount,
+                   int64_t step_index, float eps, double *ep_ret_dev, double *ep_disc_dev, int32_t *ep_len_dev, int64_t *rec_step,
+                   int32_t *rec_env, int32_t *rec_len, uint8_t *rec_info, double *rec_ret, float *rec_eps, int64_t capacity,
+                   uint32_t *count_dev, void *stream);
+
 /* ---- IQN gradient step ------------------------------------------------------------------------
  * One optimizer step of IQNAgent.train (thirdparty/IQN/agent.py:269-304) on `batch` transitions gathered from the
  * replay ring (layout above) at rows idx_dev[batch] (i64): target-network forward on next_states, local-network
