@@ -113,6 +113,9 @@ SIGNATURES = [
     ("mn_dqn_act", C.c_int, [_vp, C.POINTER(C.c_void_p), _vp, _i32, _vp, _vp, _i32, _vp]),
     ("mn_dqn_train_workspace_floats", C.c_int64, [_i32]),
     ("mn_dqn_train_step", C.c_int, [_vp] * 5 + [_i64] + [_vp] * 11 + [_i32, C.c_float] + [_dbl] * 5 + [_vp]),
+    ("mn_dqn_train_steps_workspace_floats", C.c_int64, [_i32, _i32]),
+    ("mn_dqn_train_steps", C.c_int, [_vp] * 5 + [_i64] + [_vp] * 11 + [_i32, _i32, C.c_float] + [_dbl] * 5 + [_vp]),
+    ("mn_dqn_train_steps_parts", C.c_int, [_vp] * 5 + [_i64] + [_vp] * 11 + [_i32, _i32, C.c_float] + [_dbl] * 5 + [_i32, _vp]),
     ("mn_xchg_create", C.c_int, [_i32, _i32, C.POINTER(_vp)]),
     ("mn_xchg_export", C.c_int, [_vp, _vp]),
     ("mn_xchg_import", C.c_int, [_vp, _i32, _vp]),

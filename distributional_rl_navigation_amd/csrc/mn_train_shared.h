@@ -25,9 +25,9 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {   // murmur3 finaliser
     return x ^ (x >> 16);
 }
 
-__device__ __forceinline__ uint64_t sample_base(const uint64_t *__restrict__ state) {
-    return mix64(state[0] + 0x9E3779B97F4A7C15ull * (state[1] + 1));
-}
+// the key of the draw made at call counter `counter` of the generator seeded `seed`
+__device__ __forceinline__ uint64_t sample_base_at(uint64_t seed, uint64_t counter) { return mix64(seed + 0x9E3779B97F4A7C15ull * (counter + 1)); }
+__device__ __forceinline__ uint64_t sample_base(const uint64_t *__restrict__ state) { return sample_base_at(state[0], state[1]); }
 // ReplayBuffer.sample (replay_buffer.py:42-47: random.sample(memory, k) = k DISTINCT uniform rows): slot k of the batch reads ring
 // row perm(k), where perm is a pseudo-random permutation of [0, n) keyed by the step's `base` -- a 4-round balanced Feistel network
 // on the smallest even-width power-of-two domain >= n (Luby-Rackoff: three rounds of a good round function already give a

@@ -23,6 +23,23 @@ from ..iqn.replay_buffer import ReplayBuffer
 from .policy import DQNPolicy
 
 
+def split_at_target_sync(done, n_steps, sync_every):
+    """Cut a run of `n_steps` gradient steps, `done` steps into the run, at the hard target copies that fall every `sync_every` steps: a list of
+    `(steps, sync_after)` segments in order, `sync_after` True where a copy follows the segment's last step.  The target network is constant inside a
+    segment, which is what a multi-step call (`DQNAgent.train_many`) needs.  `sync_every` None or 0: no copies among these steps."""
+    if n_steps <= 0:
+        return []
+    if not sync_every:
+        return [(n_steps, False)]
+    segments = []
+    while n_steps > 0:
+        steps = min(n_steps, sync_every - done % sync_every)
+        done += steps
+        n_steps -= steps
+        segments.append((steps, done % sync_every == 0))
+    return segments
+
+
 class DQNAgent:
     def __init__(self, state_size=26, action_size=9, learning_rate=1e-4, buffer_size=1_000_000, learning_starts=50000,
                  batch_size=32, tau=1.0, gamma=0.99, train_freq=4, gradient_steps=1, target_update_interval=10000,
@@ -84,6 +101,29 @@ class DQNAgent:
         self.n_updates += 1
         return loss.clone()
 
+    def _uses_multi_step(self):
+        from .fused_train import MULTI_MAX_BATCH
+        return self._uses_fused() and self.batch_size <= MULTI_MAX_BATCH
+
+    def train_many(self, n_steps, idx=None):
+        """`n_steps` gradient steps on fresh samples of the replay ring (or on rows `idx` [n_steps][B]); returns the [n_steps] losses and raises
+        `n_updates` by `n_steps`.  With `fused_train` and batch <= 32 they are ONE multi-step HIP call (`FusedTrainer.steps`), bit for bit the loop of
+        `train()`; anywhere else they ARE that loop.  The target network must not be copied among the steps (`split_at_target_sync`)."""
+        if n_steps <= 0:
+            return torch.zeros(0, device=self.device)
+        m = self.memory
+        if self._uses_multi_step():
+            ft = self._fused_trainer()
+            self._enter_train_path("hip")
+            losses = ft.steps((m.states, m.actions, m.rewards, m.next_states, m.dones), m.size, self.batch_size, n_steps, idx)
+            self.n_updates += n_steps
+            return losses.clone()
+        if idx is None:
+            return torch.stack([self.train() for _ in range(n_steps)])
+        if self._uses_fused():
+            return torch.stack([self.train_fused(rows) for rows in idx])
+        return torch.stack([self.train(tuple(t[rows] for t in (m.states, m.actions, m.rewards, m.next_states, m.dones))) for rows in idx])
+
     # ---- update rule -----------------------------------------------------------------------------------------------
     def train(self, experiences=None):
         """One gradient step of DQN.train (dqn.py:196-224) on `experiences` = (obs, actions [B,1] i64, rewards [B,1],
@@ -143,8 +183,9 @@ class DQNAgent:
             if (it + 1) % tgt_every == 0:                                       # dqn.py:175-176, tau = 1 -> hard copy
                 self.sync_target()
             if self.num_timesteps > self.learning_starts and (it + 1) % self.train_freq == 0 and len(self.memory) >= self.batch_size:
-                for _ in range(self.gradient_steps):
-                    losses.append(self.train())
+                # (the target copy above falls between vector steps, never among these gradient steps: one segment)
+                for steps, _ in split_at_target_sync(self.n_updates, self.gradient_steps, None):
+                    losses.extend(self.train_many(steps))
             if callback is not None:
                 callback(self, it)
         return dict(vector_steps=total_vector_steps, n_updates=self.n_updates,

@@ -16,6 +16,8 @@ from .. import _capi
 
 P_TOTAL = 27650
 MAX_BATCH = 256
+MULTI_MAX_BATCH = 32      # mn_dqn_train_steps: both 16-sample tiles of a batch in one workgroup
+MULTI_MAX_STEPS = 1024    # MN_DQN_MAX_STEPS (include/marinenav_hip.h); `FusedTrainer.steps` splits longer requests
 _ORDER = tuple(f"features_extractor.{m}" for m in ("velocity_encoder", "goal_encoder", "sensor_encoder", "hidden_layer", "hidden_layer_2",
                                                    "output_layer")) + ("q_net.0", "q_net.2", "q_net.4")
 PARAM_NAMES = tuple(f"{m}.{s}" for m in _ORDER for s in ("weight", "bias"))
@@ -56,6 +58,7 @@ class FusedTrainer:
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._ws = {}
         self._idx_out = {}
+        self._multi = {}      # (batch, n_steps) -> (workspace, losses [n_steps], rows [n_steps][batch]) of the multi-step call
         # {seed, call counter} of the in-launch batch draw (mn_iqn_sample's permutation), seeded from the replay memory's generator
         self.rng_state = torch.tensor([int(agent.memory.gen.initial_seed()) & 0x7FFFFFFFFFFFFFFF, 0], dtype=torch.int64, device=self.device)
         self._nets = (agent.q_net, agent.q_net_target)
@@ -143,3 +146,49 @@ class FusedTrainer:
         self.last_idx = out
         ag.policy.weights_changed()      # the kernel wrote the weights outside PyTorch's version counters: the act image is stale
         return self.loss[0]
+
+    def _multi_buffers(self, batch, n_steps):
+        buf = self._multi.get((batch, n_steps))
+        if buf is None:
+            n = _capi.lib().mn_dqn_train_steps_workspace_floats(batch, n_steps)
+            if n < 0:
+                raise ValueError(f"multi-step DQN gradient call: batch {batch} outside 1..{MULTI_MAX_BATCH} or n_steps {n_steps} outside 1..{MULTI_MAX_STEPS}")
+            buf = self._multi[(batch, n_steps)] = (torch.zeros(n, dtype=torch.float32, device=self.device),
+                                                   torch.zeros(n_steps, dtype=torch.float32, device=self.device),
+                                                   torch.empty((n_steps, batch), dtype=torch.int64, device=self.device))
+        return buf
+
+    def steps(self, ring, ring_size, batch, n_steps, idx=None, parts=3):
+        """`n_steps` consecutive optimizer steps as ONE call of `mn_dqn_train_steps` (batch <= 32; two launches, no launch per step): bit for bit what
+        `n_steps` calls of `step` leave.  `idx` [n_steps][batch] i64: the rows of every step; None: drawn as `step` draws them.  The target network must
+        not change among the steps: cut a run at its target copies (`split_at_target_sync`).  Requests above MN_DQN_MAX_STEPS are split.  Returns the
+        [n_steps] losses (a device view that the next call of the same shape overwrites) and sets `last_idx` [n_steps][batch].
+        `parts` (measurements): 1 the TD-target launch only, 2 the chain only, 3 both."""
+        ag = self.agent
+        states, actions, rewards, next_states, dones = ring
+        for t in ring:
+            assert t.is_cuda and t.is_contiguous()
+        assert states.dtype == torch.float32 and actions.dtype == torch.int64 and dones.dtype == torch.float32
+        if idx is not None:
+            idx = idx.to(self.device, torch.int64).contiguous()
+            n_steps, batch = idx.shape
+        if n_steps > MULTI_MAX_STEPS:
+            losses, rows = [], []
+            for k0 in range(0, n_steps, MULTI_MAX_STEPS):
+                k1 = min(n_steps, k0 + MULTI_MAX_STEPS)
+                losses.append(self.steps(ring, ring_size, batch, k1 - k0, None if idx is None else idx[k0:k1], parts).clone())
+                rows.append(self.last_idx.clone())
+            self.last_idx = torch.cat(rows)
+            return torch.cat(losses)
+        ws, losses, out = self._multi_buffers(batch, n_steps)
+        rc = _capi.lib().mn_dqn_train_steps_parts(
+            _p(states), _p(next_states), _p(actions), _p(rewards), _p(dones), int(ring_size),
+            None if idx is not None else _p(self.rng_state), _p(idx) if idx is not None else None, _p(out),
+            _p(self.local), _p(self.target), _p(ws), _p(self.grad), _p(losses), _p(self.exp_avg), _p(self.exp_avg_sq),
+            _p(self.step_dev), batch, n_steps, C.c_float(ag.gamma), C.c_double(ag.learning_rate), C.c_double(0.9), C.c_double(0.999), C.c_double(1e-8),
+            C.c_double(ag.max_grad_norm), parts, _capi.stream_ptr(self.device))
+        if rc:
+            raise _capi.MarineNavHipError(f"mn_dqn_train_steps failed ({rc}): need batch in 1..{MULTI_MAX_BATCH}, n_steps >= 1 and ring_size >= batch")
+        self.last_idx = out
+        ag.policy.weights_changed()      # once per call: the act image is rebuilt on the next act, not per step
+        return losses

@@ -3,7 +3,7 @@ path, with the interface of train_iqn.
 
     python -m distributional_rl_navigation_amd.train_dqn -C config_DQN.json [--n-envs 4096] [--batch 256] [--replay N]
         [--grad-steps G] [--total-grad-steps N] [--n-evals K] [--torch-train] [--eval-one-launch] [--eval-deferred] [--dry-run]
-        [--env-budget reference] [--episode-log [full]]
+        [--env-budget reference] [--episode-log [full]] [--train-steps-per-call {auto,1,K,multi}]
 
 Same JSON schema as train_iqn (agent, seed (list -> grid), total_timesteps, eval_freq, save_dir); the trials run one after another
 on one device.  Cadence: `train_iqn.plan_cadence` with the reference DQN's values (one batch-32 gradient step per env step, target
@@ -40,6 +40,22 @@ from .train_iqn import TRAINING_SCHEDULE, create_eval_configs, make_episode_log,
 
 REF_BATCH, REF_UPDATE_EVERY, REF_TARGET_INTERVAL, REF_LEARNING_STARTS = 32, 1, 10_000, 10_000      # config_DQN.json / sb3 DQN defaults
 EXPLORATION_FRACTION, EPS_INITIAL, EPS_FINAL = 0.1, 1.0, 0.05
+# What `--train-steps-per-call auto` takes: 1, the loop of single launches.  The multi-step call is opt-in ("multi", or a number of steps per call) until
+# profiles/dqn_multi_step_bench.txt shows its median per-step time at K = 80 below the loop's with ranges that do not overlap (README).
+AUTO_TRAIN_STEPS_PER_CALL = 1
+
+
+def steps_per_call(value):
+    """`--train-steps-per-call`: "auto" -> AUTO_TRAIN_STEPS_PER_CALL; "multi" -> None (a whole stretch between target copies per call); K >= 1 -> at most K
+    gradient steps per call (1: one `agent.train()` per step)."""
+    if value == "auto":
+        value = AUTO_TRAIN_STEPS_PER_CALL
+    if value == "multi":
+        return None
+    k = int(value)
+    if k < 1:
+        raise ValueError(f"train_steps_per_call: 'auto', 'multi' or a number >= 1, not {value!r}")
+    return k
 
 
 def make_plan(params, n_envs, batch, grad_steps=None, total_grad_steps=None, n_evals=None, budget="learner", reference=None):
@@ -117,7 +133,7 @@ def write_evaluations(exp_dir, log):
 
 def run_trial(device, params, n_envs, batch=None, replay=None, grad_steps=None, total_grad_steps=None, n_evals=None, torch_train=False,
               verbose=True, eval_one_launch=False, eval_deferred=False, eval_config=None, max_eval_steps=1000, return_agent=False, env_budget="learner",
-              reference=None, episode_log=None, on_step=None):
+              reference=None, episode_log=None, on_step=None, train_steps_per_call="auto"):
     """train_sb3_model.py on the vector env for one trial of the config grid; returns the trial directory (`return_agent`: and the agent).
     `eval_one_launch`: each evaluation as one mn_rollout_dqn launch instead of one Python iteration per env step (same results).
     `eval_deferred` (True, or a dict of DeferredEvaluations arguments such as max_pending): an evaluation point keeps the policy of the moment and the
@@ -126,9 +142,13 @@ def run_trial(device, params, n_envs, batch=None, replay=None, grad_steps=None, 
     `eval_config`: the evaluation worlds (default: the 30 of create_eval_configs); `max_eval_steps`: the step limit of an evaluation episode.
     `env_budget`, `reference`, `episode_log`: as train_iqn.run_trial's -- "reference" is the reference's env-step budget (`make_plan`), with deferred
     evaluations at its evaluation timesteps and the training-episode log on.  `on_step(it, dict(last=dict(reward, done, info, eps)))`: a hook behind
-    every vector step (device tensors)."""
+    every vector step (device tensors).
+    `train_steps_per_call` (`steps_per_call`): 1 -- one `agent.train()` per gradient step; "multi" -- the gradient steps behind a vector step as multi-step
+    calls (`DQNAgent.train_many`), one per stretch between target copies (at batch <= 32 on the fused path one HIP call each, elsewhere the loop); K > 1 -- the
+    same with at most K steps per call; "auto" -- AUTO_TRAIN_STEPS_PER_CALL.  The same files either way."""
     import torch
-    from .dqn.agent import DQNAgent
+    from .dqn.agent import DQNAgent, split_at_target_sync
+    per_call = steps_per_call(train_steps_per_call)
     from .marinenav_env.vec_env import VecMarineNavEnv
 
     exp_dir = os.path.join(params["save_dir"], "training_" + params["training_time"], "seed_" + str(params["seed"]))
@@ -188,10 +208,15 @@ def run_trial(device, params, n_envs, batch=None, replay=None, grad_steps=None, 
         obs = train_env.reset_done()
         agent.num_timesteps += n_envs
         if it + 1 >= plan["learning_starts_vector_steps"] and len(agent.memory) >= batch:
-            for _ in range(G):
-                agent.train()
-                grad_steps_done += 1
-                if grad_steps_done % sync_every == 0:
+            for steps, sync_after in split_at_target_sync(grad_steps_done, G, sync_every):
+                if per_call == 1:
+                    for _ in range(steps):
+                        agent.train()
+                else:
+                    for k0 in range(0, steps, per_call or steps):
+                        agent.train_many(min(per_call or steps, steps - k0))
+                grad_steps_done += steps
+                if sync_after:
                     agent.sync_target()
         if eval_points is not None:
             points = eval_points.get(it, ())
@@ -255,6 +280,10 @@ def main(argv=None):
                     help="learner budget (default: the reference's sample count, total_timesteps x 32 / batch)")
     ap.add_argument("--n-evals", type=int, default=None, help="evaluation points over the run (default: min(30, total_timesteps / eval_freq))")
     ap.add_argument("--torch-train", action="store_true", help="eager PyTorch gradient step instead of the fused HIP kernel")
+    ap.add_argument("--train-steps-per-call", default="auto", metavar="{auto,1,K,multi}",
+                    help="1: one launch per gradient step; multi: the gradient steps behind a vector step as multi-step calls, cut at the target copies -- at "
+                         "batch <= 32 on the fused path one mn_dqn_train_steps call each, elsewhere the loop; K > 1: the same, at most K steps per call; auto "
+                         "(default): 1 until the multi-step call is measured faster (README).  The run's files are bit-equal either way")
     ap.add_argument("--eval-one-launch", action="store_true",
                     help="run each evaluation's episodes in one HIP launch (mn_rollout_dqn) instead of one Python iteration per env step; same results")
     ap.add_argument("--eval-deferred", action="store_true",
@@ -262,6 +291,10 @@ def main(argv=None):
                          "logged as the inline form logs them (the same files); with --n-evals 300 the reference's evaluation density")
     ap.add_argument("--dry-run", action="store_true", help="print the plan of every trial as JSON and exit (no GPU needed)")
     args = ap.parse_args(argv)
+    try:
+        steps_per_call(args.train_steps_per_call)
+    except ValueError as e:
+        raise SystemExit(f"train_dqn: {e}")
     params = json.load(args.config_file)
     stamp = datetime.now().strftime("%Y-%m-%d-%H-%M-%S")
     trials = trial_params(params)
@@ -288,7 +321,8 @@ def main(argv=None):
         t0 = time.time()
         d = run_trial(device, p, args.n_envs, batch=args.batch, replay=args.replay, grad_steps=args.grad_steps,
                       total_grad_steps=args.total_grad_steps, n_evals=args.n_evals, torch_train=args.torch_train, eval_one_launch=args.eval_one_launch,
-                      eval_deferred=args.eval_deferred, env_budget=args.env_budget, episode_log=args.episode_log)
+                      eval_deferred=args.eval_deferred, env_budget=args.env_budget, episode_log=args.episode_log,
+                      train_steps_per_call=args.train_steps_per_call)
         print(f"[train_dqn] seed {p['seed']}: {time.time() - t0:.1f} s -> {d}", flush=True)
 
 

@@ -613,6 +613,32 @@ int mn_dqn_train_step(const float *ring_states, const float *ring_next_states, c
                       float *params_local, const float *params_target, float *workspace, float *grad_out, float *loss_out, float *exp_avg,
                       float *exp_avg_sq, int32_t *step_dev, int32_t batch, float gamma, double lr, double beta1, double beta2, double eps,
                       double max_norm, void *stream);
+/* MANY gradient steps per call: n_steps consecutive mn_dqn_train_step, bit for bit.  After the call params_local, exp_avg, exp_avg_sq, *step_dev,
+ * rng_state_dev[1] (advanced by n_steps), grad_out (the LAST step's clipped gradient), every losses_out[k] and every row of idx_out equal what n_steps
+ * calls of mn_dqn_train_step leave from the same state: the single step is the specification, its summation orders included.  Two launches on the
+ * caller's stream: the TD targets of all n_steps x batch samples, device-wide (the target network and the ring are constant while the steps run, and
+ * the rows of step k depend only on {seed, call counter + k, ring_size}), then ONE workgroup that carries both 16-sample tiles through every step --
+ * local forward, loss, backward, ordered sum, clip, Adam -- with no launch boundary, ticket or cross-workgroup wait between steps.
+ *   idx_dev / idx_out  [n_steps][batch] i64 (idx_dev: the rows of every step when rng_state_dev is NULL)
+ *   losses_out         [n_steps] f32
+ *   workspace          mn_dqn_train_steps_workspace_floats(batch, n_steps) floats, 16-byte aligned, no initialisation needed; one per running call
+ * The caller copies the target network BETWEEN calls (split a run of steps at the copies).  Other arguments as mn_dqn_train_step.
+ * MN_ERR_INVALID, without launching: batch outside 1..32, n_steps outside 1..MN_DQN_MAX_STEPS, ring_size < batch in draw mode, rng_state_dev and
+ * idx_dev both NULL, a NULL buffer, a misaligned workspace.  mn_dqn_train_steps_workspace_floats: < 0 for a batch or n_steps outside those ranges.
+ * mn_dqn_train_steps_parts: the same call with its launches selectable, for measurements -- parts 1: the targets (and Adam scalars) only, 2: the chain only,
+ * on the targets a parts-1 call left in the workspace, 3: both. */
+#define MN_DQN_MAX_STEPS 1024
+int64_t mn_dqn_train_steps_workspace_floats(int32_t batch, int32_t n_steps);
+int mn_dqn_train_steps(const float *ring_states, const float *ring_next_states, const int64_t *ring_actions, const float *ring_rewards,
+                       const float *ring_dones, int64_t ring_size, uint64_t *rng_state_dev, const int64_t *idx_dev, int64_t *idx_out,
+                       float *params_local, const float *params_target, float *workspace, float *grad_out, float *losses_out, float *exp_avg,
+                       float *exp_avg_sq, int32_t *step_dev, int32_t batch, int32_t n_steps, float gamma, double lr, double beta1, double beta2,
+                       double eps, double max_norm, void *stream);
+int mn_dqn_train_steps_parts(const float *ring_states, const float *ring_next_states, const int64_t *ring_actions, const float *ring_rewards,
+                             const float *ring_dones, int64_t ring_size, uint64_t *rng_state_dev, const int64_t *idx_dev, int64_t *idx_out,
+                             float *params_local, const float *params_target, float *workspace, float *grad_out, float *losses_out, float *exp_avg,
+                             float *exp_avg_sq, int32_t *step_dev, int32_t batch, int32_t n_steps, float gamma, double lr, double beta1, double beta2,
+                             double eps, double max_norm, int32_t parts, void *stream);
 
 typedef struct mn_xchg mn_xchg;
 int mn_xchg_create(int32_t rank, int32_t world, mn_xchg **out);
