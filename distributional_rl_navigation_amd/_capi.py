@@ -12,6 +12,8 @@ LIB_PATH = os.path.join(_HERE, "libmarinenav_hip.so")
 
 MAX_CORES, MAX_OBS, NUM_BEAMS, OBS_DIM, NUM_ACTIONS, MAX_STAGES = 8, 10, 11, 26, 9, 8
 PRECISION_F64, PRECISION_MIXED = 0, 1
+QUERY_VELOCITY_GIVEN, QUERY_VELOCITY_FROM_CURRENT = 0, 1
+QUERY_FLAG_COLLISION, QUERY_FLAG_OUTSIDE, QUERY_FLAG_GOAL, QUERY_FLAG_BAD_ENV = 1, 2, 4, 128
 INFO_STRINGS = ("normal", "out of boundary", "too long episode", "collision", "reach goal")
 
 
@@ -72,6 +74,8 @@ SIGNATURES = [
     ("mn_debug_side_delay_us", C.c_int, [_vp, _i32]),
     ("mn_load_worlds", C.c_int, [_vp, _i32, _i32, _pi32, _pd, _pi32, _pd, _pi32, _pd, _pd, _pd, _pd, _pd, _pd, _pf, _vp]),
     ("mn_get_worlds", C.c_int, [_vp, _i32, _i32, _pi32, _pd, _pi32, _pd, _pi32, _pd, _pd, _pd, _pd, _pd, _pd]),
+    ("mn_query_velocity", C.c_int, [_vp, _vp, _i32, _vp, _i64, _vp, _vp]),
+    ("mn_query_observation", C.c_int, [_vp, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
     ("mn_get_state", C.c_int, [_vp, _i32, _i32, _pd, _pi32, _pi64]),
     ("mn_set_state", C.c_int, [_vp, _i32, _i32, _pd, _pi32, _pi64]),
     ("mn_enable_obs64", C.c_int, [_vp, _i32]),

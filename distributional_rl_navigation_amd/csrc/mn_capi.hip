@@ -792,6 +792,48 @@ extern "C" int mn_get_worlds(mn_handle *h, int32_t first, int32_t count, int32_t
     return MN_OK;
 }
 
+// ---- queries: nothing in the handle is written (mn_query.hip) -------------------------------------------------------------------
+static int query_common(mn_handle *h, const int32_t *env_of_query_dev, int32_t env0, const void *in_dev, int64_t n_queries, hipStream_t s) {
+    if (!h) return fail(nullptr, MN_ERR_INVALID, "query: NULL handle");
+    if (n_queries < 0) return fail(h, MN_ERR_INVALID, "query: n_queries is negative");
+    if (!env_of_query_dev && (env0 < 0 || env0 >= h->A.n)) {
+        char b[128];
+        snprintf(b, sizeof(b), "query: env0 = %d is outside [0, %d) and no env_of_query array is given", env0, h->A.n);
+        return fail(h, MN_ERR_INVALID, b);
+    }
+    if (n_queries > 0 && !in_dev) return fail(h, MN_ERR_INVALID, "query: NULL input array");
+    join_reset(h, s);
+    return on_device(h);
+}
+
+extern "C" int mn_query_velocity(mn_handle *h, const int32_t *env_of_query_dev, int32_t env0, const double *xy_dev, int64_t n_queries, double *v_dev,
+                                 void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = query_common(h, env_of_query_dev, env0, xy_dev, n_queries, s);
+    if (rc) return rc;
+    if (n_queries == 0) return MN_OK;
+    if (!v_dev) return fail(h, MN_ERR_INVALID, "mn_query_velocity: v_dev is NULL");
+    mn_launch_query_velocity(h->A, h->P, env_of_query_dev, env0, xy_dev, n_queries, v_dev, s);
+    MN_HIP(h, hipGetLastError());
+    return MN_OK;
+}
+
+extern "C" int mn_query_observation(mn_handle *h, const int32_t *env_of_query_dev, int32_t env0, const double *state_dev, int32_t velocity_mode,
+                                    int64_t n_queries, float *obs_dev, double *obs64_dev, uint8_t *flags_dev, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (h && velocity_mode != MN_QUERY_VELOCITY_GIVEN && velocity_mode != MN_QUERY_VELOCITY_FROM_CURRENT)
+        return fail(h, MN_ERR_INVALID, "mn_query_observation: velocity_mode is neither MN_QUERY_VELOCITY_GIVEN nor MN_QUERY_VELOCITY_FROM_CURRENT");
+    const int rc = query_common(h, env_of_query_dev, env0, state_dev, n_queries, s);
+    if (rc) return rc;
+    if (n_queries == 0) return MN_OK;
+    if (!obs_dev && !obs64_dev && !flags_dev) return fail(h, MN_ERR_INVALID, "mn_query_observation: every output is NULL");
+    if ((uintptr_t)obs_dev & 7) return fail(h, MN_ERR_INVALID, "mn_query_observation: obs_dev must be 8-byte aligned (rows leave as float pairs)");
+    mn_launch_query_observation(h->A, h->P, env_of_query_dev, env0, state_dev, velocity_mode == MN_QUERY_VELOCITY_FROM_CURRENT, n_queries, obs_dev,
+                                obs64_dev, flags_dev, s);
+    MN_HIP(h, hipGetLastError());
+    return MN_OK;
+}
+
 extern "C" int mn_get_state(mn_handle *h, int32_t first, int32_t count, double *state, int32_t *ep_t, int64_t *tot_t) {
     int rc = range_ok(h, first, count);
     if (rc) return rc;

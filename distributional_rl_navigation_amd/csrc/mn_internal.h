@@ -140,3 +140,7 @@ void mn_launch_seed(const MnArrays &A, const uint32_t *seeds_dev, hipStream_t s)
 void mn_launch_mask_to_queue(const MnArrays &A, const uint8_t *mask, uint32_t *count, int32_t *list, hipStream_t s);
 void mn_launch_peek(const MnArrays &A, int first, int count, double *out_dev, hipStream_t s);
 void mn_launch_sleep(uint32_t us, hipStream_t s);
+// queries (mn_query.hip): read-only on A; env_of = NULL: every query in world env0
+void mn_launch_query_velocity(const MnArrays &A, const MnDev &P, const int32_t *env_of, int env0, const double *xy, int64_t nq, double *v, hipStream_t s);
+void mn_launch_query_observation(const MnArrays &A, const MnDev &P, const int32_t *env_of, int env0, const double *state, int from_current, int64_t nq,
+                                 float *obs, double *obs64, uint8_t *flags, hipStream_t s);

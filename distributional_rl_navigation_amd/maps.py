@@ -1,0 +1,91 @@
+"""Maps of a world: its flow field, and what a policy does at every pose of a grid.
+
+The reference's visualiser asks its environment two things besides replaying episodes: the current at a point
+(`env_visualizer.plot_graph` evaluates `get_velocity` on a 100 x 100 grid) and the observation of a robot placed by hand.  Here both
+are queries of `VecMarineNavEnv` (`velocity_at`, `observation_at`: one HIP launch for the whole grid, nothing in the env changes), and
+a policy map is the observation query followed by the policy's own act call on the rows it returns.  Nothing here plots.
+"""
+import numpy as np
+import torch
+
+
+def _host(t):
+    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+
+
+def flow_field(env, env_index=0, nx=100, ny=100, margin=0.0):
+    """The current of world `env_index` on the grid of env_visualizer.plot_graph: xs = linspace(-margin, width + margin, nx), ys likewise over the
+    height (`margin=2.5, nx=ny=110` is the visualiser's second form).  Returns (xs [nx], ys [ny], v [ny][nx][2]) as float64 arrays."""
+    xs = np.linspace(-float(margin), float(env.params.width) + float(margin), int(nx))
+    ys = np.linspace(-float(margin), float(env.params.height) + float(margin), int(ny))
+    pts = np.stack(np.meshgrid(xs, ys, indexing="xy"), axis=-1)      # [ny][nx][2] = (x, y)
+    v = _host(env.velocity_at(pts.reshape(-1, 2), env=env_index)).reshape(len(ys), len(xs), 2)
+    return xs, ys, v
+
+
+def pose_grid(xs, ys, thetas, speed, device="cpu"):
+    """The poses of a map, [len(thetas) * len(ys) * len(xs)][4] float64 = (x, y, theta, speed): theta is the slowest index, then y, then x."""
+    xs, ys, thetas = (torch.as_tensor(np.asarray(v, dtype=np.float64), device=device) for v in (xs, ys, thetas))
+    t, y, x = torch.meshgrid(thetas, ys, xs, indexing="ij")
+    return torch.stack((x, y, t, torch.full_like(x, float(speed))), dim=-1).reshape(-1, 4)
+
+
+def policy_map(policy, env, env_index, xs, ys, thetas, speed, chunk=65536, observe=None):
+    """What `policy` does at every pose (x, y, theta) of the grid, for a robot placed there with forward speed `speed` in world `env_index`
+    of `env` (its velocity is speed (cos theta, sin theta) + the current, as after a reset).
+
+    `policy`: any callable obs [m][26] float32 -> dict of tensors with m rows each (`iqn_policy`, `dqn_policy`, `planner_policy` below).  It is called
+    on chunks of at most `chunk` poses, in grid order.  `observe`: states [m][4] float64 -> (obs [m][26] float32, flags [m] uint8); default
+    `env.observation_at(states, env=env_index, velocity="current", return_flags=True)` -- a stand-in makes the function run without a GPU.
+    Returns a dict of arrays shaped [len(thetas)][len(ys)][len(xs)] + the trailing shape of the policy's rows, plus "flags" (the bits of
+    observation_at: collision, outside, goal)."""
+    if observe is None:
+        observe = lambda st: env.observation_at(st, env=env_index, velocity="current", return_flags=True)
+    device = env.device if env is not None and hasattr(env, "device") else "cpu"
+    poses = pose_grid(xs, ys, thetas, speed, device)
+    shape = (len(thetas), len(ys), len(xs))
+    parts, flags = {}, []
+    step = max(1, int(chunk))
+    for lo in range(0, poses.shape[0], step):
+        st = poses[lo:lo + step]
+        obs, fl = observe(st)
+        out = policy(obs)
+        for k, v in out.items():
+            if v.shape[0] != st.shape[0]:
+                raise ValueError(f"policy output {k!r} has {v.shape[0]} rows for {st.shape[0]} poses")
+            parts.setdefault(k, []).append(_host(v))
+        flags.append(_host(fl))
+    res = {k: np.concatenate(v).reshape(shape + v[0].shape[1:]) for k, v in parts.items()}
+    res["flags"] = np.concatenate(flags).reshape(shape)
+    return res
+
+
+def iqn_policy(agent, cvar=1.0, adaptive=False, quantiles=False):
+    """An IQNAgent as a map policy: action [m], the CVaR level used `cvar` [m] (`adaptive`: agent.adjust_cvar_batch per row, else the constant), `q` [m][9]
+    = mean over the 32 quantile samples and, with `quantiles`, `quantiles` [m][32][9] and `taus` [m][32].  It acts through adjust_cvar_batch and
+    act_eval_batch, the calls of the capture loop of experiments.run_experiment, so the taus come from the agent's act stream: one draw per chunk."""
+    def policy(obs):
+        n = obs.shape[0]
+        cv = agent.adjust_cvar_batch(obs) if adaptive else torch.full((n,), float(cvar), dtype=torch.float32, device=obs.device)
+        a, qt, taus = agent.act_eval_batch(obs, 0.0, cv)
+        out = dict(action=a, cvar=cv, q=qt.mean(dim=1))
+        if quantiles:
+            out["quantiles"] = qt
+            out["taus"] = taus.reshape(n, -1)
+        return out
+    return policy
+
+
+def dqn_policy(dqn):
+    """A dqn.policy.DQNPolicy as a map policy: action [m]."""
+    return lambda obs: dict(action=dqn.act_batch(obs))
+
+
+def planner_policy(kind, params):
+    """The classical baselines ("APF" | "BA", planners.planner_act_batch: one HIP launch) as a map policy: action [m].  `params`: the env's
+    parameters (`env.params`: the robot's acceleration / angular-velocity tables a, w)."""
+    from .planners import planner_act_batch
+    if kind not in ("APF", "BA"):
+        raise ValueError(f"planner_policy: kind must be 'APF' or 'BA', got {kind!r}")
+    a, w = [float(v) for v in params.a], [float(v) for v in params.w]
+    return lambda obs: dict(action=planner_act_batch(obs, kind, a, w))

@@ -381,6 +381,58 @@ class VecMarineNavEnv:
                             goal=gl[i].copy(), init_theta=float(th[i]), init_speed=float(sp[i])))
         return out
 
+    # ---- queries: ask a world without stepping it --------------------------------------------
+    def _query_env(self, env, n_queries):
+        """(index tensor or None, env0) of a query call: `env` is one world for every query (int) or an int tensor / array [Q]."""
+        if isinstance(env, (int, np.integer)):
+            return None, int(env)
+        idx = torch.as_tensor(env).to(device=self.device, dtype=torch.int32).contiguous()
+        if idx.shape != (n_queries,):
+            raise ValueError(f"env must be an int or hold one index per query ({n_queries}), got shape {tuple(idx.shape)}")
+        return idx, 0
+
+    def velocity_at(self, xy, env=0):
+        """MarineNavEnv.get_velocity (marinenav_env.py:422-455) at the points `xy` [Q, 2] of world `env` (an int, or one index per
+        point): float64 [Q, 2] on the device (C-ABI mn_query_velocity).  Reads the world tables only; nothing in the env changes."""
+        p = torch.as_tensor(xy).to(device=self.device, dtype=torch.float64).reshape(-1, 2).contiguous()
+        q = p.shape[0]
+        idx, env0 = self._query_env(env, q)
+        v = torch.empty(q, 2, dtype=torch.float64, device=self.device)
+        self._check(self.L.mn_query_velocity(self.h, _ptr(idx) if idx is not None else None, env0, _ptr(p), q, _ptr(v), self._stream()))
+        return v
+
+    def observation_at(self, states, env=0, velocity=None, dtype=torch.float32, return_flags=False):
+        """get_observation() (marinenav_env.py:273-326) of a robot in `states` -- [Q, 6] = x, y, theta, speed, velocity_x, velocity_y (the
+        columns of get_state), or [Q, 4] = x, y, theta, speed -- in world `env` (an int, or one index per state); host arrays are copied.
+        velocity="given" reports the velocity of columns 4-5 (a state after a step); "current" sets it to speed (cos theta, sin theta) +
+        the current at (x, y), like a robot placed there by reset (robot.py:79-87); default: "current" for [Q, 4], "given" for [Q, 6].
+        Returns the rows [Q, 26] as `dtype` (float32: the cast of the float64 row) on the device, with return_flags also uint8 [Q]:
+        _capi.QUERY_FLAG_COLLISION | _OUTSIDE | _GOAL, independent bits; _BAD_ENV: the index was no env, the row is NaN.  C-ABI
+        mn_query_observation: float64 arithmetic on the master tables whatever the env's precision; nothing in the env changes."""
+        st = torch.as_tensor(states).to(device=self.device, dtype=torch.float64)
+        if st.dim() != 2 or st.shape[1] not in (4, 6):
+            raise ValueError(f"states must be [Q, 4] or [Q, 6], got {tuple(st.shape)}")
+        if velocity is None:
+            velocity = "current" if st.shape[1] == 4 else "given"
+        if velocity not in ("current", "given"):
+            raise ValueError(f"velocity must be 'current' or 'given', got {velocity!r}")
+        if st.shape[1] == 4:
+            if velocity == "given":
+                raise ValueError("velocity='given' needs states [Q, 6] (columns 4-5 are the velocity)")
+            st = torch.cat([st, st.new_zeros(st.shape[0], 2)], dim=1)
+        st = st.contiguous()
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("dtype must be torch.float32 or torch.float64")
+        q = st.shape[0]
+        idx, env0 = self._query_env(env, q)
+        obs = torch.empty(q, OBS_DIM, dtype=dtype, device=self.device)
+        flags = torch.empty(q, dtype=torch.uint8, device=self.device) if return_flags else None
+        mode = _capi.QUERY_VELOCITY_FROM_CURRENT if velocity == "current" else _capi.QUERY_VELOCITY_GIVEN
+        self._check(self.L.mn_query_observation(self.h, _ptr(idx) if idx is not None else None, env0, _ptr(st), mode, q,
+                                                _ptr(obs) if dtype == torch.float32 else None, _ptr(obs) if dtype == torch.float64 else None,
+                                                _ptr(flags) if flags is not None else None, self._stream()))
+        return (obs, flags) if return_flags else obs
+
     # ---- state accessors (tests, checkpoints) ------------------------------------------------
     def get_state(self, first_env=0, count=None):
         cnt = self.n_envs - first_env if count is None else count

@@ -235,6 +235,35 @@ int mn_get_worlds(mn_handle *h, int32_t first_env, int32_t count, int32_t *n_cor
                   int32_t *clockwise, double *gamma, int32_t *n_obs, double *obs_xy, double *obs_r, double *start,
                   double *goal, double *init_theta, double *init_speed);
 
+/* Queries: ask a world without stepping it.  Both read only the handle's float64 master tables (cores, obstacles, goal, the
+ * placed counts) and the parameters -- tables a handle of either precision keeps -- compute in float64 throughout, and write
+ * NOTHING into the handle: robot state, counters, RNG rows, observation / trajectory buffers and the done queue stay as they are.
+ * The answers therefore do not depend on the handle's precision.  Query q is evaluated in world env_of_query_dev[q] ([n_queries]
+ * i32 on the device), or every query in world env0 if env_of_query_dev is NULL.  n_queries = 0 returns MN_OK without a launch.
+ * MN_ERR_INVALID (with a message in mn_last_error): NULL handle, n_queries < 0, env0 outside [0, n_envs) when no index array is
+ * given, an unknown velocity_mode, and with n_queries > 0 a NULL input or every output NULL.  An index outside [0, n_envs) INSIDE env_of_query_dev is
+ * not visible to the host: that query reads no table, its float outputs are NaN and its flags are MN_QUERY_FLAG_BAD_ENV alone
+ * (mn_query_velocity has no flags: NaN only); the other queries of the call are unaffected and the call returns MN_OK.
+ * Both calls join a pending mn_reset_done_async on `stream`.
+ *
+ * mn_query_velocity: MarineNavEnv.get_velocity(x, y) (marinenav_env.py:422-455), the current at xy_dev [n_queries][2] f64, into
+ *   v_dev [n_queries][2] f64.
+ * mn_query_observation: get_observation() (marinenav_env.py:273-326 with robot.py:125-198) of a robot in state
+ *   state_dev [n_queries][6] f64 = x, y, theta, speed, velocity_x, velocity_y (the columns of mn_get_state).
+ *   MN_QUERY_VELOCITY_GIVEN takes columns 4-5 as the robot's velocity (a state after a step); MN_QUERY_VELOCITY_FROM_CURRENT
+ *   ignores them and uses speed (cos theta, sin theta) + current(x, y), as Robot.reset_state does (robot.py:79-87: a robot
+ *   placed at a pose).  Outputs, each may be NULL: obs_dev [n_queries][26] f32 (the float32 cast of the float64 row; 8-byte aligned),
+ *   obs64_dev [n_queries][26] f64, flags_dev [n_queries] u8.  The flag bits are independent of each other (they are not the
+ *   termination ladder of mn_step): COLLISION by the reference's rule -- only the obstacle with the nearest centre is tested,
+ *   d <= r + robot_r (marinenav_env.py:329-336) --, OUTSIDE [0, width] x [0, height], GOAL within goal_dis of the goal. */
+enum { MN_QUERY_VELOCITY_GIVEN = 0, MN_QUERY_VELOCITY_FROM_CURRENT = 1 };
+enum { MN_QUERY_FLAG_COLLISION = 1, MN_QUERY_FLAG_OUTSIDE = 2, MN_QUERY_FLAG_GOAL = 4, MN_QUERY_FLAG_BAD_ENV = 128 };
+int mn_query_velocity(mn_handle *h, const int32_t *env_of_query_dev, int32_t env0, const double *xy_dev,
+                      int64_t n_queries, double *v_dev, void *stream);
+int mn_query_observation(mn_handle *h, const int32_t *env_of_query_dev, int32_t env0, const double *state_dev,
+                         int32_t velocity_mode, int64_t n_queries, float *obs_dev, double *obs64_dev,
+                         uint8_t *flags_dev, void *stream);
+
 /* Robot pose and counters (robot.py:40-44, marinenav_env.py:70-71).  state[count][6] =
  * x, y, theta, speed, velocity_x, velocity_y (float64).  NULL pointers are skipped. */
 int mn_get_state(mn_handle *h, int32_t first_env, int32_t count, double *state, int32_t *episode_timesteps,
