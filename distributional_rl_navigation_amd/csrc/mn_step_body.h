@@ -357,8 +357,11 @@ struct MnLane {
         // ---- observation (marinenav_env.py:273-326) ------------------------------------------------
         // Obstacle centres in the robot frame, m_r = R(theta)^T (c - p) (|m_r| = |c - p|), and at the same
         // time the sonar work-list: only obstacles that can intersect the fan at all -- within range + r of
-        // the robot and inside the +-60 degree wedge widened by r -- are appended, IN GENERATION ORDER, to a
-        // lane-private LDS column.  A dropped obstacle can never produce a candidate, so it can neither be
+        // the robot and inside the +-sonar_angle/2 wedge widened by r + 0.05 + 1e-3 reach -- are appended, IN GENERATION
+        // ORDER, to a lane-private LDS column.  The last term is for the snapped beam (robot.py:135-143): an outermost beam
+        // within 1e-3 rad of the vertical is cast exactly vertically, i.e. up to 1e-3 rad OUTSIDE the wedge, and a point of
+        // it at distance s <= range < reach lies up to s sin(1e-3) from the wedge's edge -- 0.08 m at sonar_range 80, which a
+        // constant 0.05 did not cover (tests/test_params_gpu.py, g18).  A dropped obstacle can never produce a candidate, so it can neither be
         // hit nor trigger the reference's `break`; the scan over the list is therefore equivalent to the
         // scan over all obstacles (robot.py:147-198).  Typically 0-3 of the 10 obstacles survive, and the
         // beam loop runs to the longest list in the wavefront instead of 10.
@@ -392,7 +395,7 @@ struct MnLane {
             const double r = obr[j];
             const double reach = reach0 + r;
             const bool rel = in && (d2 <= reach * reach) &&
-                             (!P.fan_filter || (fma(P.fan_sin, rx_, -(P.fan_cos * fabs(ry_))) >= -(r + 0.05)));
+                             (!P.fan_filter || (fma(P.fan_sin, rx_, -(P.fan_cos * fabs(ry_))) >= -fma(1.0e-3, reach, r + 0.05)));
             const unsigned gbits = (unsigned)(__ballot(rel) >> gshift) & ((1u << L) - 1u);     // obstacles L j .. L j + L - 1 of this env
             const int pos = nrel + __popc(gbits & ((1u << q) - 1u));
             if (rel) { lst_x[pos][tl] = rx_; lst_y[pos][tl] = ry_; lst_r[pos][tl] = (M)r; }

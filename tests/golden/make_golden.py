@@ -25,6 +25,11 @@ Outputs (all small, committed):
   g13_learn_loop.npz    bookkeeping of the reference IQNAgent.learn loop over 400 timesteps on the reference env
   g14_iqn_episodes.npz  run_experiments.py's evaluation_IQN loop on the reference env + pretrained agent, injected taus:
                         per-step action / CVaR / quantiles / taus, per-episode outcome and trajectory
+  g16_reset_params.npz  g1's recipe under the parameter sets of tests/params_sets.py (seeds 0-11 x 3 resets each): the 500-try limits
+                        of the start / goal, core and obstacle loops, 60 x 36 and 36 x 60 maps, pose / start / goal from the parameters
+  g17_step_params.npz   g3's recipe under other robot / sonar / reward / map parameters (5 sets x 256 steps) + stability flags
+  g18_sonar_params_edge.npz  g4's layout at sonar.range 80 and 15: the snapped outermost beam, the range limit, several obstacles on one
+                        beam; `obs_ld` = the same formulas in np.longdouble
   (g10 / g11: make_golden_dqn.py)
 """
 import contextlib
@@ -697,8 +702,353 @@ def g14_iqn_episodes():
     np.savez_compressed(os.path.join(OUT, "g14_iqn_episodes.npz"), **out)
 
 
+# ---- g16 / g17 / g18: the env parameters away from their defaults ---------------------------------------------------------
+sys.path.insert(0, os.path.dirname(OUT))
+import params_sets as PS  # noqa: E402      (tests/params_sets.py: the sets, by mn_params field name)
+
+_ENV_ATTR = {"core_r": "r"}                                     # mn_params field -> MarineNavEnv attribute where the names differ
+_ROBOT_ATTR = {"dt": "dt", "N": "N", "max_speed": "max_speed", "robot_r": "r"}
+_SONAR_ATTR = {"sonar_range": "range", "sonar_angle": "angle"}
+_BOOLS = ("reset_start_and_goal", "random_reset_state", "set_boundary")
+
+
+def apply_set(env, spec):
+    """The attribute writes a set stands for (what reset_with_eval_config does from a file, marinenav_env.py:467-555), followed by
+    the recomputations it calls (:532-533, :541-542)."""
+    for k, v in spec.items():
+        if k in ("a", "w"):
+            setattr(env.robot, k, np.array(v, dtype=float))
+        elif k in _ROBOT_ATTR:
+            setattr(env.robot, _ROBOT_ATTR[k], v)
+        elif k in _SONAR_ATTR:
+            setattr(env.robot.sonar, _SONAR_ATTR[k], v)
+        elif k in ("start", "goal"):
+            setattr(env, k, np.array(v, dtype=float))
+        elif k in ("v_range", "obs_r_range"):
+            setattr(env, k, list(v))
+        elif k in _BOOLS:
+            setattr(env, k, bool(v))
+        else:
+            setattr(env, _ENV_ATTR.get(k, k), v)
+    env.robot.compute_k()
+    env.robot.compute_actions()
+    env.robot.sonar.compute_phi()
+    env.robot.sonar.compute_beam_angles()
+
+
+class _CountingRandomState:
+    """Forwards to the env's RandomState and counts the calls, so that the tries each of reset()'s three rejection loops used can be
+    told apart: the first binomial() is drawn after 2 uniform() calls per start / goal try and one for the first core centre."""
+
+    def __init__(self, rd):
+        self.rd, self.n_uniform, self.n_binomial, self.uniform_at_first_binomial = rd, 0, 0, None
+
+    def uniform(self, *a, **kw):
+        self.n_uniform += 1
+        return self.rd.uniform(*a, **kw)
+
+    def binomial(self, *a, **kw):
+        if self.uniform_at_first_binomial is None:
+            self.uniform_at_first_binomial = self.n_uniform
+        self.n_binomial += 1
+        return self.rd.binomial(*a, **kw)
+
+    def __getattr__(self, k):
+        return getattr(self.rd, k)
+
+
+def g16_reset_params():
+    """g1's recipe under the parameter sets PS.RESET_SETS: world generation where the 500-try limits are reached, on maps that are
+    not square, and with the pose / start / goal taken from the parameters.  `tries` = candidates drawn by the start / goal, core
+    and obstacle loops."""
+    keys = ("set", "seed", "start", "goal", "cores", "obs", "ncores", "nobs", "theta0", "speed0", "obs0", "state0", "next_double", "tries")
+    rec = {k: [] for k in keys}
+    for si, (name, spec) in enumerate(PS.RESET_SETS):
+        for seed in PS.RESET_SEEDS:
+            env = MarineNavEnv(seed=seed)
+            apply_set(env, spec)
+            for _ in range(PS.RESET_REPEATS):
+                cnt = _CountingRandomState(env.rd)
+                env.rd = cnt
+                ob = env.reset()
+                env.rd = cnt.rd
+                sg = 0 if cnt.uniform_at_first_binomial is None else (cnt.uniform_at_first_binomial - 1) // 2
+                pose = 2 if env.random_reset_state else 0
+                ob_tries = (cnt.n_uniform - 2 * sg - 2 * cnt.n_binomial - pose) // 2
+                assert cnt.n_binomial > 0 and 2 * (sg + cnt.n_binomial + ob_tries) + pose == cnt.n_uniform
+                c, o, n1, n2 = world_arrays(env)
+                rec["set"].append(si); rec["seed"].append(seed)
+                rec["start"].append(env.start.copy()); rec["goal"].append(env.goal.copy())
+                rec["cores"].append(c); rec["obs"].append(o); rec["ncores"].append(n1); rec["nobs"].append(n2)
+                rec["theta0"].append(env.robot.init_theta); rec["speed0"].append(env.robot.init_speed)
+                rec["obs0"].append(ob); rec["state0"].append(robot_state(env)); rec["next_double"].append(peek_next_double(env))
+                rec["tries"].append([sg, cnt.n_binomial, ob_tries])
+    out = {k: np.array(v) for k, v in rec.items()}
+    out["set_names"] = np.array([n for n, _ in PS.RESET_SETS])
+    # what the sets are there for
+    tries, st = out["tries"], out["set"]
+    sel = lambda name: st == [n for n, _ in PS.RESET_SETS].index(name)
+    assert (tries[sel("R1")][:, 0] == 500).all()
+    r2 = tries[sel("R2")][:, 0]
+    assert (r2 == 500).sum() >= 10 and ((r2 < 500) & (r2 > 64)).sum() >= 1, r2
+    for name in ("R3", "R6"):
+        assert ((out["ncores"][sel(name)] < 8) & (tries[sel(name)][:, 1] == 500)).sum() >= 10, name
+    r4 = sel("R4")
+    assert (out["ncores"][r4] < 8).sum() >= 1 and ((out["ncores"][r4] == 8) & (tries[r4][:, 1] > 64)).sum() >= 1
+    assert ((out["nobs"][sel("R5")] < 10) & (tries[sel("R5")][:, 2] == 500)).sum() >= 10
+    for name in ("R7a", "R7b"):
+        assert (out["ncores"][sel(name)] == 8).all() and (out["nobs"][sel(name)] == 10).all()
+    # check_core tests `y + r > width` (sic, :349).  R7a (60 x 36): cores reach over the top edge, which a test against the height
+    # would refuse; R7b (36 x 60): no core above y = 36 - r although the map goes on to 60
+    assert (out["cores"][sel("R7a")][:, :, 1] + 0.5 > 36.0).any()
+    assert (out["cores"][sel("R7b")][:, :, 1] + 0.5 <= 36.0).all() and (out["obs"][sel("R7b")][:, :, 1] > 36.0).any()
+    assert (out["start"][sel("R8")] == np.array([7.0, 9.0])).all() and (out["theta0"][sel("R8")] == 2.5).all()
+    for name, _ in PS.RESET_SETS:
+        m = sel(name)
+        print(f"  g16 {name}: start/goal tries {np.bincount(np.minimum(tries[m][:, 0] // 64, 8))}, "
+              f"short of cores {(out['ncores'][m] < PS.RESET_SETS[int(st[m][0])][1].get('num_cores', 8)).sum()}/36, "
+              f"short of obstacles {(out['nobs'][m] < PS.RESET_SETS[int(st[m][0])][1].get('num_obs', 5)).sum()}/36, "
+              f"core tries max {tries[m][:, 1].max()}, obstacle tries max {tries[m][:, 2].max()}")
+    np.savez_compressed(os.path.join(OUT, "g16_reset_params.npz"), **out)
+
+
+def _eval_step(env, sin, a, ep_t):
+    env.robot.x, env.robot.y, env.robot.theta, env.robot.speed = (float(v) for v in sin)
+    env.robot.velocity = np.zeros(2)
+    env.episode_timesteps = ep_t
+    ob, r, d, info = env.step(a)
+    return ob, r, d, INFO_CODE[info["state"]], robot_state(env)
+
+
+def _hit(ob):
+    p = np.asarray(ob)[4:].reshape(11, 2)
+    return ~((p[:, 0] == 0) & (p[:, 1] == 0))
+
+
+def g17_step_params(n_worlds=8, per_world=32):
+    """g3's recipe under the parameter sets PS.STEP_SETS, plus stability flags: a beam's hit / miss, or the info code, is `stable`
+    if it is the same with sonar.range, every obstacle radius, goal_dis and robot.r each moved by +-1e-4."""
+    keys = ("set", "cores", "obs_tab", "n", "start", "goal", "state_in", "action", "ep_t", "obs", "reward", "done", "info", "state_out",
+            "beam_stable", "info_stable")
+    rec = {k: [] for k in keys}
+    eps = 1e-4
+    for si, (name, spec) in enumerate(PS.STEP_SETS):
+        rng = np.random.RandomState(1700 + si)
+        W, H = spec.get("width", 50.0), spec.get("height", 50.0)
+        first = len(rec["set"])
+        for wi in range(n_worlds):
+            nc, no, md = [(8, 10, 30.0), (6, 8, 30.0), (8, 10, 25.0), (4, 10, 30.0)][wi % 4]
+            env = MarineNavEnv(seed=17_000 + 100 * si + wi)
+            apply_set(env, spec)
+            env.num_cores, env.num_obs, env.min_start_goal_dis = nc, no, md
+            env.reset()
+            c, o, n1, n2 = world_arrays(env)
+            for j in range(per_world):
+                # a third near an obstacle, a third near the goal; of the rest S4 puts half within 0.5 m of a map edge (either side
+                # of it) and S5 three in four within 1.5 m of a core centre (a quarter of all)
+                mode = j % 3
+                if mode == 1 and n2 > 0:
+                    k = env.obstacles[rng.randint(n2)]
+                    ang = rng.uniform(0, 2 * np.pi)
+                    dist = k.r + rng.uniform(0.3, 4.0)
+                    x, y = k.x + dist * np.cos(ang), k.y + dist * np.sin(ang)
+                elif mode == 2:
+                    ang = rng.uniform(0, 2 * np.pi)
+                    dist = rng.uniform(0.5, 2.5 * env.goal_dis)
+                    x, y = env.goal[0] + dist * np.cos(ang), env.goal[1] + dist * np.sin(ang)
+                elif name == "S4" and (j // 3) % 2 == 0:
+                    x, y = rng.uniform(0, W), rng.uniform(0, H)
+                    edge = rng.randint(4)
+                    off = rng.uniform(-0.5, 0.5)
+                    if edge < 2:
+                        x = (0.0, W)[edge] + off
+                    else:
+                        y = (0.0, H)[edge - 2] + off
+                elif name == "S5" and (j // 3) % 4 != 3 and n1 > 0:
+                    k = env.cores[rng.randint(n1)]
+                    ang = rng.uniform(0, 2 * np.pi)
+                    dist = rng.uniform(0.0, 1.5)
+                    x, y = k.x + dist * np.cos(ang), k.y + dist * np.sin(ang)
+                else:
+                    x, y = rng.uniform(0, W), rng.uniform(0, H)
+                theta = rng.uniform(0, 2 * np.pi)
+                speed = rng.uniform(0, env.robot.max_speed)
+                a = int(rng.randint(9))
+                ep_t = int(rng.choice([0, 5, 999, 1000], p=[0.3, 0.3, 0.25, 0.15]))
+                sin = np.array([x, y, theta, speed])
+                ob, r, d, info, sout = _eval_step(env, sin, a, ep_t)
+                # stability: the same sample with each threshold moved by +-1e-4
+                hits, infos = [_hit(ob)], [info]
+                keep = (env.robot.sonar.range, env.goal_dis, env.robot.r, [k.r for k in env.obstacles])
+                for sg in (+eps, -eps):
+                    for what in ("range", "radius", "goal_dis", "robot_r"):
+                        if what == "range":
+                            env.robot.sonar.range = keep[0] + sg
+                        elif what == "radius":
+                            for k, rr in zip(env.obstacles, keep[3]):
+                                k.r = rr + sg
+                        elif what == "goal_dis":
+                            env.goal_dis = keep[1] + sg
+                        else:
+                            env.robot.r = keep[2] + sg
+                        ob2, _, _, info2, _ = _eval_step(env, sin, a, ep_t)
+                        hits.append(_hit(ob2)); infos.append(info2)
+                        env.robot.sonar.range, env.goal_dis, env.robot.r = keep[:3]
+                        for k, rr in zip(env.obstacles, keep[3]):
+                            k.r = rr
+                hits = np.array(hits)
+                rec["set"].append(si); rec["cores"].append(c); rec["obs_tab"].append(o); rec["n"].append([n1, n2])
+                rec["start"].append(env.start.copy()); rec["goal"].append(env.goal.copy())
+                rec["state_in"].append(sin); rec["action"].append(a); rec["ep_t"].append(ep_t)
+                rec["obs"].append(ob); rec["reward"].append(r); rec["done"].append(d); rec["info"].append(info); rec["state_out"].append(sout)
+                rec["beam_stable"].append((hits == hits[0]).all(axis=0)); rec["info_stable"].append(all(i == info for i in infos))
+        # what the set is there for: every outcome it can produce, both kinds of beams, few knife-edge items
+        info = np.array(rec["info"][first:]); hit = np.array([_hit(ob) for ob in rec["obs"][first:]])
+        bst = np.array(rec["beam_stable"][first:]); ist = np.array(rec["info_stable"][first:])
+        codes = [0, 2, 3, 4] + ([1] if spec.get("set_boundary") else [])
+        counts = {k: int((info == k).sum()) for k in codes}
+        print(f"  g17 {name}: info counts {counts}, beam hits {hit.mean():.3f}, unstable beams {(~bst).sum()}/{bst.size}, unstable infos {(~ist).sum()}/{ist.size}")
+        assert min(counts.values()) >= 10 and set(np.unique(info)) <= set(codes), counts
+        assert 0.10 <= hit.mean() <= 0.90, hit.mean()
+        assert (~bst).mean() <= 0.01 and (~ist).mean() <= 0.01
+    out = {k: np.array(v) for k, v in rec.items()}
+    out["set_names"] = np.array([n for n, _ in PS.STEP_SETS])
+    np.savez_compressed(os.path.join(OUT, "g17_step_params.npz"), **out)
+
+
+def _observation_longdouble(env):
+    """get_observation() with robot.py:125-198's slope-form intersection and marinenav_env.py:281-326's frame change evaluated in
+    np.longdouble (64-bit mantissa).  The beam angle and the snap decision (:132-136) are the reference's float64 ones: they select
+    the formula.  Returns (obs [26] longdouble, hit [11])."""
+    ld = np.longdouble
+    rb = env.robot
+    X, Y, th, rng_ = ld(rb.x), ld(rb.y), ld(rb.theta), ld(rb.sonar.range)
+    pts, hit = [], []
+    for rel_a in rb.sonar.beam_angles:
+        angle = rb.theta + rel_a
+        vert = np.abs(angle - np.pi / 2) < 1e-03 or np.abs(angle - 3 * np.pi / 2) < 1e-03
+        al = ld(rb.theta) + ld(rel_a)
+        ca, sa = np.cos(al), np.sin(al)
+        best, have, dist = None, False, ld(np.inf)
+        for ob in env.obstacles:
+            ox, oy, orad = ld(ob.x), ld(ob.y), ld(ob.r)
+            if vert:
+                M = orad * orad - (X - ox) * (X - ox)
+                if M < 0:
+                    continue
+                x1 = x2 = X
+                y1, y2 = oy - np.sqrt(M), oy + np.sqrt(M)
+            else:
+                K = np.tan(al)
+                a = 1 + K * K
+                b = 2 * K * (Y - K * X - oy) - 2 * ox
+                c = ox * ox + (Y - K * X - oy) * (Y - K * X - oy) - orad * orad
+                delta = b * b - 4 * a * c
+                if delta < 0:
+                    continue
+                x1 = (-b - np.sqrt(delta)) / (2 * a)
+                x2 = (-b + np.sqrt(delta)) / (2 * a)
+                y1 = Y + K * (x1 - X)
+                y2 = Y + K * (x2 - X)
+            n1, n2 = np.sqrt((x1 - X) ** 2 + (y1 - Y) ** 2), np.sqrt((x2 - X) ** 2 + (y2 - Y) ** 2)
+            vx, vy, nv = (x1 - X, y1 - Y, n1) if n1 < n2 else (x2 - X, y2 - Y, n2)
+            if nv > rng_:
+                continue
+            if vx * ca + vy * sa < 0:
+                continue
+            if have and nv >= dist:
+                break
+            dist, best, have = nv, (vx + X, vy + Y), True
+        pts.append(best); hit.append(have)
+    c, s = np.cos(th), np.sin(th)
+    rot = lambda px, py: (c * (px - X) + s * (py - Y), -s * (px - X) + c * (py - Y))
+    vel = (c * ld(rb.velocity[0]) + s * ld(rb.velocity[1]), -s * ld(rb.velocity[0]) + c * ld(rb.velocity[1]))
+    out = [vel[0], vel[1], *rot(ld(env.goal[0]), ld(env.goal[1]))]
+    for p, h in zip(pts, hit):
+        out.extend(rot(*p) if h else (ld(0), ld(0)))
+    return np.array(out, dtype=ld), np.array(hit)
+
+
+def g18_sonar_params_edge():
+    """Observation-only cases in g4's layout at sonar.range = 80 (on a 120 x 120 map) and 15: the outermost beam inside and outside
+    the 1e-3 rad snap window with an obstacle next to it on the side away from the fan, the range limit, an obstacle behind, several
+    obstacles on one beam; at range 80 also with sonar.angle = 0.9 pi and an obstacle on an outermost beam.  The robot stands still (speed 0, no current), so a step without acceleration or turn leaves it where it
+    is.  `obs_ld`: the same formulas in np.longdouble."""
+    cases = []
+
+    def add(name, rng_, obstacles, x, y, theta, goal=(60.0, 60.0), angle=PS.EDGE_ANGLES[0]):
+        env = MarineNavEnv(seed=0)
+        apply_set(env, dict(sonar_range=rng_, sonar_angle=angle, width=PS.EDGE_MAP, height=PS.EDGE_MAP))
+        env.cores.clear()
+        env.obstacles.clear()
+        for (ox, oy, r) in obstacles:
+            env.obstacles.append(Obstacle(ox, oy, r))
+        env.goal = np.array(goal)
+        env.robot.x, env.robot.y, env.robot.theta, env.robot.speed = x, y, theta, 0.0
+        env.robot.velocity = np.zeros(2)
+        ob = env.get_observation()
+        ob_ld, hit_ld = _observation_longdouble(env)
+        assert np.array_equal(hit_ld, _hit(ob)), name
+        o = np.zeros((MAXO, 3))
+        for i, ob_ in enumerate(obstacles):
+            o[i] = ob_
+        cases.append(dict(name=name, range=rng_, angle=angle, obs_tab=o, n_obs=len(obstacles), pose=[x, y, theta], goal=list(goal),
+                          vel=[0.0, 0.0], obs=ob, obs_ld=ob_ld.astype(np.float64)))
+        return _hit(ob)
+
+    rel = [-(2 * np.pi / 3) / 2 + i * ((2 * np.pi / 3) / 10) for i in range(11)]
+    seen = set()
+    for rng_ in (80.0, 15.0):
+        for bi in (0, 10):
+            for vert, sgn in ((np.pi / 2, 1.0), (3 * np.pi / 2, -1.0)):
+                # the side of the cast beam that faces away from the fan: clockwise of beam 0, counter-clockwise of beam 10
+                side = (1.0 if bi == 0 else -1.0) * sgn
+                x, y = 60.0, 60.0 - sgn * 50.0
+                for eps in (0.0009, -0.0009, 0.0011, -0.0011):
+                    th = vert - rel[bi] + eps
+                    assert 0.0 <= th < 2 * np.pi
+                    h = add(f"edge_r{rng_:.0f}_b{bi}_{'up' if sgn > 0 else 'down'}_{eps}", rng_, [(x + side * 0.999, y + sgn * 0.85 * rng_, 1.0)], x, y, th)
+                    seen.add((abs(eps) < 1e-3, bool(h[bi])))
+        # the range limit: the near intersection of the centre beam 1e-6 inside / outside the range
+        add(f"range_in_r{rng_:.0f}", rng_, [(20.0 + rng_ + 1.0 - 1e-6, 60.0, 1.0)], 20.0, 60.0, 0.0)
+        add(f"range_out_r{rng_:.0f}", rng_, [(20.0 + rng_ + 1.0 + 1e-6, 60.0, 1.0)], 20.0, 60.0, 0.0)
+        add(f"behind_r{rng_:.0f}", rng_, [(20.0 - 0.5 * rng_, 60.0, 1.0)], 20.0, 60.0, 0.0)
+        near, far, mid = (20.0 + 0.3 * rng_, 60.0, 1.0), (20.0 + 0.8 * rng_, 60.0, 2.0), (20.0 + 0.55 * rng_, 60.2, 0.8)
+        for order_name, order in (("nf", [near, far]), ("fn", [far, near]), ("mfn", [mid, far, near]), ("fmn", [far, mid, near]),
+                                  ("nfm", [near, far, mid])):
+            add(f"break_{order_name}_r{rng_:.0f}", rng_, order, 20.0, 60.0, 0.0)
+            add(f"break2_{order_name}_r{rng_:.0f}", rng_, order, 20.0, 60.0, 0.02)
+    assert seen == {(True, True), (False, True), (False, False)}, seen      # a snapped beam always hits; an unsnapped one does both
+    # a wide fan (0.9 pi) at range 80: an obstacle ON an outermost beam (and on its neighbour) at 0.9 x range, where the work-list's
+    # wedge test depends on sin(sonar_angle / 2) by more than an obstacle's radius
+    wide = PS.EDGE_ANGLES[1]
+    rel_w = [-wide / 2 + i * (wide / 10) for i in range(11)]
+    for bi in (0, 1, 9, 10):
+        for th in (0.3, 2.0, 4.4):
+            ang = th + rel_w[bi]
+            assert min(abs(ang - np.pi / 2), abs(ang - 3 * np.pi / 2)) > 0.01
+            ux, uy = np.cos(ang), np.sin(ang)
+            x, y = 60.0 - 36.0 * ux, 60.0 - 36.0 * uy
+            h = add(f"wide_r80_b{bi}_{th}", 80.0, [(x + 72.0 * ux, y + 72.0 * uy, 1.0)], x, y, th, angle=wide)
+            assert h[bi] and h.sum() == 1
+    obs = np.array([c["obs"] for c in cases]); obs_ld = np.array([c["obs_ld"] for c in cases])
+    print(f"  g18: {len(cases)} cases, max |obs - obs_ld| {np.abs(obs - obs_ld).max():.3e}")
+    np.savez_compressed(
+        os.path.join(OUT, "g18_sonar_params_edge.npz"),
+        names=np.array([c["name"] for c in cases]), range=np.array([c["range"] for c in cases]), angle=np.array([c["angle"] for c in cases]),
+        obs_tab=np.array([c["obs_tab"] for c in cases]), n_obs=np.array([c["n_obs"] for c in cases]),
+        pose=np.array([c["pose"] for c in cases]), goal=np.array([c["goal"] for c in cases]),
+        vel=np.array([c["vel"] for c in cases]), obs=obs, obs_ld=obs_ld)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g12", "g13", "g14", "g15"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g12", "g13", "g14", "g15", "g16", "g17", "g18"]
+    if "g16" in which:
+        g16_reset_params()
+    if "g17" in which:
+        g17_step_params()
+    if "g18" in which:
+        g18_sonar_params_edge()
     if "g12" in which:
         g12_replay()
     if "g15" in which:

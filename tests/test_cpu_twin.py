@@ -85,6 +85,38 @@ class Driver:
                                    tot.ctypes.data_as(C.POINTER(C.c_int64))) == 0
         return s, ep, tot
 
+    def worlds(self):
+        """mn_get_worlds: dict of the padded tables -- cores [n, 8, 4] = x, y, clockwise, Gamma; obstacles [n, 10, 3] = x, y, r; counts;
+        start / goal [n, 2]; theta0 / speed0 [n]."""
+        n, d, i = self.n, C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        nc = np.zeros(n, np.int32); no = np.zeros(n, np.int32); cw = np.zeros((n, 8), np.int32)
+        cxy = np.zeros((n, 8, 2)); gm = np.zeros((n, 8)); oxy = np.zeros((n, 10, 2)); orr = np.zeros((n, 10))
+        st = np.zeros((n, 2)); gl = np.zeros((n, 2)); th = np.zeros(n); sp = np.zeros(n)
+        p = lambda a, t: a.ctypes.data_as(t)
+        assert self.L.mn_get_worlds(self.h, 0, n, p(nc, i), p(cxy, d), p(cw, i), p(gm, d), p(no, i), p(oxy, d), p(orr, d), p(st, d), p(gl, d),
+                                    p(th, d), p(sp, d)) == 0
+        return dict(cores=np.concatenate([cxy, cw[:, :, None].astype(np.float64), gm[:, :, None]], axis=2),
+                    obstacles=np.concatenate([oxy, orr[:, :, None]], axis=2), ncores=nc, nobs=no, start=st, goal=gl, theta0=th, speed0=sp)
+
+    def load_worlds(self, cores, ncores, obstacles, nobs, start, goal, theta0, speed0):
+        """mn_load_worlds for all n envs from padded tables laid out like worlds()'s; returns the first observations (float64)."""
+        n, d, i = self.n, C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        cores = np.asarray(cores, np.float64); obstacles = np.asarray(obstacles, np.float64)
+        f = lambda a: np.ascontiguousarray(a, np.float64)
+        nc = np.ascontiguousarray(ncores, np.int32); no = np.ascontiguousarray(nobs, np.int32)
+        cxy = f(cores[:, :, :2]); cw = np.ascontiguousarray(cores[:, :, 2] != 0, np.int32); gm = f(cores[:, :, 3])
+        oxy = f(obstacles[:, :, :2]); orr = f(obstacles[:, :, 2])
+        st = f(start); gl = f(goal); th = f(np.broadcast_to(theta0, (n,))); sp = f(np.broadcast_to(speed0, (n,)))
+        p = lambda a, t: a.ctypes.data_as(t)
+        assert self.L.mn_load_worlds(self.h, 0, n, p(nc, i), p(cxy, d), p(cw, i), p(gm, d), p(no, i), p(oxy, d), p(orr, d), p(st, d), p(gl, d),
+                                     p(th, d), p(sp, d), self.ptr(self.obs[self.cur]), None) == 0, self.L.mn_last_error(self.h)
+        return self.obs64()
+
+    def set_state(self, state, ep_t):
+        s = np.ascontiguousarray(state, np.float64); ep = np.ascontiguousarray(ep_t, np.int32)
+        assert s.shape == (self.n, 6) and ep.shape == (self.n,)
+        assert self.L.mn_set_state(self.h, 0, self.n, s.ctypes.data_as(C.POINTER(C.c_double)), ep.ctypes.data_as(C.POINTER(C.c_int32)), None) == 0
+
     def peek(self):
         out = np.zeros(self.n)
         assert self.L.mn_peek_next_double(self.h, 0, self.n, out.ctypes.data_as(C.POINTER(C.c_double))) == 0
