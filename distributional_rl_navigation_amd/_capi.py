@@ -93,6 +93,7 @@ SIGNATURES = [
     ("mn_iqn_destroy", C.c_int, [_vp]),
     ("mn_iqn_weights_changed", C.c_int, [_vp]),
     ("mn_iqn_set_variant", C.c_int, [_vp, _i32]),
+    ("mn_iqn_set_greedy_rows", C.c_int, [_vp, _i32]),
     ("mn_iqn_set_grid", C.c_int, [_vp, _i32]),
     ("mn_iqn_set_tau_mode", C.c_int, [_vp, _i32]),
     ("mn_iqn_set_late_rows", C.c_int, [_vp, _vp, _vp, C.c_uint32, _i32]),

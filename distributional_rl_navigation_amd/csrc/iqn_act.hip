@@ -51,12 +51,14 @@ struct Form {
     const void *kernel() const { return exact ? (const void *)exact : split ? (const void *)split : (const void *)tiled; }
     size_t lds_bytes() const { return lds_floats * sizeof(float); }
 };
-enum { F_EXACT, F_EXACT_QUANT, F_SPLIT, F_SPLIT_LATE, F_SPLIT_QUANT, F_SHARED, F_SHARED_QUANT, F_TILED, N_FORMS };
+enum { F_EXACT, F_EXACT_QUANT, F_SPLIT, F_SPLIT_LATE, F_SPLIT_ROWS, F_SPLIT_LATE_ROWS, F_SPLIT_QUANT, F_SHARED, F_SHARED_QUANT, F_TILED, N_FORMS };
 const Form FORMS[N_FORMS] = {
     {iqn_qvals_kernel<false>, nullptr, nullptr, LDS_FLOATS, 512},
     {iqn_qvals_kernel<true>, nullptr, nullptr, LDS_FLOATS, 512},      // act_eval: the [n][32][9] quantile values as well
     {nullptr, sp::iqn_qvals_split_kernel<false>, nullptr, sp::LDS_ACT_FLOATS, 512},
     {nullptr, sp::iqn_qvals_split_kernel<false, false, sp::WAVES, true>, nullptr, sp::LDS_ACT_FLOATS, 512},      // late rows (mn_iqn_set_late_rows)
+    {nullptr, sp::iqn_qvals_split_kernel<false, false, sp::WAVES, false, true>, nullptr, sp::LDS_ACT_FLOATS, 512},      // only the rows that do not explore (mn_iqn_set_greedy_rows)
+    {nullptr, sp::iqn_qvals_split_kernel<false, false, sp::WAVES, true, true>, nullptr, sp::LDS_ACT_FLOATS, 512},       // ... with late rows among them
     {nullptr, sp::iqn_qvals_split_kernel<true>, nullptr, sp::LDS_FLOATS, 512},
     // launch-shared taus (12 waves per workgroup -- three per SIMD, the kernel needs 153 registers -- measured: 202-204 us against 203, no gain)
     {nullptr, sp::iqn_qvals_split_kernel<false, true, 8>, nullptr, sp::OFF_FB, 512},
@@ -102,6 +104,9 @@ struct mn_iqn_ctx {
     std::vector<hipEvent_t> ev;
     int prof_max = 0, prof_n = 0;
     uint32_t *rollout_words = nullptr;      // mn_rollout_iqn: its launch's ticket and longest episode (zero between launches)
+    bool greedy_rows = true;                // mn_iqn_set_greedy_rows
+    uint32_t *rows_buf = nullptr;           // GreedyRows of the act launches: 4 words, then the list [rows_cap]
+    int rows_cap = 0;
 };
 
 extern "C" int mn_iqn_set_grid(mn_iqn_ctx *c, int32_t max_workgroups) {
@@ -142,6 +147,7 @@ extern "C" int mn_iqn_destroy(mn_iqn_ctx *c) {
     c->each_buffer([](auto *p, size_t) { (void)hipFree(p); });
     (void)hipFree(c->late_status);
     (void)hipFree(c->rollout_words);
+    (void)hipFree(c->rows_buf);
     if (c->late_status_host) (void)hipHostFree((void *)c->late_status_host);
     if (moved) (void)hipSetDevice(cur);
     delete c;
@@ -158,6 +164,26 @@ extern "C" int mn_iqn_weights_changed(mn_iqn_ctx *c) {
 extern "C" int mn_iqn_set_variant(mn_iqn_ctx *c, int32_t variant) {
     if (!c || (variant != 0 && variant != 2)) return MN_ERR_INVALID;      // (1 and 3 were the 32x32 re-layouts of the two kernels: measured slower, removed in round 6)
     c->variant = variant;
+    return MN_OK;
+}
+
+extern "C" int mn_iqn_set_greedy_rows(mn_iqn_ctx *c, int32_t on) {
+    if (!c) return MN_ERR_INVALID;
+    c->greedy_rows = on != 0;
+    return MN_OK;
+}
+
+// The context's GreedyRows for a launch of `n` rows: allocated, or grown, on the first launch of that size (words zero: both count slots armed)
+static int greedy_rows_buffer(mn_iqn_ctx *c, int n, GreedyRows *out) {
+    if (n > c->rows_cap) {
+        uint32_t *buf = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&buf), (4 + (size_t)n) * sizeof(uint32_t)) != hipSuccess) return MN_ERR_ALLOC;
+        if (hipMemset(buf, 0, 4 * sizeof(uint32_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipFree(buf); return MN_ERR_HIP; }
+        (void)hipFree(c->rows_buf);      // (behind the synchronisation: no launch still reads it)
+        c->rows_buf = buf;
+        c->rows_cap = n;
+    }
+    *out = GreedyRows{reinterpret_cast<int32_t *>(c->rows_buf + 4), c->rows_buf};
     return MN_OK;
 }
 
@@ -260,13 +286,15 @@ extern "C" int mn_iqn_set_late_bound_ms(mn_iqn_ctx *c, double ms) {
 }
 
 // The form a launch of `n` rows runs in (variants, mn_iqn_set_variant: 0 = exact-f32 16x16x4 kernel, 2 = split-f16 kernel; tau modes, mn_iqn_set_tau_mode:
-// shared taus run with the environments in the MFMA columns from sp::TILED_MIN_ENVS rows, in mode 3 always, and never with quantiles)
-static const Form &form_of(const mn_iqn_ctx *c, int n, bool quantiles, bool late) {
+// shared taus run with the environments in the MFMA columns from sp::TILED_MIN_ENVS rows, in mode 3 always, and never with quantiles).  `rows`: the launch
+// writes nothing but actions and its preparation launch has settled the exploring rows (launch_act), so only the listed rows are evaluated.
+static const Form &form_of(const mn_iqn_ctx *c, int n, bool quantiles, bool late, bool rows) {
     if (c->tau_mode != 0) {
         if (!quantiles && ((c->tau_mode == 1 && n >= sp::TILED_MIN_ENVS) || c->tau_mode == 3)) return FORMS[F_TILED];
         return FORMS[quantiles ? F_SHARED_QUANT : F_SHARED];
     }
     if (c->variant != 2) return FORMS[quantiles ? F_EXACT_QUANT : F_EXACT];
+    if (rows && !quantiles) return FORMS[late ? F_SPLIT_LATE_ROWS : F_SPLIT_ROWS];
     return FORMS[quantiles ? F_SPLIT_QUANT : late ? F_SPLIT_LATE : F_SPLIT];
 }
 
@@ -307,7 +335,15 @@ static int launch_act(mn_iqn_ctx *c, const float *obs_dev, const float *taus_dev
     // split-f16 kernel has this form; per-row CVaR (adaptive policies) needs per-environment taus.
     const bool shared = c->tau_mode != 0, rng = rng_state_dev != nullptr;
     if (shared && (c->variant != 2 || cvar_row_dev)) return MN_ERR_INVALID;
-    const Form &f = form_of(c, n, quantiles_dev != nullptr, late.mask != nullptr);
+    // Only the rows that do not explore (mn_iqn_set_greedy_rows): the library's own draws, per-row taus, nothing asked for but the actions.  Q values and
+    // quantiles are read by the caller for every row, and injected uniforms (mn_iqn_act) have no preparation launch to settle them in.
+    const bool listed = c->greedy_rows && rng && !shared && c->variant == 2 && actions_dev && !qvals_dev && !quantiles_dev && eps > 0.f;
+    GreedyRows rows = {};
+    if (listed) {
+        const int rc = greedy_rows_buffer(c, n, &rows);
+        if (rc) return rc;
+    }
+    const Form &f = form_of(c, n, quantiles_dev != nullptr, late.mask != nullptr, listed);
     const bool prof = c->prof_n < c->prof_max;
     if (prof) (void)hipEventRecord(c->ev[2 * c->prof_n], s);
 
@@ -326,7 +362,8 @@ static int launch_act(mn_iqn_ctx *c, const float *obs_dev, const float *taus_dev
         const int rng_blocks = draw_blocks(c, ((long)n * (K_TAUS + 1) + 3) / 4);
         if (f.split)
             hipLaunchKernelGGL(sp::iqn_split_prep_kernel, dim3(pack_blocks + rng_blocks), dim3(256), 0, s, w, (const float *)c->consts_sp,
-                               c->packed_sp, (const uint64_t *)rng_state_dev, draws_dev, n, cvar_row_dev, cvar, pack_blocks);
+                               c->packed_sp, (const uint64_t *)rng_state_dev, draws_dev, n, cvar_row_dev, cvar, pack_blocks, eps, listed ? actions_dev : nullptr,
+                               rows);
         else
             hipLaunchKernelGGL(iqn_prep_kernel, dim3(pack_blocks + rng_blocks), dim3(256), 0, s, w, c->packed,
                                (const uint64_t *)rng_state_dev, draws_dev, n, cvar_row_dev, cvar, pack_blocks);
@@ -343,7 +380,7 @@ static int launch_act(mn_iqn_ctx *c, const float *obs_dev, const float *taus_dev
                            (const float *)c->taux, qvals_dev, explore_u_dev, eps, actions_dev, n, rng_state_dev);
     else if (f.split)
         hipLaunchKernelGGL(f.split, grid, block, f.lds_bytes(), s, obs_dev, taus_dev, (const uint32_t *)c->packed_sp, qvals_dev, explore_u_dev, eps,
-                           actions_dev, n, rng_state_dev, quantiles_dev, shared ? (const float *)c->h1_sp : nullptr, late);
+                           actions_dev, n, rng_state_dev, quantiles_dev, shared ? (const float *)c->h1_sp : nullptr, late, rows);
     else
         hipLaunchKernelGGL(f.exact, grid, block, f.lds_bytes(), s, obs_dev, taus_dev, (const float *)c->packed, qvals_dev, explore_u_dev, eps,
                            actions_dev, n, rng_state_dev, quantiles_dev);

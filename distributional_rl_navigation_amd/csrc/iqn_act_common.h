@@ -50,13 +50,36 @@ __device__ __forceinline__ float tau_draw(int e, int j, uint32_t k0, uint32_t k1
     return u01((uint32_t)((long)e * K_TAUS + j), k0, k1) * cvar;
 }
 
+// IQNAgent.act's random action of an exploring row (agent.py:199-203, !(u > eps)): one function for every kernel that writes it, so the bits cannot differ
+__device__ __forceinline__ int explore_action(float u, float eps) {
+    const int act = (int)(u / eps * (float)A_OUT);
+    return act > A_OUT - 1 ? A_OUT - 1 : act;
+}
+
+// The rows of an act call that need the network (mn_iqn_set_greedy_rows): the preparation launch, which draws every row's exploration uniform, writes the
+// action of an exploring row itself and appends every other row to `list` (any order); the act kernel then deals the list out evenly.  words[0], [1] = two
+// count slots used in turn, [2] = the slot of the call in flight (preparation -> act kernel), [3] = the slot of the next call (act kernel -> preparation):
+// the preparation launch zeroes the slot it does not count in, so the count is re-armed on the device, without a launch or a memset of its own.
+struct GreedyRows {
+    int32_t *list;        // [n]
+    uint32_t *words;      // [4]
+};
+
 // The random numbers of one act call: blocks [pack_blocks, gridDim.x) fill draws[0 .. 32 n) with tau = U[0,1) * cvar
 // (model.py:149-153; per-row cvar if cvar_row) and draws[32 n .. 33 n) with the exploration uniforms of IQNAgent.act
-// (agent.py:199).
+// (agent.py:199).  ROWS: the thread that draws row e's uniform also settles the row -- actions[e] for an exploring row, an entry of rows.list for any
+// other; a wavefront's entries are counted by ballot and appended with one atomic.
+template <bool ROWS = false>
 __device__ __forceinline__ void draw_block(const uint64_t *__restrict__ rng_state, float *__restrict__ draws, int n,
-                                           const float *__restrict__ cvar_row, float cvar, int pack_blocks) {
+                                           const float *__restrict__ cvar_row, float cvar, int pack_blocks, float eps = 0.f,
+                                           int32_t *__restrict__ actions = nullptr, const GreedyRows rows = {}) {
     uint32_t k0, k1;
     draw_keys(rng_state[0], rng_state[1], k0, k1);
+    [[maybe_unused]] uint32_t slot = 0;
+    if constexpr (ROWS) {
+        slot = rows.words[3] & 1u;
+        if ((int)blockIdx.x == pack_blocks && threadIdx.x == 0) { rows.words[slot ^ 1u] = 0u; rows.words[2] = slot; }
+    }
     const long total4 = ((long)n * (K_TAUS + 1) + 3) / 4;          // float4 groups
     const long stride = (long)((int)gridDim.x - pack_blocks) * 256;
     for (long q = (long)((int)blockIdx.x - pack_blocks) * 256 + threadIdx.x; q < total4; q += stride) {
@@ -71,5 +94,29 @@ __device__ __forceinline__ void draw_block(const uint64_t *__restrict__ rng_stat
         if (4 * q + 3 < (long)n * (K_TAUS + 1)) *reinterpret_cast<float4 *>(draws + 4 * q) = make_float4(v[0], v[1], v[2], v[3]);
         else
             for (int j = 0; j < 4 && 4 * q + j < (long)n * (K_TAUS + 1); ++j) draws[4 * q + j] = v[j];
+        if constexpr (ROWS) {      // (the lanes of a wavefront leave this loop from the top lane down: ballots count the lanes still in it)
+            const int lane = threadIdx.x & 63;
+            const long e0 = 4 * q - (long)n * K_TAUS;      // row of v[0]
+            bool keep[4];
+            int at[4], total = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool row = e0 + j >= 0 && e0 + j < n;
+                keep[j] = row && v[j] > eps;               // greedy iff u > eps (agent.py:200)
+                if (row && !keep[j]) actions[e0 + j] = explore_action(v[j], eps);
+                const unsigned long long m = __ballot(keep[j]);
+                at[j] = total + __popcll(m & ((1ull << lane) - 1ull));
+                total += __popcll(m);
+            }
+            if (total) {
+                const int leader = __builtin_ctzll(__ballot(true));
+                int base = 0;
+                if (lane == leader) base = (int)atomicAdd(rows.words + slot, (uint32_t)total);
+                base = __shfl(base, leader);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (keep[j] && base + at[j] < n) rows.list[base + at[j]] = (int32_t)(e0 + j);      // (< n: always, while the slot started at zero)
+            }
+        }
     }
 }

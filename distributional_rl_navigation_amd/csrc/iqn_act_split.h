@@ -244,16 +244,19 @@ __global__ __launch_bounds__(256) void iqn_split_pack_kernel(IqnWeights w, const
     if (i < OFF_FB) packed[i] = pack_word(w, consts, i);
 }
 
-// weight image (when stale; consts from iqn_split_consts_kernel earlier in the stream) + the call's random numbers
+// weight image (when stale; consts from iqn_split_consts_kernel earlier in the stream) + the call's random numbers; with `rows` (GreedyRows) also the
+// actions of the exploring rows and the list of the others, for the act kernel's ROWS form
 __global__ __launch_bounds__(256) void iqn_split_prep_kernel(IqnWeights w, const float *__restrict__ consts, uint32_t *__restrict__ packed,
                                                              const uint64_t *__restrict__ rng_state, float *__restrict__ draws, int n,
-                                                             const float *__restrict__ cvar_row, float cvar, int pack_blocks) {
+                                                             const float *__restrict__ cvar_row, float cvar, int pack_blocks, float eps = 0.f,
+                                                             int32_t *__restrict__ actions = nullptr, const GreedyRows rows = {}) {
     if ((int)blockIdx.x < pack_blocks) {
         const int i = blockIdx.x * blockDim.x + threadIdx.x;
         if (i < OFF_FB) packed[i] = pack_word(w, consts, i);
         return;
     }
-    draw_block(rng_state, draws, n, cvar_row, cvar, pack_blocks);
+    if (rows.words) draw_block<true>(rng_state, draws, n, cvar_row, cvar, pack_blocks, eps, actions, rows);
+    else draw_block(rng_state, draws, n, cvar_row, cvar, pack_blocks);
 }
 
 __device__ __forceinline__ f32x4 mf(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
@@ -931,6 +934,10 @@ __device__ __forceinline__ float q_quantiles(const float *__restrict__ lds, cons
 //                another stream under this kernel: mn_reset_done_async) are taken LAST by their wavefront, each after its "row is final"
 //                word (`late_flag[e] == tick`, written by the reset wave behind its write-through row) has arrived; `late_mask` = the
 //                step's done flags.  Same arithmetic, same results; a wavefront handles at most 64 rows in this form (launch_act checks).
+// ROWS = true : only the rows of `rows.list` (GreedyRows: those that do not explore, settled and listed by iqn_split_prep_kernel) are evaluated, and their
+//                argmax is the action.  List position i belongs to workgroup i % gridDim.x, wavefront (i / gridDim.x) % NW: every wavefront gets
+//                ceil(count / wavefronts) rows whatever the rows are, and a short list spreads over the CUs before it stacks up on one.  A workgroup
+//                without a position returns before it copies the image.  With LATE the two bit sets are over the wavefront's <= 64 list positions.
 struct LateRows {
     const uint8_t *mask;       // [n] != 0: the row is rewritten by the reset running beside this launch
     const uint32_t *flag;      // [n] == tick once it has been
@@ -941,14 +948,15 @@ struct LateRows {
 };
 constexpr uint64_t LATE_BOUND_TICKS = 50000000ull;      // 0.5 s of the 100 MHz counter
 
-template <bool QUANT, bool SHARED = false, int NW = WAVES, bool LATE = false>
+template <bool QUANT, bool SHARED = false, int NW = WAVES, bool LATE = false, bool ROWS = false>
 __global__ __launch_bounds__(64 * NW) void iqn_qvals_split_kernel(const float *__restrict__ obs, const float *__restrict__ taus,
                                                                  const uint32_t *__restrict__ packed, float *__restrict__ qvals,
                                                                  const float *__restrict__ explore_u, float eps,
                                                                  int32_t *__restrict__ actions, int n, uint64_t *__restrict__ rng_state,
                                                                  float *__restrict__ quantiles, const float *__restrict__ h1 = nullptr,
-                                                                 const LateRows late = {}) {
+                                                                 const LateRows late = {}, const GreedyRows rows = {}) {
     static_assert(!LATE || (!QUANT && !SHARED), "late rows: the acting form with per-environment taus");
+    static_assert(!ROWS || (!QUANT && !SHARED), "listed rows: the acting form with per-environment taus");
 #ifndef SP_LATE_PRIO
 #define SP_LATE_PRIO 0
 #endif
@@ -956,6 +964,13 @@ __global__ __launch_bounds__(64 * NW) void iqn_qvals_split_kernel(const float *_
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     if (rng_state && blockIdx.x == 0 && tid == 0) rng_state[1] += 1;   // the draws of this call were made by the prep kernel
+    [[maybe_unused]] int n_rows = 0;       // ROWS: length of the list
+    if constexpr (ROWS) {
+        const uint32_t slot = rows.words[2] & 1u, count = rows.words[slot];
+        n_rows = count < (uint32_t)n ? (int)count : n;
+        if (blockIdx.x == 0 && tid == 0) rows.words[3] = slot ^ 1u;      // the next call counts in the other slot
+        if ((int)blockIdx.x >= n_rows) return;
+    }
     // the acting form has no use for the output layer's MFMA operands (act_eval's quantiles): its feature buffers sit there, and the 4 KB
     // that frees are what lets a reset workgroup (3.1 KB of LDS) share the CU with this one
     constexpr int IMG = QUANT ? OFF_FB : OFF_W4H;
@@ -1004,21 +1019,33 @@ __global__ __launch_bounds__(64 * NW) void iqn_qvals_split_kernel(const float *_
     f16x8 cbh[2][NT], cbl[2][NT];
     CosJob cj;
     cj.hk0 = hk0;
-    const int e_first = blockIdx.x * waves_per_block + wave, e_stride = gridDim.x * waves_per_block;
+    // the wave's rows: e_first + k e_stride; ROWS: the rows at those positions of the list
+    const int e_first = ROWS ? blockIdx.x + gridDim.x * wave : blockIdx.x * waves_per_block + wave, e_stride = gridDim.x * waves_per_block;
+    [[maybe_unused]] const auto listed = [&](int pos) {      // (wave-uniform) row at list position `pos`, n behind the list's end
+        pos = __builtin_amdgcn_readfirstlane(pos);
+        const int r = pos < n_rows ? rows.list[pos] : n;
+        return (unsigned)r < (unsigned)n ? r : n;
+    };
     // LATE: the wave's rows as two bit sets (bit k = row e_first + k e_stride): final observations first, late ones last
     [[maybe_unused]] unsigned long long rows_now = 0, rows_late = 0;
     [[maybe_unused]] bool is_late = false;
+    [[maybe_unused]] int e_lane = 0;       // LATE && ROWS: lane k holds the row of bit k
+    [[maybe_unused]] const auto row_of = [&](int k) { return ROWS ? __builtin_amdgcn_readlane(e_lane, k) : e_first + k * e_stride; };
     int e0 = e_first;
     if constexpr (LATE) {
-        const int e_l = e_first + lane * e_stride;
+        int e_l = e_first + lane * e_stride;
+        if constexpr (ROWS) {
+            const int r = e_l < n_rows ? rows.list[e_l] : n;
+            e_l = e_lane = (unsigned)r < (unsigned)n ? r : n;
+        }
         const bool v = e_l < n, l = v && late.mask[v ? e_l : 0] != 0;
         const unsigned long long mv = __ballot(v), ml = __ballot(l);
         rows_now = mv & ~ml; rows_late = ml;
-        if (rows_now) { const int k = __builtin_ctzll(rows_now); rows_now &= rows_now - 1; e0 = e_first + k * e_stride; }
-        else if (rows_late) { const int k = __builtin_ctzll(rows_late); rows_late &= rows_late - 1; e0 = e_first + k * e_stride; is_late = true; }
+        if (rows_now) { const int k = __builtin_ctzll(rows_now); rows_now &= rows_now - 1; e0 = row_of(k); }
+        else if (rows_late) { const int k = __builtin_ctzll(rows_late); rows_late &= rows_late - 1; e0 = row_of(k); is_late = true; }
         else e0 = n;
         e0 = __builtin_amdgcn_readfirstlane(e0);
-    }
+    } else if constexpr (ROWS) e0 = listed(e_first);
     if (!SHARED && e0 < n) {
         float tau[NT];
 #pragma unroll
@@ -1038,23 +1065,28 @@ __global__ __launch_bounds__(64 * NW) void iqn_qvals_split_kernel(const float *_
                 cbl[kb][nt] = cat4(l[0], l[1], l[2], l[3]);
             }
     }
-    int e_follow = n;      // LATE: the row after `e` (n: none)
+    int e_follow = n;      // LATE, ROWS: the row after `e` (n: none)
     [[maybe_unused]] bool follow_late = false;
-    for (int e = e0; e < n; e = LATE ? e_follow : e + e_stride) {
+    [[maybe_unused]] int pos_ahead = e_first + e_stride, e_ahead = n;      // ROWS without LATE: list position of e_follow, and the row behind e_follow
+    if constexpr (ROWS && !LATE) e_follow = listed(pos_ahead);
+    for (int e = e0; e < n;) {
         [[maybe_unused]] unsigned long long tk[16];
 #define SP_TICK(i) do { if (SP_ABL & 64) { __builtin_amdgcn_sched_barrier(0); tk[i] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
         SP_TICK(0);
-        const float u_explore = (explore_u && eps > 0.f) ? explore_u[__builtin_amdgcn_readfirstlane(e)] : 2.0f;     // used ~10 us later
+        const float u_explore = (!ROWS && explore_u && eps > 0.f) ? explore_u[__builtin_amdgcn_readfirstlane(e)] : 2.0f;     // used ~10 us later
         [[maybe_unused]] const bool late_row = is_late;
         if constexpr (LATE) {
             e_follow = n; follow_late = false;
-            if (rows_now) { const int k = __builtin_ctzll(rows_now); rows_now &= rows_now - 1; e_follow = e_first + k * e_stride; }
-            else if (rows_late) { const int k = __builtin_ctzll(rows_late); rows_late &= rows_late - 1; e_follow = e_first + k * e_stride; follow_late = true; }
+            if (rows_now) { const int k = __builtin_ctzll(rows_now); rows_now &= rows_now - 1; e_follow = row_of(k); }
+            else if (rows_late) { const int k = __builtin_ctzll(rows_late); rows_late &= rows_late - 1; e_follow = row_of(k); follow_late = true; }
             e_follow = __builtin_amdgcn_readfirstlane(e_follow);
             is_late = follow_late;
+        } else if constexpr (ROWS) {      // requested an iteration ahead of the taus it addresses
+            pos_ahead += e_stride;
+            e_ahead = listed(pos_ahead);
         }
         if constexpr (!SHARED) {   // the next environment's taus (the last iteration re-reads its own: straight-line code); consumed from stage 5 on
-            const int e_nx = LATE ? (e_follow < n ? e_follow : e) : (e + e_stride < n ? e + e_stride : e);
+            const int e_nx = (LATE || ROWS) ? (e_follow < n ? e_follow : e) : (e + e_stride < n ? e + e_stride : e);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) cj.tau[nt] = taus[(size_t)e_nx * K_TAUS + 16 * nt + col];
         }
@@ -1175,9 +1207,9 @@ __global__ __launch_bounds__(64 * NW) void iqn_qvals_split_kernel(const float *_
 #undef SP_ARG
             if (lane == 0) {
                 int act = arg;
-                if (explore_u && eps > 0.f) {
+                if (!ROWS && explore_u && eps > 0.f) {       // (a listed row is known to be greedy)
                     const float u = u_explore;               // greedy iff u > eps (agent.py:200); requested at the top of the iteration
-                    if (!(u > eps)) { act = (int)(u / eps * (float)A_OUT); act = act > A_OUT - 1 ? A_OUT - 1 : act; }
+                    if (!(u > eps)) act = explore_action(u, eps);
                 }
                 actions[e] = act;
             }
@@ -1188,6 +1220,9 @@ __global__ __launch_bounds__(64 * NW) void iqn_qvals_split_kernel(const float *_
                    tk[1] - tk[0], tk[2] - tk[1], tk[3] - tk[2], tk[4] - tk[3], tk[5] - tk[4], tk[6] - tk[5], tk[7] - tk[6], tk[8] - tk[7], tk[9] - tk[8], tk[10] - tk[9],
                    tk[11] - tk[10], tk[12] - tk[11], tk[12] - tk[0]);
 #undef SP_TICK
+        if constexpr (LATE) e = e_follow;
+        else if constexpr (ROWS) { e = e_follow; e_follow = e_ahead; }
+        else e += e_stride;
     }
 }
 

@@ -124,6 +124,7 @@ class IQNAgent(ReferenceLoopMixin):
         self._act_rng = None                         # the act path's own counter-based tau / exploration draws (fused_act.ActRng)
         self.use_library_rng = True                  # False: taus / exploration uniforms from torch.rand on self.gen
         self.shared_taus = False                     # opt-in: one set of 32 taus per act LAUNCH instead of per row (fused_act(shared_taus=True))
+        self.act_greedy_rows_only = True             # act_batch: the network runs only on the rows that do not explore (fused_act(greedy_rows=...)); False: on every row, same actions
         self.use_fused_graph = False                 # opt-in: the fused gradient steps of one training event as one captured hipGraph (train_steps_from_memory)
         self.reset_under_act = False                 # vec_step: the episode resets of a vector step run on the env's own stream UNDER the next step's act kernel (which takes
                                                      # the finished envs' rows last) instead of in front of it: same results, ~28 us off every vector step's critical path.  The
@@ -244,11 +245,13 @@ class IQNAgent(ReferenceLoopMixin):
         if states.is_cuda and self.use_fused_act:
             from .fused_act import fused_act
             if not self.use_library_rng:
-                return fused_act(self.qnetwork_local, states.contiguous(), eps, cvar, generator=self.gen, shared_taus=self.shared_taus, late_env=late_env)
+                return fused_act(self.qnetwork_local, states.contiguous(), eps, cvar, generator=self.gen, shared_taus=self.shared_taus, late_env=late_env,
+                                 greedy_rows=self.act_greedy_rows_only)
             if self._act_rng is None:
                 from .fused_act import ActRng
                 self._act_rng = ActRng(self.gen.initial_seed(), states.device)
-            return fused_act(self.qnetwork_local, states.contiguous(), eps, cvar, rng=self._act_rng, shared_taus=self.shared_taus, late_env=late_env)
+            return fused_act(self.qnetwork_local, states.contiguous(), eps, cvar, rng=self._act_rng, shared_taus=self.shared_taus, late_env=late_env,
+                             greedy_rows=self.act_greedy_rows_only)
         if late_env is not None:
             late_env.join_reset()
         q = self.qvals_batch(states, cvar)

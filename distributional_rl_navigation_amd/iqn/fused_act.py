@@ -44,6 +44,7 @@ class ActContext:
         self._sig = None
         self.variant = self.DEFAULT_VARIANT
         self.tau_mode = 0
+        self.greedy_rows = True
         self._ptrs = (C.c_void_p * 14)()
         self._fin = weakref.finalize(self, _capi.lib().mn_iqn_destroy, h)
 
@@ -78,6 +79,17 @@ class ActContext:
         if rc:
             raise _capi.MarineNavHipError(f"mn_iqn_set_variant failed ({rc})")
         self.variant = int(variant)
+
+    def set_greedy_rows(self, on):
+        """True (default): an act call that returns nothing but actions runs the network only on the rows that do not explore -- the preparation
+        launch writes the exploring rows' actions and lists the others (C-ABI mn_iqn_set_greedy_rows).  False: every row is evaluated.  Same
+        actions, draws and call counter either way."""
+        if bool(on) == self.greedy_rows:
+            return
+        rc = _capi.lib().mn_iqn_set_greedy_rows(self.h, int(bool(on)))
+        if rc:
+            raise _capi.MarineNavHipError(f"mn_iqn_set_greedy_rows failed ({rc})")
+        self.greedy_rows = bool(on)
 
     def set_tau_mode(self, mode):
         """0 = every observation row its own 32 taus (default, the reference's per-call draw); 1 = one set of 32 taus per launch:
@@ -231,7 +243,7 @@ def set_late_bound_ms(net, ms):
 
 @torch.no_grad()
 def fused_act(net, states, eps=0.0, cvar=1.0, taus=None, generator=None, want_qvals=False, rng=None, want_quantiles=False,
-              shared_taus=False, late_env=None):
+              shared_taus=False, late_env=None, greedy_rows=None):
     """IQNAgent.act for states [n, 26] on the GPU in ONE kernel: encoders, cosine embedding, Hadamard
     product, hidden layers, mean over K = 32 taus, argmax and epsilon-greedy.
     Returns actions [n] int32; with want_qvals (actions, Q [n, 9]); with want_quantiles -- the batched
@@ -240,7 +252,9 @@ def fused_act(net, states, eps=0.0, cvar=1.0, taus=None, generator=None, want_qv
     in its own preparation launch (no torch.rand kernels), and without it they come from torch.rand on `generator`.
     `shared_taus` (opt-in): ONE set of 32 taus (x the scalar `cvar`) for all n rows of the call instead of 32 per row -- layer 1 of
     the network becomes a constant of the launch (mn_iqn_set_tau_mode; 216 instead of 372 matrix instructions per row).  Injected
-    `taus` are then [32]; a per-row `cvar` tensor (adaptive policies) needs per-row taus and keeps the default mode."""
+    `taus` are then [32]; a per-row `cvar` tensor (adaptive policies) needs per-row taus and keeps the default mode.
+    `greedy_rows` (None: as the network's context is set, on by default): with `rng`, `eps` > 0 and nothing but actions asked for, only the rows
+    that do not explore go through the network (ActContext.set_greedy_rows); False evaluates every row.  Same results."""
     assert states.is_cuda and states.dtype == torch.float32 and states.is_contiguous()
     n = states.shape[0]
     dev = states.device
@@ -253,6 +267,8 @@ def fused_act(net, states, eps=0.0, cvar=1.0, taus=None, generator=None, want_qv
     q = torch.empty(n, net.action_size, dtype=torch.float32, device=dev) if want_qvals else None
     quant = torch.empty(n, net.K, net.action_size, dtype=torch.float32, device=dev) if want_quantiles else None
     stream = _capi.stream_ptr(dev)
+    if greedy_rows is not None:
+        ctx.set_greedy_rows(greedy_rows)
     joined_after = _arm_late_rows(ctx, late_env, n, want_quantiles)      # (after set_tau_mode: the form of THIS launch decides)
     if taus is None and rng is not None:
         cv_row = cvar.to(device=dev, dtype=torch.float32).contiguous() if torch.is_tensor(cvar) else None

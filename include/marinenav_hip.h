@@ -333,6 +333,14 @@ int mn_iqn_weights_changed(mn_iqn_ctx *c);
  * Same network in both; they differ by float32 rounding only.  Anything else is MN_ERR_INVALID (1 and 3 were the 32x32 re-layouts of the two kernels,
  * measured 2.6 % / 4 % slower on MI355X in rounds 2 / 4 and removed in round 6). */
 int mn_iqn_set_variant(mn_iqn_ctx *c, int32_t variant);
+/* Whether an act launch that returns nothing but actions evaluates only the rows that do not explore (on != 0: the default).  For an exploring row
+ * (u <= eps, agent.py:199-203) the action depends on neither Q nor the observation, so the preparation launch of mn_iqn_act_rng -- which draws every row's
+ * exploration uniform -- writes that action itself and lists the other rows, and the act kernel deals the list out evenly over its wavefronts: the launch
+ * shrinks with the share of exploring rows (at eps ~ 1 to almost nothing, at eps = 0.05 by 1 row in 32 per wavefront).  Applies to mn_iqn_act_rng with variant 2,
+ * per-row taus, actions_dev set, qvals_dev == quantiles_dev == NULL and eps > 0, with or without late rows; an exploring late row is never waited for.  Every
+ * other call evaluates every row as before.  Actions, draws and the call counter are bit for bit those of `on` == 0; the list lives in the context
+ * (int32 [n], allocated on the first launch of a size; that launch synchronises the device once). */
+int mn_iqn_set_greedy_rows(mn_iqn_ctx *c, int32_t on);
 /* How an act launch's quantile fractions are drawn (round 4).
  *   0 (default): every observation row gets its own 32 taus -- what a batch of independent calls of the reference's batch-1
  *      IQNAgent.act (agent.py:186-205 -> model.py:149-153) would draw.  mn_iqn_act takes taus [n][32]; mn_iqn_act_rng writes
