@@ -32,6 +32,15 @@ class MnParams(C.Structure):
     ]
 
 
+class MnDqnLearner(C.Structure):
+    """mn_dqn_learner: the device pointers of one DQN learner of a group (mn_dqn_group_create)."""
+    _fields_ = [(n, C.c_void_p) for n in ("ring_states", "ring_next_states", "ring_actions", "ring_rewards", "ring_dones", "rng_state", "params_local",
+                                          "params_target", "grad", "exp_avg", "exp_avg_sq", "step")]
+
+
+DQN_MAX_LEARNERS = 64      # MN_DQN_MAX_LEARNERS
+
+
 class MarineNavHipError(RuntimeError):
     pass
 
@@ -121,6 +130,10 @@ SIGNATURES = [
     ("mn_dqn_train_steps_workspace_floats", C.c_int64, [_i32, _i32]),
     ("mn_dqn_train_steps", C.c_int, [_vp] * 5 + [_i64] + [_vp] * 11 + [_i32, _i32, C.c_float] + [_dbl] * 5 + [_vp]),
     ("mn_dqn_train_steps_parts", C.c_int, [_vp] * 5 + [_i64] + [_vp] * 11 + [_i32, _i32, C.c_float] + [_dbl] * 5 + [_i32, _vp]),
+    ("mn_dqn_group_create", C.c_int, [C.POINTER(MnDqnLearner), _i32, C.POINTER(_vp)]),
+    ("mn_dqn_group_destroy", C.c_int, [_vp]),
+    ("mn_dqn_group_train_step", C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, C.c_float] + [_dbl] * 5 + [_vp]),
+    ("mn_dqn_group_train_steps", C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, C.c_float] + [_dbl] * 5 + [_vp]),
     ("mn_xchg_create", C.c_int, [_i32, _i32, C.POINTER(_vp)]),
     ("mn_xchg_export", C.c_int, [_vp, _vp]),
     ("mn_xchg_import", C.c_int, [_vp, _i32, _vp]),

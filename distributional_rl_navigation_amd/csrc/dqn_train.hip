@@ -26,6 +26,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <new>
+
 #include "marinenav_hip.h"
 #include "mn_train_shared.h"
 
@@ -178,8 +180,10 @@ struct DqnTrainArgs {
     double lr, b1, b2, eps, max_norm;
 };
 
-__global__ __launch_bounds__(THREADS) void dqn_train_step_kernel(const DqnTrainArgs a) {
-    __shared__ __attribute__((aligned(16))) float S[S_TOTAL];
+// One workgroup of one learner's step: workgroup blockIdx.x of gridDim.x.  The body of dqn_train_step_kernel AND of dqn_train_step_groups_kernel (below,
+// where blockIdx.y picks the learner whose buffers `a` names): one instruction sequence per output element, whichever kernel it is inlined into.
+__device__ __forceinline__ void dqn_train_step_body(const DqnTrainArgs &a) {
+    __shared__ __attribute__((aligned(16))) float S[S_TOTAL];      // (the LDS of whichever kernel inlines the body)
     __shared__ int s_act[TILE];
     __shared__ float s_red[WAVES];
     __shared__ float s_misc[4];      // loss terms' sum, clip coefficient, Adam step size, sqrt of the second bias correction
@@ -331,6 +335,10 @@ __global__ __launch_bounds__(THREADS) void dqn_train_step_kernel(const DqnTrainA
         }
 }
 
+__global__ __launch_bounds__(THREADS) void dqn_train_step_kernel(const DqnTrainArgs a) {
+    dqn_train_step_body(a);
+}
+
 
 // ---- many steps per call (mn_dqn_train_steps) ----------------------------------------------------------------------------------------------------------
 // n_steps consecutive steps of the kernel above from one call, bit for bit: the same tiles, the same instruction sequence per output element and the
@@ -377,7 +385,8 @@ __device__ __forceinline__ void chain_handoff() {
 
 // TD targets of all n_steps x batch samples, 16 consecutive samples (k, b) = (j / batch, j % batch) per tile -- a sample's Q row depends on its own MFMA row
 // only, so the regrouping does not change a bit -- and the double-precision Adam scalars of every step, off the chain.
-__global__ __launch_bounds__(THREADS) void dqn_multi_target_kernel(const DqnStepsArgs a) {
+// (The body of dqn_multi_target_kernel and of its grouped form: tiles over blockIdx.x of gridDim.x.)
+__device__ __forceinline__ void dqn_multi_target_body(const DqnStepsArgs &a) {
     __shared__ __attribute__((aligned(16))) float S[S_TOTAL];
     const int total = a.n_steps * a.batch;
     const uint64_t seed = a.rng_state ? a.rng_state[0] : 0, counter = a.rng_state ? a.rng_state[1] : 0;
@@ -415,6 +424,10 @@ __global__ __launch_bounds__(THREADS) void dqn_multi_target_kernel(const DqnStep
     }
 }
 
+__global__ __launch_bounds__(THREADS) void dqn_multi_target_kernel(const DqnStepsArgs a) {
+    dqn_multi_target_body(a);
+}
+
 // The chain: ONE workgroup of ceil(batch / 16) groups of 512 threads, group g carrying batch slots [16 g, 16 g + 16) through every step.
 struct ChainGroup {      // a thread's view of its group; asked for anew in every phase of a step, so that nothing of it lives across the phases
     int tid, lt, grp, slot0;
@@ -434,7 +447,8 @@ __device__ __forceinline__ ChainGroup chain_group(float *S_all, int *s_act_all, 
     return g;
 }
 
-__global__ __launch_bounds__(CHAIN_THREADS) void dqn_multi_chain_kernel(const DqnStepsArgs a) {
+// (The body of dqn_multi_chain_kernel and of its grouped form, where one workgroup per learner runs it on that learner's buffers.)
+__device__ __forceinline__ void dqn_multi_chain_body(const DqnStepsArgs &a) {
     __shared__ __attribute__((aligned(16))) float S_all[CHAIN_TILES * S_TOTAL];
     __shared__ int s_act_all[CHAIN_TILES * TILE];
     __shared__ float s_red[WAVES];
@@ -572,7 +586,192 @@ __global__ __launch_bounds__(CHAIN_THREADS) void dqn_multi_chain_kernel(const Dq
     }
 }
 
+__global__ __launch_bounds__(CHAIN_THREADS) void dqn_multi_chain_kernel(const DqnStepsArgs a) {
+    dqn_multi_chain_body(a);
+}
+
+
+// ---- many learners per launch (mn_dqn_group_*) -----------------------------------------------------------------------------------------------------------
+// G independent learners with common hyper-parameters in one launch: the learner is a grid dimension.  Workgroup (w, g) of dqn_train_step_groups_kernel IS
+// workgroup w of learner g's dqn_train_step_kernel -- the same body on g's own ring, networks, moments, counters and its own slice of the workspace (rows,
+// partial losses, ticket) -- and likewise for the two kernels of the multi-step call.  No learner reads what another writes, so each is bit for bit what it
+// is when launched alone.  The learners' pointers come from a device-resident table: the row address is wave-uniform, the loads are scalar and the pointers
+// sit where the kernel arguments of the single forms sit, in scalar registers.
+struct DqnLearnerRow {      // mn_dqn_learner with the kernels' names
+    const float *states, *next_states;
+    const int64_t *actions;
+    const float *rewards, *dones;
+    uint64_t *rng_state;
+    float *params;
+    const float *target;
+    float *grad, *m, *v;
+    int32_t *step;
+};
+
+struct DqnGroupArgs {      // what a call has in common for the group; idx / idx_out: [G][n_steps][batch] or NULL; loss: [G][n_steps]; ws: [G][ws_stride]
+    const DqnLearnerRow *table;
+    int64_t ring_size;
+    const int64_t *idx;
+    int64_t *idx_out;
+    float *ws;
+    int64_t ws_stride;
+    float *loss;
+    int batch;
+    float gamma;
+    double lr, b1, b2, eps, max_norm;
+    int n_steps;      // 1 for the single step
+    float w1, b2f, w2, eps_f, batch_f, inv_batch;      // as DqnStepsArgs
+};
+
+// learner g's arguments of the single form
+__device__ __forceinline__ void learner_args(DqnTrainArgs &a, const DqnGroupArgs &ga, int g) {
+    const DqnLearnerRow r = ga.table[g];
+    const int64_t rows = (int64_t)g * ga.n_steps * ga.batch;
+    a.states = r.states; a.next_states = r.next_states; a.actions = r.actions; a.rewards = r.rewards; a.dones = r.dones;
+    a.ring_size = ga.ring_size;
+    a.rng_state = ga.idx ? nullptr : r.rng_state;      // given rows: the draw state is left alone, as in the single calls
+    a.idx = ga.idx ? ga.idx + rows : nullptr;
+    a.idx_out = ga.idx_out ? ga.idx_out + rows : nullptr;
+    a.params = r.params; a.target = r.target; a.grad = r.grad; a.m = r.m; a.v = r.v; a.step = r.step;
+    a.ws = ga.ws + (int64_t)g * ga.ws_stride;
+    a.loss = ga.loss + (int64_t)g * ga.n_steps;
+    a.batch = ga.batch; a.gamma = ga.gamma; a.lr = ga.lr; a.b1 = ga.b1; a.b2 = ga.b2; a.eps = ga.eps; a.max_norm = ga.max_norm;
+}
+
+__device__ __forceinline__ void learner_steps_args(DqnStepsArgs &a, const DqnGroupArgs &ga, int g) {
+    learner_args(a, ga, g);
+    a.n_steps = ga.n_steps;
+    a.w1 = ga.w1; a.b2f = ga.b2f; a.w2 = ga.w2; a.eps_f = ga.eps_f; a.batch_f = ga.batch_f; a.inv_batch = ga.inv_batch;
+}
+
+__global__ __launch_bounds__(THREADS) void dqn_train_step_groups_kernel(const DqnGroupArgs ga) {      // grid (ceil(batch / 16), G)
+    DqnTrainArgs a;
+    learner_args(a, ga, blockIdx.y);
+    dqn_train_step_body(a);
+}
+
+__global__ __launch_bounds__(THREADS) void dqn_multi_target_groups_kernel(const DqnGroupArgs ga) {      // grid (tiles, G)
+    DqnStepsArgs a;
+    learner_steps_args(a, ga, blockIdx.y);
+    dqn_multi_target_body(a);
+}
+
+__global__ __launch_bounds__(CHAIN_THREADS) void dqn_multi_chain_groups_kernel(const DqnGroupArgs ga) {      // grid (G): workgroup g is learner g's whole chain
+    DqnStepsArgs a;
+    learner_steps_args(a, ga, blockIdx.x);
+    dqn_multi_chain_body(a);
+}
+
+__host__ constexpr int64_t round4(int64_t n) { return (n + 3) & ~(int64_t)3; }
+
+// [lo, hi) byte extents overlap
+bool overlap(const void *p, size_t np, const void *q, size_t nq) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + nq && b < a + np;
+}
+
 }  // namespace
+
+struct mn_dqn_group {
+    DqnLearnerRow *table_dev;
+    int n;
+    bool all_draw;      // every learner has a draw state
+};
+
+extern "C" int mn_dqn_group_create(const mn_dqn_learner *learners_host, int32_t n_learners, mn_dqn_group **out) {
+    if (!out) return MN_ERR_INVALID;
+    *out = nullptr;
+    if (!learners_host || n_learners < 1 || n_learners > MN_DQN_MAX_LEARNERS) return MN_ERR_INVALID;
+    DqnLearnerRow rows[MN_DQN_MAX_LEARNERS];
+    struct Extent { const void *p; size_t n; int owner; };
+    Extent written[6 * MN_DQN_MAX_LEARNERS], targets[MN_DQN_MAX_LEARNERS];
+    int n_written = 0;
+    bool all_draw = true;
+    constexpr size_t VEC = (size_t)P_TOTAL * sizeof(float);
+    for (int g = 0; g < n_learners; ++g) {
+        const mn_dqn_learner &l = learners_host[g];
+        if (!l.ring_states || !l.ring_next_states || !l.ring_actions || !l.ring_rewards || !l.ring_dones || !l.params_local || !l.params_target || !l.grad ||
+            !l.exp_avg || !l.exp_avg_sq || !l.step)
+            return MN_ERR_INVALID;
+        rows[g] = DqnLearnerRow{l.ring_states, l.ring_next_states, l.ring_actions, l.ring_rewards, l.ring_dones, l.rng_state, l.params_local, l.params_target,
+                                l.grad, l.exp_avg, l.exp_avg_sq, l.step};
+        written[n_written++] = Extent{l.params_local, VEC, g};
+        written[n_written++] = Extent{l.grad, VEC, g};
+        written[n_written++] = Extent{l.exp_avg, VEC, g};
+        written[n_written++] = Extent{l.exp_avg_sq, VEC, g};
+        written[n_written++] = Extent{l.step, sizeof(int32_t), g};
+        if (l.rng_state) written[n_written++] = Extent{l.rng_state, 2 * sizeof(uint64_t), g};
+        else all_draw = false;
+        targets[g] = Extent{l.params_target, VEC, g};
+    }
+    // learners that alias would race silently: nothing one learner writes may overlap what another writes, or the target network another reads
+    for (int i = 0; i < n_written; ++i) {
+        for (int j = i + 1; j < n_written; ++j)
+            if (written[i].owner != written[j].owner && overlap(written[i].p, written[i].n, written[j].p, written[j].n)) return MN_ERR_INVALID;
+        for (int g = 0; g < n_learners; ++g)
+            if (written[i].owner != g && overlap(written[i].p, written[i].n, targets[g].p, targets[g].n)) return MN_ERR_INVALID;
+    }
+    mn_dqn_group *grp = new (std::nothrow) mn_dqn_group{nullptr, n_learners, all_draw};
+    if (!grp) return MN_ERR_HIP;
+    if (hipMalloc(&grp->table_dev, sizeof(DqnLearnerRow) * n_learners) != hipSuccess ||
+        hipMemcpy(grp->table_dev, rows, sizeof(DqnLearnerRow) * n_learners, hipMemcpyHostToDevice) != hipSuccess) {
+        if (grp->table_dev) (void)hipFree(grp->table_dev);
+        delete grp;
+        return MN_ERR_HIP;
+    }
+    *out = grp;
+    return MN_OK;
+}
+
+extern "C" int mn_dqn_group_destroy(mn_dqn_group *g) {
+    if (!g) return MN_ERR_INVALID;
+    const hipError_t e = hipFree(g->table_dev);
+    delete g;
+    return e == hipSuccess ? MN_OK : MN_ERR_HIP;
+}
+
+namespace {
+
+// the checks and the kernel arguments the two grouped calls share (n_steps 1: the single step); the caller sets ws_stride
+int group_args(DqnGroupArgs &ga, const mn_dqn_group *g, int64_t ring_size, const int64_t *idx_dev, int64_t *idx_out, float *workspace, float *losses_out,
+               int32_t batch, int32_t max_batch, int32_t n_steps, float gamma, double lr, double beta1, double beta2, double eps, double max_norm) {
+    if (!g || !workspace || !losses_out) return MN_ERR_INVALID;
+    if (batch <= 0 || batch > max_batch || n_steps < 1 || n_steps > MAX_STEPS) return MN_ERR_INVALID;
+    if (ring_size < batch || ring_size > 0x7fffffff) return MN_ERR_INVALID;
+    if (!idx_dev && !g->all_draw) return MN_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(workspace) % 16) return MN_ERR_INVALID;
+    ga.table = g->table_dev; ga.ring_size = ring_size; ga.idx = idx_dev; ga.idx_out = idx_out; ga.ws = workspace; ga.loss = losses_out;
+    ga.batch = batch; ga.gamma = gamma; ga.lr = lr; ga.b1 = beta1; ga.b2 = beta2; ga.eps = eps; ga.max_norm = max_norm; ga.n_steps = n_steps;
+    ga.w1 = (float)(1.0 - beta1); ga.b2f = (float)beta2; ga.w2 = (float)(1.0 - beta2); ga.eps_f = (float)eps;
+    ga.batch_f = (float)batch; ga.inv_batch = 1.f / (float)batch;
+    return MN_OK;
+}
+
+}  // namespace
+
+extern "C" int mn_dqn_group_train_step(mn_dqn_group *g, int64_t ring_size, const int64_t *idx_dev, int64_t *idx_out, float *workspace, float *losses_out,
+                                       int32_t batch, float gamma, double lr, double beta1, double beta2, double eps, double max_norm, void *stream) {
+    DqnGroupArgs ga;
+    const int rc = group_args(ga, g, ring_size, idx_dev, idx_out, workspace, losses_out, batch, MAX_BATCH_DQN, 1, gamma, lr, beta1, beta2, eps, max_norm);
+    if (rc != MN_OK) return rc;
+    const int n_part = (batch + TILE - 1) / TILE;
+    ga.ws_stride = round4(ws_total(n_part));
+    hipLaunchKernelGGL(dqn_train_step_groups_kernel, dim3(n_part, g->n), dim3(THREADS), 0, (hipStream_t)stream, ga);
+    return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
+}
+
+extern "C" int mn_dqn_group_train_steps(mn_dqn_group *g, int64_t ring_size, const int64_t *idx_dev, int64_t *idx_out, float *workspace, float *losses_out,
+                                        int32_t batch, int32_t n_steps, float gamma, double lr, double beta1, double beta2, double eps, double max_norm,
+                                        void *stream) {
+    DqnGroupArgs ga;
+    const int rc = group_args(ga, g, ring_size, idx_dev, idx_out, workspace, losses_out, batch, CHAIN_BATCH, n_steps, gamma, lr, beta1, beta2, eps, max_norm);
+    if (rc != MN_OK) return rc;
+    ga.ws_stride = round4(ms_total(n_steps));
+    const int tiles = (n_steps * batch + TILE - 1) / TILE, n_part = (batch + TILE - 1) / TILE;
+    hipLaunchKernelGGL(dqn_multi_target_groups_kernel, dim3(tiles < 1024 ? tiles : 1024, g->n), dim3(THREADS), 0, (hipStream_t)stream, ga);
+    hipLaunchKernelGGL(dqn_multi_chain_groups_kernel, dim3(g->n), dim3(n_part * THREADS), 0, (hipStream_t)stream, ga);
+    return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
+}
 
 extern "C" int64_t mn_dqn_train_workspace_floats(int32_t batch) {
     if (batch <= 0 || batch > MAX_BATCH_DQN) return -1;

@@ -3,10 +3,11 @@ path, with the interface of train_iqn.
 
     python -m distributional_rl_navigation_amd.train_dqn -C config_DQN.json [--n-envs 4096] [--batch 256] [--replay N]
         [--grad-steps G] [--total-grad-steps N] [--n-evals K] [--torch-train] [--eval-one-launch] [--eval-deferred] [--dry-run]
-        [--env-budget reference] [--episode-log [full]] [--train-steps-per-call {auto,1,K,multi}]
+        [--env-budget reference] [--episode-log [full]] [--train-steps-per-call {auto,1,K,multi}] [--together]
 
 Same JSON schema as train_iqn (agent, seed (list -> grid), total_timesteps, eval_freq, save_dir); the trials run one after another
-on one device.  Cadence: `train_iqn.plan_cadence` with the reference DQN's values (one batch-32 gradient step per env step, target
+on one device, or -- `--together` -- the seeds of a config in lockstep with ONE launch per gradient step for all of them (`run_trials_together`,
+dqn/group_train.py): the same per-seed files.  Cadence: `train_iqn.plan_cadence` with the reference DQN's values (one batch-32 gradient step per env step, target
 copy every 10 000 env steps) -- the reference's learner budget in batches of `--batch`, every run fraction rescaled.  Learning starts
 after ceil(10 000 / n_envs) vector steps (sb3's learning_starts), exploration falls linearly from 1.0 to 0.05 over the first 10 % of the
 planned run (exploration_fraction), the target network is hard-copied every `target_sync_grad_steps` gradient steps, the curriculum
@@ -131,6 +132,132 @@ def write_evaluations(exp_dir, log):
              actions=actions)
 
 
+class TrialRun:
+    """One trial of the config grid, set up and ready to be driven vector step by vector step: what `run_trial` and `run_trials_together` share.  A vector
+    step of a trial is `collect(it)` (act, env step, episode log, `on_step`, replay append, resets), then the gradient steps behind it (`trains_after(it)`:
+    the caller runs them, alone or grouped with other trials', and counts them in `grad_steps_done`), then `evaluate_points(it)`; `finish()` closes the run."""
+
+    def __init__(self, device, params, n_envs, batch=None, replay=None, grad_steps=None, total_grad_steps=None, n_evals=None, torch_train=False,
+                 verbose=True, eval_one_launch=False, eval_deferred=False, eval_config=None, max_eval_steps=1000, env_budget="learner",
+                 reference=None, episode_log=None, on_step=None):
+        from .dqn.agent import DQNAgent
+        from .marinenav_env.vec_env import VecMarineNavEnv
+        self.params, self.verbose, self.on_step, self.eval_one_launch, self.max_eval_steps = params, verbose, on_step, eval_one_launch, max_eval_steps
+        self.exp_dir = exp_dir = os.path.join(params["save_dir"], "training_" + params["training_time"], "seed_" + str(params["seed"]))
+        ref_mode = env_budget == "reference"
+        n_envs, batch, replay = resolve_budget_args(env_budget, n_envs, batch, replay)
+        self.n_envs, self.batch = n_envs, batch
+        self.plan = plan = make_plan(params, n_envs, batch, grad_steps, total_grad_steps, n_evals, budget=env_budget, reference=reference)
+        if ref_mode:
+            if replay is not None and replay != plan["replay"]:
+                raise ValueError(f"env_budget='reference' keeps the reference's replay ring ({plan['replay']} rows); {replay} contradicts it")
+            replay = plan["replay"]
+            eval_deferred = eval_deferred or True      # (300 evaluation points: each only keeps the policy of the moment)
+        self.eval_points = plan_eval_points(plan, n_envs) if ref_mode else None
+        os.makedirs(exp_dir, exist_ok=True)
+        with open(os.path.join(exp_dir, "trial_config.json"), "w+") as f:
+            json.dump(dict(params, batched=dict(plan, n_envs=n_envs, world=1, batch=batch, replay=replay)), f)
+        with open(os.path.join(exp_dir, "training_schedule.json"), "w+") as f:
+            json.dump(TRAINING_SCHEDULE, f)
+        if verbose:
+            print(f"[train_dqn] seed {params['seed']}: {plan['vector_steps']} vector steps x {n_envs} envs; {plan['total_grad_steps']} grad steps of "
+                  f"batch {batch} (reference: {plan['reference_grad_steps']} of 32); target copy every {plan['target_sync_grad_steps']} grad steps; "
+                  f"evaluation every {plan['eval_every_vector_steps']} vector steps", flush=True)
+
+        self.train_env = VecMarineNavEnv(n_envs, seed=params["seed"], schedule=TRAINING_SCHEDULE, timestep_scale=plan["timestep_scale"], device=device,
+                                         precision="f64")
+        if eval_config is None:
+            eval_config = create_eval_configs(device)
+        self.eval_config = eval_config
+        self.eval_env = VecMarineNavEnv(len(eval_config), device=device, precision="f64")
+        self.agent = agent = DQNAgent(26, 9, buffer_size=replay, batch_size=batch, learning_starts=0, device=device, seed=params["seed"] + 100,
+                                      fused_train=not torch_train)
+        self.report_scale = params["total_timesteps"] / (plan["vector_steps"] * n_envs)      # evaluations.npz counts reference-scaled env steps
+        self.log = dict(timesteps=[], rewards=[], times=[], energies=[], successes=[], actions=[])
+        self.best = -np.inf
+        self.t0 = t0 = time.time()
+        self.deferred = None
+        if eval_deferred:
+            from .dqn.deferred_eval import DeferredEvaluations, can_defer
+            if can_defer(agent):
+                self.deferred = DeferredEvaluations(agent, eval_config, exp_dir, **dict(dict(max_steps=max_eval_steps, verbose=verbose, label=f"seed {params['seed']} ",
+                                                                                             n_evals=plan["n_evals"], t0=t0),
+                                                                                        **(eval_deferred if isinstance(eval_deferred, dict) else {})))
+            else:
+                print("[train_dqn] eval_deferred: the policy does not act through the fused kernel here (CPU or another net_arch); evaluations stay inline", flush=True)
+        self.ep_log = make_episode_log(episode_log, env_budget, n_envs, plan["eval_every_vector_steps"], self.train_env.discount, device)
+        self.n_points = 0
+        self.obs = self.train_env.reset()
+        self.grad_steps_done = 0
+
+    def collect(self, it):
+        """Act, step the envs, log, append the transitions to the replay ring, reset the finished envs."""
+        agent, train_env, obs = self.agent, self.train_env, self.obs
+        eps = exploration_rate(it, self.plan)
+        a = agent.act_batch(obs, eps)
+        nxt, reward, done, info = train_env.step(a)
+        if self.ep_log is not None:
+            self.ep_log.step(reward, done, info, it, eps)
+        if self.on_step is not None:
+            self.on_step(it, dict(last=dict(reward=reward, done=done, info=info, eps=eps)))
+        agent.memory.add_vector_step(obs, a, reward, nxt, done)
+        self.obs = train_env.reset_done()
+        agent.num_timesteps += self.n_envs
+
+    def trains_after(self, it):
+        """Whether gradient steps follow vector step `it` (behind `collect(it)`): plan["grad_steps_per_vector_step"] of them, cut at the target copies that
+        fall every plan["target_sync_grad_steps"]."""
+        return it + 1 >= self.plan["learning_starts_vector_steps"] and len(self.agent.memory) >= self.batch
+
+    def evaluate_points(self, it):
+        """The evaluation points (inline or deferred) and the episode-log rows behind vector step `it` and its gradient steps."""
+        plan, params, agent, n_envs, ep_log, log, exp_dir = self.plan, self.params, self.agent, self.n_envs, self.ep_log, self.log, self.exp_dir
+        if self.eval_points is not None:
+            points = self.eval_points.get(it, ())
+        elif ((it + 1) % plan["eval_every_vector_steps"] == 0 or it + 1 == plan["vector_steps"]) and self.n_points < plan["n_evals"]:
+            points = (int(round((it + 1) * n_envs * self.report_scale)),)
+        else:
+            points = ()
+        if ep_log is not None:
+            if len(points):      # a summary row per evaluation interval, the evaluation's timestep on it
+                ep_log.drain(points[-1])
+            elif ep_log.due():
+                ep_log.drain(int(round((it + 1) * n_envs * self.report_scale)), row=False)
+        for timestep in points:
+            self.n_points += 1
+            if self.deferred is not None:      # keep the policy of this moment; its episodes run with the other pending points'
+                self.deferred.snapshot(timestep)
+                continue
+            ev = evaluate(agent, self.eval_env, self.eval_config, max_steps=self.max_eval_steps, one_launch=self.eval_one_launch)
+            log["timesteps"].append(timestep)
+            for k in ("rewards", "times", "energies", "successes", "actions"):
+                log[k].append(ev[k])
+            write_evaluations(exp_dir, log)
+            save_zip(agent, os.path.join(exp_dir, "latest_model.zip"))
+            mean_r = float(np.mean(ev["rewards"]))
+            if mean_r > self.best:
+                self.best = mean_r
+                save_zip(agent, os.path.join(exp_dir, "best_model.zip"))
+            if self.verbose:
+                print(f"[train_dqn] seed {params['seed']} eval {len(log['timesteps'])}/{plan['n_evals']} at {log['timesteps'][-1]} steps: "
+                      f"{int(np.sum(ev['successes']))}/{len(self.eval_config)} successes, mean return {mean_r:.2f} ({time.time() - self.t0:.1f} s)", flush=True)
+
+    def finish(self):
+        import torch
+        if self.deferred is not None:
+            self.deferred.flush()
+            self.deferred.close()
+        if self.ep_log is not None:
+            if self.ep_log.row_open:      # (what ended behind the last evaluation point)
+                self.ep_log.drain(int(round(self.plan["vector_steps"] * self.n_envs * self.report_scale)))
+            self.ep_log.close()
+            self.ep_log.save(self.exp_dir)
+        torch.cuda.synchronize()
+        self.train_env.close()
+        self.eval_env.close()
+        return self.exp_dir
+
+
 def run_trial(device, params, n_envs, batch=None, replay=None, grad_steps=None, total_grad_steps=None, n_evals=None, torch_train=False,
               verbose=True, eval_one_launch=False, eval_deferred=False, eval_config=None, max_eval_steps=1000, return_agent=False, env_budget="learner",
               reference=None, episode_log=None, on_step=None, train_steps_per_call="auto"):
@@ -146,119 +273,88 @@ def run_trial(device, params, n_envs, batch=None, replay=None, grad_steps=None, 
     `train_steps_per_call` (`steps_per_call`): 1 -- one `agent.train()` per gradient step; "multi" -- the gradient steps behind a vector step as multi-step
     calls (`DQNAgent.train_many`), one per stretch between target copies (at batch <= 32 on the fused path one HIP call each, elsewhere the loop); K > 1 -- the
     same with at most K steps per call; "auto" -- AUTO_TRAIN_STEPS_PER_CALL.  The same files either way."""
-    import torch
-    from .dqn.agent import DQNAgent, split_at_target_sync
+    from .dqn.agent import split_at_target_sync
     per_call = steps_per_call(train_steps_per_call)
-    from .marinenav_env.vec_env import VecMarineNavEnv
-
-    exp_dir = os.path.join(params["save_dir"], "training_" + params["training_time"], "seed_" + str(params["seed"]))
-    ref_mode = env_budget == "reference"
-    n_envs, batch, replay = resolve_budget_args(env_budget, n_envs, batch, replay)
-    plan = make_plan(params, n_envs, batch, grad_steps, total_grad_steps, n_evals, budget=env_budget, reference=reference)
-    if ref_mode:
-        if replay is not None and replay != plan["replay"]:
-            raise ValueError(f"env_budget='reference' keeps the reference's replay ring ({plan['replay']} rows); {replay} contradicts it")
-        replay = plan["replay"]
-        eval_deferred = eval_deferred or True      # (300 evaluation points: each only keeps the policy of the moment)
-    eval_points = plan_eval_points(plan, n_envs) if ref_mode else None
-    os.makedirs(exp_dir, exist_ok=True)
-    with open(os.path.join(exp_dir, "trial_config.json"), "w+") as f:
-        json.dump(dict(params, batched=dict(plan, n_envs=n_envs, world=1, batch=batch, replay=replay)), f)
-    with open(os.path.join(exp_dir, "training_schedule.json"), "w+") as f:
-        json.dump(TRAINING_SCHEDULE, f)
-    if verbose:
-        print(f"[train_dqn] seed {params['seed']}: {plan['vector_steps']} vector steps x {n_envs} envs; {plan['total_grad_steps']} grad steps of "
-              f"batch {batch} (reference: {plan['reference_grad_steps']} of 32); target copy every {plan['target_sync_grad_steps']} grad steps; "
-              f"evaluation every {plan['eval_every_vector_steps']} vector steps", flush=True)
-
-    train_env = VecMarineNavEnv(n_envs, seed=params["seed"], schedule=TRAINING_SCHEDULE, timestep_scale=plan["timestep_scale"], device=device,
-                                precision="f64")
-    if eval_config is None:
-        eval_config = create_eval_configs(device)
-    eval_env = VecMarineNavEnv(len(eval_config), device=device, precision="f64")
-    agent = DQNAgent(26, 9, buffer_size=replay, batch_size=batch, learning_starts=0, device=device, seed=params["seed"] + 100,
-                     fused_train=not torch_train)
+    run = TrialRun(device, params, n_envs, batch=batch, replay=replay, grad_steps=grad_steps, total_grad_steps=total_grad_steps, n_evals=n_evals,
+                   torch_train=torch_train, verbose=verbose, eval_one_launch=eval_one_launch, eval_deferred=eval_deferred, eval_config=eval_config,
+                   max_eval_steps=max_eval_steps, env_budget=env_budget, reference=reference, episode_log=episode_log, on_step=on_step)
+    agent, plan = run.agent, run.plan
     G, sync_every = plan["grad_steps_per_vector_step"], plan["target_sync_grad_steps"]
-    report_scale = params["total_timesteps"] / (plan["vector_steps"] * n_envs)      # evaluations.npz counts reference-scaled env steps
-    log = dict(timesteps=[], rewards=[], times=[], energies=[], successes=[], actions=[])
-    best = -np.inf
-    t0 = time.time()
-    deferred = None
-    if eval_deferred:
-        from .dqn.deferred_eval import DeferredEvaluations, can_defer
-        if can_defer(agent):
-            deferred = DeferredEvaluations(agent, eval_config, exp_dir, **dict(dict(max_steps=max_eval_steps, verbose=verbose, label=f"seed {params['seed']} ",
-                                                                                    n_evals=plan["n_evals"], t0=t0),
-                                                                               **(eval_deferred if isinstance(eval_deferred, dict) else {})))
-        else:
-            print("[train_dqn] eval_deferred: the policy does not act through the fused kernel here (CPU or another net_arch); evaluations stay inline", flush=True)
-    ep_log = make_episode_log(episode_log, env_budget, n_envs, plan["eval_every_vector_steps"], train_env.discount, device)
-    n_points = 0
-    obs = train_env.reset()
-    grad_steps_done = 0
     for it in range(plan["vector_steps"]):
-        eps = exploration_rate(it, plan)
-        a = agent.act_batch(obs, eps)
-        nxt, reward, done, info = train_env.step(a)
-        if ep_log is not None:
-            ep_log.step(reward, done, info, it, eps)
-        if on_step is not None:
-            on_step(it, dict(last=dict(reward=reward, done=done, info=info, eps=eps)))
-        agent.memory.add_vector_step(obs, a, reward, nxt, done)
-        obs = train_env.reset_done()
-        agent.num_timesteps += n_envs
-        if it + 1 >= plan["learning_starts_vector_steps"] and len(agent.memory) >= batch:
-            for steps, sync_after in split_at_target_sync(grad_steps_done, G, sync_every):
+        run.collect(it)
+        if run.trains_after(it):
+            for steps, sync_after in split_at_target_sync(run.grad_steps_done, G, sync_every):
                 if per_call == 1:
                     for _ in range(steps):
                         agent.train()
                 else:
                     for k0 in range(0, steps, per_call or steps):
                         agent.train_many(min(per_call or steps, steps - k0))
-                grad_steps_done += steps
+                run.grad_steps_done += steps
                 if sync_after:
                     agent.sync_target()
-        if eval_points is not None:
-            points = eval_points.get(it, ())
-        elif ((it + 1) % plan["eval_every_vector_steps"] == 0 or it + 1 == plan["vector_steps"]) and n_points < plan["n_evals"]:
-            points = (int(round((it + 1) * n_envs * report_scale)),)
-        else:
-            points = ()
-        if ep_log is not None:
-            if len(points):      # a summary row per evaluation interval, the evaluation's timestep on it
-                ep_log.drain(points[-1])
-            elif ep_log.due():
-                ep_log.drain(int(round((it + 1) * n_envs * report_scale)), row=False)
-        for timestep in points:
-            n_points += 1
-            if deferred is not None:      # keep the policy of this moment; its episodes run with the other pending points'
-                deferred.snapshot(timestep)
-                continue
-            ev = evaluate(agent, eval_env, eval_config, max_steps=max_eval_steps, one_launch=eval_one_launch)
-            log["timesteps"].append(timestep)
-            for k in ("rewards", "times", "energies", "successes", "actions"):
-                log[k].append(ev[k])
-            write_evaluations(exp_dir, log)
-            save_zip(agent, os.path.join(exp_dir, "latest_model.zip"))
-            mean_r = float(np.mean(ev["rewards"]))
-            if mean_r > best:
-                best = mean_r
-                save_zip(agent, os.path.join(exp_dir, "best_model.zip"))
-            if verbose:
-                print(f"[train_dqn] seed {params['seed']} eval {len(log['timesteps'])}/{plan['n_evals']} at {log['timesteps'][-1]} steps: "
-                      f"{int(np.sum(ev['successes']))}/{len(eval_config)} successes, mean return {mean_r:.2f} ({time.time() - t0:.1f} s)", flush=True)
-    if deferred is not None:
-        deferred.flush()
-        deferred.close()
-    if ep_log is not None:
-        if ep_log.row_open:      # (what ended behind the last evaluation point)
-            ep_log.drain(int(round(plan["vector_steps"] * n_envs * report_scale)))
-        ep_log.close()
-        ep_log.save(exp_dir)
-    torch.cuda.synchronize()
-    train_env.close()
-    eval_env.close()
+        run.evaluate_points(it)
+    exp_dir = run.finish()
     return (exp_dir, agent) if return_agent else exp_dir
+
+
+def group_trials(trials, limit=None):
+    """The trials of a config grid that can train together: lists of indices into `trials`, in order, each of trials that differ only in their seed (hence
+    share a plan), at most `limit` (default MN_DQN_MAX_LEARNERS = 64) to a list."""
+    if limit is None:
+        from ._capi import DQN_MAX_LEARNERS as limit
+    by_key = {}
+    for i, p in enumerate(trials):
+        key = json.dumps({k: v for k, v in p.items() if k != "seed"}, sort_keys=True, default=str)
+        by_key.setdefault(key, []).append(i)
+    return [idx[k:k + limit] for idx in by_key.values() for k in range(0, len(idx), limit)]
+
+
+def run_trials_together(device, trials, n_envs, torch_train=False, on_step=None, return_agents=False, train_steps_per_call="auto", **kwargs):
+    """`run_trial` for several trials that differ only in their seed (one list of `group_trials`), in LOCKSTEP: per vector step every trial collects as it
+    does alone -- its own envs, agent, exploration, generator, replay ring, episode log and hook -- then the gradient steps behind that vector step run for
+    ALL trials through one `LearnerGroup` (dqn/group_train.py): one launch per gradient step, or one multi-step call per stretch between target copies,
+    instead of one per trial; then every trial handles its evaluation points.  Every learner is bit for bit what it is alone, so each seed's directory
+    holds what `run_trial` writes, with the same contents.  `on_step`: None or one hook per trial.  `train_steps_per_call` and the other arguments as
+    `run_trial`'s.  Returns the trial directories (`return_agents`: and the agents)."""
+    from .dqn.agent import split_at_target_sync
+    from .dqn.group_train import LearnerGroup
+    if torch_train:
+        raise ValueError("training trials together needs the fused gradient step: there is no grouped form of the eager PyTorch step (torch_train)")
+    trials = list(trials)
+    if len(group_trials(trials)) != 1:
+        raise ValueError("trials that train together differ only in their seed, and are at most 64 (group_trials)")
+    per_call = steps_per_call(train_steps_per_call)
+    hooks = list(on_step) if on_step is not None else [None] * len(trials)
+    runs = [TrialRun(device, p, n_envs, on_step=h, **kwargs) for p, h in zip(trials, hooks)]
+    plan = runs[0].plan
+    assert all(r.plan == plan for r in runs)
+    group = LearnerGroup([r.agent for r in runs])
+    G, sync_every = plan["grad_steps_per_vector_step"], plan["target_sync_grad_steps"]
+    done = 0
+    for it in range(plan["vector_steps"]):
+        for r in runs:
+            r.collect(it)
+        trains = [r.trains_after(it) for r in runs]
+        assert all(t == trains[0] for t in trains)      # (equal plans, equally full rings)
+        if trains[0]:
+            for steps, sync_after in split_at_target_sync(done, G, sync_every):
+                if per_call == 1:
+                    for _ in range(steps):
+                        group.train()
+                else:
+                    for k0 in range(0, steps, per_call or steps):
+                        group.train_many(min(per_call or steps, steps - k0))
+                done += steps
+                if sync_after:
+                    group.sync_target()
+            for r in runs:
+                r.grad_steps_done = done
+        for r in runs:
+            r.evaluate_points(it)
+    dirs = [r.finish() for r in runs]
+    group.close()
+    return (dirs, [r.agent for r in runs]) if return_agents else dirs
 
 
 def main(argv=None):
@@ -289,8 +385,15 @@ def main(argv=None):
     ap.add_argument("--eval-deferred", action="store_true",
                     help="evaluations: a point only keeps the policy of the moment; all pending points run later as ONE mn_rollout_dqn_groups launch and are "
                          "logged as the inline form logs them (the same files); with --n-evals 300 the reference's evaluation density")
-    ap.add_argument("--dry-run", action="store_true", help="print the plan of every trial as JSON and exit (no GPU needed)")
+    ap.add_argument("--together", action="store_true",
+                    help="train the trials that differ only in their seed in lockstep, up to 64 at a time: their gradient steps share ONE launch per step (or one "
+                         "multi-step call per stretch, with --train-steps-per-call multi / K) through mn_dqn_group_train_step[s]; every seed's files equal the "
+                         "sequential run's.  Needs the fused gradient step (not --torch-train); a trial without companions runs as without the option")
+    ap.add_argument("--dry-run", action="store_true", help="print the plan of every trial as JSON and exit (no GPU needed); with --together also which trials "
+                                                           "would share a group")
     args = ap.parse_args(argv)
+    if args.together and args.torch_train:
+        raise SystemExit("train_dqn: --together needs the fused HIP gradient step: there is no grouped form of the eager PyTorch step (--torch-train)")
     try:
         steps_per_call(args.train_steps_per_call)
     except ValueError as e:
@@ -300,6 +403,7 @@ def main(argv=None):
     trials = trial_params(params)
     for p in trials:
         p["training_time"] = stamp
+    groups = group_trials(trials) if args.together else [[i] for i in range(len(trials))]
     if args.dry_run:
         n_envs, batch, replay = resolve_budget_args(args.env_budget, args.n_envs, args.batch, args.replay)
         for p in trials:
@@ -313,16 +417,26 @@ def main(argv=None):
             print(json.dumps(dict(seed=p["seed"], n_envs=n_envs, batch=batch, replay=plan.get("replay", replay), fused=not args.torch_train,
                                   eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred or args.env_budget == "reference", **extra, eps_start=exploration_rate(0, plan), eps_end=exploration_rate(int(np.ceil(plan["exploration_vector_steps"])), plan),
                                   plan=plan)))
+        if args.together:
+            print(json.dumps(dict(together=[dict(group=k, seeds=[trials[i]["seed"] for i in g], one_launch_per_gradient_step=len(g) > 1)
+                                            for k, g in enumerate(groups)])))
         return
     import torch
     device = "cuda:0" if args.device in (None, "cuda") else args.device
     torch.cuda.set_device(torch.device(device))
-    for p in trials:
+    common = dict(batch=args.batch, replay=args.replay, grad_steps=args.grad_steps, total_grad_steps=args.total_grad_steps, n_evals=args.n_evals,
+                  torch_train=args.torch_train, eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred, env_budget=args.env_budget,
+                  episode_log=args.episode_log, train_steps_per_call=args.train_steps_per_call)
+    for g in groups:
         t0 = time.time()
-        d = run_trial(device, p, args.n_envs, batch=args.batch, replay=args.replay, grad_steps=args.grad_steps,
-                      total_grad_steps=args.total_grad_steps, n_evals=args.n_evals, torch_train=args.torch_train, eval_one_launch=args.eval_one_launch,
-                      eval_deferred=args.eval_deferred, env_budget=args.env_budget, episode_log=args.episode_log,
-                      train_steps_per_call=args.train_steps_per_call)
+        if len(g) > 1:
+            seeds = [trials[i]["seed"] for i in g]
+            print(f"[train_dqn] seeds {seeds} train together: one launch per gradient step for the {len(g)} of them", flush=True)
+            dirs = run_trials_together(device, [trials[i] for i in g], args.n_envs, **common)
+            print(f"[train_dqn] seeds {seeds}: {time.time() - t0:.1f} s -> {os.path.dirname(dirs[0])}", flush=True)
+            continue
+        p = trials[g[0]]
+        d = run_trial(device, p, args.n_envs, **common)
         print(f"[train_dqn] seed {p['seed']}: {time.time() - t0:.1f} s -> {d}", flush=True)
 
 

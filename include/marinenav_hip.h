@@ -676,6 +676,41 @@ int mn_dqn_train_steps_parts(const float *ring_states, const float *ring_next_st
                              float *params_local, const float *params_target, float *workspace, float *grad_out, float *losses_out, float *exp_avg,
                              float *exp_avg_sq, int32_t *step_dev, int32_t batch, int32_t n_steps, float gamma, double lr, double beta1, double beta2,
                              double eps, double max_norm, int32_t parts, void *stream);
+/* MANY LEARNERS per launch: G independent DQN learners with common hyper-parameters (the seeds of one config) take their gradient step in ONE launch, or
+ * their n_steps steps in one multi-step call.  The learner is a grid dimension: workgroup (w, g) of the grouped step is workgroup w of learner g's
+ * mn_dqn_train_step on g's own buffers and its own slice of the workspace, the grouped multi-step call runs learner g's TD-target tiles and, as workgroup g,
+ * its whole chain.  The kernels inline the same bodies as the single calls, so EVERY learner is bit for bit what mn_dqn_train_step / mn_dqn_train_steps
+ * leave from the same state -- parameters, moments, step and draw counters, gradient, every loss, every row.
+ * mn_dqn_learner: the device pointers of ONE learner (arguments of the same names of mn_dqn_train_step; grad = grad_out, step = step_dev), caller-owned
+ * and alive as long as the group is used.  rng_state may be NULL if the group is only ever called with rows (idx_dev).
+ * mn_dqn_group_create validates on the host, uploads the pointer table once (one allocation, one synchronous copy) and returns the handle.
+ * MN_ERR_INVALID: n_learners outside 1..MN_DQN_MAX_LEARNERS, a NULL among the required pointers, or two learners that alias -- a buffer one learner
+ * writes (params_local, grad, exp_avg, exp_avg_sq over their 27 650 floats, step, a non-NULL rng_state) overlapping a buffer another learner writes or
+ * the params_target another reads: such learners would race silently.  Learners may share a ring.
+ * Per call, common to the group: ring_size (a lockstep run has the rings equally full), batch and the hyper-parameters.
+ *   idx_dev     [G][n_steps][batch] i64, the rows of every learner and step (the draw states are left alone), or NULL: every learner draws from its own
+ *               rng_state, which advances as in the single calls (MN_ERR_INVALID if a learner of the group has none)
+ *   idx_out     [G][n_steps][batch] i64 or NULL;  losses_out [G][n_steps] f32   (n_steps = 1 for mn_dqn_group_train_step)
+ *   workspace   [G][stride] f32, 16-byte aligned, ZERO before the first call (the tickets of the step stay zero behind every launch); stride =
+ *               mn_dqn_train_workspace_floats(batch) (step) or mn_dqn_train_steps_workspace_floats(batch, n_steps) (multi-step call), rounded up to a
+ *               multiple of 4 floats; one workspace per concurrently running call
+ * Limits as the single calls': batch 1..256 (step), batch 1..32 and n_steps 1..MN_DQN_MAX_STEPS (multi-step call), batch <= ring_size < 2^31; outside them,
+ * for a NULL group / workspace / losses_out or a misaligned workspace: MN_ERR_INVALID, without launching.  One launch (step) or two (multi-step call) on
+ * the caller's stream, no allocation, no host synchronisation.  The target networks are copied by the caller BETWEEN calls. */
+typedef struct mn_dqn_learner {      /* device pointers of ONE learner, caller-owned */
+    const float *ring_states, *ring_next_states; const int64_t *ring_actions; const float *ring_rewards, *ring_dones;
+    uint64_t *rng_state;             /* {seed, call counter}; may be NULL if the group is only ever called with rows */
+    float *params_local; const float *params_target; float *grad, *exp_avg, *exp_avg_sq; int32_t *step;
+} mn_dqn_learner;
+typedef struct mn_dqn_group mn_dqn_group;
+#define MN_DQN_MAX_LEARNERS 64
+int mn_dqn_group_create(const mn_dqn_learner *learners_host, int32_t n_learners, mn_dqn_group **out);
+int mn_dqn_group_destroy(mn_dqn_group *g);
+int mn_dqn_group_train_step(mn_dqn_group *g, int64_t ring_size, const int64_t *idx_dev, int64_t *idx_out, float *workspace, float *losses_out,
+                            int32_t batch, float gamma, double lr, double beta1, double beta2, double eps, double max_norm, void *stream);
+int mn_dqn_group_train_steps(mn_dqn_group *g, int64_t ring_size, const int64_t *idx_dev, int64_t *idx_out, float *workspace, float *losses_out,
+                             int32_t batch, int32_t n_steps, float gamma, double lr, double beta1, double beta2, double eps, double max_norm,
+                             void *stream);
 
 typedef struct mn_xchg mn_xchg;
 int mn_xchg_create(int32_t rank, int32_t world, mn_xchg **out);
