@@ -41,6 +41,15 @@ class MnDqnLearner(C.Structure):
 DQN_MAX_LEARNERS = 64      # MN_DQN_MAX_LEARNERS
 
 
+class MnIqnLearner(C.Structure):
+    """mn_iqn_learner: the device pointers of one IQN learner of a group (mn_iqn_group_create)."""
+    _fields_ = [(n, C.c_void_p) for n in ("ring_states", "ring_next_states", "ring_actions", "ring_rewards", "ring_dones", "rng_state", "params_local",
+                                          "params_target", "workspace", "grad", "loss", "exp_avg", "exp_avg_sq", "step", "idx_out", "taus_out")]
+
+
+IQN_MAX_LEARNERS = 64      # MN_IQN_MAX_LEARNERS
+
+
 class MarineNavHipError(RuntimeError):
     pass
 
@@ -134,6 +143,9 @@ SIGNATURES = [
     ("mn_dqn_group_destroy", C.c_int, [_vp]),
     ("mn_dqn_group_train_step", C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, C.c_float] + [_dbl] * 5 + [_vp]),
     ("mn_dqn_group_train_steps", C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, C.c_float] + [_dbl] * 5 + [_vp]),
+    ("mn_iqn_group_create", C.c_int, [C.POINTER(MnIqnLearner), _i32, _i32, C.POINTER(_vp)]),
+    ("mn_iqn_group_destroy", C.c_int, [_vp]),
+    ("mn_iqn_group_train_step", C.c_int, [_vp, _i64, _vp, _vp, _vp, C.c_float] + [_dbl] * 5 + [_vp]),
     ("mn_xchg_create", C.c_int, [_i32, _i32, C.POINTER(_vp)]),
     ("mn_xchg_export", C.c_int, [_vp, _vp]),
     ("mn_xchg_import", C.c_int, [_vp, _i32, _vp]),

@@ -103,7 +103,7 @@ static int dev_info(DevInfo *out) {
         if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return MN_ERR_HIP;
         // the forward / backward kernel's dynamic LDS (97 KB) is above the default limit: raised once per device
         const void *kernels[] = {reinterpret_cast<const void *>(iqn_train_fwdbwd<false, false>), reinterpret_cast<const void *>(iqn_train_fwdbwd<false, true>),
-                                 reinterpret_cast<const void *>(iqn_train_fwdbwd<true, true>)};
+                                 reinterpret_cast<const void *>(iqn_train_fwdbwd<true, true>), reinterpret_cast<const void *>(iqn_group_fwdbwd_kernel)};
         for (const void *kf : kernels)
             if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) return MN_ERR_HIP;
         int a = 0, b = 0;
@@ -297,6 +297,97 @@ extern "C" int mn_iqn_train_adam(float *params, float *grad, float *exp_avg, flo
     if ((grad_rewritten || grad_scale != 1.0f) && grad_rewritten != 2)      // the reduction kernel's partial sums of squares no longer describe grad (2: mn_iqn_train_exchange already wrote them for grad_scale * grad)
         hipLaunchKernelGGL(iqn_grad_sumsq, dim3(N_RED), dim3(RED_COLS), 0, s, grad, workspace + ws_sq(batch / BE), grad_scale);
     return launch_adam(params, grad, exp_avg, exp_avg_sq, step_dev, workspace, batch / BE, lr, beta1, beta2, eps, max_norm, grad_scale, s);
+}
+
+// ---- many learners per launch (mn_iqn_group_*; kernels and rationale: "many learners per launch" in iqn_train.hip) ------------------------------------------
+struct mn_iqn_group {
+    IqnLearnerRow *table_dev;
+    int n, batch;
+    bool all_draw;      // every learner has a generator state
+};
+
+// [lo, hi) byte extents overlap
+static bool extents_overlap(const void *p, size_t np, const void *q, size_t nq) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + nq && b < a + np;
+}
+
+extern "C" int mn_iqn_group_create(const mn_iqn_learner *learners_host, int32_t n_learners, int32_t batch, mn_iqn_group **out) {
+    if (!out) return MN_ERR_INVALID;
+    *out = nullptr;
+    if (!learners_host || n_learners < 1 || n_learners > MN_IQN_MAX_LEARNERS) return MN_ERR_INVALID;
+    if (batch <= 0 || batch > MAX_BATCH || batch % BE) return MN_ERR_INVALID;
+    struct Extent { const void *p; size_t n; int owner; };
+    constexpr int PER = 10;      // written buffers per learner, at most
+    std::unique_ptr<IqnLearnerRow[]> rows(new (std::nothrow) IqnLearnerRow[MN_IQN_MAX_LEARNERS]);
+    std::unique_ptr<Extent[]> written(new (std::nothrow) Extent[PER * MN_IQN_MAX_LEARNERS]);
+    if (!rows || !written) return MN_ERR_ALLOC;
+    Extent targets[MN_IQN_MAX_LEARNERS];
+    int n_written = 0;
+    bool all_draw = true;
+    constexpr size_t VEC = (size_t)P_TOTAL * sizeof(float);
+    const size_t ws_bytes = (size_t)ws_total(batch / BE) * sizeof(float);
+    for (int g = 0; g < n_learners; ++g) {
+        const mn_iqn_learner &l = learners_host[g];
+        if (!l.ring_states || !l.ring_next_states || !l.ring_actions || !l.ring_rewards || !l.ring_dones || !l.params_local || !l.params_target ||
+            !l.workspace || !l.grad || !l.loss || !l.exp_avg || !l.exp_avg_sq || !l.step)
+            return MN_ERR_INVALID;
+        rows[g] = IqnLearnerRow{l.ring_states, l.ring_next_states, l.ring_actions, l.ring_rewards, l.ring_dones, l.rng_state, l.params_local, l.params_target,
+                                l.workspace, l.grad, l.loss, l.exp_avg, l.exp_avg_sq, l.step, l.idx_out, l.taus_out};
+        written[n_written++] = Extent{l.params_local, VEC, g};
+        written[n_written++] = Extent{l.grad, VEC, g};
+        written[n_written++] = Extent{l.exp_avg, VEC, g};
+        written[n_written++] = Extent{l.exp_avg_sq, VEC, g};
+        written[n_written++] = Extent{l.workspace, ws_bytes, g};
+        written[n_written++] = Extent{l.loss, sizeof(float), g};
+        written[n_written++] = Extent{l.step, sizeof(int32_t), g};
+        if (l.rng_state) written[n_written++] = Extent{l.rng_state, 2 * sizeof(uint64_t), g};
+        else all_draw = false;
+        if (l.idx_out) written[n_written++] = Extent{l.idx_out, (size_t)batch * sizeof(int64_t), g};
+        if (l.taus_out) written[n_written++] = Extent{l.taus_out, 2 * (size_t)batch * NQ * sizeof(float), g};
+        targets[g] = Extent{l.params_target, VEC, g};
+    }
+    // learners that alias would race silently: nothing one learner writes may overlap what another writes, or the target network another reads
+    for (int i = 0; i < n_written; ++i) {
+        for (int j = i + 1; j < n_written; ++j)
+            if (written[i].owner != written[j].owner && extents_overlap(written[i].p, written[i].n, written[j].p, written[j].n)) return MN_ERR_INVALID;
+        for (int g = 0; g < n_learners; ++g)
+            if (written[i].owner != g && extents_overlap(written[i].p, written[i].n, targets[g].p, targets[g].n)) return MN_ERR_INVALID;
+    }
+    mn_iqn_group *grp = new (std::nothrow) mn_iqn_group{nullptr, n_learners, batch, all_draw};
+    if (!grp) return MN_ERR_ALLOC;
+    if (hipMalloc(reinterpret_cast<void **>(&grp->table_dev), sizeof(IqnLearnerRow) * n_learners) != hipSuccess ||
+        hipMemcpy(grp->table_dev, rows.get(), sizeof(IqnLearnerRow) * n_learners, hipMemcpyHostToDevice) != hipSuccess) {
+        if (grp->table_dev) (void)hipFree(grp->table_dev);
+        delete grp;
+        return MN_ERR_HIP;
+    }
+    *out = grp;
+    return MN_OK;
+}
+
+extern "C" int mn_iqn_group_destroy(mn_iqn_group *g) {
+    if (!g) return MN_ERR_INVALID;
+    const hipError_t e = hipFree(g->table_dev);
+    delete g;
+    return e == hipSuccess ? MN_OK : MN_ERR_HIP;
+}
+
+extern "C" int mn_iqn_group_train_step(mn_iqn_group *g, int64_t ring_size, const int64_t *idx_dev, const float *taus_target_dev, const float *taus_local_dev,
+                                       float gamma, double lr, double beta1, double beta2, double eps, double max_norm, void *stream) {
+    if (!g) return MN_ERR_INVALID;
+    const bool given = idx_dev != nullptr;
+    if ((taus_target_dev != nullptr) != given || (taus_local_dev != nullptr) != given) return MN_ERR_INVALID;
+    if (!given && (!g->all_draw || ring_size < g->batch || ring_size > 0x7fffffff)) return MN_ERR_INVALID;
+    DevInfo dev;
+    if (int rc = dev_info(&dev)) return rc;      // (first call on a device: raises the forward / backward kernels' dynamic-LDS limit)
+    hipStream_t s = (hipStream_t)stream;
+    const int n_part = g->batch / BE;
+    const IqnGroupArgs ga = {g->table_dev, idx_dev, taus_target_dev, taus_local_dev, ring_size, g->batch, gamma};
+    hipLaunchKernelGGL(iqn_group_fwdbwd_kernel, dim3(n_part, g->n), dim3(THREADS), LDS_BYTES, s, ga);
+    hipLaunchKernelGGL(iqn_group_reduce_kernel, dim3(N_RED, g->n), dim3(RED_COLS * RED_SEG), 0, s, (const IqnLearnerRow *)g->table_dev, n_part, given ? 0 : 1);
+    hipLaunchKernelGGL(iqn_group_adam_kernel, dim3(N_ADAM, g->n), dim3(256), 0, s, (const IqnLearnerRow *)g->table_dev, n_part, lr, beta1, beta2, eps, max_norm);
+    return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
 }
 
 // ---- one-shot gradient exchange of a shared learner over IPC-mapped mailboxes (see iqn_grad_gather) ---------------------------------

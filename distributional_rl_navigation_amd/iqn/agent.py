@@ -11,6 +11,7 @@ import json
 import os
 import random
 import sys
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -97,6 +98,111 @@ def evaluation_from_traces(reward, done, info, action, discount, energy_tab, dt,
     tl = tally(reward, done, info, action, discount, energy_tab)
     return (tl["actions"], [float(x) for x in tl["ret"]], [bool(x) for x in (tl["last_info"] == 4)], [float(dt * N * l) for l in tl["length"]],
             [float(x) for x in tl["energy"]])
+
+
+VecStepState = namedtuple("VecStepState", "obs reward done info due under_act")      # IQNAgent.vec_collect -> vec_finish
+
+
+class VecLoop:
+    """`IQNAgent.learn_vec`'s loop in the parts a driver can interleave with other agents' (train_iqn.run_trials_together): per vector step `collect(it)` (act,
+    step + append, resets in front; returns the cadence's tick), the gradient steps the tick asks for -- the caller's: the agent's own
+    `train_steps_from_memory(grad_steps_per_update)` or a `LearnerGroup` for all agents at once -- and `finish(it, loss)` (target copy, resets under the next
+    act, counters, guard, episode log, evaluation points, hook); `end()` behind the last step, `close()` in any case.  `learn_vec` is this loop for one agent."""
+
+    def __init__(self, agent, total_vector_steps, train_env, eval_env=None, eval_config=None, eval_freq=None, eval_log_path=None, total_timesteps=None,
+                 world_size=1, cvar=1.0, verbose=True, train_every=None, on_step=None, report_timestep_scale=1.0, eval_adaptive=True, reset_under_act=True,
+                 eval_one_launch=False, eval_deferred=False, episode_log=None, eval_points=None, max_eval_steps=1000):
+        self.agent, self.train_env, self.eval_env, self.eval_config = agent, train_env, eval_env, eval_config
+        self.eval_freq, self.eval_log_path, self.cvar, self.verbose, self.on_step = eval_freq, eval_log_path, cvar, verbose, on_step
+        self.eval_adaptive, self.eval_one_launch, self.episode_log, self.eval_points, self.max_eval_steps = eval_adaptive, eval_one_launch, episode_log, eval_points, max_eval_steps
+        n = train_env.n_envs
+        self.per_iter = n * world_size
+        # evaluation npz `timesteps` are reported as current_timestep * report_timestep_scale (train_iqn: reference-
+        # equivalent timesteps, so scripts/plot_eval_returns.py keeps its x axis)
+        agent._report_scale = float(report_timestep_scale)
+        self.total_timesteps = total_vector_steps * self.per_iter if total_timesteps is None else total_timesteps
+        self.train_every = agent.UPDATE_EVERY if train_every is None else train_every
+        self.obs = train_env.reset()
+        self.ep_ret = torch.zeros(n, device=agent.device)
+        self.ep_len = torch.zeros(n, device=agent.device)
+        self.stats = dict(episodes=0, successes=0, collisions=0, timeouts=0, loss=None)
+        # this loop never looks at `obs` between two vector steps, so the resets can run under the next step's act kernel (see `reset_under_act`) -- checked on this
+        # device by the loop's first steps (UnderActGuard: falls back to resets in front with one log line if the reset launch does not run beside the act kernel)
+        self.was_under_act, agent.reset_under_act = agent.reset_under_act, bool(reset_under_act)
+        self.guard = UnderActGuard(agent, train_env)
+        agent.under_act_fallback = None
+        self.deferred = (agent._deferred_evaluations(eval_deferred, eval_env, eval_config, eval_adaptive, eval_log_path)
+                         if eval_deferred and eval_env is not None else None)
+        self._state = self._eps = None
+        self._points, self._evaluate_now = (), False
+
+    def collect(self, it):
+        agent = self.agent
+        self._eps = eps = agent.linear_eps(self.total_timesteps)
+        if self.eval_points is None:
+            self._evaluate_now = self.eval_env is not None and cadence_tick(agent, self.train_every, self.eval_freq).evaluate      # (the state vec_collect's own tick sees)
+            self._points = (None,) if self._evaluate_now else ()
+        else:
+            self._points = tuple(self.eval_points.get(it, ()))
+            self._evaluate_now = self.eval_env is not None and len(self._points) > 0
+        self._state = agent.vec_collect(self.train_env, self.obs, eps, self.cvar, self.train_every)
+        return self._state.due
+
+    def finish(self, it, loss=None):
+        agent, train_env, stats, episode_log, points, eps = self.agent, self.train_env, self.stats, self.episode_log, self._points, self._eps
+        st = self._state
+        self.obs = agent.vec_finish(train_env, st, self.per_iter)
+        reward, done, info = st.reward, st.done, st.info
+        self.guard.after_step(it)
+        if loss is not None:
+            stats["loss"] = loss
+        if episode_log is not None:
+            episode_log.step(reward, done, info, it, eps)
+            if len(points):      # a summary row per evaluation interval, the evaluation's timestep on it
+                episode_log.drain(int(round(agent.current_timestep * agent._report_scale)) if points[-1] is None else points[-1])
+            elif episode_log.due():
+                episode_log.drain(int(round(agent.current_timestep * agent._report_scale)), row=False)
+        if self.on_step is not None:
+            stats["last"] = dict(reward=reward, done=done, info=info, eps=eps)
+        if self.verbose:
+            self.ep_ret += (train_env.discount ** self.ep_len) * reward
+            self.ep_len += 1
+            d = done.bool()
+            stats["episodes"] += int(d.sum())
+            stats["successes"] += int((info == 4).sum())
+            stats["collisions"] += int((info == 3).sum())
+            stats["timeouts"] += int((info == 2).sum())
+            self.ep_ret.masked_fill_(d, 0.0); self.ep_len.masked_fill_(d, 0.0)
+        for point in (points if self._evaluate_now else ()):
+            if self.deferred is not None:
+                self.deferred.snapshot(vector_step=it, timestep=point)
+            else:
+                agent._evaluate_inline(it, point, self.eval_env, self.eval_config, self.eval_log_path, self.eval_adaptive, self.eval_one_launch, self.max_eval_steps)
+        if self.on_step is not None:
+            self.on_step(it, stats)
+
+    def end(self):
+        agent, episode_log = self.agent, self.episode_log
+        if self.deferred is not None:
+            self.deferred.flush()
+        if episode_log is not None:
+            if episode_log.row_open:      # (what ended behind the last evaluation point)
+                episode_log.drain(int(round(agent.current_timestep * agent._report_scale)))
+            episode_log.close()
+        # the end-of-run look at the bounded waits happens while `reset_under_act` still says how this loop ran (every rank, evaluation env or not)
+        if hasattr(self.train_env, "join_reset"):
+            self.train_env.join_reset()
+        agent.check_learner()
+
+    def close(self):
+        agent = self.agent
+        if self.deferred is not None:
+            self.deferred.close()
+        self.guard.close()
+        agent.under_act_fallback = self.guard.fallback
+        agent.reset_under_act = self.was_under_act
+        if hasattr(self.train_env, "join_reset"):
+            self.train_env.join_reset()
 
 
 class IQNAgent(ReferenceLoopMixin):
@@ -487,80 +593,19 @@ class IQNAgent(ReferenceLoopMixin):
         included).  `max_eval_steps`: the step limit of an inline evaluation episode.
         `episode_log` (episode_log.EpisodeLog): the training episodes' record -- one more launch behind every vector step, drained (without a host
         look) at the evaluation points and wherever its arrays could fill up, closed at the end of the loop."""
-        n = train_env.n_envs
-        per_iter = n * world_size
-        # evaluation npz `timesteps` are reported as current_timestep * report_timestep_scale (train_iqn: reference-
-        # equivalent timesteps, so scripts/plot_eval_returns.py keeps its x axis)
-        self._report_scale = float(report_timestep_scale)
-        if total_timesteps is None:
-            total_timesteps = total_vector_steps * per_iter
-        train_every = self.UPDATE_EVERY if train_every is None else train_every
-        obs = train_env.reset()
-        ep_ret = torch.zeros(n, device=self.device)
-        ep_len = torch.zeros(n, device=self.device)
-        stats = dict(episodes=0, successes=0, collisions=0, timeouts=0, loss=None)
-        # this loop never looks at `obs` between two vector steps, so the resets can run under the next step's act kernel (see `reset_under_act`) -- checked on this
-        # device by the loop's first steps (UnderActGuard: falls back to resets in front with one log line if the reset launch does not run beside the act kernel)
-        was_under_act, self.reset_under_act = self.reset_under_act, bool(reset_under_act)
-        guard = UnderActGuard(self, train_env)
-        self.under_act_fallback = None
-        deferred = self._deferred_evaluations(eval_deferred, eval_env, eval_config, eval_adaptive, eval_log_path) if eval_deferred and eval_env is not None else None
+        loop = VecLoop(self, total_vector_steps, train_env, eval_env=eval_env, eval_config=eval_config, eval_freq=eval_freq, eval_log_path=eval_log_path,
+                       total_timesteps=total_timesteps, world_size=world_size, cvar=cvar, verbose=verbose, train_every=train_every, on_step=on_step,
+                       report_timestep_scale=report_timestep_scale, eval_adaptive=eval_adaptive, reset_under_act=reset_under_act, eval_one_launch=eval_one_launch,
+                       eval_deferred=eval_deferred, episode_log=episode_log, eval_points=eval_points, max_eval_steps=max_eval_steps)
         try:
             for it in range(total_vector_steps):
-                eps = self.linear_eps(total_timesteps)
-                if eval_points is None:
-                    evaluate_now = eval_env is not None and cadence_tick(self, train_every, eval_freq).evaluate      # (the state vec_step's own tick sees)
-                    points = (None,) if evaluate_now else ()
-                else:
-                    points = tuple(eval_points.get(it, ()))
-                    evaluate_now = eval_env is not None and len(points) > 0
-                obs, reward, done, info, loss = self.vec_step(train_env, obs, eps, cvar, train_every, per_iter)
-                guard.after_step(it)
-                if loss is not None:
-                    stats["loss"] = loss
-                if episode_log is not None:
-                    episode_log.step(reward, done, info, it, eps)
-                    if len(points):      # a summary row per evaluation interval, the evaluation's timestep on it
-                        episode_log.drain(int(round(self.current_timestep * self._report_scale)) if points[-1] is None else points[-1])
-                    elif episode_log.due():
-                        episode_log.drain(int(round(self.current_timestep * self._report_scale)), row=False)
-                if on_step is not None:
-                    stats["last"] = dict(reward=reward, done=done, info=info, eps=eps)
-                if verbose:
-                    ep_ret += (train_env.discount ** ep_len) * reward
-                    ep_len += 1
-                    d = done.bool()
-                    stats["episodes"] += int(d.sum())
-                    stats["successes"] += int((info == 4).sum())
-                    stats["collisions"] += int((info == 3).sum())
-                    stats["timeouts"] += int((info == 2).sum())
-                    ep_ret.masked_fill_(d, 0.0); ep_len.masked_fill_(d, 0.0)
-                for point in (points if evaluate_now else ()):
-                    if deferred is not None:
-                        deferred.snapshot(vector_step=it, timestep=point)
-                    else:
-                        self._evaluate_inline(it, point, eval_env, eval_config, eval_log_path, eval_adaptive, eval_one_launch, max_eval_steps)
-                if on_step is not None:
-                    on_step(it, stats)
-            if deferred is not None:
-                deferred.flush()
-            if episode_log is not None:
-                if episode_log.row_open:      # (what ended behind the last evaluation point)
-                    episode_log.drain(int(round(self.current_timestep * self._report_scale)))
-                episode_log.close()
-            # the end-of-run look at the bounded waits happens while `reset_under_act` still says how this loop ran (every rank, evaluation env or not)
-            if hasattr(train_env, "join_reset"):
-                train_env.join_reset()
-            self.check_learner()
+                due = loop.collect(it)
+                loss = self.train_steps_from_memory(self.grad_steps_per_update) if due.train else None      # 1 = the reference's cadence (agent.py:129-133)
+                loop.finish(it, loss)
+            loop.end()
         finally:
-            if deferred is not None:
-                deferred.close()
-            guard.close()
-            self.under_act_fallback = guard.fallback
-            self.reset_under_act = was_under_act
-            if hasattr(train_env, "join_reset"):
-                train_env.join_reset()
-        return stats
+            loop.close()
+        return loop.stats
 
     def _evaluate_inline(self, it, timestep, eval_env, eval_config, eval_log_path, eval_adaptive, one_launch, max_steps):
         """An evaluation point of learn_vec, evaluated now: greedy and -- `eval_adaptive` -- adaptive, the `best_*` rule, the latest checkpoint.
@@ -611,8 +656,16 @@ class IQNAgent(ReferenceLoopMixin):
         mn_reset_done -> (cadence permitting) sample + train + target sync.  Everything is enqueued on
         the current HIP stream; nothing synchronises with the host.
         Returns (obs for the next act, reward, done, info, loss or None)."""
+        st = self.vec_collect(train_env, obs, eps, cvar, train_every)
+        loss = self.train_steps_from_memory(self.grad_steps_per_update) if st.due.train else None      # 1 = the reference's cadence (agent.py:129-133)
+        obs = self.vec_finish(train_env, st, per_iter)
+        return obs, st.reward, st.done, st.info, loss
+
+    def vec_collect(self, train_env, obs, eps, cvar=1.0, train_every=None):
+        """The part of `vec_step` in front of the gradient steps: act_batch -> mn_step + replay append -> the cadence's tick -> (resets in front: mn_reset_done).
+        Returns a VecStepState; the caller performs the gradient steps `state.due.train` asks for -- `train_steps_from_memory(grad_steps_per_update)`, or a
+        `LearnerGroup` for several agents in lockstep (iqn/group_train.py) -- and then calls `vec_finish`."""
         train_every = self.UPDATE_EVERY if train_every is None else train_every
-        per_iter = train_env.n_envs if per_iter is None else per_iter
         under_act = bool(self.reset_under_act) and obs.is_cuda and hasattr(train_env, "take_late_rows") and self.use_fused_act
         if under_act:      # only the default acting form takes late rows: with any other the reset stays in front (no cross-stream events for nothing)
             from .fused_act import late_rows_possible
@@ -628,22 +681,26 @@ class IQNAgent(ReferenceLoopMixin):
                 self.memory.add_vector_step(obs, actions, reward, next_obs, done)
             else:
                 self.memory.add_batch(obs, actions, reward, next_obs, done.float())
-        loss = None
         due = cadence_tick(self, train_every)      # iqn/cadence.py: agent.py:126-147's rule (+ the target cadence in gradient steps)
         # first observations where done (`reset_under_act`: on the env's own stream, under the next call's act kernel, which takes those rows last -- launched BEHIND the
         # training event: a reset wavefront finds room beside an act workgroup, not beside a gradient step's, whose launches it would only hold up)
         if not under_act:
             obs = train_env.reset_done()
-        if due.train:
-            loss = self.train_steps_from_memory(self.grad_steps_per_update)      # 1 = the reference's cadence (agent.py:129-133)
-        if due.sync:
+        return VecStepState(obs, reward, done, info, due, under_act)
+
+    def vec_finish(self, train_env, state, per_iter=None):
+        """The part of `vec_step` behind the gradient steps: target copy if due, (resets under the next act: mn_reset_done_async), counters.  Returns the
+        observations for the next act."""
+        per_iter = train_env.n_envs if per_iter is None else per_iter
+        obs = state.obs
+        if state.due.sync:
             self._sync_target()
-        if under_act:
+        if state.under_act:
             obs = train_env.reset_done(under_next_act=True)
         if self.current_timestep >= self.learning_starts:
             self.learning_timestep += 1
         self.current_timestep += per_iter
-        return obs, reward, done, info, loss
+        return obs
 
     def _rollout_evaluation(self, eval_env, greedy, max_steps):
         """The evaluation episodes of `evaluation_vec` as ONE mn_rollout_iqn launch (iqn/fused_act.rollout_iqn) -- the traces, or None where the

@@ -7,7 +7,7 @@ eval_freq, save_dir), same per-trial outputs (`trial_config.json`, `training_sch
 GPUs (independent learners per rank by default, `--shared-learner` for one IQN with an RCCL
 gradient all-reduce).
 
-    python -m distributional_rl_navigation_amd.train_iqn -C config_IQN.json [--n-envs 4096] [--env-budget reference] [--episode-log [full]] [--dry-run]
+    python -m distributional_rl_navigation_amd.train_iqn -C config_IQN.json [--n-envs 4096] [--env-budget reference] [--episode-log [full]] [--together] [--dry-run]
 
 Cadence.  The reference does one batch-32 gradient step per 4 env steps (replay ratio 8 sampled per generated
 transition).  Two modes (`--env-budget`):
@@ -200,6 +200,99 @@ def make_episode_log(option, env_budget, n_envs, eval_every_vector_steps, discou
     return EpisodeLog(n_envs, n_envs * steps, discount, device, full=option == "full")
 
 
+class TrialRun:
+    """One trial of `run_trial` in the parts a lockstep driver needs (`run_trials_together`): the constructor does everything in front of the loop -- plan,
+    directory and its JSON files, envs, agent, episode log -- and leaves `learn_args`, the arguments of `IQNAgent.learn_vec` (or of its loop in parts,
+    `iqn.agent.VecLoop`); `conclude()` does everything behind it."""
+
+    def __init__(self, device, params, n_envs, rank=0, world=1, shared=False, batch=None, replay=None, verbose=True,
+                 grad_steps=None, torch_train=False, total_grad_steps=None, n_evals=None, cvar=1.0, precision="f64",
+                 exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1,
+                 eval_one_launch=False, eval_deferred=False, env_budget="learner", reference=None, episode_log=None, eval_config=None, max_eval_steps=1000,
+                 on_step=None):
+        import torch
+        from .iqn.agent import IQNAgent
+        from .marinenav_env.vec_env import VecMarineNavEnv
+
+        exp_dir = os.path.join(params["save_dir"], "training_" + params["training_time"], "seed_" + str(params["seed"]))
+        if world > 1 and not shared:
+            exp_dir = os.path.join(exp_dir, f"rank_{rank}")
+        writer = rank == 0 or not shared
+        ref_mode = env_budget == "reference"
+        if ref_mode and (world > 1 or shared):
+            raise ValueError("env_budget='reference' is the reference's single-learner experiment: one process, one GPU")
+        n_envs, batch, replay = resolve_budget_args(env_budget, n_envs, batch, replay)
+        total = n_envs * world
+        plan = plan_cadence(params["total_timesteps"], params["eval_freq"], total, batch,
+                            grad_steps_per_vector_step=grad_steps, total_grad_steps=total_grad_steps, n_evals=n_evals, budget=env_budget, reference=reference)
+        if ref_mode:
+            if replay is not None and replay != plan["replay"]:
+                raise ValueError(f"env_budget='reference' keeps the reference's replay ring ({plan['replay']} rows); {replay} contradicts it")
+            replay = plan["replay"]
+        if plan["total_grad_steps"] * batch < 0.1 * plan["reference_samples"]:
+            raise ValueError(f"planned learner budget ({plan['total_grad_steps']} grad steps x {batch}) is more than 10x below the "
+                             f"reference's ({plan['reference_grad_steps']} x 32): raise --total-grad-steps")
+        if writer:
+            os.makedirs(exp_dir, exist_ok=True)
+            with open(os.path.join(exp_dir, "trial_config.json"), "w+") as f:
+                json.dump(dict(params, batched=dict(plan, n_envs=n_envs, world=world, batch=batch, replay=replay)), f)
+            with open(os.path.join(exp_dir, "training_schedule.json"), "w+") as f:
+                json.dump(TRAINING_SCHEDULE, f)
+            if verbose:
+                print(f"[train_iqn] {plan['vector_steps']} vector steps x {total} envs = {plan['env_steps']:.3g} env steps; "
+                      f"{plan['total_grad_steps']} grad steps of batch {batch} ({plan['grad_steps_per_vector_step']} per vector step; "
+                      f"reference: {plan['reference_grad_steps']} of 32); replay ratio {plan['replay_ratio']:.3g} sampled / generated "
+                      f"transition (reference {plan['reference_replay_ratio']:.0f}); target copy every {plan['target_sync_grad_steps']} "
+                      f"grad steps; evaluation every {plan['eval_every_vector_steps']} vector steps")
+
+        train_env = VecMarineNavEnv(n_envs, seed=params["seed"], first_index=rank * n_envs, schedule=TRAINING_SCHEDULE,
+                                    timestep_scale=plan["timestep_scale"], device=device, precision=precision)
+        if eval_config is None:
+            eval_config = create_eval_configs(device)
+        if writer:
+            with open(os.path.join(exp_dir, "eval_config.json"), "w+") as f:
+                json.dump(eval_config, f)
+        eval_env = VecMarineNavEnv(len(eval_config), device=device, precision=precision) if writer else None
+
+        agent = IQNAgent(26, 9, n_step=n_step, BATCH_SIZE=batch, BUFFER_SIZE=replay, device=device,
+                         seed=params["seed"] + 100 + (0 if shared else rank), distributed=shared and world > 1,
+                         UPDATE_EVERY=1, learning_starts=plan["learning_starts"] if ref_mode else 0, rank=rank if shared else 0, final_eps=final_eps,
+                         **(dict(exploration_fraction=plan["exploration_fraction"]) if ref_mode else {}))
+        agent.grad_steps_per_update = plan["grad_steps_per_vector_step"]
+        agent.target_sync_grad_steps = max(1, int(round(plan["target_sync_grad_steps"] * target_sync_mult)))
+        agent.exchange = exchange
+        agent.shared_taus = bool(shared_taus)
+        if torch_train:
+            agent.use_fused_train = False          # PyTorch autograd + Adam instead of csrc/iqn_train.hip
+        log = make_episode_log(episode_log, env_budget, n_envs, plan["eval_every_vector_steps"], train_env.discount, device)
+        if ref_mode and not eval_deferred:
+            eval_deferred = True      # (300 evaluation points: each only keeps the policy of the moment)
+        if max_eval_steps != 1000 and eval_deferred:
+            eval_deferred = dict(dict(max_steps=max_eval_steps), **(eval_deferred if isinstance(eval_deferred, dict) else {}))
+        self.learn_args = dict(total_vector_steps=plan["vector_steps"], train_env=train_env, eval_env=eval_env, eval_config=eval_config,
+                               eval_freq=plan["eval_every_vector_steps"], eval_log_path=exp_dir if writer else None,
+                               total_timesteps=plan["vector_steps"] * total, world_size=world, cvar=cvar, verbose=False,
+                               report_timestep_scale=params["total_timesteps"] / (plan["vector_steps"] * total), eval_adaptive=eval_adaptive,
+                               eval_one_launch=eval_one_launch, eval_deferred=eval_deferred, on_step=on_step, episode_log=log, max_eval_steps=max_eval_steps,
+                               eval_points=plan_eval_points(plan, total) if ref_mode else None)
+        self.exp_dir, self.writer, self.plan, self.agent, self.train_env, self.eval_env, self.log = exp_dir, writer, plan, agent, train_env, eval_env, log
+
+    def conclude(self):
+        import torch
+        exp_dir, writer, agent, train_env, eval_env, log = self.exp_dir, self.writer, self.agent, self.train_env, self.eval_env, self.log
+        if writer:
+            agent.qnetwork_local.save(exp_dir)
+            if log is not None:
+                log.save(exp_dir)
+        train_env.close()
+        if eval_env is not None:
+            eval_env.close()
+        torch.cuda.synchronize()
+        return exp_dir
+
+
+
+
 def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None, replay=None, verbose=True,
               grad_steps=None, torch_train=False, total_grad_steps=None, n_evals=None, cvar=1.0, precision="f64",
               exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1,
@@ -224,80 +317,82 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None,
     summary row of the training episodes per evaluation interval, "full": training_episodes.npz with every episode's record (episode_log.py).
     `eval_config`: the evaluation worlds (default: the 30 of create_eval_configs); `max_eval_steps`: the step limit of an evaluation episode;
     `on_step`: learn_vec's hook; `return_agent`: return (directory, agent)."""
+    run = TrialRun(device, params, n_envs, rank=rank, world=world, shared=shared, batch=batch, replay=replay, verbose=verbose, grad_steps=grad_steps,
+                   torch_train=torch_train, total_grad_steps=total_grad_steps, n_evals=n_evals, cvar=cvar, precision=precision, exchange=exchange,
+                   shared_taus=shared_taus, target_sync_mult=target_sync_mult, final_eps=final_eps, eval_adaptive=eval_adaptive, n_step=n_step,
+                   eval_one_launch=eval_one_launch, eval_deferred=eval_deferred, env_budget=env_budget, reference=reference, episode_log=episode_log,
+                   eval_config=eval_config, max_eval_steps=max_eval_steps, on_step=on_step)
+    run.agent.learn_vec(**run.learn_args)
+    exp_dir = run.conclude()
+    return (exp_dir, run.agent) if return_agent else exp_dir
+
+
+def group_trials(trials, limit=None):
+    """The trials of a config grid that can train together: lists of indices into `trials`, in order, each of trials that differ only in their seed (hence
+    share a plan), at most `limit` (default MN_IQN_MAX_LEARNERS = 64) to a list."""
+    if limit is None:
+        from ._capi import IQN_MAX_LEARNERS as limit
+    by_key = {}
+    for i, p in enumerate(trials):
+        key = json.dumps({k: v for k, v in p.items() if k != "seed"}, sort_keys=True, default=str)
+        by_key.setdefault(key, []).append(i)
+    return [idx[k:k + limit] for idx in by_key.values() for k in range(0, len(idx), limit)]
+
+
+TOGETHER_REFUSALS = dict(
+    torch_train="--together needs the fused HIP gradient step: there is no grouped form of the PyTorch step (--torch-train)",
+    shared="--together trains independent learners, one per seed; a shared learner (--shared-learner) exchanges its gradient with other ranks, which has no grouped form",
+    procs="--together runs the seeds in ONE process so that their gradient steps can share launches; -P > 1 would put them into separate processes",
+    world="--together is the single-process, single-GPU form; it is not combinable with torch.distributed.run (WORLD_SIZE > 1)")
+
+
+def run_trials_together(device, trials, n_envs, on_step=None, return_agents=False, torch_train=False, shared=False, world=1, **kwargs):
+    """`run_trial` for several trials that differ only in their seed (one list of `group_trials`), in LOCKSTEP: per vector step every trial collects as it
+    does alone -- its own envs, agent, exploration, generators, replay ring, episode log, UnderActGuard and hook -- then, if the cadence says train (the same
+    for all: equal plans, equally full rings), the gradient steps behind that vector step run for ALL trials through one `LearnerGroup`
+    (iqn/group_train.py: three launches per gradient step instead of one to three per trial); then every trial finishes the step -- target copy on its own
+    cadence, resets, counters, evaluation points, log.  The order of launches per agent is `vec_step`'s, and every learner is bit for bit what it is alone,
+    so each seed's directory holds what `run_trial` writes, with the same contents.  The device is synchronised once per vector step (see the loop).  `on_step`: None or one hook per trial; the other arguments as
+    `run_trial`'s.  Returns the trial directories (`return_agents`: and the agents)."""
     import torch
-    from .iqn.agent import IQNAgent
-    from .marinenav_env.vec_env import VecMarineNavEnv
-
-    exp_dir = os.path.join(params["save_dir"], "training_" + params["training_time"], "seed_" + str(params["seed"]))
-    if world > 1 and not shared:
-        exp_dir = os.path.join(exp_dir, f"rank_{rank}")
-    writer = rank == 0 or not shared
-    ref_mode = env_budget == "reference"
-    if ref_mode and (world > 1 or shared):
-        raise ValueError("env_budget='reference' is the reference's single-learner experiment: one process, one GPU")
-    n_envs, batch, replay = resolve_budget_args(env_budget, n_envs, batch, replay)
-    total = n_envs * world
-    plan = plan_cadence(params["total_timesteps"], params["eval_freq"], total, batch,
-                        grad_steps_per_vector_step=grad_steps, total_grad_steps=total_grad_steps, n_evals=n_evals, budget=env_budget, reference=reference)
-    if ref_mode:
-        if replay is not None and replay != plan["replay"]:
-            raise ValueError(f"env_budget='reference' keeps the reference's replay ring ({plan['replay']} rows); {replay} contradicts it")
-        replay = plan["replay"]
-    if plan["total_grad_steps"] * batch < 0.1 * plan["reference_samples"]:
-        raise ValueError(f"planned learner budget ({plan['total_grad_steps']} grad steps x {batch}) is more than 10x below the "
-                         f"reference's ({plan['reference_grad_steps']} x 32): raise --total-grad-steps")
-    if writer:
-        os.makedirs(exp_dir, exist_ok=True)
-        with open(os.path.join(exp_dir, "trial_config.json"), "w+") as f:
-            json.dump(dict(params, batched=dict(plan, n_envs=n_envs, world=world, batch=batch, replay=replay)), f)
-        with open(os.path.join(exp_dir, "training_schedule.json"), "w+") as f:
-            json.dump(TRAINING_SCHEDULE, f)
-        if verbose:
-            print(f"[train_iqn] {plan['vector_steps']} vector steps x {total} envs = {plan['env_steps']:.3g} env steps; "
-                  f"{plan['total_grad_steps']} grad steps of batch {batch} ({plan['grad_steps_per_vector_step']} per vector step; "
-                  f"reference: {plan['reference_grad_steps']} of 32); replay ratio {plan['replay_ratio']:.3g} sampled / generated "
-                  f"transition (reference {plan['reference_replay_ratio']:.0f}); target copy every {plan['target_sync_grad_steps']} "
-                  f"grad steps; evaluation every {plan['eval_every_vector_steps']} vector steps")
-
-    train_env = VecMarineNavEnv(n_envs, seed=params["seed"], first_index=rank * n_envs, schedule=TRAINING_SCHEDULE,
-                                timestep_scale=plan["timestep_scale"], device=device, precision=precision)
-    if eval_config is None:
-        eval_config = create_eval_configs(device)
-    if writer:
-        with open(os.path.join(exp_dir, "eval_config.json"), "w+") as f:
-            json.dump(eval_config, f)
-    eval_env = VecMarineNavEnv(len(eval_config), device=device, precision=precision) if writer else None
-
-    agent = IQNAgent(26, 9, n_step=n_step, BATCH_SIZE=batch, BUFFER_SIZE=replay, device=device,
-                     seed=params["seed"] + 100 + (0 if shared else rank), distributed=shared and world > 1,
-                     UPDATE_EVERY=1, learning_starts=plan["learning_starts"] if ref_mode else 0, rank=rank if shared else 0, final_eps=final_eps,
-                     **(dict(exploration_fraction=plan["exploration_fraction"]) if ref_mode else {}))
-    agent.grad_steps_per_update = plan["grad_steps_per_vector_step"]
-    agent.target_sync_grad_steps = max(1, int(round(plan["target_sync_grad_steps"] * target_sync_mult)))
-    agent.exchange = exchange
-    agent.shared_taus = bool(shared_taus)
+    from .iqn.agent import VecLoop
+    from .iqn.group_train import LearnerGroup
     if torch_train:
-        agent.use_fused_train = False          # PyTorch autograd + Adam instead of csrc/iqn_train.hip
-    log = make_episode_log(episode_log, env_budget, n_envs, plan["eval_every_vector_steps"], train_env.discount, device)
-    if ref_mode and not eval_deferred:
-        eval_deferred = True      # (300 evaluation points: each only keeps the policy of the moment)
-    if max_eval_steps != 1000 and eval_deferred:
-        eval_deferred = dict(dict(max_steps=max_eval_steps), **(eval_deferred if isinstance(eval_deferred, dict) else {}))
-    agent.learn_vec(total_vector_steps=plan["vector_steps"], train_env=train_env, eval_env=eval_env, eval_config=eval_config,
-                    eval_freq=plan["eval_every_vector_steps"], eval_log_path=exp_dir if writer else None,
-                    total_timesteps=plan["vector_steps"] * total, world_size=world, cvar=cvar, verbose=False,
-                    report_timestep_scale=params["total_timesteps"] / (plan["vector_steps"] * total), eval_adaptive=eval_adaptive,
-                    eval_one_launch=eval_one_launch, eval_deferred=eval_deferred, on_step=on_step, episode_log=log, max_eval_steps=max_eval_steps,
-                    eval_points=plan_eval_points(plan, total) if ref_mode else None)
-    if writer:
-        agent.qnetwork_local.save(exp_dir)
-        if log is not None:
-            log.save(exp_dir)
-    train_env.close()
-    if eval_env is not None:
-        eval_env.close()
-    torch.cuda.synchronize()
-    return (exp_dir, agent) if return_agent else exp_dir
+        raise ValueError(TOGETHER_REFUSALS["torch_train"])
+    if shared or world > 1:
+        raise ValueError(TOGETHER_REFUSALS["shared" if shared else "world"])
+    trials = list(trials)
+    if len(group_trials(trials)) != 1:
+        raise ValueError("trials that train together differ only in their seed, and are at most 64 (group_trials)")
+    hooks = list(on_step) if on_step is not None else [None] * len(trials)
+    runs = [TrialRun(device, p, n_envs, on_step=h, **kwargs) for p, h in zip(trials, hooks)]
+    plan = runs[0].plan
+    assert all(r.plan == plan for r in runs)
+    loops, group = [], None
+    try:
+        for r in runs:
+            loops.append(VecLoop(r.agent, **r.learn_args))
+        group = LearnerGroup([r.agent for r in runs])
+        G = runs[0].agent.grad_steps_per_update
+        for it in range(plan["vector_steps"]):
+            dues = [lp.collect(it) for lp in loops]
+            assert all(d.train == dues[0].train for d in dues), "the seeds of a group train on one cadence"
+            losses = group.train_many(G) if dues[0].train else None
+            for k, lp in enumerate(loops):
+                lp.finish(it, None if losses is None else losses[k])
+            # The host must not run ahead of the device here.  With the launches of several seeds -- each env with a reset stream of its own -- queued many vector
+            # steps deep, the lockstep loop measured 4.1 ms per vector step for five seeds; with the queue drained once per vector step 1.25 ms (one seed alone:
+            # 0.68 ms).  One synchronisation per vector step of ALL seeds; it changes no result.
+            torch.cuda.synchronize(device)
+        for lp in loops:
+            lp.end()
+    finally:
+        for lp in loops:
+            lp.close()
+        if group is not None:
+            group.close()
+    dirs = [r.conclude() for r in runs]
+    return (dirs, [r.agent for r in runs]) if return_agents else dirs
 
 
 def _worker_device(requested, i, n_gpu):
@@ -362,7 +457,17 @@ def main(argv=None):
     ap.add_argument("--eval-deferred", action="store_true",
                     help="evaluations: a point only keeps the policy of the moment; all pending points run later as ONE mn_rollout_iqn_groups launch on tau streams of "
                          "their own (iqn/deferred_eval.py).  With --n-evals 300: the reference's evaluation density")
+    ap.add_argument("--together", action="store_true",
+                    help="train the trials that differ only in their seed in lockstep in one process, up to 64 at a time: their gradient steps share three launches per "
+                         "step (forward / backward, reduction, clip + Adam with the seed as a grid dimension: mn_iqn_group_train_step); every seed's files equal the "
+                         "sequential run's.  Not with --torch-train, --shared-learner, -P > 1 or torch.distributed.run; a trial without companions runs as without "
+                         "the option")
     args = ap.parse_args(argv)
+    if args.together:
+        refused = [k for k, on in (("torch_train", args.torch_train), ("shared", args.shared_learner), ("procs", args.num_procs > 1),
+                                   ("world", int(os.environ.get("WORLD_SIZE", "1")) > 1)) if on]
+        if refused:
+            raise SystemExit("train_iqn: " + TOGETHER_REFUSALS[refused[0]])
     params = json.load(args.config_file)
     if args.dry_run:
         n_envs, batch, replay = resolve_budget_args(args.env_budget, args.n_envs, args.batch, args.replay)
@@ -377,6 +482,10 @@ def main(argv=None):
             print(json.dumps(dict(seed=p["seed"], n_envs=n_envs, batch=batch, replay=plan.get("replay", replay), env_budget=args.env_budget,
                                   eval_deferred=args.eval_deferred or args.env_budget == "reference",
                                   episode_log=(args.env_budget == "reference") if args.episode_log is None else args.episode_log, plan=plan)))
+        if args.together:
+            trials = trial_params(params)
+            print(json.dumps(dict(together=[dict(group=k, seeds=[trials[i]["seed"] for i in g], grouped_gradient_launches=len(g) > 1)
+                                            for k, g in enumerate(group_trials(trials))])))
         return
     import torch
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
@@ -412,6 +521,18 @@ def main(argv=None):
             for j in jobs:
                 j.get()
             pool.join()
+        return
+    if args.together:
+        import time
+        for g in group_trials(trials):
+            t0 = time.time()
+            if len(g) > 1:
+                seeds = [trials[i]["seed"] for i in g]
+                print(f"[train_iqn] seeds {seeds} train together: three launches per gradient step for the {len(g)} of them", flush=True)
+                dirs = run_trials_together(device, [trials[i] for i in g], args.n_envs, verbose=True, **kw)
+                print(f"[train_iqn] seeds {seeds}: {time.time() - t0:.1f} s -> {os.path.dirname(dirs[0])}", flush=True)
+            else:
+                run_trial(device, trials[g[0]], args.n_envs, verbose=True, **kw)
         return
     for p in trials:
         run_trial(device, p, args.n_envs, rank, world, args.shared_learner, verbose=True, **kw)

@@ -712,6 +712,39 @@ int mn_dqn_group_train_steps(mn_dqn_group *g, int64_t ring_size, const int64_t *
                              int32_t batch, int32_t n_steps, float gamma, double lr, double beta1, double beta2, double eps, double max_norm,
                              void *stream);
 
+/* MANY IQN LEARNERS per launch: G independent IQN learners with common hyper-parameters (the seeds of one config) take their gradient step in THREE launches
+ * on the caller's stream, the learner being the second grid dimension of each: forward / backward (batch / 2 x G workgroups, every workgroup computing the TD
+ * targets of its own two batch elements), the fixed-order reduction (280 x G) and clip + Adam (140 x G).  These are the forms of the single step in which no
+ * workgroup waits for another workgroup of its launch, so a grouped launch may be larger than the device; the fused one- and two-launch forms of
+ * mn_iqn_train_step have no grouped counterpart.  The kernels inline the same bodies as the single calls: EVERY learner is bit for bit what mn_iqn_train_step
+ * (any of its forms) leaves from the same state -- loss, parameters, clipped gradient, moments, step counter, generator state, the drawn rows and taus -- and
+ * grouped and single calls may be interleaved on one learner in any order: the hand-off epoch, the tickets and the staging tag live in the learner's own
+ * workspace.  A grouped step stages nothing (MN_TRAIN_STAGE_NEXT has no grouped form) and marks the workspace "nothing staged"; mn_iqn_train_set_mode and the
+ * MN_TRAIN_* flags do not apply.
+ * mn_iqn_learner: the device pointers of ONE learner -- the pointer arguments of mn_iqn_train_step of the same names (grad = grad_out, loss = loss_out, step =
+ * step_dev); caller-owned, alive as long as the group is used.  workspace: that learner's own, mn_iqn_train_workspace_floats(batch) floats, initialised by
+ * mn_iqn_train_workspace_init.  rng_state, idx_out and taus_out may be NULL in a group that is only ever called with given batches.
+ * mn_iqn_group_create validates on the host, uploads the pointer table once (one allocation, one synchronous copy) and returns the handle.  MN_ERR_INVALID:
+ * n_learners outside 1..MN_IQN_MAX_LEARNERS, batch odd, < 2 or > 1024, a NULL among the required pointers, or two learners that alias -- a buffer one learner
+ * writes (params_local, grad, exp_avg, exp_avg_sq over their 35 785 floats, the workspace over its floats, loss, step, and where given rng_state [2] u64,
+ * idx_out [batch] i64, taus_out [2][batch][8] f32) overlapping a buffer another learner writes or the params_target another reads.  Learners may share a ring.
+ * mn_iqn_group_train_step: idx_dev [G][batch] i64, taus_target_dev / taus_local_dev [G][batch][8] f32 -- all three NULL: every learner draws its batch from
+ * its own rng_state over the first ring_size rows and advances it exactly as mn_iqn_train_step does; all three given: the generator states are left alone.
+ * MN_ERR_INVALID without launching: a NULL group, a mixed NULL / non-NULL triple, ring_size < batch or >= 2^31 when drawing, drawing in a group with a learner
+ * without rng_state.  No allocation, no synchronisation.  The target networks are copied by the caller BETWEEN calls. */
+typedef struct mn_iqn_learner {      /* device pointers of ONE learner, caller-owned */
+    const float *ring_states, *ring_next_states; const int64_t *ring_actions; const float *ring_rewards, *ring_dones;
+    uint64_t *rng_state;             /* {seed, call counter}; may be NULL if the group is only ever called with given batches */
+    float *params_local; const float *params_target; float *workspace, *grad, *loss, *exp_avg, *exp_avg_sq; int32_t *step;
+    int64_t *idx_out; float *taus_out;      /* the drawn rows [batch] and taus [2][batch][8] of the last drawn step, or NULL */
+} mn_iqn_learner;
+typedef struct mn_iqn_group mn_iqn_group;
+#define MN_IQN_MAX_LEARNERS 64
+int mn_iqn_group_create(const mn_iqn_learner *learners_host, int32_t n_learners, int32_t batch, mn_iqn_group **out);
+int mn_iqn_group_destroy(mn_iqn_group *g);
+int mn_iqn_group_train_step(mn_iqn_group *g, int64_t ring_size, const int64_t *idx_dev, const float *taus_target_dev, const float *taus_local_dev, float gamma,
+                            double lr, double beta1, double beta2, double eps, double max_norm, void *stream);
+
 typedef struct mn_xchg mn_xchg;
 int mn_xchg_create(int32_t rank, int32_t world, mn_xchg **out);
 int mn_xchg_export(mn_xchg *x, void *handle_out);
