@@ -50,6 +50,14 @@ class MnIqnLearner(C.Structure):
 IQN_MAX_LEARNERS = 64      # MN_IQN_MAX_LEARNERS
 
 
+class MnIqnActor(C.Structure):
+    """mn_iqn_actor: the handles and device pointers of one IQN actor of a group (mn_iqn_actor_group_create); `weights` is a HOST array of 14 device pointers."""
+    _fields_ = [(n, C.c_void_p) for n in ("ctx", "weights", "rng_state", "draws", "ring_states", "ring_next_states", "ring_actions", "ring_rewards", "ring_dones")]
+
+
+IQN_MAX_ACTORS = 64      # MN_IQN_MAX_ACTORS
+
+
 class MarineNavHipError(RuntimeError):
     pass
 
@@ -146,6 +154,10 @@ SIGNATURES = [
     ("mn_iqn_group_create", C.c_int, [C.POINTER(MnIqnLearner), _i32, _i32, C.POINTER(_vp)]),
     ("mn_iqn_group_destroy", C.c_int, [_vp]),
     ("mn_iqn_group_train_step", C.c_int, [_vp, _i64, _vp, _vp, _vp, C.c_float] + [_dbl] * 5 + [_vp]),
+    ("mn_iqn_actor_group_create", C.c_int, [C.POINTER(MnIqnActor), _i32, _i32, C.POINTER(_vp)]),
+    ("mn_iqn_actor_group_destroy", C.c_int, [_vp]),
+    ("mn_iqn_actor_group_act", C.c_int, [_vp, _vp, C.c_float, C.c_float, _vp, _vp]),
+    ("mn_iqn_actor_group_append", C.c_int, [_vp] * 6 + [_i64, _i64, _vp]),
     ("mn_xchg_create", C.c_int, [_i32, _i32, C.POINTER(_vp)]),
     ("mn_xchg_export", C.c_int, [_vp, _vp]),
     ("mn_xchg_import", C.c_int, [_vp, _i32, _vp]),

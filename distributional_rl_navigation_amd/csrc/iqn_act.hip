@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "marinenav_hip.h"
+#include "iqn_actor_group.h"
 
 #define MN_IQN_VARIANT_DEFAULT 2
 
@@ -37,6 +38,7 @@ namespace {
 #include "iqn_act_exact.h"
 #include "iqn_act_split.h"
 #include "iqn_act_tiled.h"
+#include "iqn_act_group.h"
 
 // A kernel form = (kernel, dynamic LDS, workgroup size); the member of its family is set.  mn_iqn_create raises the LDS limit of every entry and
 // launch_act launches the entry form_of picks with that entry's size, so the registered and the launched size of a form are one number.
@@ -441,6 +443,119 @@ extern "C" int mn_iqn_act_rng(mn_iqn_ctx *c, const float *obs_dev, const float *
     if (!rng_state_dev) return MN_ERR_INVALID;
     return launch_act(c, obs_dev, nullptr, weights, qvals_dev, nullptr, eps, actions_dev, quantiles_dev, n, num_taus,
                       rng_state_dev, draws_dev, cvar_row_dev, cvar, stream);
+}
+
+// ---- many actors per launch (mn_iqn_actor_group_*; kernels: iqn_act_group.h; the append: replay.hip) -------------------------------------------------------
+static bool extents_overlap(const void *p, size_t np, const void *q, size_t nq) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + nq && b < a + np;
+}
+
+extern "C" int mn_iqn_actor_group_create(const mn_iqn_actor *actors_host, int32_t n_actors, int32_t rows_per_group, mn_iqn_actor_group **out) {
+    if (!out) return MN_ERR_INVALID;
+    *out = nullptr;
+    if (!actors_host || n_actors < 1 || n_actors > MN_IQN_MAX_ACTORS || rows_per_group < 1) return MN_ERR_INVALID;
+    if ((long)rows_per_group * (K_TAUS + 1) >= (1L << 32)) return MN_ERR_INVALID;      // 32-bit draw index, as a single call
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) return MN_ERR_NO_DEVICE;
+    const size_t draws_bytes = (size_t)rows_per_group * (K_TAUS + 1) * sizeof(float);
+    bool rings = true;
+    for (int g = 0; g < n_actors; ++g) {
+        const mn_iqn_actor &a = actors_host[g];
+        IqnWeights w;
+        if (!a.ctx || !load_weights(a.weights, &w) || !a.rng_state || !a.draws) return MN_ERR_INVALID;
+        if (a.ctx->device != dev || a.ctx->variant != 2 || a.ctx->tau_mode != 0) return MN_ERR_INVALID;
+        const void *ring[5] = {a.ring_states, a.ring_next_states, a.ring_actions, a.ring_rewards, a.ring_dones};
+        int given = 0;
+        for (const void *p : ring) given += p != nullptr;
+        if (given != 0 && given != 5) return MN_ERR_INVALID;
+        rings = rings && given == 5;
+        // actors that alias would race silently: nothing one actor writes may be what another writes
+        for (int h = 0; h < g; ++h) {
+            const mn_iqn_actor &b = actors_host[h];
+            if (a.ctx == b.ctx || extents_overlap(a.draws, draws_bytes, b.draws, draws_bytes) ||
+                extents_overlap(a.rng_state, 2 * sizeof(uint64_t), b.rng_state, 2 * sizeof(uint64_t)))
+                return MN_ERR_INVALID;
+            const void *other[5] = {b.ring_states, b.ring_next_states, b.ring_actions, b.ring_rewards, b.ring_dones};
+            for (const void *p : ring)
+                for (const void *q : other)
+                    if (p && p == q) return MN_ERR_INVALID;
+        }
+    }
+    if (!rings)      // (a group that only ever acts has no ring at all)
+        for (int g = 0; g < n_actors; ++g)
+            if (actors_host[g].ring_states) return MN_ERR_INVALID;
+    // ---- the device from here on: the grouped kernels' LDS limit, every context's greedy-row buffer, the table
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return MN_ERR_HIP;
+    for (const void *k : {(const void *)sp::iqn_group_act_kernel<false>, (const void *)sp::iqn_group_act_kernel<true>})
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sp::LDS_ACT_FLOATS * sizeof(float))) != hipSuccess) return MN_ERR_HIP;
+    mn_iqn_actor_group *grp = new mn_iqn_actor_group{};
+    grp->n_groups = n_actors; grp->rows = rows_per_group; grp->device = dev; grp->n_cu = prop.multiProcessorCount; grp->rings = rings;
+    std::vector<IqnActorRow> table(n_actors);
+    for (int g = 0; g < n_actors; ++g) {
+        const mn_iqn_actor &a = actors_host[g];
+        GreedyRows rows;
+        const int rc = greedy_rows_buffer(a.ctx, rows_per_group, &rows);
+        if (rc) { delete grp; return rc; }
+        grp->ctx[g] = a.ctx;
+        grp->rows_buf[g] = a.ctx->rows_buf;
+        IqnActorRow &r = table[g];
+        for (int i = 0; i < 14; ++i) r.weights[i] = a.weights[i];
+        r.consts = a.ctx->consts_sp; r.packed = a.ctx->packed_sp; r.rng_state = a.rng_state; r.draws = a.draws; r.rows_buf = a.ctx->rows_buf;
+        r.ring_states = a.ring_states; r.ring_next_states = a.ring_next_states; r.ring_actions = a.ring_actions;
+        r.ring_rewards = a.ring_rewards; r.ring_dones = a.ring_dones;
+    }
+    if (hipMalloc(reinterpret_cast<void **>(&grp->table_dev), sizeof(IqnActorRow) * n_actors) != hipSuccess ||
+        hipMemcpy(grp->table_dev, table.data(), sizeof(IqnActorRow) * n_actors, hipMemcpyHostToDevice) != hipSuccess) {
+        if (grp->table_dev) (void)hipFree(grp->table_dev);
+        delete grp;
+        return MN_ERR_HIP;
+    }
+    *out = grp;
+    return MN_OK;
+}
+
+extern "C" int mn_iqn_actor_group_destroy(mn_iqn_actor_group *g) {
+    if (!g) return MN_ERR_INVALID;
+    const hipError_t e = hipFree(g->table_dev);
+    delete g;
+    return e == hipSuccess ? MN_OK : MN_ERR_HIP;
+}
+
+// Workgroups per group of the grouped act launch.  Every workgroup that has a row copies the 154-KB image into LDS, one workgroup per CU at a time: G x
+// act_grid(n) workgroups can be several rounds of CUs that each pay that copy again, so a group gets its share of the CUs (results do not depend on it).
+// mn_iqn_set_grid on the FIRST actor's context replaces the share by its own cap (measurements: scripts/iqn_group_collect_bench.py).
+static int group_act_grid(const mn_iqn_actor_group *g) {
+    const int blocks = (g->rows + 7) / 8, share = g->n_cu / g->n_groups > 1 ? g->n_cu / g->n_groups : 1;
+    const int cap = g->ctx[0]->max_blocks > 0 ? g->ctx[0]->max_blocks : share;
+    return blocks < cap ? blocks : cap;
+}
+
+extern "C" int mn_iqn_actor_group_act(mn_iqn_actor_group *g, const float *obs_dev, float cvar, float eps, int32_t *actions_dev, void *stream) {
+    if (!g || !obs_dev || !actions_dev) return MN_ERR_INVALID;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != g->device) return MN_ERR_INVALID;
+    const int G = g->n_groups, n = g->rows;
+    for (int i = 0; i < G; ++i) {      // what a context's setters may have changed since the group was made
+        const mn_iqn_ctx *c = g->ctx[i];
+        if (c->variant != 2 || c->tau_mode != 0 || c->late.mask || c->greedy_rows != g->ctx[0]->greedy_rows || c->rows_buf != g->rows_buf[i]) return MN_ERR_INVALID;
+    }
+    const bool listed = g->ctx[0]->greedy_rows && eps > 0.f;
+    uint64_t stale = 0;
+    for (int i = 0; i < G; ++i)
+        if (g->ctx[i]->dirty_sp) { stale |= 1ull << i; g->ctx[i]->dirty_sp = false; }
+    hipStream_t s = (hipStream_t)stream;
+    const IqnActorRow *table = g->table_dev;
+    if (stale) hipLaunchKernelGGL(sp::iqn_group_consts_kernel, dim3(sp::CONST_BLOCKS, G), dim3(256), 0, s, table, stale);
+    const int pack_blocks = stale ? sp::PACK_BLOCKS : 0, rng_blocks = draw_blocks(g->ctx[0], ((long)n * (K_TAUS + 1) + 3) / 4);
+    hipLaunchKernelGGL(sp::iqn_group_prep_kernel, dim3(pack_blocks + rng_blocks, G), dim3(256), 0, s, table, stale, n, cvar, pack_blocks, eps, actions_dev,
+                       listed ? 1 : 0);
+    const dim3 grid(group_act_grid(g), G), block(64 * sp::WAVES);
+    const size_t lds = sp::LDS_ACT_FLOATS * sizeof(float);
+    if (listed) hipLaunchKernelGGL(sp::iqn_group_act_kernel<true>, grid, block, lds, s, table, obs_dev, eps, actions_dev, n);
+    else hipLaunchKernelGGL(sp::iqn_group_act_kernel<false>, grid, block, lds, s, table, obs_dev, eps, actions_dev, n);
+    return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
 }
 
 #include "mfma_probe.h"

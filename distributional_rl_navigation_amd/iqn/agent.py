@@ -136,17 +136,35 @@ class VecLoop:
         self._state = self._eps = None
         self._points, self._evaluate_now = (), False
 
-    def collect(self, it):
+    def eps_now(self):
+        """The exploration rate of the vector step that comes next."""
+        return self.agent.linear_eps(self.total_timesteps)
+
+    def _begin(self, it):
+        """What a vector step settles before it collects: its exploration rate and its evaluation points."""
         agent = self.agent
-        self._eps = eps = agent.linear_eps(self.total_timesteps)
+        self._eps = eps = self.eps_now()
         if self.eval_points is None:
             self._evaluate_now = self.eval_env is not None and cadence_tick(agent, self.train_every, self.eval_freq).evaluate      # (the state vec_collect's own tick sees)
             self._points = (None,) if self._evaluate_now else ()
         else:
             self._points = tuple(self.eval_points.get(it, ()))
             self._evaluate_now = self.eval_env is not None and len(self._points) > 0
-        self._state = agent.vec_collect(self.train_env, self.obs, eps, self.cvar, self.train_every)
+        return eps
+
+    def collect(self, it):
+        eps = self._begin(it)
+        self._state = self.agent.vec_collect(self.train_env, self.obs, eps, self.cvar, self.train_every)
         return self._state.due
+
+    def collect_given(self, it, obs, reward, done, info):
+        """`collect` for a vector step whose collect phase was done for this agent (iqn/group_collect.py: the act at `eps_now()`, the env step, the append
+        to this agent's ring -- `memory.advance` included -- and the resets in front, all on a stacked env): `obs` = this agent's rows for the next act,
+        `reward`, `done`, `info` = its rows of the step's outputs.  Calls neither `act_batch` nor the env; returns the cadence's tick as `collect` does."""
+        self._begin(it)
+        due = cadence_tick(self.agent, self.train_every)      # (behind the append, as vec_collect asks it)
+        self._state = VecStepState(obs, reward, done, info, due, False)
+        return due
 
     def finish(self, it, loss=None):
         agent, train_env, stats, episode_log, points, eps = self.agent, self.train_env, self.stats, self.episode_log, self._points, self._eps

@@ -42,6 +42,46 @@ def shard_seeds(n_envs, seed=0, first_index=0):
             & np.uint64(0xFFFFFFFF)).astype(np.uint32)
 
 
+def stacked_seeds(n_envs, seeds):
+    """Per-env seeds of a STACKED env: the rows of `len(seeds)` envs of `n_envs` rows each, one after the other -- rows [g n, (g + 1) n) are seeded as
+    `VecMarineNavEnv(n_envs, seed=seeds[g])` seeds its own (`shard_seeds`), so they generate that env's worlds bit for bit."""
+    return np.concatenate([shard_seeds(n_envs, s) for s in seeds])
+
+
+class StackedRows:
+    """The rows [g n, (g + 1) n) of a stacked `VecMarineNavEnv` -- one seed's envs among those of G seeds that share ONE handle (`stacked_seeds`) -- as
+    the train env of that seed's loop (`iqn.agent.VecLoop` with `collect_given`, `IQNAgent.vec_finish`): `n_envs`, `discount`, the seed's slice of the
+    stacked `reset()` (which runs once, at the first view that asks), `join_reset`.  The stacked env is stepped, reset and closed by its owner, once for all
+    views: `close` here does nothing."""
+
+    def __init__(self, stacked, group, n_envs):
+        self.stacked, self.group, self.n_envs = stacked, int(group), int(n_envs)
+        if self.n_envs < 1 or self.group < 0 or (self.group + 1) * self.n_envs > stacked.n_envs:
+            raise ValueError(f"StackedRows: rows [{self.group * self.n_envs}, {(self.group + 1) * self.n_envs}) are not rows of an env of {stacked.n_envs}")
+        self.device = stacked.device
+
+    @property
+    def discount(self):
+        return self.stacked.discount
+
+    @property
+    def rows(self):
+        return slice(self.group * self.n_envs, (self.group + 1) * self.n_envs)
+
+    def reset(self):
+        st = self.stacked
+        if not getattr(st, "_stack_was_reset", False):
+            st.reset()
+            st._stack_was_reset = True
+        return st.obs[self.rows]
+
+    def join_reset(self):
+        self.stacked.join_reset()
+
+    def close(self):
+        pass
+
+
 class VecMarineNavEnv:
     """n_envs independent MarineNavEnv instances stepped by one kernel launch.
 

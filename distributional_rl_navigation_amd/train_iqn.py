@@ -7,7 +7,7 @@ eval_freq, save_dir), same per-trial outputs (`trial_config.json`, `training_sch
 GPUs (independent learners per rank by default, `--shared-learner` for one IQN with an RCCL
 gradient all-reduce).
 
-    python -m distributional_rl_navigation_amd.train_iqn -C config_IQN.json [--n-envs 4096] [--env-budget reference] [--episode-log [full]] [--together] [--dry-run]
+    python -m distributional_rl_navigation_amd.train_iqn -C config_IQN.json [--n-envs 4096] [--env-budget reference] [--episode-log [full]] [--together [--stack-envs]] [--dry-run]
 
 Cadence.  The reference does one batch-32 gradient step per 4 env steps (replay ratio 8 sampled per generated
 transition).  Two modes (`--env-budget`):
@@ -209,7 +209,7 @@ class TrialRun:
                  grad_steps=None, torch_train=False, total_grad_steps=None, n_evals=None, cvar=1.0, precision="f64",
                  exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1,
                  eval_one_launch=False, eval_deferred=False, env_budget="learner", reference=None, episode_log=None, eval_config=None, max_eval_steps=1000,
-                 on_step=None):
+                 on_step=None, train_env=None):
         import torch
         from .iqn.agent import IQNAgent
         from .marinenav_env.vec_env import VecMarineNavEnv
@@ -245,8 +245,11 @@ class TrialRun:
                       f"transition (reference {plan['reference_replay_ratio']:.0f}); target copy every {plan['target_sync_grad_steps']} "
                       f"grad steps; evaluation every {plan['eval_every_vector_steps']} vector steps")
 
-        train_env = VecMarineNavEnv(n_envs, seed=params["seed"], first_index=rank * n_envs, schedule=TRAINING_SCHEDULE,
-                                    timestep_scale=plan["timestep_scale"], device=device, precision=precision)
+        if train_env is None:      # (given: this seed's rows of a stacked env, run_trials_together(stack_envs=True))
+            train_env = VecMarineNavEnv(n_envs, seed=params["seed"], first_index=rank * n_envs, schedule=TRAINING_SCHEDULE,
+                                        timestep_scale=plan["timestep_scale"], device=device, precision=precision)
+        elif train_env.n_envs != n_envs:
+            raise ValueError(f"the train env given holds {train_env.n_envs} rows; the plan is for {n_envs}")
         if eval_config is None:
             eval_config = create_eval_configs(device)
         if writer:
@@ -343,17 +346,39 @@ TOGETHER_REFUSALS = dict(
     torch_train="--together needs the fused HIP gradient step: there is no grouped form of the PyTorch step (--torch-train)",
     shared="--together trains independent learners, one per seed; a shared learner (--shared-learner) exchanges its gradient with other ranks, which has no grouped form",
     procs="--together runs the seeds in ONE process so that their gradient steps can share launches; -P > 1 would put them into separate processes",
-    world="--together is the single-process, single-GPU form; it is not combinable with torch.distributed.run (WORLD_SIZE > 1)")
+    world="--together is the single-process, single-GPU form; it is not combinable with torch.distributed.run (WORLD_SIZE > 1)",
+    stack_envs="--stack-envs stacks the envs of seeds that train together in one handle; it needs --together",
+    stack_n_step="--stack-envs appends 1-step transitions in one grouped launch; n_step > 1 keeps its window per seed and has no stacked form",
+    stack_shared_taus="--stack-envs acts with per-row taus in one grouped launch; launch-shared taus (--shared-taus) have no stacked form")
 
 
-def run_trials_together(device, trials, n_envs, on_step=None, return_agents=False, torch_train=False, shared=False, world=1, **kwargs):
+def stacked_train_env(device, trials, n_envs, env_budget="learner", batch=None, replay=None, grad_steps=None, total_grad_steps=None, n_evals=None, reference=None,
+                      precision="f64"):
+    """The ONE train env of trials that train together with stacked envs, and the rows per seed: `VecMarineNavEnv(G n, ...)` whose rows [g n, (g + 1) n)
+    are seeded, scheduled and scaled as trial g's own env of n rows is (`TrialRun`), so every row steps and resets as it does there."""
+    from .marinenav_env.vec_env import VecMarineNavEnv, stacked_seeds
+    n, batch, replay = resolve_budget_args(env_budget, n_envs, batch, replay)
+    p = trials[0]
+    plan = plan_cadence(p["total_timesteps"], p["eval_freq"], n, batch, grad_steps_per_vector_step=grad_steps, total_grad_steps=total_grad_steps, n_evals=n_evals,
+                        budget=env_budget, reference=reference)
+    env = VecMarineNavEnv(len(trials) * n, seeds=stacked_seeds(n, [t["seed"] for t in trials]), schedule=TRAINING_SCHEDULE, timestep_scale=plan["timestep_scale"],
+                          device=device, precision=precision)
+    return env, n
+
+
+def run_trials_together(device, trials, n_envs, on_step=None, return_agents=False, torch_train=False, shared=False, world=1, stack_envs=False, sync_every_step=None,
+                        **kwargs):
     """`run_trial` for several trials that differ only in their seed (one list of `group_trials`), in LOCKSTEP: per vector step every trial collects as it
     does alone -- its own envs, agent, exploration, generators, replay ring, episode log, UnderActGuard and hook -- then, if the cadence says train (the same
     for all: equal plans, equally full rings), the gradient steps behind that vector step run for ALL trials through one `LearnerGroup`
     (iqn/group_train.py: three launches per gradient step instead of one to three per trial); then every trial finishes the step -- target copy on its own
     cadence, resets, counters, evaluation points, log.  The order of launches per agent is `vec_step`'s, and every learner is bit for bit what it is alone,
     so each seed's directory holds what `run_trial` writes, with the same contents.  The device is synchronised once per vector step (see the loop).  `on_step`: None or one hook per trial; the other arguments as
-    `run_trial`'s.  Returns the trial directories (`return_agents`: and the agents)."""
+    `run_trial`'s.  Returns the trial directories (`return_agents`: and the agents).
+    `stack_envs`: the collect phase is shared too -- the seeds' envs are the rows of ONE handle (`stacked_train_env`) and per vector step there is one
+    act launch at the common exploration rate, one env step, one append into all rings, one reset launch in front (iqn/group_collect.py: `CollectorGroup`)
+    instead of one of each per seed; every seed then finishes the step on its own rows (`VecLoop.collect_given`).  Every seed's files stay what `run_trial`
+    writes.  Needs n_step = 1 and per-row taus.  `sync_every_step`: the device synchronisation per vector step (None: on with per-seed envs, off with stacked ones -- see the loop; results do not depend on it)."""
     import torch
     from .iqn.agent import VecLoop
     from .iqn.group_train import LearnerGroup
@@ -364,26 +389,53 @@ def run_trials_together(device, trials, n_envs, on_step=None, return_agents=Fals
     trials = list(trials)
     if len(group_trials(trials)) != 1:
         raise ValueError("trials that train together differ only in their seed, and are at most 64 (group_trials)")
+    if stack_envs:
+        if kwargs.get("n_step", 1) != 1:
+            raise ValueError(TOGETHER_REFUSALS["stack_n_step"])
+        if kwargs.get("shared_taus", False):
+            raise ValueError(TOGETHER_REFUSALS["stack_shared_taus"])
     hooks = list(on_step) if on_step is not None else [None] * len(trials)
-    runs = [TrialRun(device, p, n_envs, on_step=h, **kwargs) for p, h in zip(trials, hooks)]
+    stacked, views = None, [None] * len(trials)
+    if stack_envs:
+        from .iqn.group_collect import CollectorGroup
+        from .marinenav_env.vec_env import StackedRows
+        env_kw = {k: kwargs[k] for k in ("env_budget", "batch", "replay", "grad_steps", "total_grad_steps", "n_evals", "reference", "precision") if k in kwargs}
+        stacked, n_rows = stacked_train_env(device, trials, n_envs, **env_kw)
+        views = [StackedRows(stacked, g, n_rows) for g in range(len(trials))]
+    runs = [TrialRun(device, p, n_envs, on_step=h, train_env=v, **kwargs) for p, h, v in zip(trials, hooks, views)]
     plan = runs[0].plan
     assert all(r.plan == plan for r in runs)
-    loops, group = [], None
+    loops, group, collectors = [], None, None
     try:
         for r in runs:
             loops.append(VecLoop(r.agent, **r.learn_args))
         group = LearnerGroup([r.agent for r in runs])
+        if stack_envs:      # (behind the LearnerGroup: the fused trainer it makes re-allocates the networks' parameters into its flat buffers)
+            collectors = CollectorGroup([r.agent for r in runs], stacked)
+            obs, cvar = stacked.obs, runs[0].learn_args["cvar"]
         G = runs[0].agent.grad_steps_per_update
         for it in range(plan["vector_steps"]):
-            dues = [lp.collect(it) for lp in loops]
+            if stack_envs:
+                eps = loops[0].eps_now()
+                assert all(lp.eps_now() == eps for lp in loops), "the seeds of a group explore at one rate"
+                actions = collectors.act(obs, eps, cvar)
+                next_obs, reward, done, info = stacked.step(actions)
+                collectors.append(obs, actions, reward, next_obs, done)
+                obs = stacked.reset_done()
+                dues = [lp.collect_given(it, obs[v.rows], reward[v.rows], done[v.rows], info[v.rows]) for lp, v in zip(loops, views)]
+            else:
+                dues = [lp.collect(it) for lp in loops]
             assert all(d.train == dues[0].train for d in dues), "the seeds of a group train on one cadence"
             losses = group.train_many(G) if dues[0].train else None
             for k, lp in enumerate(loops):
                 lp.finish(it, None if losses is None else losses[k])
             # The host must not run ahead of the device here.  With the launches of several seeds -- each env with a reset stream of its own -- queued many vector
             # steps deep, the lockstep loop measured 4.1 ms per vector step for five seeds; with the queue drained once per vector step 1.25 ms (one seed alone:
-            # 0.68 ms).  One synchronisation per vector step of ALL seeds; it changes no result.
-            torch.cuda.synchronize(device)
+            # 0.68 ms).  One synchronisation per vector step of ALL seeds; it changes no result.  The stacked loop has ONE env handle and issues its collect on
+            # one stream: there the synchronisation only costs (five seeds: 1 005 -> 965 us per vector step at n = 80, 317 -> 281 us at n = 4 096, ranges
+            # apart; profiles/iqn_group_collect_bench.txt), so it runs without.
+            if sync_every_step if sync_every_step is not None else not stack_envs:
+                torch.cuda.synchronize(device)
         for lp in loops:
             lp.end()
     finally:
@@ -391,7 +443,11 @@ def run_trials_together(device, trials, n_envs, on_step=None, return_agents=Fals
             lp.close()
         if group is not None:
             group.close()
+        if collectors is not None:
+            collectors.close()
     dirs = [r.conclude() for r in runs]
+    if stacked is not None:
+        stacked.close()
     return (dirs, [r.agent for r in runs]) if return_agents else dirs
 
 
@@ -462,7 +518,15 @@ def main(argv=None):
                          "step (forward / backward, reduction, clip + Adam with the seed as a grid dimension: mn_iqn_group_train_step); every seed's files equal the "
                          "sequential run's.  Not with --torch-train, --shared-learner, -P > 1 or torch.distributed.run; a trial without companions runs as without "
                          "the option")
+    ap.add_argument("--stack-envs", action="store_true",
+                    help="with --together: the seeds' envs are the rows of ONE env handle and a vector step is one act launch, one env step, one replay append and one "
+                         "reset launch for all of them (mn_iqn_actor_group_act / _append) instead of one of each per seed; every seed's files stay equal to the "
+                         "sequential run's.  Not with --shared-taus")
     args = ap.parse_args(argv)
+    if args.stack_envs and not args.together:
+        raise SystemExit("train_iqn: " + TOGETHER_REFUSALS["stack_envs"])
+    if args.stack_envs and args.shared_taus:
+        raise SystemExit("train_iqn: " + TOGETHER_REFUSALS["stack_shared_taus"])
     if args.together:
         refused = [k for k, on in (("torch_train", args.torch_train), ("shared", args.shared_learner), ("procs", args.num_procs > 1),
                                    ("world", int(os.environ.get("WORLD_SIZE", "1")) > 1)) if on]
@@ -484,7 +548,8 @@ def main(argv=None):
                                   episode_log=(args.env_budget == "reference") if args.episode_log is None else args.episode_log, plan=plan)))
         if args.together:
             trials = trial_params(params)
-            print(json.dumps(dict(together=[dict(group=k, seeds=[trials[i]["seed"] for i in g], grouped_gradient_launches=len(g) > 1)
+            stacked = lambda g: dict(stacked_env_rows=len(g) * n_envs, rows_per_seed=n_envs) if args.stack_envs and len(g) > 1 else {}
+            print(json.dumps(dict(together=[dict(group=k, seeds=[trials[i]["seed"] for i in g], grouped_gradient_launches=len(g) > 1, **stacked(g))
                                             for k, g in enumerate(group_trials(trials))])))
         return
     import torch
@@ -529,7 +594,7 @@ def main(argv=None):
             if len(g) > 1:
                 seeds = [trials[i]["seed"] for i in g]
                 print(f"[train_iqn] seeds {seeds} train together: three launches per gradient step for the {len(g)} of them", flush=True)
-                dirs = run_trials_together(device, [trials[i] for i in g], args.n_envs, verbose=True, **kw)
+                dirs = run_trials_together(device, [trials[i] for i in g], args.n_envs, verbose=True, stack_envs=args.stack_envs, **kw)
                 print(f"[train_iqn] seeds {seeds}: {time.time() - t0:.1f} s -> {os.path.dirname(dirs[0])}", flush=True)
             else:
                 run_trial(device, trials[g[0]], args.n_envs, verbose=True, **kw)

@@ -745,6 +745,42 @@ int mn_iqn_group_destroy(mn_iqn_group *g);
 int mn_iqn_group_train_step(mn_iqn_group *g, int64_t ring_size, const int64_t *idx_dev, const float *taus_target_dev, const float *taus_local_dev, float gamma,
                             double lr, double beta1, double beta2, double eps, double max_norm, void *stream);
 
+/* MANY IQN ACTORS per launch: the act call and the replay append of G actors with one row count (the seeds of one config, stacked in ONE env handle of G n
+ * rows: actor g owns rows [g n, (g + 1) n)) in one launch each on the caller's stream, the actor being the second grid dimension.  The kernels run the single
+ * calls' own bodies: actor g gets, bit for bit, what mn_iqn_act_rng(ctx_g, obs + 26 g n, weights_g, rng_state_g, draws_g, NULL, cvar, eps, actions + g n,
+ * NULL, NULL, n, 32, stream) leaves -- the actions, the [33 n] draws keyed by the row's index INSIDE the group, the call counter + 1, the context's
+ * split-f16 image and constants rebuilt exactly when that context is stale (the stale contexts travel as a 64-bit mask argument), its stale flag cleared --
+ * so single and grouped calls may be interleaved on one context.  With mn_iqn_set_greedy_rows on (the default) and eps > 0 only the rows that do not explore
+ * run the network, each group listing its rows in its own context's buffer; with eps == 0 or the switch off every row runs.
+ * mn_iqn_actor: the pointers of ONE actor, caller-owned, alive while the group is used; weights is read at create (the 14 device pointers are copied into the
+ * group's device table).  The five ring pointers are mn_replay_append's and may ALL be NULL in EVERY actor of a group that only ever acts.
+ * mn_iqn_actor_group_create validates on the host, makes sure every context's greedy-row buffer holds rows_per_group rows and uploads the table once (one
+ * allocation, one synchronous copy); nothing allocates or synchronises afterwards.  MN_ERR_INVALID, before anything touches the device: n_actors outside
+ * 1..MN_IQN_MAX_ACTORS, rows_per_group < 1, a NULL among the required pointers, rings given in part, a context on another device than the current one, a
+ * context that is not variant 2 with per-row taus (tau mode 0), or two actors that share a context, overlap in draws or rng_state, or share a ring array.
+ * mn_iqn_actor_group_act: obs_dev [G n][26], actions_dev [G n].  MN_ERR_INVALID without launching: a NULL argument, another current device, a context whose
+ * variant or tau mode was changed, contexts that disagree on mn_iqn_set_greedy_rows, a context with late rows armed (mn_iqn_set_late_rows has no grouped
+ * form), or a context whose greedy-row buffer a larger single call has replaced since create.  Workgroups per group: min(ceil(n / 8), max(1, CUs / G)) --
+ * every workgroup with a row copies the 154-KB image into LDS, so a group gets its share of the CUs; mn_iqn_set_grid on the FIRST actor's context replaces
+ * the share by its own cap (results do not depend on the count).
+ * mn_iqn_actor_group_append: mn_replay_append per actor -- row i of group g goes to slot (ptr + i - first) mod capacity of ring g, first = max(0, n -
+ * capacity), rows below first are not stored: the bytes mn_step_append writes.  ptr and capacity are common to the group; the caller advances ptr.
+ * MN_ERR_INVALID: a group without rings, a NULL argument, capacity <= 0, ptr outside [0, capacity). */
+typedef struct mn_iqn_actor {        /* device pointers / handles of ONE actor, caller-owned */
+    mn_iqn_ctx *ctx;                 /* its act context: weight image, scale constants, greedy-row list, stale flag */
+    const float *const *weights;     /* host array of 14 device pointers, as mn_iqn_act */
+    uint64_t *rng_state;             /* {seed, call counter} */
+    float *draws;                    /* [33 * rows_per_group] */
+    float *ring_states, *ring_next_states; int64_t *ring_actions; float *ring_rewards, *ring_dones;
+} mn_iqn_actor;
+typedef struct mn_iqn_actor_group mn_iqn_actor_group;
+#define MN_IQN_MAX_ACTORS 64
+int mn_iqn_actor_group_create(const mn_iqn_actor *actors_host, int32_t n_actors, int32_t rows_per_group, mn_iqn_actor_group **out);
+int mn_iqn_actor_group_destroy(mn_iqn_actor_group *g);
+int mn_iqn_actor_group_act(mn_iqn_actor_group *g, const float *obs_dev, float cvar, float eps, int32_t *actions_dev, void *stream);
+int mn_iqn_actor_group_append(mn_iqn_actor_group *g, const float *obs_dev, const int32_t *actions_dev, const float *reward_dev,
+                              const float *next_obs_dev, const uint8_t *done_dev, int64_t ptr, int64_t capacity, void *stream);
+
 typedef struct mn_xchg mn_xchg;
 int mn_xchg_create(int32_t rank, int32_t world, mn_xchg **out);
 int mn_xchg_export(mn_xchg *x, void *handle_out);
