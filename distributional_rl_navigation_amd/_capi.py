@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libmarinenav_hip.so")
 
 MAX_CORES, MAX_OBS, NUM_BEAMS, OBS_DIM, NUM_ACTIONS, MAX_STAGES = 8, 10, 11, 26, 9, 8
 PRECISION_F64, PRECISION_MIXED = 0, 1
+RESET_IN_FRONT, RESET_UNDER_ACT, RESET_OWED = 0, 1, 2      # mn_reset_placement / mn_reset_done_next_act (include/marinenav_hip.h)
 QUERY_VELOCITY_GIVEN, QUERY_VELOCITY_FROM_CURRENT = 0, 1
 QUERY_FLAG_COLLISION, QUERY_FLAG_OUTSIDE, QUERY_FLAG_GOAL, QUERY_FLAG_BAD_ENV = 1, 2, 4, 128
 INFO_STRINGS = ("normal", "out of boundary", "too long episode", "collision", "reach goal")
@@ -95,9 +96,14 @@ SIGNATURES = [
     ("mn_random_actions", C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, _i32, _vp, _vp]),
     ("mn_reset_done", C.c_int, [_vp, _pf, _vp]),
     ("mn_reset_done_async", C.c_int, [_vp, _pf, _vp, C.POINTER(_vp), C.POINTER(C.c_uint32)]),
+    ("mn_reset_placement", _i32, [C.c_float, _i32, _i64, _i32, _i32, _i32]),
+    ("mn_reset_done_next_act", C.c_int, [_vp, _pf, _vp, C.c_float, _i32, _i32, C.POINTER(_vp), C.POINTER(C.c_uint32), _pi32]),
+    ("mn_set_reset_owed_max_rows", C.c_int, [_vp, _i32]),
+    ("mn_reset_is_owed", _i32, [_vp]),
     ("mn_reset_join", C.c_int, [_vp, _vp]),
     ("mn_set_reset_under_act_max", C.c_int, [_vp, _i32, C.POINTER(C.c_int64)]),
     ("mn_debug_side_delay_us", C.c_int, [_vp, _i32]),
+    ("mn_debug_read", C.c_int, [_vp, _i32, _vp, _i64]),
     ("mn_load_worlds", C.c_int, [_vp, _i32, _i32, _pi32, _pd, _pi32, _pd, _pi32, _pd, _pd, _pd, _pd, _pd, _pd, _pf, _vp]),
     ("mn_get_worlds", C.c_int, [_vp, _i32, _i32, _pi32, _pd, _pi32, _pd, _pi32, _pd, _pd, _pd, _pd, _pd, _pd]),
     ("mn_query_velocity", C.c_int, [_vp, _vp, _i32, _vp, _i64, _vp, _vp]),
@@ -177,6 +183,8 @@ SIGNATURES = [
     ("mn_iqn_refresh", C.c_int, [_vp, C.POINTER(C.c_void_p), _vp]),
     ("mn_iqn_act", C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_void_p), _vp, _vp, C.c_float, _vp, _vp, _i32, _i32, _vp]),
     ("mn_iqn_act_rng", C.c_int, [_vp, _vp, C.POINTER(C.c_void_p), _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _i32, _i32, _vp]),
+    ("mn_iqn_last_greedy_rows", C.c_int, [_vp, _vp, _pi32, _i32, _pi32]),
+    ("mn_iqn_act_rng_env", C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_void_p), _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _i32, _i32, _vp]),
     ("mn_replay_append", C.c_int, [_vp] * 10 + [_i64, _i64, _i64, _vp]),
     ("mn_episode_log", C.c_int, [_vp, _vp, _vp, _i32, _dbl, _i64, C.c_float] + [_vp] * 9 + [_i64, _vp, _vp]),
     ("mn_iqn_train_workspace_floats", C.c_int64, [_i32]),

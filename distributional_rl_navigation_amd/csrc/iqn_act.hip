@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "marinenav_hip.h"
+#include "mn_internal.h"
 #include "iqn_actor_group.h"
 
 #define MN_IQN_VARIANT_DEFAULT 2
@@ -189,6 +190,23 @@ static int greedy_rows_buffer(mn_iqn_ctx *c, int n, GreedyRows *out) {
     return MN_OK;
 }
 
+// The rows the last act launch with listed rows evaluated (test hook): *count_out of them, the first min(count, cap) indices in list_host (any order).
+// Synchronises `stream`.  Count 0 and MN_OK before the first such launch.
+extern "C" int mn_iqn_last_greedy_rows(mn_iqn_ctx *c, void *stream, int32_t *list_host, int32_t cap, int32_t *count_out) {
+    if (!c || !count_out || cap < 0 || (cap > 0 && !list_host)) return MN_ERR_INVALID;
+    *count_out = 0;
+    if (!c->rows_buf) return MN_OK;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return MN_ERR_HIP;
+    uint32_t w[4];
+    if (hipMemcpy(w, c->rows_buf, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) return MN_ERR_HIP;
+    const uint32_t count = w[w[2] & 1u];      // words[2]: the slot the last preparation launch counted in
+    if (count > (uint32_t)c->rows_cap) return MN_ERR_HIP;
+    *count_out = (int32_t)count;
+    const uint32_t k = count < (uint32_t)cap ? count : (uint32_t)cap;
+    if (k && hipMemcpy(list_host, c->rows_buf + 4, k * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return MN_ERR_HIP;
+    return MN_OK;
+}
+
 extern "C" int mn_iqn_set_tau_mode(mn_iqn_ctx *c, int32_t mode) {
     if (!c || mode < 0 || mode > 3) return MN_ERR_INVALID;
     c->tau_mode = mode;
@@ -319,7 +337,7 @@ static void pack_image(mn_iqn_ctx *c, const IqnWeights &w, hipStream_t s) {
 static int launch_act(mn_iqn_ctx *c, const float *obs_dev, const float *taus_dev, const float *const *weights, float *qvals_dev,
                       const float *explore_u_dev, float eps, int32_t *actions_dev, float *quantiles_dev, int32_t n,
                       int32_t num_taus, uint64_t *rng_state_dev, float *draws_dev, const float *cvar_row_dev, float cvar,
-                      void *stream) {
+                      void *stream, mn_handle *env = nullptr) {
     // ---- prologue: arguments, the launch's form, its armed late rows
     IqnWeights w;
     if (!c || !obs_dev || !load_weights(weights, &w) || (!qvals_dev && !actions_dev && !quantiles_dev)) return MN_ERR_INVALID;
@@ -346,6 +364,13 @@ static int launch_act(mn_iqn_ctx *c, const float *obs_dev, const float *taus_dev
         if (rc) return rc;
     }
     const Form &f = form_of(c, n, quantiles_dev != nullptr, late.mask != nullptr, listed);
+    // `env` (mn_iqn_act_rng_env) may owe the reset of its last step's finished envs: the split form's preparation launch takes it along (mn_prep_reset.hip);
+    // any other form reads its observations behind a plain reset launch
+    const bool fusable = f.split && rng && !shared;
+    if (env && !fusable) {
+        const int rc = mn_owed_reset_settle(env, s);
+        if (rc) return rc;
+    }
     const bool prof = c->prof_n < c->prof_max;
     if (prof) (void)hipEventRecord(c->ev[2 * c->prof_n], s);
 
@@ -362,7 +387,11 @@ static int launch_act(mn_iqn_ctx *c, const float *obs_dev, const float *taus_dev
                                (const float *)c->h1_sp, c->timg, c->taux);
     } else if (rng) {      // (n x 32 taus and n exploration uniforms, as float4 groups)
         const int rng_blocks = draw_blocks(c, ((long)n * (K_TAUS + 1) + 3) / 4);
-        if (f.split)
+        MnOwedReset owed;
+        if (fusable && env && mn_owed_reset_take(env, s, &owed))
+            mn_launch_prep_reset(owed, MnPrepLaunch{weights, c->consts_sp, c->packed_sp, pack_blocks != 0, rng_state_dev, draws_dev, n, cvar_row_dev, cvar, eps,
+                                                    listed ? actions_dev : nullptr, rows.list, rows.words, 32 * c->n_cu}, s);
+        else if (f.split)
             hipLaunchKernelGGL(sp::iqn_split_prep_kernel, dim3(pack_blocks + rng_blocks), dim3(256), 0, s, w, (const float *)c->consts_sp,
                                c->packed_sp, (const uint64_t *)rng_state_dev, draws_dev, n, cvar_row_dev, cvar, pack_blocks, eps, listed ? actions_dev : nullptr,
                                rows);
@@ -443,6 +472,14 @@ extern "C" int mn_iqn_act_rng(mn_iqn_ctx *c, const float *obs_dev, const float *
     if (!rng_state_dev) return MN_ERR_INVALID;
     return launch_act(c, obs_dev, nullptr, weights, qvals_dev, nullptr, eps, actions_dev, quantiles_dev, n, num_taus,
                       rng_state_dev, draws_dev, cvar_row_dev, cvar, stream);
+}
+
+extern "C" int mn_iqn_act_rng_env(mn_iqn_ctx *c, mn_handle *env, const float *obs_dev, const float *const *weights, uint64_t *rng_state_dev,
+                                  float *draws_dev, const float *cvar_row_dev, float cvar, float eps, int32_t *actions_dev,
+                                  float *qvals_dev, float *quantiles_dev, int32_t n, int32_t num_taus, void *stream) {
+    if (!rng_state_dev) return MN_ERR_INVALID;
+    return launch_act(c, obs_dev, nullptr, weights, qvals_dev, nullptr, eps, actions_dev, quantiles_dev, n, num_taus,
+                      rng_state_dev, draws_dev, cvar_row_dev, cvar, stream, env);
 }
 
 // ---- many actors per launch (mn_iqn_actor_group_*; kernels: iqn_act_group.h; the append: replay.hip) -------------------------------------------------------

@@ -68,8 +68,9 @@ struct GreedyRows {
 // The random numbers of one act call: blocks [pack_blocks, gridDim.x) fill draws[0 .. 32 n) with tau = U[0,1) * cvar
 // (model.py:149-153; per-row cvar if cvar_row) and draws[32 n .. 33 n) with the exploration uniforms of IQNAgent.act
 // (agent.py:199).  ROWS: the thread that draws row e's uniform also settles the row -- actions[e] for an exploring row, an entry of rows.list for any
-// other; a wavefront's entries are counted by ballot and appended with one atomic.
-template <bool ROWS = false>
+// other; a wavefront's entries are counted by ballot and appended with one atomic.  BT = threads of a drawing block (the draws are counter-based: what
+// is drawn does not depend on it; 64 in the launch that also resets episodes, mn_prep_reset.hip); `pack_blocks` = the launch's blocks in front of them.
+template <bool ROWS = false, int BT = 256>
 __device__ __forceinline__ void draw_block(const uint64_t *__restrict__ rng_state, float *__restrict__ draws, int n,
                                            const float *__restrict__ cvar_row, float cvar, int pack_blocks, float eps = 0.f,
                                            int32_t *__restrict__ actions = nullptr, const GreedyRows rows = {}) {
@@ -81,8 +82,8 @@ __device__ __forceinline__ void draw_block(const uint64_t *__restrict__ rng_stat
         if ((int)blockIdx.x == pack_blocks && threadIdx.x == 0) { rows.words[slot ^ 1u] = 0u; rows.words[2] = slot; }
     }
     const long total4 = ((long)n * (K_TAUS + 1) + 3) / 4;          // float4 groups
-    const long stride = (long)((int)gridDim.x - pack_blocks) * 256;
-    for (long q = (long)((int)blockIdx.x - pack_blocks) * 256 + threadIdx.x; q < total4; q += stride) {
+    const long stride = (long)((int)gridDim.x - pack_blocks) * BT;
+    for (long q = (long)((int)blockIdx.x - pack_blocks) * BT + threadIdx.x; q < total4; q += stride) {
         float v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {

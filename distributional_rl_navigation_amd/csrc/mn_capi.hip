@@ -42,8 +42,15 @@ struct mn_handle {
     int32_t under_act_max = MN_RESET_UNDER_ACT_MAX_DEFAULT;      // mn_reset_done_async: above this peak the reset runs in front of the act kernel
     bool async_ready = false;              // side stream, events, `ready`, the peak words: all there
     int32_t side_delay_us = 0;             // mn_debug_side_delay_us (tests): a sleeping kernel in front of every reset launch on the side stream
+    // mn_reset_done_next_act: the last step's finished envs await their reset -- the next act call's preparation launch runs it (mn_iqn_act_rng_env), or
+    // whichever entry point touches the handle's state first settles it (settle_owed)
+    bool reset_owed = false;
+    float *owed_obs = nullptr;
+    hipStream_t owed_stream = nullptr;     // the stream the step ran on
+    int32_t owed_max_rows = MN_RESET_OWED_MAX_ROWS_DEFAULT;      // mn_set_reset_owed_max_rows
 };
 
+#define MT_WORDS 624      // one env's MT19937 row (mn_reset_body.h: MT_N)
 static thread_local std::string g_create_err;
 
 #define MN_HIP(h, call)                                                                                     \
@@ -60,6 +67,22 @@ static thread_local std::string g_create_err;
 static int fail(mn_handle *h, int code, const char *msg) {
     if (h) h->err = msg; else g_create_err = msg;
     return code;
+}
+
+// mn_reset_done's launch: the queue-driven reset of the last step's finished envs on `s`, inside the profiling window's event pairs
+static void launch_reset_done(mn_handle *h, float *obs_dev, hipStream_t s) {
+    const bool prof = h->prof_reset_n < h->prof_max;
+    if (prof) (void)hipEventRecord(h->ev_reset[2 * h->prof_reset_n], s);
+    mn_launch_reset(h->A, h->P, h->params.precision, h->A.queue_count + h->last_parity * MN_QWORDS, 0, h->A.queue, 0, obs_dev, s, h->peak_dev, h->seen_dev, true);
+    if (prof) { (void)hipEventRecord(h->ev_reset[2 * h->prof_reset_n + 1], s); h->prof_reset_n++; }
+}
+// An owed reset (mn_reset_done_next_act) as a plain reset launch on `s`.  The ONE place a debt is paid outside the act call that was meant to take it:
+// join_reset and on_device call it, and through them every entry point that reads or writes the handle's state.
+static void settle_owed(mn_handle *h, hipStream_t s) {
+    if (!h->reset_owed) return;
+    if (s != h->owed_stream) (void)hipStreamSynchronize(h->owed_stream);      // (another stream than the step's: nothing orders the two)
+    launch_reset_done(h, h->owed_obs, s);
+    h->reset_owed = false;
 }
 
 // Every entry point that touches device memory runs on the device the handle was created on: a caller that has
@@ -79,11 +102,22 @@ static int on_device(mn_handle *h) {
         if (hipEventSynchronize(h->ev_reset_end) != hipSuccess) return fail(h, MN_ERR_HIP, "waiting for the asynchronous reset failed");
         h->reset_pending = false;
     }
+    // ... and an owed one (mn_reset_done_next_act) that no act call has taken: launched now, on the stream its step ran on, and waited for
+    if (h->reset_owed) {
+        const hipStream_t s = h->owed_stream;
+        settle_owed(h, s);
+        if (hipStreamSynchronize(s) != hipSuccess) return fail(h, MN_ERR_HIP, "waiting for the owed reset failed");
+    }
     return MN_OK;
 }
-// stream-side join: everything enqueued on `s` from here on runs after the asynchronous reset
+// stream-side join: everything enqueued on `s` from here on runs after the asynchronous reset, and after an owed one, which is launched here
 static void join_reset(mn_handle *h, hipStream_t s) {
-    if (h && h->reset_pending) {
+    if (!h) return;
+    if (h->reset_owed) {
+        int cur = -1;
+        if (hipGetDevice(&cur) == hipSuccess && cur == h->device) settle_owed(h, s);      // (a foreign device: on_device reports it, nothing was launched)
+    }
+    if (h->reset_pending) {
         if (hipStreamWaitEvent(s, h->ev_reset_end, 0) == hipSuccess) h->reset_pending = false;
     }
 }
@@ -176,6 +210,7 @@ extern "C" int mn_destroy(mn_handle *h) {
     int cur = -1;
     const bool moved = hipGetDevice(&cur) == hipSuccess && h->device >= 0 && cur != h->device;
     if (moved) (void)hipSetDevice(h->device);   // free on the owning device, then restore the caller's
+    if (h->reset_owed) { const hipStream_t s = h->owed_stream; settle_owed(h, s); (void)hipStreamSynchronize(s); }      // the caller's obs buffer gets its rows
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->ev_reset) (void)hipEventDestroy(e);
     if (h->side) { (void)hipStreamSynchronize(h->side); (void)hipStreamDestroy(h->side); }
@@ -252,6 +287,7 @@ extern "C" int32_t mn_num_envs(const mn_handle *h) { return h ? h->A.n : 0; }
 extern "C" int mn_set_params(mn_handle *h, const mn_params *p) {
     if (!h || !p) return MN_ERR_INVALID;
     if (p->precision != h->params.precision) return fail(h, MN_ERR_INVALID, "precision is fixed at mn_create");
+    if (h->reset_owed) MN_ON_DEVICE(h);      // an owed reset runs with the parameters of its step
     return derive(h, *p);
 }
 
@@ -276,6 +312,7 @@ extern "C" int mn_set_schedule(mn_handle *h, int32_t n, const int64_t *ts, const
                                const double *md, double timestep_scale) {
     if (!h || n < 0 || n > MN_MAX_STAGES) return fail(h, MN_ERR_INVALID, "schedule: 0..8 stages");
     if (n > 0 && (!ts || !nc || !no || !md)) return MN_ERR_INVALID;
+    if (h->reset_owed) MN_ON_DEVICE(h);      // an owed reset runs with the schedule of its step
     for (int i = 0; i < n; ++i) {
         if (nc[i] < 0 || nc[i] > MN_MAX_CORES || no[i] < 0 || no[i] > MN_MAX_OBS) return fail(h, MN_ERR_INVALID, "schedule world size exceeds capacity (8 cores, 10 obstacles)");
         h->P.sched_t[i] = ts[i]; h->P.sched_nc[i] = nc[i]; h->P.sched_no[i] = no[i]; h->P.sched_md[i] = md[i];
@@ -585,7 +622,19 @@ extern "C" int mn_set_debug_skip(mn_handle *h, int32_t mask) {
 // (a latency chain that leaves the chip idle when it runs alone) but not thousands.  So the launch goes under the act kernel only while the last
 // reset launch the host has seen started at most `under_act_max` episodes (mn_set_reset_under_act_max; the count arrives through a host-mapped word,
 // no synchronisation); otherwise this IS mn_reset_done and *ready_out is NULL.
-extern "C" int mn_reset_done_async(mn_handle *h, float *obs_dev, void *stream, const uint32_t **ready_out, uint32_t *tick_out) {
+// The rule of mn_reset_done_next_act (include/marinenav_hip.h)
+extern "C" int32_t mn_reset_placement(float eps, int32_t n_rows, int64_t peak, int32_t under_act_max, int32_t owed_max_rows, int32_t fallback) {
+    if (under_act_max == 0x7fffffff) return MN_RESET_UNDER_ACT;      // forced: the preflight tests the under-act arrangement itself
+    const bool front = fallback != 0 || under_act_max < 0 || peak < 0 || peak > (int64_t)under_act_max;
+    if (owed_max_rows < 0) return front ? MN_RESET_IN_FRONT : MN_RESET_UNDER_ACT;
+    if (front) return MN_RESET_OWED;
+    if (!(eps >= 0.f) || n_rows <= 0) return MN_RESET_UNDER_ACT;      // nothing known about the act launch
+    const double rows = (1.0 - (eps < 1.f ? (double)eps : 1.0)) * (double)n_rows;      // the rows that do not explore: the ones the launch evaluates
+    return rows <= (double)owed_max_rows ? MN_RESET_OWED : MN_RESET_UNDER_ACT;
+}
+
+static int reset_done_placed(mn_handle *h, float *obs_dev, void *stream, bool next_act, float eps, int32_t n_rows, int32_t fallback,
+                             const uint32_t **ready_out, uint32_t *tick_out, int32_t *placement_out) {
     if (!h || !obs_dev || !ready_out || !tick_out) return MN_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     join_reset(h, s);
@@ -616,11 +665,17 @@ extern "C" int mn_reset_done_async(mn_handle *h, float *obs_dev, void *stream, c
     // the estimate: the launches' own decaying peak of their episode counts, as of the last launch whose word has arrived (the host may run several
     // launches ahead of the device) -- a burst of episode ends keeps the resets in front for ~20 vector steps
     const uint32_t seen = *h->seen_host;
-    if (h->under_act_max < 0 || (h->under_act_max != 0x7fffffff && (seen == 0xffffffffu || seen > (uint32_t)h->under_act_max))) {
-        const bool prof = h->prof_reset_n < h->prof_max;
-        if (prof) (void)hipEventRecord(h->ev_reset[2 * h->prof_reset_n], s);
-        mn_launch_reset(h->A, h->P, h->params.precision, h->A.queue_count + h->last_parity * MN_QWORDS, 0, h->A.queue, 0, obs_dev, s, h->peak_dev, h->seen_dev, true);
-        if (prof) { (void)hipEventRecord(h->ev_reset[2 * h->prof_reset_n + 1], s); h->prof_reset_n++; }
+    // (mn_reset_done_async knows nothing of the next act call and whoever calls it makes that call through mn_iqn_act_rng: never owed)
+    const int32_t place = mn_reset_placement(eps, n_rows, seen == 0xffffffffu ? -1 : (int64_t)seen, h->under_act_max, next_act ? h->owed_max_rows : -1, fallback);
+    if (placement_out) *placement_out = place;
+    if (place == MN_RESET_OWED) {
+        h->reset_owed = true;
+        h->owed_obs = obs_dev;
+        h->owed_stream = s;
+        return MN_OK;
+    }
+    if (place == MN_RESET_IN_FRONT) {
+        launch_reset_done(h, obs_dev, s);
         MN_HIP(h, hipGetLastError());
         return MN_OK;
     }
@@ -638,6 +693,47 @@ extern "C" int mn_reset_done_async(mn_handle *h, float *obs_dev, void *stream, c
     *ready_out = h->ready;
     *tick_out = h->tick;
     return MN_OK;
+}
+
+extern "C" int mn_reset_done_async(mn_handle *h, float *obs_dev, void *stream, const uint32_t **ready_out, uint32_t *tick_out) {
+    return reset_done_placed(h, obs_dev, stream, false, -1.f, 0, 0, ready_out, tick_out, nullptr);
+}
+
+extern "C" int mn_reset_done_next_act(mn_handle *h, float *obs_dev, void *stream, float eps, int32_t n_rows, int32_t fallback, const uint32_t **ready_out,
+                                      uint32_t *tick_out, int32_t *placement_out) {
+    if (!placement_out) return MN_ERR_INVALID;
+    return reset_done_placed(h, obs_dev, stream, true, eps, n_rows, fallback, ready_out, tick_out, placement_out);
+}
+
+// owed_max_rows: mn_reset_done_next_act owes the reset to the next act call while that call evaluates at most this many rows ((1 - eps) n_rows), and wherever
+// it would otherwise run in front of the act kernel (-1: never owed; 0x7fffffff: wherever the forced under-act mode does not rule)
+extern "C" int mn_set_reset_owed_max_rows(mn_handle *h, int32_t owed_max_rows) {
+    if (!h) return MN_ERR_INVALID;
+    h->owed_max_rows = owed_max_rows;
+    return MN_OK;
+}
+
+extern "C" int32_t mn_reset_is_owed(const mn_handle *h) { return h && h->reset_owed ? 1 : 0; }
+
+// The act launch's side of an owed reset (mn_internal.h): iqn_act.hip's launch routine takes the debt into its preparation launch, or settles it
+bool mn_owed_reset_take(mn_handle *h, hipStream_t s, MnOwedReset *out) {
+    if (!h || !h->reset_owed) return false;
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) return false;
+    if (s != h->owed_stream) (void)hipStreamSynchronize(h->owed_stream);
+    // (inside a profiling window the launch that runs the reset is timed as the handle's reset launch of this step, as mn_reset_done's is)
+    const bool prof = h->prof_reset_n < h->prof_max;
+    *out = MnOwedReset{&h->A, &h->P, h->params.precision, h->A.queue_count + h->last_parity * MN_QWORDS, h->A.queue, h->owed_obs, h->peak_dev, h->seen_dev,
+                       mn_prep_reset_blocks(*h->seen_host, h->A.n), prof ? h->ev_reset[2 * h->prof_reset_n] : nullptr,
+                       prof ? h->ev_reset[2 * h->prof_reset_n + 1] : nullptr};
+    if (prof) h->prof_reset_n++;
+    h->reset_owed = false;
+    return true;
+}
+int mn_owed_reset_settle(mn_handle *h, hipStream_t s) {
+    if (!h) return MN_OK;
+    join_reset(h, s);
+    return h->reset_owed ? fail(h, MN_ERR_INVALID, "the handle's owed reset lives on another HIP device") : MN_OK;
 }
 
 // under_act_max: mn_reset_done_async launches under the next act kernel while the decaying peak of the episodes started per reset launch (as of the last
@@ -667,10 +763,7 @@ extern "C" int mn_reset_done(mn_handle *h, float *obs_dev, void *stream) {
     if (!h || !obs_dev) return MN_ERR_INVALID;
     join_reset(h, (hipStream_t)stream);
     MN_ON_DEVICE(h);
-    const bool prof = h->prof_reset_n < h->prof_max;
-    if (prof) (void)hipEventRecord(h->ev_reset[2 * h->prof_reset_n], (hipStream_t)stream);
-    mn_launch_reset(h->A, h->P, h->params.precision, h->A.queue_count + h->last_parity * MN_QWORDS, 0, h->A.queue, 0, obs_dev, (hipStream_t)stream, h->peak_dev, h->seen_dev, true);
-    if (prof) { (void)hipEventRecord(h->ev_reset[2 * h->prof_reset_n + 1], (hipStream_t)stream); h->prof_reset_n++; }
+    launch_reset_done(h, obs_dev, (hipStream_t)stream);
     MN_HIP(h, hipGetLastError());
     return MN_OK;
 }
@@ -941,6 +1034,21 @@ extern "C" int mn_peek_next_double(mn_handle *h, int32_t first, int32_t count, d
     mn_launch_peek(h->A, first, count, h->peek_scratch, nullptr);
     MN_HIP(h, hipGetLastError());
     MN_HIP(h, hipMemcpy(out, h->peek_scratch, (size_t)count * 8, hipMemcpyDeviceToHost));
+    return MN_OK;
+}
+
+// Test hook: the first `bytes` bytes of one of the handle's raw device arrays, as they are (padding included) -- what no other accessor hands out: the RNG
+// rows and positions, and the compact tables the mixed-precision step kernel reads.  Waits for the device first, like the other host accessors.
+extern "C" int mn_debug_read(mn_handle *h, int32_t field, void *out, int64_t bytes) {
+    if (!h || !out || bytes < 0) return MN_ERR_INVALID;
+    MN_ON_DEVICE(h);
+    const size_t np = (size_t)h->A.npad;
+    const void *src[MN_DEBUG_N_FIELDS] = {h->A.mt, h->A.mt_pos, h->A.qcx, h->A.qcy, h->A.qcg, h->A.qox, h->A.qoy, h->A.qor};
+    const size_t size[MN_DEBUG_N_FIELDS] = {np * MT_WORDS * 4, np * 4, np * MN_MAX_CORES * 4, np * MN_MAX_CORES * 4, np * MN_MAX_CORES * 4,
+                                            np * MN_MAX_OBS * 4, np * MN_MAX_OBS * 4, np * MN_MAX_OBS * 4};
+    if (field < 0 || field >= MN_DEBUG_N_FIELDS || (size_t)bytes > size[field]) return fail(h, MN_ERR_INVALID, "mn_debug_read: unknown field, or more bytes than it has");
+    MN_HIP(h, hipDeviceSynchronize());
+    MN_HIP(h, hipMemcpy(out, src[field], (size_t)bytes, hipMemcpyDeviceToHost));
     return MN_OK;
 }
 

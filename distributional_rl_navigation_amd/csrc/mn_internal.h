@@ -136,6 +136,43 @@ void mn_launch_reset_under_act(const MnArrays &A, const MnDev &P, int precision,
                                uint32_t *ready, uint32_t tick, uint32_t *peak_dev, uint32_t *peak_host, hipStream_t s);
 void mn_launch_reset(const MnArrays &A, const MnDev &P, int precision, const uint32_t *count_dev, uint32_t count_host,
                      const int32_t *list_dev, int mode, float *obs, hipStream_t s, uint32_t *peak_dev = nullptr, uint32_t *peak_host = nullptr, bool sharded = false);
+// The resets of the last step and the preparation of the next act call in one launch (mn_prep_reset.hip; mn_iqn_act_rng_env).  MnOwedReset: the handle's
+// side -- what mn_launch_reset would be given, `blocks` reset wavefronts (mn_prep_reset_blocks); MnPrepLaunch: the act context's side -- what the
+// preparation launch of mn_iqn_act_rng would be given (`pack`: the weight image is stale; rows_words NULL: every row goes through the network).
+#define MN_PREP_RESET_MIN_BLOCKS 256
+#define MN_PREP_RESET_MAX_BLOCKS 8192
+struct MnOwedReset {
+    const MnArrays *A;
+    const MnDev *P;
+    int precision;
+    const uint32_t *count_dev;
+    const int32_t *list;
+    float *obs;
+    uint32_t *peak_dev, *peak_host;
+    int blocks;
+    hipEvent_t ev_begin, ev_end;      // the handle's profiling pair for this reset (mn_profile_begin .. mn_profile_reset_end), or NULL: recorded around the launch
+};
+struct MnPrepLaunch {
+    const float *const *weights;      // the 14 pointers of the C ABI
+    const float *consts;
+    uint32_t *packed;
+    bool pack;
+    const uint64_t *rng_state;
+    float *draws;
+    int n;
+    const float *cvar_row;
+    float cvar, eps;
+    int32_t *actions;
+    int32_t *rows_list;
+    uint32_t *rows_words;
+    int max_draw_blocks;              // of 64 threads
+};
+int mn_prep_reset_blocks(uint32_t seen, int n);
+void mn_launch_prep_reset(const MnOwedReset &o, const MnPrepLaunch &p, hipStream_t s);
+// the handle's owed reset (mn_capi.hip; mn_reset_done_next_act), for the act launch that takes it: mn_owed_reset_take fills *out and clears the debt (1), or
+// returns 0 when nothing is owed -- or the handle lives on another device, which the settling call then reports; mn_owed_reset_settle launches it on `s`
+bool mn_owed_reset_take(mn_handle *h, hipStream_t s, MnOwedReset *out);
+int mn_owed_reset_settle(mn_handle *h, hipStream_t s);
 void mn_launch_seed(const MnArrays &A, const uint32_t *seeds_dev, hipStream_t s);
 void mn_launch_mask_to_queue(const MnArrays &A, const uint8_t *mask, uint32_t *count, int32_t *list, hipStream_t s);
 void mn_launch_peek(const MnArrays &A, int first, int count, double *out_dev, hipStream_t s);

@@ -62,6 +62,7 @@ class UnderActGuard:
 
     def _fall_back(self, step, k):
         self.agent.reset_under_act = False
+        self.agent.reset_fallback = True      # (vec_step: from here on the resets may still ride in the next act call's preparation launch, never under the act kernel)
         self.env.join_reset()
         self._end_preflight()
         self.fallback = dict(step=int(step), timeouts=int(k))
@@ -100,7 +101,7 @@ def evaluation_from_traces(reward, done, info, action, discount, energy_tab, dt,
             [float(x) for x in tl["energy"]])
 
 
-VecStepState = namedtuple("VecStepState", "obs reward done info due under_act")      # IQNAgent.vec_collect -> vec_finish
+VecStepState = namedtuple("VecStepState", "obs reward done info due under_act eps fallback", defaults=(None, False))      # IQNAgent.vec_collect -> vec_finish
 
 
 class VecLoop:
@@ -219,6 +220,7 @@ class VecLoop:
         self.guard.close()
         agent.under_act_fallback = self.guard.fallback
         agent.reset_under_act = self.was_under_act
+        agent.reset_fallback = False
         if hasattr(self.train_env, "join_reset"):
             self.train_env.join_reset()
 
@@ -255,6 +257,7 @@ class IQNAgent(ReferenceLoopMixin):
                                                      # `obs` vec_step returns then has rows still being written: hand it back to vec_step, or call `train_env.join_reset()` before
                                                      # reading it.  On in learn_vec / train_iqn / bench.py; off by default for callers that look at `obs` between steps
         self.use_train_graph = False                 # opt-in: grad step replayed from a captured hipGraph (measured: no gain, the step is bound by kernel time, not launches)
+        self.reset_fallback = False                  # UnderActGuard went back to resets in front: vec_step then offers them to the next act call's preparation launch (mn_reset_done_next_act, fallback)
         self._late_acknowledged = 0                  # late-row time-outs of the act context that a loop has already answered by going back to resets in front (UnderActGuard)
         self.under_act_fallback = None               # learn_vec: dict(step, timeouts) if that happened in the last loop
         self._graph = None
@@ -688,7 +691,9 @@ class IQNAgent(ReferenceLoopMixin):
         if under_act:      # only the default acting form takes late rows: with any other the reset stays in front (no cross-stream events for nothing)
             from .fused_act import late_rows_possible
             under_act = late_rows_possible(self.qnetwork_local, obs.shape[0], self.shared_taus)
-        actions = self.act_batch(obs, eps, cvar, late_env=train_env if under_act or getattr(train_env, "late_rows", None) is not None else None)
+        fallback = (not under_act and bool(self.reset_fallback) and obs.is_cuda and self.use_fused_act and self.use_library_rng and self.n_step == 1
+                    and hasattr(train_env, "take_owed_reset") and train_env.reset_owed_max_rows >= 0)
+        actions = self.act_batch(obs, eps, cvar, late_env=train_env if under_act or fallback or getattr(train_env, "late_rows", None) is not None else None)
         if obs.is_cuda and hasattr(train_env, "step_append") and self.n_step == 1:
             # mn_step_append: the step kernel itself writes (obs_t, a, r, obs_t+1 incl. terminal observations, done)
             # into the replay ring -- no separate append launch, obs_t+1 is not re-read
@@ -702,9 +707,9 @@ class IQNAgent(ReferenceLoopMixin):
         due = cadence_tick(self, train_every)      # iqn/cadence.py: agent.py:126-147's rule (+ the target cadence in gradient steps)
         # first observations where done (`reset_under_act`: on the env's own stream, under the next call's act kernel, which takes those rows last -- launched BEHIND the
         # training event: a reset wavefront finds room beside an act workgroup, not beside a gradient step's, whose launches it would only hold up)
-        if not under_act:
+        if not (under_act or fallback):
             obs = train_env.reset_done()
-        return VecStepState(obs, reward, done, info, due, under_act)
+        return VecStepState(obs, reward, done, info, due, under_act or fallback, eps, fallback)
 
     def vec_finish(self, train_env, state, per_iter=None):
         """The part of `vec_step` behind the gradient steps: target copy if due, (resets under the next act: mn_reset_done_async), counters.  Returns the
@@ -713,8 +718,8 @@ class IQNAgent(ReferenceLoopMixin):
         obs = state.obs
         if state.due.sync:
             self._sync_target()
-        if state.under_act:
-            obs = train_env.reset_done(under_next_act=True)
+        if state.under_act:      # (eps and the row count of the next act call: the library may leave the resets to that call's preparation launch)
+            obs = train_env.reset_done(under_next_act=True, **({} if state.eps is None else dict(eps=state.eps, n_rows=obs.shape[0], fallback=state.fallback)))
         if self.current_timestep >= self.learning_starts:
             self.learning_timestep += 1
         self.current_timestep += per_iter

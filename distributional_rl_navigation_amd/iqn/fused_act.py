@@ -270,14 +270,20 @@ def fused_act(net, states, eps=0.0, cvar=1.0, taus=None, generator=None, want_qv
     if greedy_rows is not None:
         ctx.set_greedy_rows(greedy_rows)
     joined_after = _arm_late_rows(ctx, late_env, n, want_quantiles)      # (after set_tau_mode: the form of THIS launch decides)
+    # an env that left its resets to this call (reset_done(under_next_act=True, eps=...)): the library's own draws have a preparation launch that runs them;
+    # every other path reads `states` behind a plain reset launch
+    owed = late_env is not None and hasattr(late_env, "take_owed_reset") and late_env.take_owed_reset()
+    if owed and not (taus is None and rng is not None):
+        late_env.join_reset()
+        owed = False
     if taus is None and rng is not None:
         cv_row = cvar.to(device=dev, dtype=torch.float32).contiguous() if torch.is_tensor(cvar) else None
         draws = rng.draws(n, net.K)
-        rc = _capi.lib().mn_iqn_act_rng(ctx.h, _p(states), ctx.weights(net), _p(rng.state), _p(draws), _p(cv_row),
-                                        C.c_float(1.0 if cv_row is not None else float(cvar)), C.c_float(float(eps)),
-                                        _p(actions), _p(q), _p(quant), n, net.K, stream)
+        args = (_p(states), ctx.weights(net), _p(rng.state), _p(draws), _p(cv_row), C.c_float(1.0 if cv_row is not None else float(cvar)), C.c_float(float(eps)),
+                _p(actions), _p(q), _p(quant), n, net.K, stream)
+        rc = _capi.lib().mn_iqn_act_rng_env(ctx.h, late_env.h, *args) if owed else _capi.lib().mn_iqn_act_rng(ctx.h, *args)
         if rc:
-            raise _capi.MarineNavHipError(f"mn_iqn_act_rng failed ({rc})")
+            raise _capi.MarineNavHipError(f"mn_iqn_act_rng{'_env' if owed else ''} failed ({rc})")
         t = draws[:net.K].view(1, net.K).expand(n, net.K) if shared else draws[:n * net.K].view(n, net.K)
     elif shared:
         t1 = (torch.rand(net.K, device=dev, generator=generator) if taus is None else taus.to(device=dev, dtype=torch.float32).reshape(-1))

@@ -135,6 +135,9 @@ class VecMarineNavEnv:
         self.late_rows = None      # reset_done(under_next_act=True)
         self.reset_under_act_max = self.RESET_UNDER_ACT_MAX_DEFAULT
         self.reset_launches = [0, 0]      # ... how many of those calls the library ran [in front of, under] the next act kernel
+        self.reset_owed = False           # ... and whether the last one left its resets to the next act call (`eps` given: mn_reset_done_next_act)
+        self.resets_owed = 0              # how many did (they count in reset_launches[0]: such a reset runs in front of the act kernel, inside its preparation launch)
+        self.reset_owed_max_rows = self.RESET_OWED_MAX_ROWS_DEFAULT
 
     # ---- lifecycle ---------------------------------------------------------------------------
     def close(self):
@@ -296,19 +299,33 @@ class VecMarineNavEnv:
         self._check(self.L.mn_random_actions(int(action_seed), int(step), int(self.first_index), self.n_envs, _ptr(a), self._stream()))
         return a
 
-    def reset_done(self, keep_terminal_obs=False, under_next_act=False):
+    def reset_done(self, keep_terminal_obs=False, under_next_act=False, eps=None, n_rows=None, fallback=False):
         """The caller-side `if done: state = env.reset()` (agent.py:152-170) for the whole batch.
         Overwrites the rows of finished envs in ``self.obs`` with their first observation; with
         keep_terminal_obs the pre-reset observations are preserved in ``self.terminal_obs``.
         `under_next_act` (mn_reset_done_async): the reset runs on the handle's own stream, off the caller's critical path; ``self.late_rows``
         = (done flags, "row is final" words, tick) is what the next act launch needs to take the finished envs' rows last
         (`fused_act(..., late_rows=env.take_late_rows())`).  Until `join_reset()` -- or the next step / reset of this env -- the rows of
-        finished envs in ``self.obs`` must not be read by anything else on the caller's stream."""
+        finished envs in ``self.obs`` must not be read by anything else on the caller's stream.
+        `eps` (with `under_next_act`; mn_reset_done_next_act): the eps of the caller's next act call of `n_rows` rows (default: every env), and `fallback`: the
+        caller's check of the under-act arrangement has failed (never under the act kernel).  The library may then OWE the reset (``self.reset_owed``):
+        nothing is launched, and the next `fused_act(..., late_env=self)` runs it inside its preparation launch (set_reset_owed_max_rows has the rule);
+        anything else that touches the env settles it with a plain reset launch first."""
         if keep_terminal_obs:
             if self._terminal_obs is None:
                 self._terminal_obs = torch.empty_like(self.obs)
             self._terminal_obs.copy_(self.obs)
-        if under_next_act:
+        self.reset_owed = False
+        if under_next_act and eps is not None:
+            ready, tick, place = C.c_void_p(), C.c_uint32(), C.c_int32()
+            self._check(self.L.mn_reset_done_next_act(self.h, _ptr(self.obs), self._stream(), C.c_float(float(eps)), int(self.n_envs if n_rows is None else n_rows),
+                                                      int(bool(fallback)), C.byref(ready), C.byref(tick), C.byref(place)))
+            self.late_rows = (self.done, ready.value, tick.value) if ready.value else None
+            self.reset_owed = place.value == _capi.RESET_OWED
+            self.resets_owed += int(self.reset_owed)
+            if not fallback:      # (reset_launches counts the calls of a loop that asks for resets under the act kernel, as before)
+                self.reset_launches[1 if ready.value else 0] += 1
+        elif under_next_act:
             ready, tick = C.c_void_p(), C.c_uint32()
             self._check(self.L.mn_reset_done_async(self.h, _ptr(self.obs), self._stream(), C.byref(ready), C.byref(tick)))
             # (the library runs it in front after all -- ready NULL -- while many episodes end per vector step: set_reset_under_act_max)
@@ -329,9 +346,34 @@ class VecMarineNavEnv:
         self._check(self.L.mn_set_reset_under_act_max(self.h, self.reset_under_act_max, C.byref(last)))
         return last.value
 
+    RESET_OWED_MAX_ROWS_DEFAULT = 500      # = MN_RESET_OWED_MAX_ROWS_DEFAULT (include/marinenav_hip.h)
+
+    def set_reset_owed_max_rows(self, max_rows=None):
+        """`reset_done(under_next_act=True, eps=...)` leaves the reset to the next act call's preparation launch while that call evaluates at most this many
+        rows, (1 - eps) n_rows, and wherever the reset would otherwise run in front of the act kernel (None: the library's default, 500; -1: never; 2**31 - 1:
+        always, except while `set_reset_under_act_max(2**31 - 1)` forces every reset under the act kernel)."""
+        self.reset_owed_max_rows = self.RESET_OWED_MAX_ROWS_DEFAULT if max_rows is None else int(max_rows)
+        self._check(self.L.mn_set_reset_owed_max_rows(self.h, self.reset_owed_max_rows))
+
+    def take_owed_reset(self):
+        """True once if the last `reset_done(under_next_act=True, eps=...)` left its resets to the next act call (which then acts through mn_iqn_act_rng_env)."""
+        owed, self.reset_owed = getattr(self, "reset_owed", False), False
+        return owed
+
     def debug_side_delay_us(self, us):
         """Test hook (mn_debug_side_delay_us): every reset launch under the act kernel is held back by `us` microseconds on the handle's own stream."""
         self._check(self.L.mn_debug_side_delay_us(self.h, int(us)))
+
+    def debug_read(self, field):
+        """Test hook (mn_debug_read): a raw device array of the handle as a numpy array, padding included -- "mt" [npad, 624] u32, "mt_pos" [npad] i32, and the
+        compact tables "qcx" "qcy" [8, npad] i32, "qcg" [8, npad] f32, "qox" "qoy" [10, npad] i32, "qor" [10, npad] f32."""
+        npad = (self.n_envs + 255) // 256 * 256
+        code, shape, dt = {"mt": (0, (npad, 624), np.uint32), "mt_pos": (1, (npad,), np.int32), "qcx": (2, (MAX_CORES, npad), np.int32),
+                           "qcy": (3, (MAX_CORES, npad), np.int32), "qcg": (4, (MAX_CORES, npad), np.float32), "qox": (5, (MAX_OBS, npad), np.int32),
+                           "qoy": (6, (MAX_OBS, npad), np.int32), "qor": (7, (MAX_OBS, npad), np.float32)}[field]
+        out = np.zeros(shape, dt)
+        self._check(self.L.mn_debug_read(self.h, code, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
 
     def take_late_rows(self):
         """The pending `reset_done(under_next_act=True)`'s late rows for ONE act launch (None if there is none)."""
@@ -339,8 +381,9 @@ class VecMarineNavEnv:
         return lr
 
     def join_reset(self):
-        """Everything enqueued on the current stream from here on runs after a pending `reset_done(under_next_act=True)`."""
+        """Everything enqueued on the current stream from here on runs after a pending `reset_done(under_next_act=True)`; an owed one is launched here."""
         self.late_rows = None
+        self.reset_owed = False
         self._check(self.L.mn_reset_join(self.h, self._stream()))
 
     @property

@@ -217,6 +217,51 @@ int mn_reset_done_async(mn_handle *h, float *obs_dev, void *stream, const uint32
 int mn_reset_join(mn_handle *h, void *stream);
 int mn_set_reset_under_act_max(mn_handle *h, int32_t under_act_max, int64_t *last_seen);
 int mn_debug_side_delay_us(mn_handle *h, int32_t us);
+/* Test hook: the first `bytes` bytes of a raw device array of the handle, padding included (rows are padded to a multiple of 256 envs): MN_DEBUG_MT the
+ * MT19937 rows [npad][624] u32, MN_DEBUG_MT_POS their positions [npad] i32, MN_DEBUG_QCX .. MN_DEBUG_QOR the compact tables of the mixed-precision step
+ * kernel ([8][npad] cores: x, y as i32 fixed point, signed Gamma f32; [10][npad] obstacles: x, y, radius).  Waits for the device. */
+#define MN_DEBUG_MT 0
+#define MN_DEBUG_MT_POS 1
+#define MN_DEBUG_QCX 2
+#define MN_DEBUG_QCY 3
+#define MN_DEBUG_QCG 4
+#define MN_DEBUG_QOX 5
+#define MN_DEBUG_QOY 6
+#define MN_DEBUG_QOR 7
+#define MN_DEBUG_N_FIELDS 8
+int mn_debug_read(mn_handle *h, int32_t field, void *out, int64_t bytes);
+
+/* mn_reset_done_async for a caller that knows its next act call: `eps` and `n_rows` of that call (eps < 0: unknown) and whether its own check of the
+ * under-act arrangement has failed (`fallback` != 0: never under the act kernel).  *placement_out says where the reset of the last step's finished envs runs:
+ *   MN_RESET_IN_FRONT  launched here on `stream` (mn_reset_done);
+ *   MN_RESET_UNDER_ACT launched here on the handle's own stream, *ready_out / *tick_out as mn_reset_done_async;
+ *   MN_RESET_OWED      NOTHING is launched: the handle records that those envs await their reset, and the caller's next act call, made through
+ *                      mn_iqn_act_rng_env with this handle, runs the resets INSIDE its preparation launch -- reset wavefronts first in the grid, the call's
+ *                      draws (and the pack of a stale weight image) beside them -- and its act kernel without late rows: no second stream, no events.
+ *                      Every other entry point that reads or writes the handle's state settles the debt first with a plain reset launch (on its stream; the
+ *                      entry points that synchronise with the host wait for it), so the results are those of MN_RESET_IN_FRONT whatever the caller does next.
+ * mn_reset_placement is the rule, a pure function of (eps, n_rows, peak = the decaying episode peak or -1, under_act_max, owed_max_rows, fallback):
+ *   under_act_max == 0x7fffffff (forced: the callers' preflight)      -> UNDER_ACT
+ *   owed_max_rows < 0 (mn_set_reset_owed_max_rows; off)                -> as mn_reset_done_async
+ *   fallback, under_act_max < 0, peak unknown or above under_act_max   -> OWED (where mn_reset_done_async would go in front)
+ *   else: the act launch evaluates about (1 - eps) n_rows rows; at most owed_max_rows of them -- too short a launch to pay for two cross-stream
+ *   events -- -> OWED, more (or eps unknown) -> UNDER_ACT.
+ * MN_RESET_OWED_MAX_ROWS_DEFAULT = 500 rows: at 65 536 envs and ~300 episode ends per step the owed arm wins by 9.4 us per vector step at ~430 rows; at 3 277
+ * rows (eps 0.95) only by 1.6 us, which is inside the run-to-run spread sessions on this hardware have seen (up to 2.3 us), and it loses 6.6 us at 13 107
+ * (eps 0.8), where the act kernel is long enough to hide a reset launch beside it (profiles/reset_in_prep.txt).  Nothing was measured between 430 and 3 277
+ * rows, nor with thousands of episode ends per step, so the default stays just above the last point that is clearly won. */
+#define MN_RESET_IN_FRONT 0
+#define MN_RESET_UNDER_ACT 1
+#define MN_RESET_OWED 2
+#ifndef MN_RESET_OWED_MAX_ROWS_DEFAULT
+#define MN_RESET_OWED_MAX_ROWS_DEFAULT 500
+#endif
+int32_t mn_reset_placement(float eps, int32_t n_rows, int64_t peak, int32_t under_act_max, int32_t owed_max_rows, int32_t fallback);
+int mn_reset_done_next_act(mn_handle *h, float *obs_dev, void *stream, float eps, int32_t n_rows, int32_t fallback, const uint32_t **ready_out,
+                           uint32_t *tick_out, int32_t *placement_out);
+int mn_set_reset_owed_max_rows(mn_handle *h, int32_t owed_max_rows);
+/* 1 while a reset is owed (mn_reset_done_next_act chose MN_RESET_OWED and nothing has settled it yet), else 0 */
+int32_t mn_reset_is_owed(const mn_handle *h);
 
 /* MarineNavEnv.reset_with_eval_config (marinenav_env.py:467-555), world + pose fields, for `count`
  * consecutive envs starting at first_env.  Host arrays, row-major:
@@ -357,6 +402,9 @@ int mn_iqn_set_greedy_rows(mn_iqn_ctx *c, int32_t on);
  *   2: as 1, but always the wavefront-per-row form; 3: as 1, but always the environment-tiled form (A / B measurements, tests).
  * A row's result for GIVEN taus is the same function in both modes up to float32 rounding (tests). */
 int mn_iqn_set_tau_mode(mn_iqn_ctx *c, int32_t mode);
+/* Test hook: the rows the context's last act launch with listed rows (mn_iqn_set_greedy_rows) put through the network -- *count_out of them, the first
+ * min(count, cap) row indices in list_host (host memory; any order).  Synchronises `stream`; count 0 before the first such launch. */
+int mn_iqn_last_greedy_rows(mn_iqn_ctx *c, void *stream, int32_t *list_host, int32_t cap, int32_t *count_out);
 /* Late rows of the NEXT act launch of this context (mn_reset_done_async): mask_dev [n] u8 != 0 marks the rows whose observation another
  * stream is still writing, flags_dev [n] / tick say when a row is final (flags_dev[e] == tick; the row itself written through at agent
  * scope before the word).  The launch takes those rows last and reads them past the caches; results equal those of a launch behind the
@@ -417,6 +465,12 @@ int mn_iqn_act(mn_iqn_ctx *c, const float *obs_dev, const float *taus_dev, const
 int mn_iqn_act_rng(mn_iqn_ctx *c, const float *obs_dev, const float *const *weights, uint64_t *rng_state_dev,
                    float *draws_dev, const float *cvar_row_dev, float cvar, float eps, int32_t *actions_dev,
                    float *qvals_dev, float *quantiles_dev, int32_t n, int32_t num_taus, void *stream);
+/* mn_iqn_act_rng for the observations of `env`: if the handle owes a reset (mn_reset_done_next_act: MN_RESET_OWED) the call's preparation launch also
+ * runs it (mn_prep_reset.hip) -- for the acting form that has such a launch (variant 2, per-row taus); any other form settles the debt with a plain reset
+ * launch on `stream` first.  With nothing owed, or env == NULL, exactly mn_iqn_act_rng.  Same actions, draws and call counter either way. */
+int mn_iqn_act_rng_env(mn_iqn_ctx *c, mn_handle *env, const float *obs_dev, const float *const *weights, uint64_t *rng_state_dev,
+                       float *draws_dev, const float *cvar_row_dev, float cvar, float eps, int32_t *actions_dev,
+                       float *qvals_dev, float *quantiles_dev, int32_t n, int32_t num_taus, void *stream);
 /* IQN EPISODES in ONE launch: mn_rollout_policy with the learned policy (IQNAgent.evaluation_vec, agent.py:319-398).  Every env of `h` runs its
  * CURRENT episode -- starting from the observation in obs_dev -- for up to n_steps steps; per step it acts exactly as one mn_iqn_act_rng call of
  * context `ctx` on the n current rows at eps = 0 would for its row (taus of call counter rng_state_dev[1] + t, x the scalar `cvar` or, with
