@@ -59,6 +59,15 @@ class MnIqnActor(C.Structure):
 IQN_MAX_ACTORS = 64      # MN_IQN_MAX_ACTORS
 
 
+class MnDqnActor(C.Structure):
+    """mn_dqn_actor: the device pointers of one DQN actor of a group (mn_dqn_actor_group_create); `weights` is a HOST array of 18 device pointers."""
+    _fields_ = [("weights", C.c_void_p), ("image", C.c_void_p), ("seed", C.c_uint64)] + [(n, C.c_void_p) for n in (
+        "ring_states", "ring_next_states", "ring_actions", "ring_rewards", "ring_dones")]
+
+
+DQN_MAX_ACTORS = 64      # MN_DQN_MAX_ACTORS
+
+
 class MarineNavHipError(RuntimeError):
     pass
 
@@ -164,6 +173,12 @@ SIGNATURES = [
     ("mn_iqn_actor_group_destroy", C.c_int, [_vp]),
     ("mn_iqn_actor_group_act", C.c_int, [_vp, _vp, C.c_float, C.c_float, _vp, _vp]),
     ("mn_iqn_actor_group_append", C.c_int, [_vp] * 6 + [_i64, _i64, _vp]),
+    ("mn_dqn_act_rng", C.c_int, [_vp, C.POINTER(C.c_void_p), _vp, _i32, C.c_uint64, C.c_uint64, C.c_float, _vp, _vp, _vp, _i32, _vp]),
+    ("mn_dqn_actor_group_create", C.c_int, [C.POINTER(MnDqnActor), _i32, _i32, C.POINTER(_vp)]),
+    ("mn_dqn_actor_group_destroy", C.c_int, [_vp]),
+    ("mn_dqn_actor_group_set_grid", C.c_int, [_vp, _i32]),
+    ("mn_dqn_actor_group_act", C.c_int, [_vp, _vp, C.c_float, C.c_uint64, C.POINTER(C.c_uint64), _vp, _vp]),
+    ("mn_dqn_actor_group_append", C.c_int, [_vp] * 6 + [_i64, _i64, _vp]),
     ("mn_xchg_create", C.c_int, [_i32, _i32, C.POINTER(_vp)]),
     ("mn_xchg_export", C.c_int, [_vp, _vp]),
     ("mn_xchg_import", C.c_int, [_vp, _i32, _vp]),

@@ -10,6 +10,7 @@
 
 #include "marinenav_hip.h"
 #include "iqn_actor_group.h"
+#include "dqn_actor_group.h"
 
 namespace {
 
@@ -39,12 +40,12 @@ __global__ __launch_bounds__(256) void replay_append_kernel(const float2 *__rest
 }
 
 // replay_append_kernel for the G rings of an actor group: rows [g n_group, (g + 1) n_group) of the vector step go to ring g = blockIdx.y, taken from the
-// device table by the block's group alone (scalar loads); `n` of a group's rows are stored, from its row `first` on
-__global__ __launch_bounds__(256) void replay_append_groups_kernel(const IqnActorRow *__restrict__ table, const float2 *__restrict__ obs,
-                                                                   const int32_t *__restrict__ actions, const float *__restrict__ reward,
-                                                                   const float2 *__restrict__ next_obs, const uint8_t *__restrict__ done,
-                                                                   int64_t n_group, int64_t first, int64_t n, int64_t ptr, int64_t cap) {
-    const IqnActorRow &r = table[blockIdx.y];
+// device table by the block's group alone (scalar loads); `n` of a group's rows are stored, from its row `first` on.  Row = the table row of an IQN or a
+// DQN actor: both name their ring arrays alike.
+template <class Row>
+__device__ __forceinline__ void append_group_rows(const Row &r, const float2 *__restrict__ obs, const int32_t *__restrict__ actions,
+                                                  const float *__restrict__ reward, const float2 *__restrict__ next_obs,
+                                                  const uint8_t *__restrict__ done, int64_t n_group, int64_t first, int64_t n, int64_t ptr, int64_t cap) {
     float2 *__restrict__ r_states = reinterpret_cast<float2 *>(r.ring_states), *__restrict__ r_next = reinterpret_cast<float2 *>(r.ring_next_states);
     const int64_t base = (int64_t)blockIdx.y * n_group + first, total = n * ROW4;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -60,6 +61,36 @@ __global__ __launch_bounds__(256) void replay_append_groups_kernel(const IqnActo
             r.ring_dones[slot] = done[base + row] ? 1.0f : 0.0f;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void replay_append_groups_kernel(const IqnActorRow *__restrict__ table, const float2 *__restrict__ obs,
+                                                                   const int32_t *__restrict__ actions, const float *__restrict__ reward,
+                                                                   const float2 *__restrict__ next_obs, const uint8_t *__restrict__ done,
+                                                                   int64_t n_group, int64_t first, int64_t n, int64_t ptr, int64_t cap) {
+    append_group_rows(table[blockIdx.y], obs, actions, reward, next_obs, done, n_group, first, n, ptr, cap);
+}
+
+__global__ __launch_bounds__(256) void replay_append_dqn_groups_kernel(const DqnActorRow *__restrict__ table, const float2 *__restrict__ obs,
+                                                                       const int32_t *__restrict__ actions, const float *__restrict__ reward,
+                                                                       const float2 *__restrict__ next_obs, const uint8_t *__restrict__ done,
+                                                                       int64_t n_group, int64_t first, int64_t n, int64_t ptr, int64_t cap) {
+    append_group_rows(table[blockIdx.y], obs, actions, reward, next_obs, done, n_group, first, n, ptr, cap);
+}
+
+// the grouped append of a group object of either kind: argument checks, then `kernel` on grid (blocks, G)
+template <class Group, class Kernel>
+int launch_group_append(Kernel kernel, Group *g, const float *obs_dev, const int32_t *actions_dev, const float *reward_dev, const float *next_obs_dev,
+                        const uint8_t *done_dev, int64_t ptr, int64_t capacity, void *stream) {
+    if (!g || !g->rings || !obs_dev || !actions_dev || !reward_dev || !next_obs_dev || !done_dev) return MN_ERR_INVALID;
+    if (capacity <= 0 || ptr < 0 || ptr >= capacity) return MN_ERR_INVALID;
+    int64_t first = 0, n = g->rows;
+    if (n > capacity) { first = n - capacity; n = capacity; }   // only the newest `capacity` rows survive (deque maxlen)
+    int64_t blocks = (n * ROW4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks, (unsigned)g->n_groups), dim3(256), 0, (hipStream_t)stream, g->table_dev,
+                       reinterpret_cast<const float2 *>(obs_dev), actions_dev, reward_dev, reinterpret_cast<const float2 *>(next_obs_dev), done_dev,
+                       (int64_t)g->rows, first, n, ptr, capacity);
+    return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
 }
 
 }  // namespace
@@ -87,14 +118,11 @@ extern "C" int mn_replay_append(const float *obs_dev, const int32_t *actions_dev
 // mn_replay_append for every actor of a group in one launch: row i of group g goes to slot (ptr + i - first) mod capacity of ring g
 extern "C" int mn_iqn_actor_group_append(mn_iqn_actor_group *g, const float *obs_dev, const int32_t *actions_dev, const float *reward_dev,
                                          const float *next_obs_dev, const uint8_t *done_dev, int64_t ptr, int64_t capacity, void *stream) {
-    if (!g || !g->rings || !obs_dev || !actions_dev || !reward_dev || !next_obs_dev || !done_dev) return MN_ERR_INVALID;
-    if (capacity <= 0 || ptr < 0 || ptr >= capacity) return MN_ERR_INVALID;
-    int64_t first = 0, n = g->rows;
-    if (n > capacity) { first = n - capacity; n = capacity; }   // only the newest `capacity` rows survive (deque maxlen)
-    int64_t blocks = (n * ROW4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(replay_append_groups_kernel, dim3((unsigned)blocks, (unsigned)g->n_groups), dim3(256), 0, (hipStream_t)stream,
-                       (const IqnActorRow *)g->table_dev, reinterpret_cast<const float2 *>(obs_dev), actions_dev, reward_dev,
-                       reinterpret_cast<const float2 *>(next_obs_dev), done_dev, (int64_t)g->rows, first, n, ptr, capacity);
-    return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
+    return launch_group_append(replay_append_groups_kernel, g, obs_dev, actions_dev, reward_dev, next_obs_dev, done_dev, ptr, capacity, stream);
+}
+
+// the same into the rings of a DQN actor group
+extern "C" int mn_dqn_actor_group_append(mn_dqn_actor_group *g, const float *obs_dev, const int32_t *actions_dev, const float *reward_dev,
+                                         const float *next_obs_dev, const uint8_t *done_dev, int64_t ptr, int64_t capacity, void *stream) {
+    return launch_group_append(replay_append_dqn_groups_kernel, g, obs_dev, actions_dev, reward_dev, next_obs_dev, done_dev, ptr, capacity, stream);
 }

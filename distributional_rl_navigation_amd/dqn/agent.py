@@ -11,6 +11,11 @@ transition).
 Acting runs on the DQN act kernel (csrc/dqn_act.hip via DQNPolicy).  The gradient step is eager PyTorch by default; with
 `fused_train=True` (GPU, batch <= 256) every step drawn from the replay ring -- `train()` without an explicit batch, hence `learn_vec`
 -- is ONE launch of the fused HIP step (csrc/dqn_train.hip, dqn/fused_train.py) on the same parameters and the same Adam state.
+
+`fused_collect=True` (GPU, `policy.use_fused_act`) moves the collect phase onto the device: `act_batch(obs, eps)` is ONE launch that also draws the
+exploration (csrc/dqn_collect.hip, C-ABI mn_dqn_act_rng) from the library's counter-based generator under the seed `seed + 4321` and the call counter
+`act_calls` -- pinned to the host twin tests/dqn_rng_twin.py -- and the env step writes the transitions into the replay ring itself
+(`train_env.step_append`).  The draws differ from the torch.Generator's, so it is opt-in.
 """
 import copy
 import os
@@ -44,7 +49,7 @@ class DQNAgent:
     def __init__(self, state_size=26, action_size=9, learning_rate=1e-4, buffer_size=1_000_000, learning_starts=50000,
                  batch_size=32, tau=1.0, gamma=0.99, train_freq=4, gradient_steps=1, target_update_interval=10000,
                  exploration_fraction=0.1, exploration_initial_eps=1.0, exploration_final_eps=0.05, max_grad_norm=10,
-                 device="cuda:0", seed=0, fused_train=False):
+                 device="cuda:0", seed=0, fused_train=False, fused_collect=False):
         self.device = torch.device(device)
         torch.manual_seed(seed)                                    # sb3 set_random_seed (base_class.py) before the policy is built
         self.policy = DQNPolicy(state_size, action_size, device=device)
@@ -66,6 +71,8 @@ class DQNAgent:
         self.learning_rate = learning_rate
         self.fused_train = fused_train      # True: steps drawn from the ring run csrc/dqn_train.hip (GPU, batch <= 256)
         self._fused, self._train_path = None, "torch"
+        self.fused_collect = fused_collect      # True: act_batch is ONE mn_dqn_act_rng launch with the library's draws (GPU, policy.use_fused_act)
+        self.act_seed, self.act_calls = int(seed) + 4321, 0      # ... keyed by this seed and the number of act_batch calls so far
 
     # ---- the fused HIP gradient step -------------------------------------------------------------------------------
     def _fused_trainer(self):
@@ -154,7 +161,15 @@ class DQNAgent:
 
     @torch.no_grad()
     def act_batch(self, obs, eps):
-        """dqn.py:232-262 per env: a uniform random action with probability eps, else argmax_a Q."""
+        """dqn.py:232-262 per env: a uniform random action with probability eps, else argmax_a Q.  With `fused_collect` one launch whose draws are
+        `tests/dqn_rng_twin.dqn_actions(act_seed, act_calls, eps, greedy)`; `act_calls` advances by one per call, whatever eps is."""
+        if self.uses_fused_collect():
+            obs = obs.to(self.device, torch.float32).view(-1, self.policy.state_size).contiguous()
+            if not self.policy._fusable(obs):
+                raise RuntimeError("fused_collect: the policy cannot act through the fused kernel on this batch (empty, or another net_arch); there is no other form")
+            actions = self.policy.act_rng(obs, self.act_seed, self.act_calls, eps)
+            self.act_calls += 1
+            return actions
         greedy = self.policy.act_batch(obs)
         if eps <= 0.0:
             return greedy
@@ -162,6 +177,9 @@ class DQNAgent:
         u = torch.rand(n, device=obs.device, generator=self.gen)
         rnd = torch.randint(0, self.action_size, (n,), device=obs.device, dtype=torch.int32, generator=self.gen)
         return torch.where(u < eps, rnd, greedy)
+
+    def uses_fused_collect(self):
+        return self.fused_collect and self.device.type == "cuda" and self.policy.use_fused_act
 
     # ---- vector loop -----------------------------------------------------------------------------------------------
     def learn_vec(self, total_vector_steps, train_env, total_timesteps=None, callback=None):
@@ -176,8 +194,11 @@ class DQNAgent:
         for it in range(total_vector_steps):
             eps = self.exploration_rate(total_timesteps)
             a = self.act_batch(obs, eps)
-            nxt, reward, done, info = train_env.step(a)
-            self.memory.add_vector_step(obs, a, reward, nxt, done)
+            if self.uses_fused_collect():      # the step kernel appends the transitions itself
+                nxt, reward, done, info = train_env.step_append(a, obs, self.memory)
+            else:
+                nxt, reward, done, info = train_env.step(a)
+                self.memory.add_vector_step(obs, a, reward, nxt, done)
             obs = train_env.reset_done()
             self.num_timesteps += n
             if (it + 1) % tgt_every == 0:                                       # dqn.py:175-176, tau = 1 -> hard copy

@@ -147,6 +147,25 @@ class DQNPolicy(nn.Module):
         return q, a
 
     @torch.no_grad()
+    def act_rng(self, obs, seed, call_index, eps, want_u=False, want_q=False):
+        """Epsilon-greedy actions of a contiguous float32 device batch in ONE launch (C-ABI mn_dqn_act_rng): row e explores iff its uniform
+        u01(e, draw_keys(seed, call_index)) is <= eps.  Returns the int32 actions, or (actions, uniforms or None, Q-values or None) with `want_u` / `want_q`."""
+        import ctypes as C
+        from .. import _capi
+        st, repack = self._image(obs.device)
+        n = obs.shape[0]
+        a = torch.empty(n, dtype=torch.int32, device=obs.device)
+        u = torch.empty(n, dtype=torch.float32, device=obs.device) if want_u else None
+        q = torch.empty(n, self.action_size, dtype=torch.float32, device=obs.device) if want_q else None
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        mask = (1 << 64) - 1
+        rc = _capi.lib().mn_dqn_act_rng(p(obs), st["ptrs"], p(st["image"]), int(repack), int(seed) & mask, int(call_index) & mask, C.c_float(float(eps)),
+                                        p(u), p(q), p(a), n, _capi.stream_ptr(obs.device))
+        if rc:
+            raise _capi.MarineNavHipError(f"mn_dqn_act_rng failed ({rc})")
+        return (a, u, q) if want_u or want_q else a
+
+    @torch.no_grad()
     def export_image(self, out):
         """The weight image the HIP kernels would act with NOW, packed into `out` -- an [image_floats()] float32 tensor on the policy's device, 16-byte
         aligned -- on the current stream (C-ABI mn_dqn_export_image): a snapshot `rollout_dqn_groups` can act with later, whatever happens to the

@@ -3,7 +3,7 @@ path, with the interface of train_iqn.
 
     python -m distributional_rl_navigation_amd.train_dqn -C config_DQN.json [--n-envs 4096] [--batch 256] [--replay N]
         [--grad-steps G] [--total-grad-steps N] [--n-evals K] [--torch-train] [--eval-one-launch] [--eval-deferred] [--dry-run]
-        [--env-budget reference] [--episode-log [full]] [--train-steps-per-call {auto,1,K,multi}] [--together]
+        [--env-budget reference] [--episode-log [full]] [--train-steps-per-call {auto,1,K,multi}] [--fused-collect] [--together [--stack-envs]]
 
 Same JSON schema as train_iqn (agent, seed (list -> grid), total_timesteps, eval_freq, save_dir); the trials run one after another
 on one device, or -- `--together` -- the seeds of a config in lockstep with ONE launch per gradient step for all of them (`run_trials_together`,
@@ -22,6 +22,11 @@ policy.pth with q_net.* and q_net_target.*).
 `--env-budget reference`: the reference's own experiment instead of its learner budget in big batches -- total_timesteps env steps in vector steps of
 N = 80, one batch-32 gradient step per env step from learning_starts on (2 990 000), target copy every 10 000 of them, the 1 M-row ring, evaluations logged
 at the reference's timesteps (deferred), and training_log.npz from the device-side episode log (episode_log.py; `--episode-log [full]` elsewhere).
+
+`--fused-collect`: the collect phase on the device -- the act launch draws the exploration itself (C-ABI mn_dqn_act_rng, the library's counter-based
+generator instead of torch.Generator: other draws, hence opt-in) and the env step appends the transitions (mn_step_append).  `--together --stack-envs`:
+the seeds' envs are the rows of ONE handle and each vector step is one act, one step, one append and one reset launch for all of them
+(dqn/group_collect.py); every seed's files equal those of its own `--fused-collect` run.
 
 `--eval-deferred`: an evaluation point only keeps the policy of the moment (a weight image and the parameters, device copies on the training
 stream); the episodes of all pending points run later as ONE mn_rollout_dqn_groups launch (dqn/deferred_eval.py) and are logged as above -- the same
@@ -139,7 +144,7 @@ class TrialRun:
 
     def __init__(self, device, params, n_envs, batch=None, replay=None, grad_steps=None, total_grad_steps=None, n_evals=None, torch_train=False,
                  verbose=True, eval_one_launch=False, eval_deferred=False, eval_config=None, max_eval_steps=1000, env_budget="learner",
-                 reference=None, episode_log=None, on_step=None):
+                 reference=None, episode_log=None, on_step=None, fused_collect=False, train_env=None):
         from .dqn.agent import DQNAgent
         from .marinenav_env.vec_env import VecMarineNavEnv
         self.params, self.verbose, self.on_step, self.eval_one_launch, self.max_eval_steps = params, verbose, on_step, eval_one_launch, max_eval_steps
@@ -164,14 +169,16 @@ class TrialRun:
                   f"batch {batch} (reference: {plan['reference_grad_steps']} of 32); target copy every {plan['target_sync_grad_steps']} grad steps; "
                   f"evaluation every {plan['eval_every_vector_steps']} vector steps", flush=True)
 
-        self.train_env = VecMarineNavEnv(n_envs, seed=params["seed"], schedule=TRAINING_SCHEDULE, timestep_scale=plan["timestep_scale"], device=device,
-                                         precision="f64")
+        if train_env is None:      # (given: this seed's rows of a stacked env, run_trials_together(stack_envs=True))
+            train_env = VecMarineNavEnv(n_envs, seed=params["seed"], schedule=TRAINING_SCHEDULE, timestep_scale=plan["timestep_scale"], device=device,
+                                        precision="f64")
+        self.train_env = train_env
         if eval_config is None:
             eval_config = create_eval_configs(device)
         self.eval_config = eval_config
         self.eval_env = VecMarineNavEnv(len(eval_config), device=device, precision="f64")
         self.agent = agent = DQNAgent(26, 9, buffer_size=replay, batch_size=batch, learning_starts=0, device=device, seed=params["seed"] + 100,
-                                      fused_train=not torch_train)
+                                      fused_train=not torch_train, fused_collect=fused_collect)
         self.report_scale = params["total_timesteps"] / (plan["vector_steps"] * n_envs)      # evaluations.npz counts reference-scaled env steps
         self.log = dict(timesteps=[], rewards=[], times=[], energies=[], successes=[], actions=[])
         self.best = -np.inf
@@ -195,14 +202,30 @@ class TrialRun:
         agent, train_env, obs = self.agent, self.train_env, self.obs
         eps = exploration_rate(it, self.plan)
         a = agent.act_batch(obs, eps)
-        nxt, reward, done, info = train_env.step(a)
+        fused = agent.uses_fused_collect()
+        if fused:      # the step kernel appends the transitions itself
+            nxt, reward, done, info = train_env.step_append(a, obs, agent.memory)
+        else:
+            nxt, reward, done, info = train_env.step(a)
         if self.ep_log is not None:
             self.ep_log.step(reward, done, info, it, eps)
         if self.on_step is not None:
             self.on_step(it, dict(last=dict(reward=reward, done=done, info=info, eps=eps)))
-        agent.memory.add_vector_step(obs, a, reward, nxt, done)
+        if not fused:
+            agent.memory.add_vector_step(obs, a, reward, nxt, done)
         self.obs = train_env.reset_done()
         agent.num_timesteps += self.n_envs
+
+    def collect_given(self, it, obs, reward, done, info):
+        """What is left of `collect(it)` when the act, the env step, the append and the resets were made for this seed's rows of a stacked env
+        (`run_trials_together(stack_envs=True)`): the episode log, `on_step`, the timestep count.  `obs`: the rows' observations after the resets."""
+        eps = exploration_rate(it, self.plan)
+        if self.ep_log is not None:
+            self.ep_log.step(reward, done, info, it, eps)
+        if self.on_step is not None:
+            self.on_step(it, dict(last=dict(reward=reward, done=done, info=info, eps=eps)))
+        self.obs = obs
+        self.agent.num_timesteps += self.n_envs
 
     def trains_after(self, it):
         """Whether gradient steps follow vector step `it` (behind `collect(it)`): plan["grad_steps_per_vector_step"] of them, cut at the target copies that
@@ -260,7 +283,7 @@ class TrialRun:
 
 def run_trial(device, params, n_envs, batch=None, replay=None, grad_steps=None, total_grad_steps=None, n_evals=None, torch_train=False,
               verbose=True, eval_one_launch=False, eval_deferred=False, eval_config=None, max_eval_steps=1000, return_agent=False, env_budget="learner",
-              reference=None, episode_log=None, on_step=None, train_steps_per_call="auto"):
+              reference=None, episode_log=None, on_step=None, train_steps_per_call="auto", fused_collect=False):
     """train_sb3_model.py on the vector env for one trial of the config grid; returns the trial directory (`return_agent`: and the agent).
     `eval_one_launch`: each evaluation as one mn_rollout_dqn launch instead of one Python iteration per env step (same results).
     `eval_deferred` (True, or a dict of DeferredEvaluations arguments such as max_pending): an evaluation point keeps the policy of the moment and the
@@ -272,12 +295,15 @@ def run_trial(device, params, n_envs, batch=None, replay=None, grad_steps=None, 
     every vector step (device tensors).
     `train_steps_per_call` (`steps_per_call`): 1 -- one `agent.train()` per gradient step; "multi" -- the gradient steps behind a vector step as multi-step
     calls (`DQNAgent.train_many`), one per stretch between target copies (at batch <= 32 on the fused path one HIP call each, elsewhere the loop); K > 1 -- the
-    same with at most K steps per call; "auto" -- AUTO_TRAIN_STEPS_PER_CALL.  The same files either way."""
+    same with at most K steps per call; "auto" -- AUTO_TRAIN_STEPS_PER_CALL.  The same files either way.
+    `fused_collect`: the collect phase on the device (`DQNAgent(fused_collect=True)`): one exploring act launch with the library's draws, the append inside
+    the env step.  Other exploration draws than the default's, so other files."""
     from .dqn.agent import split_at_target_sync
     per_call = steps_per_call(train_steps_per_call)
     run = TrialRun(device, params, n_envs, batch=batch, replay=replay, grad_steps=grad_steps, total_grad_steps=total_grad_steps, n_evals=n_evals,
                    torch_train=torch_train, verbose=verbose, eval_one_launch=eval_one_launch, eval_deferred=eval_deferred, eval_config=eval_config,
-                   max_eval_steps=max_eval_steps, env_budget=env_budget, reference=reference, episode_log=episode_log, on_step=on_step)
+                   max_eval_steps=max_eval_steps, env_budget=env_budget, reference=reference, episode_log=episode_log, on_step=on_step,
+                   fused_collect=fused_collect)
     agent, plan = run.agent, run.plan
     G, sync_every = plan["grad_steps_per_vector_step"], plan["target_sync_grad_steps"]
     for it in range(plan["vector_steps"]):
@@ -310,31 +336,74 @@ def group_trials(trials, limit=None):
     return [idx[k:k + limit] for idx in by_key.values() for k in range(0, len(idx), limit)]
 
 
-def run_trials_together(device, trials, n_envs, torch_train=False, on_step=None, return_agents=False, train_steps_per_call="auto", **kwargs):
+TOGETHER_REFUSALS = dict(
+    torch_train="--together needs the fused HIP gradient step: there is no grouped form of the eager PyTorch step (--torch-train)",
+    stack_envs="--stack-envs stacks the envs of seeds that train together in one handle; it needs --together")
+
+
+def stacked_train_env(device, trials, n_envs, env_budget="learner", batch=None, replay=None, grad_steps=None, total_grad_steps=None, n_evals=None, reference=None):
+    """The ONE train env of trials that train together with stacked envs, and the rows per seed: `VecMarineNavEnv(G n, ...)` whose rows [g n, (g + 1) n)
+    are seeded, scheduled and scaled as trial g's own env of n rows is (`TrialRun`), so every row steps and resets as it does there."""
+    from .marinenav_env.vec_env import VecMarineNavEnv, stacked_seeds
+    n, batch, replay = resolve_budget_args(env_budget, n_envs, batch, replay)
+    plan = make_plan(trials[0], n, batch, grad_steps, total_grad_steps, n_evals, budget=env_budget, reference=reference)
+    env = VecMarineNavEnv(len(trials) * n, seeds=stacked_seeds(n, [t["seed"] for t in trials]), schedule=TRAINING_SCHEDULE, timestep_scale=plan["timestep_scale"],
+                          device=device, precision="f64")
+    return env, n
+
+
+def run_trials_together(device, trials, n_envs, torch_train=False, on_step=None, return_agents=False, train_steps_per_call="auto", stack_envs=False,
+                        **kwargs):
     """`run_trial` for several trials that differ only in their seed (one list of `group_trials`), in LOCKSTEP: per vector step every trial collects as it
     does alone -- its own envs, agent, exploration, generator, replay ring, episode log and hook -- then the gradient steps behind that vector step run for
     ALL trials through one `LearnerGroup` (dqn/group_train.py): one launch per gradient step, or one multi-step call per stretch between target copies,
     instead of one per trial; then every trial handles its evaluation points.  Every learner is bit for bit what it is alone, so each seed's directory
     holds what `run_trial` writes, with the same contents.  `on_step`: None or one hook per trial.  `train_steps_per_call` and the other arguments as
-    `run_trial`'s.  Returns the trial directories (`return_agents`: and the agents)."""
+    `run_trial`'s.  Returns the trial directories (`return_agents`: and the agents).
+    `stack_envs` (implies `fused_collect`): the collect phase is shared too -- the seeds' envs are the rows of ONE handle (`stacked_train_env`) and per vector
+    step there is one act launch at the common exploration rate, one env step, one append into all rings and one reset launch (dqn/group_collect.py:
+    `CollectorGroup`) instead of one chain per seed; every seed then finishes the step on its own rows (`TrialRun.collect_given`).  Every seed's files are
+    what `run_trial(fused_collect=True)` writes."""
+    import torch
     from .dqn.agent import split_at_target_sync
     from .dqn.group_train import LearnerGroup
     if torch_train:
         raise ValueError("training trials together needs the fused gradient step: there is no grouped form of the eager PyTorch step (torch_train)")
+    if stack_envs and torch.device(device).type != "cuda":
+        raise ValueError(f"stack_envs: the stacked collect runs on HIP kernels; device {device} has none")
     trials = list(trials)
     if len(group_trials(trials)) != 1:
         raise ValueError("trials that train together differ only in their seed, and are at most 64 (group_trials)")
     per_call = steps_per_call(train_steps_per_call)
     hooks = list(on_step) if on_step is not None else [None] * len(trials)
-    runs = [TrialRun(device, p, n_envs, on_step=h, **kwargs) for p, h in zip(trials, hooks)]
+    stacked, views, collectors = None, [None] * len(trials), None
+    if stack_envs:
+        from .dqn.group_collect import CollectorGroup
+        from .marinenav_env.vec_env import StackedRows
+        kwargs["fused_collect"] = True
+        env_kw = {k: kwargs[k] for k in ("env_budget", "batch", "replay", "grad_steps", "total_grad_steps", "n_evals", "reference") if k in kwargs}
+        stacked, n_rows = stacked_train_env(device, trials, n_envs, **env_kw)
+        views = [StackedRows(stacked, g, n_rows) for g in range(len(trials))]
+    runs = [TrialRun(device, p, n_envs, on_step=h, train_env=v, **kwargs) for p, h, v in zip(trials, hooks, views)]
     plan = runs[0].plan
     assert all(r.plan == plan for r in runs)
     group = LearnerGroup([r.agent for r in runs])
+    if stack_envs:      # (behind the LearnerGroup: the fused trainer it makes re-allocates the networks' parameters into its flat buffers)
+        collectors = CollectorGroup([r.agent for r in runs], stacked)
+        obs = stacked.obs
     G, sync_every = plan["grad_steps_per_vector_step"], plan["target_sync_grad_steps"]
     done = 0
     for it in range(plan["vector_steps"]):
-        for r in runs:
-            r.collect(it)
+        if stack_envs:
+            actions = collectors.act(obs, exploration_rate(it, plan))
+            next_obs, reward, ended, info = stacked.step(actions)
+            collectors.append(obs, actions, reward, next_obs, ended)
+            obs = stacked.reset_done()
+            for r, v in zip(runs, views):
+                r.collect_given(it, obs[v.rows], reward[v.rows], ended[v.rows], info[v.rows])
+        else:
+            for r in runs:
+                r.collect(it)
         trains = [r.trains_after(it) for r in runs]
         assert all(t == trains[0] for t in trains)      # (equal plans, equally full rings)
         if trains[0]:
@@ -354,6 +423,9 @@ def run_trials_together(device, trials, n_envs, torch_train=False, on_step=None,
             r.evaluate_points(it)
     dirs = [r.finish() for r in runs]
     group.close()
+    if collectors is not None:
+        collectors.close()
+        stacked.close()
     return (dirs, [r.agent for r in runs]) if return_agents else dirs
 
 
@@ -389,11 +461,20 @@ def main(argv=None):
                     help="train the trials that differ only in their seed in lockstep, up to 64 at a time: their gradient steps share ONE launch per step (or one "
                          "multi-step call per stretch, with --train-steps-per-call multi / K) through mn_dqn_group_train_step[s]; every seed's files equal the "
                          "sequential run's.  Needs the fused gradient step (not --torch-train); a trial without companions runs as without the option")
+    ap.add_argument("--fused-collect", action="store_true",
+                    help="collect on the device: ONE act launch that draws the exploration itself (mn_dqn_act_rng, the library's counter-based generator "
+                         "instead of torch.Generator: other draws) and the replay append inside the env step (mn_step_append)")
+    ap.add_argument("--stack-envs", action="store_true",
+                    help="with --together: the envs of the seeds that train together are the rows of ONE handle, and each vector step is one act, one step, one "
+                         "append and one reset launch for all of them; implies --fused-collect, and every seed's files equal its own --fused-collect run's")
     ap.add_argument("--dry-run", action="store_true", help="print the plan of every trial as JSON and exit (no GPU needed); with --together also which trials "
                                                            "would share a group")
     args = ap.parse_args(argv)
     if args.together and args.torch_train:
-        raise SystemExit("train_dqn: --together needs the fused HIP gradient step: there is no grouped form of the eager PyTorch step (--torch-train)")
+        raise SystemExit("train_dqn: " + TOGETHER_REFUSALS["torch_train"])
+    if args.stack_envs and not args.together:
+        raise SystemExit("train_dqn: " + TOGETHER_REFUSALS["stack_envs"])
+    fused_collect = args.fused_collect or args.stack_envs
     try:
         steps_per_call(args.train_steps_per_call)
     except ValueError as e:
@@ -415,10 +496,11 @@ def main(argv=None):
                 raise SystemExit(f"train_dqn: {e}")
             extra = dict(env_budget=args.env_budget, episode_log=True if args.episode_log is None else args.episode_log) if args.env_budget == "reference" else {}
             print(json.dumps(dict(seed=p["seed"], n_envs=n_envs, batch=batch, replay=plan.get("replay", replay), fused=not args.torch_train,
-                                  eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred or args.env_budget == "reference", **extra, eps_start=exploration_rate(0, plan), eps_end=exploration_rate(int(np.ceil(plan["exploration_vector_steps"])), plan),
+                                  eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred or args.env_budget == "reference", **extra, **(dict(fused_collect=True) if fused_collect else {}), eps_start=exploration_rate(0, plan), eps_end=exploration_rate(int(np.ceil(plan["exploration_vector_steps"])), plan),
                                   plan=plan)))
         if args.together:
-            print(json.dumps(dict(together=[dict(group=k, seeds=[trials[i]["seed"] for i in g], one_launch_per_gradient_step=len(g) > 1)
+            stacked = lambda g: dict(stacked_env_rows=len(g) * n_envs, rows_per_seed=n_envs) if args.stack_envs and len(g) > 1 else {}
+            print(json.dumps(dict(together=[dict(group=k, seeds=[trials[i]["seed"] for i in g], one_launch_per_gradient_step=len(g) > 1, **stacked(g))
                                             for k, g in enumerate(groups)])))
         return
     import torch
@@ -426,13 +508,14 @@ def main(argv=None):
     torch.cuda.set_device(torch.device(device))
     common = dict(batch=args.batch, replay=args.replay, grad_steps=args.grad_steps, total_grad_steps=args.total_grad_steps, n_evals=args.n_evals,
                   torch_train=args.torch_train, eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred, env_budget=args.env_budget,
-                  episode_log=args.episode_log, train_steps_per_call=args.train_steps_per_call)
+                  episode_log=args.episode_log, train_steps_per_call=args.train_steps_per_call, fused_collect=fused_collect)
     for g in groups:
         t0 = time.time()
         if len(g) > 1:
             seeds = [trials[i]["seed"] for i in g]
-            print(f"[train_dqn] seeds {seeds} train together: one launch per gradient step for the {len(g)} of them", flush=True)
-            dirs = run_trials_together(device, [trials[i] for i in g], args.n_envs, **common)
+            print(f"[train_dqn] seeds {seeds} train together: one launch per gradient step for the {len(g)} of them"
+                  + (", their envs stacked in one handle" if args.stack_envs else ""), flush=True)
+            dirs = run_trials_together(device, [trials[i] for i in g], args.n_envs, stack_envs=args.stack_envs, **common)
             print(f"[train_dqn] seeds {seeds}: {time.time() - t0:.1f} s -> {os.path.dirname(dirs[0])}", flush=True)
             continue
         p = trials[g[0]]

@@ -835,6 +835,53 @@ int mn_iqn_actor_group_act(mn_iqn_actor_group *g, const float *obs_dev, float cv
 int mn_iqn_actor_group_append(mn_iqn_actor_group *g, const float *obs_dev, const int32_t *actions_dev, const float *reward_dev,
                               const float *next_obs_dev, const uint8_t *done_dev, int64_t ptr, int64_t capacity, void *stream);
 
+/* ---- DQN collect on the device (csrc/dqn_collect.hip): the epsilon-greedy act of DQN training in ONE launch.  mn_dqn_act plus the exploration: row e
+ * draws u_e = u01(e, k0, k1), (k0, k1) = draw_keys(seed, call_index) -- the counter-based generator of the IQN act kernels (csrc/iqn_act_common.h) -- and
+ * acts greedily iff u_e > eps, else with min((int)(u_e / eps * 9.0f), 8) in float32; !(eps > 0): greedy everywhere.  seed and call_index are passed by
+ * value: there is no generator state on the device and nothing to advance; the caller counts its calls.
+ *   obs_dev, weights[18], image_dev, repack, n   as mn_dqn_act
+ *   explore_u_dev   [n] the uniforms, or NULL
+ *   qvals_dev       [n][9] Q-values of EVERY row, exploring ones included, or NULL.  A row's Q-values and greedy action are mn_dqn_act's bit for bit.
+ *                   With NULL only rows that act greedily need the network: a wavefront whose 16 rows all explore skips it, and a workgroup whose
+ *                   rows all explore does not load the weight image
+ *   actions_dev     [n], required
+ * MN_ERR_INVALID, without launching: a NULL obs_dev / weights / weight / image_dev / actions_dev, n <= 0.  No allocation, no host synchronisation. */
+int mn_dqn_act_rng(const float *obs_dev, const float *const *weights, float *image_dev, int32_t repack, uint64_t seed, uint64_t call_index, float eps,
+                   float *explore_u_dev, float *qvals_dev, int32_t *actions_dev, int32_t n, void *stream);
+
+/* MANY DQN ACTORS per launch: mn_dqn_act_rng and mn_replay_append of G actors with one row count (the seeds of one config, stacked in ONE env handle of
+ * G n rows: actor g owns rows [g n, (g + 1) n)), the actor being the second grid dimension.  Actor g gets, bit for bit, what mn_dqn_act_rng(obs + 26 g n,
+ * weights_g, image_g, stale bit g, seed_g, call_index_host[g], eps, NULL, NULL, actions + g n, n, stream) and mn_replay_append into its ring leave: the
+ * draw's index is the row INSIDE the group.  Nothing is hidden in the library, so grouped and single calls interleave freely.
+ * mn_dqn_actor: caller-owned, alive while the group is used; the 18 weight pointers are copied into the group's device table at create.  The five ring
+ * pointers are mn_replay_append's and may ALL be NULL in EVERY actor of a group that only ever acts.
+ * mn_dqn_actor_group_create: one allocation, one synchronous copy; nothing allocates or synchronises afterwards.  MN_ERR_INVALID, before anything touches
+ * the device: n_actors outside 1..MN_DQN_MAX_ACTORS, rows_per_group < 1, a NULL weights / weight / image, rings given in part, or two actors that share an
+ * image or a ring array.
+ * mn_dqn_actor_group_act: at most two launches.  The weight images of the actors whose bit of stale_mask is set are rebuilt first (one launch on grid
+ * (pack blocks, G), skipped when the mask is 0); then the act launch.  call_index_host [G] is read during the call (copied into the argument block: no
+ * device copy, no synchronisation).  Workgroups per group: min(ceil(tiles / 8), max(1, CUs / G)), tiles = ceil(n / 16);
+ * mn_dqn_actor_group_set_grid(g, k) replaces the share max(1, CUs / G) by k (0: the default again); results do not depend on the count.  MN_ERR_INVALID
+ * without launching: a NULL argument, a bit of stale_mask at or above G, another current device than at create.
+ * mn_dqn_actor_group_append: mn_iqn_actor_group_append's semantics into this table's rings -- row i of group g goes to slot (ptr + i - first) mod capacity
+ * of ring g, first = max(0, n - capacity); ptr and capacity are common to the group; the caller advances ptr.  MN_ERR_INVALID: a group without rings, a
+ * NULL argument, capacity <= 0, ptr outside [0, capacity). */
+typedef struct mn_dqn_actor {        /* device pointers of ONE actor, caller-owned */
+    const float *const *weights;     /* host array of 18 device pointers, as mn_dqn_act */
+    float *image;                    /* its weight image, mn_dqn_image_floats() floats */
+    uint64_t seed;                   /* of its exploration draws */
+    float *ring_states, *ring_next_states; int64_t *ring_actions; float *ring_rewards, *ring_dones;
+} mn_dqn_actor;
+typedef struct mn_dqn_actor_group mn_dqn_actor_group;
+#define MN_DQN_MAX_ACTORS 64
+int mn_dqn_actor_group_create(const mn_dqn_actor *actors_host, int32_t n_actors, int32_t rows_per_group, mn_dqn_actor_group **out);
+int mn_dqn_actor_group_destroy(mn_dqn_actor_group *g);
+int mn_dqn_actor_group_set_grid(mn_dqn_actor_group *g, int32_t workgroups_per_group);
+int mn_dqn_actor_group_act(mn_dqn_actor_group *g, const float *obs_dev, float eps, uint64_t stale_mask, const uint64_t *call_index_host,
+                           int32_t *actions_dev, void *stream);
+int mn_dqn_actor_group_append(mn_dqn_actor_group *g, const float *obs_dev, const int32_t *actions_dev, const float *reward_dev,
+                              const float *next_obs_dev, const uint8_t *done_dev, int64_t ptr, int64_t capacity, void *stream);
+
 typedef struct mn_xchg mn_xchg;
 int mn_xchg_create(int32_t rank, int32_t world, mn_xchg **out);
 int mn_xchg_export(mn_xchg *x, void *handle_out);
