@@ -119,6 +119,9 @@ SIGNATURES = [
     ("mn_query_observation", C.c_int, [_vp, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
     ("mn_get_state", C.c_int, [_vp, _i32, _i32, _pd, _pi32, _pi64]),
     ("mn_set_state", C.c_int, [_vp, _i32, _i32, _pd, _pi32, _pi64]),
+    ("mn_state_bytes", _i64, [_vp]),
+    ("mn_state_save", C.c_int, [_vp, _vp, _i64, _vp]),
+    ("mn_state_load", C.c_int, [_vp, _vp, _i64, _vp]),
     ("mn_enable_obs64", C.c_int, [_vp, _i32]),
     ("mn_get_obs64", C.c_int, [_vp, _i32, _i32, _pd]),
     ("mn_get_reward64", C.c_int, [_vp, _i32, _i32, _pd]),

@@ -633,33 +633,38 @@ extern "C" int32_t mn_reset_placement(float eps, int32_t n_rows, int64_t peak, i
     return rows <= (double)owed_max_rows ? MN_RESET_OWED : MN_RESET_UNDER_ACT;
 }
 
+// The pieces of an asynchronous reset (mn_reset_done_async, mn_reset_done_next_act; mn_state_load for a blob that carries the peak words): created on first use
+static int ensure_async(mn_handle *h) {
+    if (h->async_ready) return MN_OK;
+    // a stream of ANOTHER priority gets a hardware queue of its own: created with the default priority it can end up sharing the queue of the caller's
+    // stream (HIP deals streams out over a few queues; with an RCCL communicator in the process it did), and then the reset launch simply runs in front of
+    // the act kernel again, behind two cross-stream events (measured: 0.380 instead of 0.360 ms per vector step)
+    // (every piece is created if it is not there yet -- a call that failed half way is completed by the next one -- and `async_ready` is set last)
+    int prio_lo = 0, prio_hi = 0;
+    MN_HIP(h, hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+    if (!h->side) MN_HIP(h, hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, prio_hi));
+    if (!h->ev_stepped) MN_HIP(h, hipEventCreateWithFlags(&h->ev_stepped, hipEventDisableTiming));
+    if (!h->ev_reset_end) MN_HIP(h, hipEventCreateWithFlags(&h->ev_reset_end, hipEventDisableTiming));
+    if (!h->ready) { int rc = dev_alloc(h, &h->ready, (size_t)h->A.npad); if (rc) return rc; }
+    if (!h->seen_host) {
+        void *hp = nullptr;
+        MN_HIP(h, hipHostMalloc(&hp, sizeof(uint32_t), hipHostMallocMapped));
+        *(volatile uint32_t *)hp = 0xffffffffu;      // nothing seen yet: the first launches run in front
+        h->seen_host = (volatile uint32_t *)hp;
+    }
+    if (!h->seen_dev) MN_HIP(h, hipHostGetDevicePointer((void **)&h->seen_dev, (void *)h->seen_host, 0));
+    if (!h->peak_dev) { int rc = dev_alloc(h, &h->peak_dev, 1); if (rc) return rc; }
+    h->async_ready = true;
+    return MN_OK;
+}
+
 static int reset_done_placed(mn_handle *h, float *obs_dev, void *stream, bool next_act, float eps, int32_t n_rows, int32_t fallback,
                              const uint32_t **ready_out, uint32_t *tick_out, int32_t *placement_out) {
     if (!h || !obs_dev || !ready_out || !tick_out) return MN_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     join_reset(h, s);
     MN_ON_DEVICE(h);
-    if (!h->async_ready) {
-        // a stream of ANOTHER priority gets a hardware queue of its own: created with the default priority it can end up sharing the queue of the caller's
-        // stream (HIP deals streams out over a few queues; with an RCCL communicator in the process it did), and then the reset launch simply runs in front of
-        // the act kernel again, behind two cross-stream events (measured: 0.380 instead of 0.360 ms per vector step)
-        // (every piece is created if it is not there yet -- a call that failed half way is completed by the next one -- and `async_ready` is set last)
-        int prio_lo = 0, prio_hi = 0;
-        MN_HIP(h, hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-        if (!h->side) MN_HIP(h, hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, prio_hi));
-        if (!h->ev_stepped) MN_HIP(h, hipEventCreateWithFlags(&h->ev_stepped, hipEventDisableTiming));
-        if (!h->ev_reset_end) MN_HIP(h, hipEventCreateWithFlags(&h->ev_reset_end, hipEventDisableTiming));
-        if (!h->ready) { int rc = dev_alloc(h, &h->ready, (size_t)h->A.npad); if (rc) return rc; }
-        if (!h->seen_host) {
-            void *hp = nullptr;
-            MN_HIP(h, hipHostMalloc(&hp, sizeof(uint32_t), hipHostMallocMapped));
-            *(volatile uint32_t *)hp = 0xffffffffu;      // nothing seen yet: the first launches run in front
-            h->seen_host = (volatile uint32_t *)hp;
-        }
-        if (!h->seen_dev) MN_HIP(h, hipHostGetDevicePointer((void **)&h->seen_dev, (void *)h->seen_host, 0));
-        if (!h->peak_dev) { int rc = dev_alloc(h, &h->peak_dev, 1); if (rc) return rc; }
-        h->async_ready = true;
-    }
+    { const int arc = ensure_async(h); if (arc) return arc; }
     *ready_out = nullptr;
     *tick_out = 0;
     // the estimate: the launches' own decaying peak of their episode counts, as of the last launch whose word has arrived (the host may run several
@@ -961,6 +966,132 @@ extern "C" int mn_set_state(mn_handle *h, int32_t first, int32_t count, const do
     }
     if (ep_t) MN_HIP(h, hipMemcpy(h->A.ep_t + first, ep_t, (size_t)count * 4, hipMemcpyHostToDevice));
     if (tot_t) MN_HIP(h, hipMemcpy(h->A.tot_t + first, tot_t, (size_t)count * 8, hipMemcpyHostToDevice));
+    return MN_OK;
+}
+
+// ---- snapshot and restore (mn_state.hip; blob layout in mn_internal.h) ------------------------------------------------------------
+// Every member of mn_handle, and whether a snapshot carries it:
+//   A (the device arrays)        carried: pose, episode constants, ep_t / tot_t / counts, both sets of world tables, MT rows and positions, both halves of the
+//                                done-queue.  NOT carried: obs64 / rew64 / traj (last-step outputs kept for parity reads only)
+//   P, params                    validated, not restored: the blob loads only into a handle with the same params (the lane counts aside: results do not depend
+//                                on them) and the same schedule; P.debug_skip exists in ablation builds only
+//   step_parity, last_parity     carried: which half of the done-queue the next step fills / the next reset drains
+//   tick                         carried; `ready` is zeroed by the load launch (its words are only ever compared with ticks handed out later)
+//   peak_dev, *seen_host         carried (the decaying episode peak the reset placement reads); async_ready decides whether there is one
+//   under_act_max, owed_max_rows carried: the placement thresholds (mn_set_reset_under_act_max, mn_set_reset_owed_max_rows)
+//   reset_pending, reset_owed, owed_obs, owed_stream    always settled before a save or a load: nothing to carry
+//   seeds_dev, mask_count, list_scratch, peek_scratch   scratch, rewritten by every call that reads it
+//   obs64_buf, rew64_buf, traj_trace*, side_delay_us, profiling events and counters, side stream, events, device, allocs, err    configuration of the
+//                                process or of a test, not state of the envs
+static void state_header(const mn_handle *h, MnStateHeader *o) {
+    memset(o, 0, sizeof(*o));
+    o->magic = MN_STATE_MAGIC; o->version = MN_STATE_VERSION;
+    o->n = h->A.n; o->precision = h->params.precision;
+    o->bytes = mn_state_layout_bytes(h->A.n, h->A.qcap);
+    o->header_bytes = MN_STATE_HEADER_BYTES; o->qcap = h->A.qcap;
+    o->params = h->params;
+    o->n_stages = h->P.n_stages; o->timestep_scale = h->P.timestep_scale;
+    for (int i = 0; i < h->P.n_stages; ++i) {
+        o->sched_t[i] = h->P.sched_t[i]; o->sched_nc[i] = h->P.sched_nc[i]; o->sched_no[i] = h->P.sched_no[i]; o->sched_md[i] = h->P.sched_md[i];
+    }
+    o->step_parity = h->step_parity; o->last_parity = h->last_parity;
+    o->tick = h->tick;
+    o->under_act_max = h->under_act_max; o->owed_max_rows = h->owed_max_rows;
+    o->has_peak = h->async_ready ? 1u : 0u;
+    o->peak = 0u; o->seen = 0xffffffffu;      // (with has_peak the save launch reads both on the device)
+}
+
+// the first field in which the blob's params / schedule differ from the handle's, or NULL
+static const char *state_first_difference(const MnStateHeader &b, const MnStateHeader &m, char *buf, size_t len) {
+    struct F { const char *name; size_t off, size; };
+#define PF(f) {"params." #f, offsetof(mn_params, f), sizeof(((mn_params *)0)->f)}
+    static const F fields[] = {PF(width), PF(height), PF(core_r), PF(v_rel_max), PF(p), PF(v_range), PF(obs_r_range), PF(clear_r), PF(goal_dis), PF(timestep_penalty),
+                               PF(collision_penalty), PF(goal_reward), PF(discount), PF(min_start_goal_dis), PF(init_theta), PF(init_speed), PF(dt), PF(robot_r),
+                               PF(max_speed), PF(a), PF(w), PF(sonar_range), PF(sonar_angle), PF(num_cores), PF(num_obs), PF(reset_start_and_goal),
+                               PF(random_reset_state), PF(set_boundary), PF(max_episode_steps), PF(N), PF(num_beams)};
+#undef PF
+    for (const F &f : fields)
+        if (memcmp((const char *)&b.params + f.off, (const char *)&m.params + f.off, f.size) != 0) return f.name;
+    if (b.n_stages != m.n_stages) return "schedule.n_stages";
+    if (memcmp(&b.timestep_scale, &m.timestep_scale, 8) != 0) return "schedule.timestep_scale";
+    for (int i = 0; i < m.n_stages; ++i) {
+        const char *what = b.sched_t[i] != m.sched_t[i] ? "timesteps" : b.sched_nc[i] != m.sched_nc[i] ? "num_cores" : b.sched_no[i] != m.sched_no[i] ? "num_obs"
+                           : memcmp(&b.sched_md[i], &m.sched_md[i], 8) != 0 ? "min_start_goal_dis" : nullptr;
+        if (what) { snprintf(buf, len, "schedule.%s[%d]", what, i); return buf; }
+    }
+    return nullptr;
+}
+
+extern "C" int64_t mn_state_bytes(const mn_handle *h) { return h ? mn_state_layout_bytes(h->A.n, h->A.qcap) : (int64_t)MN_ERR_INVALID; }
+
+static int state_args_ok(mn_handle *h, const void *blob_dev, int64_t bytes, const char *who) {
+    char b[200];
+    if (!h) { snprintf(b, sizeof(b), "%s: NULL handle", who); return fail(nullptr, MN_ERR_INVALID, b); }
+    if (!blob_dev) { snprintf(b, sizeof(b), "%s: blob_dev is NULL", who); return fail(h, MN_ERR_INVALID, b); }
+    if ((uintptr_t)blob_dev & 15) { snprintf(b, sizeof(b), "%s: blob_dev must be 16-byte aligned (the RNG rows move as 128-bit vectors)", who); return fail(h, MN_ERR_INVALID, b); }
+    const int64_t need = mn_state_layout_bytes(h->A.n, h->A.qcap);
+    if (bytes < need) {
+        snprintf(b, sizeof(b), "%s: the buffer has %lld bytes, the handle's state needs %lld (mn_state_bytes)", who, (long long)bytes, (long long)need);
+        return fail(h, MN_ERR_INVALID, b);
+    }
+    return MN_OK;
+}
+
+extern "C" int mn_state_save(mn_handle *h, void *blob_dev, int64_t bytes, void *stream) {
+    int rc = state_args_ok(h, blob_dev, bytes, "mn_state_save");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    join_reset(h, s);      // an owed reset is launched here, a pending one joined: the snapshot is of the state every other entry point would see
+    MN_ON_DEVICE(h);
+    MnStateHeader hdr;
+    state_header(h, &hdr);
+    mn_launch_state(true, h->A, hdr, blob_dev, h->peak_dev, h->seen_dev, nullptr, s);
+    MN_HIP(h, hipGetLastError());
+    return MN_OK;
+}
+
+extern "C" int mn_state_load(mn_handle *h, const void *blob_dev, int64_t bytes, void *stream) {
+    int rc = state_args_ok(h, blob_dev, bytes, "mn_state_load");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    join_reset(h, s);
+    MN_ON_DEVICE(h);
+    MnStateHeader mine, blob;
+    state_header(h, &mine);
+    MN_HIP(h, hipMemcpyAsync(&blob, blob_dev, sizeof(blob), hipMemcpyDeviceToHost, s));
+    MN_HIP(h, hipStreamSynchronize(s));
+    char b[256], fb[64];
+    if (blob.magic != MN_STATE_MAGIC) {
+        snprintf(b, sizeof(b), "mn_state_load: not a state blob (magic word 0x%08x, expected 0x%08x)", blob.magic, MN_STATE_MAGIC);
+        return fail(h, MN_ERR_INVALID, b);
+    }
+    if (blob.version != MN_STATE_VERSION) {
+        snprintf(b, sizeof(b), "mn_state_load: blob format version %u, this library reads version %u", blob.version, MN_STATE_VERSION);
+        return fail(h, MN_ERR_INVALID, b);
+    }
+    if (blob.n != mine.n) {
+        snprintf(b, sizeof(b), "mn_state_load: the blob holds n = %d envs, the handle %d", blob.n, mine.n);
+        return fail(h, MN_ERR_INVALID, b);
+    }
+    if (blob.precision != mine.precision) {
+        snprintf(b, sizeof(b), "mn_state_load: the blob was saved with precision %d, the handle has %d", blob.precision, mine.precision);
+        return fail(h, MN_ERR_INVALID, b);
+    }
+    if (blob.bytes != mine.bytes || blob.header_bytes != mine.header_bytes || blob.qcap != mine.qcap)
+        return fail(h, MN_ERR_INVALID, "mn_state_load: the blob's byte count, header size or queue capacity is not what this library lays out for the handle");
+    const char *diff = state_first_difference(blob, mine, fb, sizeof(fb));
+    if (diff) {
+        snprintf(b, sizeof(b), "mn_state_load: the blob was saved from a handle with another %s", diff);
+        return fail(h, MN_ERR_INVALID, b);
+    }
+    // accepted: from here on the handle changes
+    if (blob.has_peak && (rc = ensure_async(h)) != MN_OK) return rc;
+    h->step_parity = blob.step_parity; h->last_parity = blob.last_parity;
+    h->tick = blob.tick;
+    h->under_act_max = blob.under_act_max; h->owed_max_rows = blob.owed_max_rows;
+    if (h->seen_host) *h->seen_host = blob.seen;      // (the stream is idle: no reset launch of it is still to write the word)
+    mn_launch_state(false, h->A, blob, const_cast<void *>(blob_dev), h->peak_dev, h->seen_dev, h->ready, s);
+    MN_HIP(h, hipGetLastError());
     return MN_OK;
 }
 

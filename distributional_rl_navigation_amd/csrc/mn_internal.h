@@ -93,6 +93,49 @@ struct MnRing {
     int64_t ptr, cap;
 };
 
+// Snapshot of a handle (mn_state_save / mn_state_load; kernels in mn_state.hip, host side in mn_capi.hip).  The blob is one device buffer:
+//   [0, MN_STATE_HEADER_BYTES)   MnStateHeader, zero-filled behind it
+//   mt          [n][624] u32     every env's MT19937 row
+//   queue_count [2][MN_QWORDS]   both halves of the done-queue's shard counters ...
+//   queue       [MN_QSHARDS][qcap] i32   ... and the shard lists (qcap is a function of n)
+//                                        CANONICAL in the blob: per shard the live entries ([0, count) of the half the last step filled) in ascending order, zeros
+//                                        behind them -- the order the step kernel's waves appended in is wave timing, not state; the blob is a function of the history
+//   f64 rows    [MN_STATE_F64_ROWS][n]   x y theta speed vx vy | start_x start_y goal_x goal_y init_theta init_speed | cx cy cg [8] | ox oy orad [10] | tot_t (i64)
+//   i32 rows    [MN_STATE_I32_ROWS][n]   ep_t counts mt_pos | qcx qcy qcg [8] | qox qoy qor [10]   (qcg / qor are f32, moved as words)
+// Rows are compact over n (the handle pads them to npad); every section starts 8-byte aligned, the MT rows 16-byte aligned; there are no gaps.
+#define MN_STATE_MAGIC 0x54534e4du      // "MNST"
+#define MN_STATE_VERSION 1
+#define MN_STATE_HEADER_BYTES 1024
+#define MN_STATE_F64_ROWS (12 + 3 * MN_MAX_CORES + 3 * MN_MAX_OBS + 1)
+#define MN_STATE_I32_ROWS (3 + 3 * MN_MAX_CORES + 3 * MN_MAX_OBS)
+#define MN_STATE_MT_WORDS 624
+struct MnStateHeader {
+    uint32_t magic, version;
+    int32_t n, precision;
+    int64_t bytes;                       // of the whole blob
+    int32_t header_bytes, qcap;
+    mn_params params;
+    // the schedule (mn_set_schedule); its position is a function of each env's tot_t, which the rows carry
+    int32_t n_stages, pad0;
+    double timestep_scale;
+    int64_t sched_t[MN_MAX_STAGES];
+    int32_t sched_nc[MN_MAX_STAGES], sched_no[MN_MAX_STAGES];
+    double sched_md[MN_MAX_STAGES];
+    // the host-side words of mn_handle that later calls depend on (enumerated in mn_capi.hip: state_header)
+    int32_t step_parity, last_parity;
+    uint32_t tick;
+    int32_t under_act_max, owed_max_rows;
+    uint32_t has_peak;                   // the handle had its asynchronous-reset pieces (async_ready): peak / seen are its words, else 0 / 0xffffffff
+    uint32_t peak, seen;                 // the decaying episode peak: device word and host-mapped copy, read by the save launch in stream order
+};
+static_assert(sizeof(MnStateHeader) <= MN_STATE_HEADER_BYTES, "MnStateHeader outgrew its slot");
+static inline int64_t mn_state_layout_bytes(int64_t n, int64_t qcap) {
+    return MN_STATE_HEADER_BYTES + n * MN_STATE_MT_WORDS * 4 + 2 * MN_QWORDS * 4 + MN_QSHARDS * qcap * 4 + MN_STATE_F64_ROWS * n * 8 + MN_STATE_I32_ROWS * n * 4;
+}
+// one launch: save = handle -> blob (hdr is written in front, with the two peak words read on the device), else blob -> handle (`ready`, if there is one, is
+// zeroed: no stale word may equal a tick the restored counter will hand out again; *peak_dev = hdr.peak)
+void mn_launch_state(bool save, const MnArrays &A, const MnStateHeader &hdr, void *blob, uint32_t *peak_dev, uint32_t *seen_dev, uint32_t *ready, hipStream_t s);
+
 // kernels (defined in mn_step.hip / mn_reset.hip)
 void mn_launch_step(const MnArrays &A, const MnDev &P, int precision, int lanes, const int32_t *actions, float *obs,
                     float *reward, uint8_t *done, uint8_t *info, int parity, const MnRing *ring, hipStream_t s);

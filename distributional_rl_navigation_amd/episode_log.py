@@ -200,6 +200,30 @@ class EpisodeLog:
         """(ret, disc, length) of the running episodes as numpy (synchronises)."""
         return self.ep_ret.cpu().numpy(), self.ep_disc.cpu().numpy(), self.ep_len.cpu().numpy()
 
+    # ---- checkpoints ---------------------------------------------------------------------------
+    def state_dict(self):
+        """The log as CPU tensors, numpy arrays and plain numbers: the running episodes' accumulators, the counter and the record slots in use since the last
+        drain (device side), the open summary row's chunks, the closed rows and -- `full` -- every record taken so far (host side).  The copies still in
+        flight are waited for and taken in first, in drain order, exactly as a later drain would take them."""
+        self._collect(wait=True)
+        k = min(self.capacity, self.n * self.steps_since_drain)
+        return dict(n=self.n, capacity=self.capacity, full=self.full, ep_ret=self.ep_ret.cpu(), ep_disc=self.ep_disc.cpu(), ep_len=self.ep_len.cpu(),
+                    count=self.count.cpu(), rec={name: self.rec[name][:k].cpu() for name, _ in RECORD_FIELDS}, steps_since_drain=int(self.steps_since_drain),
+                    row_open=bool(self.row_open), interval=[dict(c) for c in self._interval], rows=[dict(r) for r in self.rows],
+                    all=[dict(c) for c in self._all], dropped=int(self.dropped))
+
+    def load_state_dict(self, sd):
+        if (int(sd["n"]), int(sd["capacity"]), bool(sd["full"])) != (self.n, self.capacity, self.full):
+            raise ValueError(f"EpisodeLog.load_state_dict: the state is of a log of {sd['n']} envs, {sd['capacity']} slots, full={sd['full']}; this one has "
+                             f"{self.n}, {self.capacity}, full={self.full}")
+        self._collect(wait=True)
+        self.ep_ret.copy_(sd["ep_ret"]); self.ep_disc.copy_(sd["ep_disc"]); self.ep_len.copy_(sd["ep_len"]); self.count.copy_(sd["count"])
+        for name, _ in RECORD_FIELDS:
+            k = sd["rec"][name].numel()
+            self.rec[name][:k].copy_(sd["rec"][name])
+        self.steps_since_drain, self.row_open, self.dropped = int(sd["steps_since_drain"]), bool(sd["row_open"]), int(sd["dropped"])
+        self._interval, self.rows, self._all = [dict(c) for c in sd["interval"]], [dict(r) for r in sd["rows"]], [dict(c) for c in sd["all"]]
+
     def save(self, directory):
         """training_log.npz (the summary rows) and, with `full`, training_episodes.npz (the records, canonical order) in `directory`."""
         import os

@@ -92,6 +92,18 @@ class UnderActGuard:
     def close(self):
         self._end_preflight()
 
+    def state_dict(self):
+        """The verdict so far: still watching or not, the fallback if there was one, and the env threshold the end of the preflight restores (None behind it)."""
+        return dict(active=bool(self.active), fallback=None if self.fallback is None else dict(self.fallback), restore=self._restore,
+                    reset_under_act=bool(self.agent.reset_under_act), reset_fallback=bool(self.agent.reset_fallback))
+
+    def load_state_dict(self, sd):
+        """Into the guard of a fresh loop whose env has ALREADY been given its saved state (the handle's threshold came with it): the resumed loop neither
+        repeats a preflight that has ended nor forgets a fallback.  The late-row time-outs of the saving process are not carried: this process's act context
+        counts its own from zero, and a loop that fell back no longer looks at them."""
+        self.active, self.fallback, self._restore = bool(sd["active"]), None if sd["fallback"] is None else dict(sd["fallback"]), sd["restore"]
+        self.agent.reset_under_act, self.agent.reset_fallback = bool(sd["reset_under_act"]), bool(sd["reset_fallback"])
+
 
 def evaluation_from_traces(reward, done, info, action, discount, energy_tab, dt, N):
     """The evaluation lists of IQNAgent.evaluation_vec from the traces (numpy [T][n]) of its episodes, whichever way they were produced:
@@ -224,6 +236,34 @@ class VecLoop:
         if hasattr(self.train_env, "join_reset"):
             self.train_env.join_reset()
 
+    # ---- checkpoints ---------------------------------------------------------------------------
+    def state_dict(self, next_step):
+        """The loop's own state behind a finished vector step (`next_step` = the index of the step that comes next): the observations the next act reads, the
+        verbose accumulators, `stats`, the guard's verdict, and the state of the deferred evaluations (flushed first) and of the episode log.  The agent, its
+        ring and the envs have their own `state_dict()`; train_iqn's checkpoint holds them side by side."""
+        if hasattr(self.train_env, "join_reset"):      # (rows of `obs` may still await their reset: an owed one is launched here, one under the act kernel joined)
+            self.train_env.join_reset()
+        stats = {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in self.stats.items() if k != "last"}
+        return dict(next_step=int(next_step), obs=self.obs.cpu(), ep_ret=self.ep_ret.cpu(), ep_len=self.ep_len.cpu(), stats=stats, guard=self.guard.state_dict(),
+                    deferred=None if self.deferred is None else self.deferred.state_dict(),
+                    episode_log=None if self.episode_log is None else self.episode_log.state_dict())
+
+    def load_state_dict(self, sd):
+        """Into a fresh loop over the same arguments, AFTER the agent, its ring and the train env were given their states.  Returns the index of the vector
+        step to continue with."""
+        if (sd["deferred"] is None) != (self.deferred is None) or (sd["episode_log"] is None) != (self.episode_log is None):
+            raise ValueError("VecLoop.load_state_dict: the saved loop and this one differ in their deferred evaluations or their episode log")
+        self.obs = self.train_env.obs if hasattr(self.train_env, "obs") else self.obs
+        self.obs.copy_(sd["obs"])
+        self.ep_ret.copy_(sd["ep_ret"]); self.ep_len.copy_(sd["ep_len"])
+        self.stats = {k: (v.to(self.agent.device) if torch.is_tensor(v) else v) for k, v in sd["stats"].items()}
+        self.guard.load_state_dict(sd["guard"])
+        if self.deferred is not None:
+            self.deferred.load_state_dict(sd["deferred"])
+        if self.episode_log is not None:
+            self.episode_log.load_state_dict(sd["episode_log"])
+        return int(sd["next_step"])
+
 
 class IQNAgent(ReferenceLoopMixin):
     def __init__(self, state_size, action_size, layer_size=64, n_step=1, BATCH_SIZE=32, BUFFER_SIZE=1_000_000,
@@ -311,6 +351,107 @@ class IQNAgent(ReferenceLoopMixin):
         self.device = torch.device(device)
         self.optimizer = self._make_adam()
         self._train_path = None
+
+    _COUNTERS = ("current_timestep", "learning_timestep", "grad_steps", "_last_sync_at")
+    _EVAL_LISTS = ("eval_timesteps", "eval_actions", "eval_rewards", "eval_successes", "eval_times", "eval_energies")
+
+    def _adam_state(self):
+        """(exp_avg [P], exp_avg_sq [P], step) of the one Adam state both gradient-step paths update, from whichever path holds it: the fused step's flat
+        buffers and device counter, or torch.optim.Adam's per-parameter state."""
+        params = list(self.qnetwork_local.parameters())
+        ft = self._fused if self._fused is not None and self._fused.owns(self) else None
+        st0 = self.optimizer.state.get(params[0], None)
+        opt_step = int(float(st0["step"])) if st0 is not None and "step" in st0 else 0
+        if ft is not None:      # (the optimizer's moments are views of these)
+            return ft.exp_avg.detach().cpu().clone(), ft.exp_avg_sq.detach().cpu().clone(), opt_step if self._train_path == "torch" else int(ft.step_dev.item())
+        flat = lambda key: torch.cat([(self.optimizer.state[p][key] if key in self.optimizer.state.get(p, {}) else torch.zeros_like(p)).detach().reshape(-1).cpu()
+                                      for p in params])
+        return flat("exp_avg"), flat("exp_avg_sq"), opt_step
+
+    def _load_adam_state(self, exp_avg, exp_avg_sq, step):
+        """The reverse: into the fused trainer's buffers where this agent trains through it (the optimizer's views of them follow), and into the optimizer's
+        own state in any case, step count included -- so whichever path runs next finds what the saving agent's path left (`_enter_train_path`)."""
+        params = list(self.qnetwork_local.parameters())
+        if self.use_fused_train and self.device.type == "cuda":
+            ft = self._fused_trainer()
+            ft.exp_avg.copy_(exp_avg); ft.exp_avg_sq.copy_(exp_avg_sq)
+            ft.step_dev.fill_(int(step))
+        opt = self.optimizer
+        on_dev = any(g.get("fused") or g.get("capturable") for g in opt.param_groups)
+        off = 0
+        with torch.no_grad():
+            for p in params:
+                n = p.numel()
+                st = opt.state[p]
+                if "exp_avg" not in st:
+                    st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(p), torch.zeros_like(p)
+                if "step" not in st:
+                    st["step"] = torch.zeros((), dtype=torch.float32, device=p.device if on_dev else "cpu")
+                st["exp_avg"].copy_(exp_avg[off:off + n].view(p.shape)); st["exp_avg_sq"].copy_(exp_avg_sq[off:off + n].view(p.shape))
+                st["step"].fill_(float(int(step)))
+                off += n
+        self._train_path = None      # both paths hold the same state now: nothing to hand over at the next step
+
+    def state_dict(self):
+        """Everything of the agent a continued run depends on, as CPU tensors and plain numbers (the replay ring has its own: `memory.state_dict()`): both
+        networks, the Adam state of whichever gradient-step path holds it, the counters the cadences and the exploration schedule read, the evaluation
+        record, the act stream's {seed, counter}, the gradient step's sampling state, and the generators the non-fused paths draw from (this agent's, torch's
+        CPU and device generators, python's `random`).  Caches are not state: the act kernel's weight image, a staged next batch, captured graphs,
+        the draw buffers and the workspaces are rebuilt by the next call that needs them."""
+        import copy
+        ft = self._fused if self._fused is not None and self._fused.owns(self) else None
+        m, v, step = self._adam_state()
+        cpu = lambda net: {k: t.detach().cpu().clone() for k, t in net.state_dict().items()}
+        sd = dict(local=cpu(self.qnetwork_local), target=cpu(self.qnetwork_target), exp_avg=m, exp_avg_sq=v, adam_step=int(step),
+                  counters={k: int(getattr(self, k)) for k in self._COUNTERS}, report_scale=float(getattr(self, "_report_scale", 1.0)),
+                  eval_lists={k: copy.deepcopy(getattr(self, k)) for k in self._EVAL_LISTS}, best_eval=copy.deepcopy(self.best_eval),
+                  act_rng=None if self._act_rng is None else self._act_rng.state.cpu(), train_rng=None if ft is None else ft.rng_state.cpu(),
+                  gen=self.gen.get_state(), torch_cpu_rng=torch.get_rng_state(),
+                  torch_device_rng=torch.cuda.get_rng_state(self.device) if self.device.type == "cuda" else None, py_random=random.getstate())
+        return sd
+
+    def load_state_dict(self, sd):
+        """Continue where `state_dict()` was taken: bit-identical from here on, on either gradient-step path (a state saved by the fused HIP step loads into an
+        agent that trains through PyTorch and the other way round -- the moments and the step count are handed over as `_enter_train_path` hands them)."""
+        import copy
+        with torch.no_grad():      # in place: the parameters may be views of the fused trainer's flat buffers
+            for net, key in ((self.qnetwork_local, "local"), (self.qnetwork_target, "target")):
+                own = net.state_dict()
+                if own.keys() != sd[key].keys():
+                    raise ValueError(f"IQNAgent.load_state_dict: the saved {key} network has other parameters ({sorted(set(own) ^ set(sd[key]))})")
+                for k, t in own.items():
+                    t.copy_(sd[key][k])
+        self._load_adam_state(sd["exp_avg"], sd["exp_avg_sq"], sd["adam_step"])
+        for k in self._COUNTERS:
+            setattr(self, k, int(sd["counters"][k]))
+        self._report_scale = float(sd["report_scale"])
+        for k in self._EVAL_LISTS:
+            setattr(self, k, copy.deepcopy(sd["eval_lists"][k]))
+        self.best_eval = copy.deepcopy(sd["best_eval"])
+        if sd["act_rng"] is not None:
+            if self._act_rng is None:
+                from .fused_act import ActRng
+                self._act_rng = ActRng(self.gen.initial_seed(), self.device)
+            self._act_rng.state.copy_(sd["act_rng"])
+        else:
+            self._act_rng = None
+        ft = self._fused if self._fused is not None and self._fused.owns(self) else None
+        if sd["train_rng"] is not None and ft is None and self.use_fused_train and self.device.type == "cuda":
+            ft = self._fused_trainer()
+        if ft is not None:
+            if sd["train_rng"] is not None:
+                ft.rng_state.copy_(sd["train_rng"])
+            ft._staged_key = None      # caches: the next call rebuilds them (the staged and the unstaged step, a rebuilt image: the same bits)
+            ft._graph, ft._graph_key = None, None
+        self._graph = None
+        self.gen.set_state(sd["gen"])
+        torch.set_rng_state(sd["torch_cpu_rng"])
+        if sd["torch_device_rng"] is not None and self.device.type == "cuda":
+            torch.cuda.set_rng_state(sd["torch_device_rng"], self.device)
+        random.setstate(sd["py_random"])
+        if self.device.type == "cuda":
+            from .fused_act import weights_changed
+            weights_changed(self.qnetwork_local)      # (the copies above went through PyTorch, which the act context tracks; this costs one re-pack)
 
     def adjust_cvar_batch(self, states):
         """Batched adjust_cvar on device: states [n, 26] -> cvar [n]."""
@@ -503,6 +644,11 @@ class IQNAgent(ReferenceLoopMixin):
             self._allreduce_grads()          # average first, then clip: same as one big-batch learner
         torch.nn.utils.clip_grad_norm_(self.qnetwork_local.parameters(), 0.5)
         self.optimizer.step()
+        if experiences[0].is_cuda:
+            # torch.optim.Adam(fused=True) writes the weights without bumping the parameters' version counters, which is what the act path's cached weight
+            # image goes by (iqn/fused_act.py): it has to be told, or acting goes on with the weights of the last image
+            from .fused_act import weights_changed
+            weights_changed(self.qnetwork_local)
         self.grad_steps += 1
         return loss.detach()
 

@@ -186,6 +186,18 @@ class DeferredEvaluations:
             self._envs.close()
             self._envs = None
 
+    # ---- checkpoints ---------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """What a continued run needs of the deferred evaluations once nothing is pending: `flush()` runs first -- legal at any point, because every
+        group of a grouped launch is bit for bit a launch of its own and the training streams are untouched -- and then the count of snapshots taken (the
+        j of the seed formula) is all there is; the record logged so far and the best-so-far score live in the agent (`IQNAgent.state_dict`)."""
+        self.flush()
+        return dict(n_taken=int(self.n_taken), launches=int(self.launches), steps_run=list(self.steps_run))
+
+    def load_state_dict(self, sd):
+        assert not self.pending, "load_state_dict into DeferredEvaluations with pending snapshots"
+        self.n_taken, self.launches, self.steps_run = int(sd["n_taken"]), int(sd["launches"]), list(sd["steps_run"])
+
     # ---- host half -----------------------------------------------------------------------------------------------------
     def log_traces(self, traces, metas, params, discount):
         """Log the checkpoints `metas` (dicts with timestep / grad_steps / vector_step) from the numpy traces [T][len(metas) * R] of their launch, in

@@ -150,5 +150,31 @@ class ReplayBuffer:
         idx = self.sample_indices(b)
         return (self.states[idx], self.actions[idx], self.rewards[idx], self.next_states[idx], self.dones[idx])
 
+    # ---- checkpoints ---------------------------------------------------------------------------
+    def state_dict(self):
+        """The ring as CPU tensors and plain numbers: rows [0, size) only (a young run fills a fraction of its capacity), `ptr`, `size`, `version`, the
+        sampling generator's state and -- n_step > 1 -- the per-stream window.  `load_state_dict` into a ring of the same capacity continues bit for bit:
+        the same rows, the same next `sample()`, the same next n-step transition."""
+        s = self.size
+        sd = dict(capacity=self.capacity, n_step=int(self.n_step), size=int(s), ptr=int(self.ptr), version=int(self.version), gen=self.gen.get_state(),
+                  states=self.states[:s].cpu(), next_states=self.next_states[:s].cpu(), actions=self.actions[:s].cpu(), rewards=self.rewards[:s].cpu(),
+                  dones=self.dones[:s].cpu(), hist=None)
+        if self._hist is not None:
+            h = self._hist
+            sd["hist"] = dict(s=h["s"].cpu(), a=h["a"].cpu(), r=h["r"].cpu(), count=int(h["count"]))
+        return sd
+
+    def load_state_dict(self, sd):
+        if int(sd["capacity"]) != self.capacity or int(sd["n_step"]) != int(self.n_step):
+            raise ValueError(f"ReplayBuffer.load_state_dict: the state is of a ring of {sd['capacity']} rows with n_step {sd['n_step']}, this one has "
+                             f"{self.capacity} rows and n_step {self.n_step}")
+        s = int(sd["size"])
+        for name in ("states", "next_states", "actions", "rewards", "dones"):
+            getattr(self, name)[:s].copy_(sd[name])
+        self.size, self.ptr, self.version = s, int(sd["ptr"]), int(sd["version"])
+        self.gen.set_state(sd["gen"])
+        h = sd.get("hist")
+        self._hist = None if h is None else dict(s=h["s"].to(self.device), a=h["a"].to(self.device), r=h["r"].to(self.device), count=int(h["count"]))
+
     def __len__(self):
         return self.size

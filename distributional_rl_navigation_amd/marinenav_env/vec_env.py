@@ -536,6 +536,63 @@ class VecMarineNavEnv:
                                         _np_ptr(ep, C.c_int32) if ep is not None else None,
                                         _np_ptr(tot, C.c_int64) if tot is not None else None))
 
+    # ---- snapshots: mark a point, go on, come back (C-ABI mn_state_save / mn_state_load) ------
+    def state_bytes(self):
+        return int(self.L.mn_state_bytes(self.h))
+
+    def save_state(self, out=None):
+        """Everything a later call on the handle reads -- pose, episode constants, counters, both sets of world tables, every env's RNG stream, the done-queue
+        and the handle's host-side words -- packed by ONE launch into a uint8 device tensor (`out`, or a new one).  An owed reset is launched first and a reset
+        under the act kernel joined, as by `join_reset()`.  The observation buffers are this object's, not the handle's: `state_dict()` has those too."""
+        nb = self.state_bytes()
+        if out is None:
+            out = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device and out.numel() >= nb
+        self.late_rows = None
+        self.reset_owed = False
+        self._check(self.L.mn_state_save(self.h, _ptr(out), int(out.numel()), self._stream()))
+        return out
+
+    def load_state(self, blob):
+        """Put a `save_state()` blob of this env -- or of another one with the same n_envs, precision, params and schedule -- back: from here on the handle
+        behaves exactly as the saved one would have.  Anything else is refused (MarineNavHipError names the first difference) and changes nothing."""
+        b = blob.to(device=self.device, dtype=torch.uint8).contiguous()
+        self._check(self.L.mn_state_load(self.h, _ptr(b), int(b.numel()), self._stream()))
+        self.late_rows = None
+        self.reset_owed = False
+        self._loaded_blob = b      # (the unpack launch may still be reading it)
+
+    def state_dict(self):
+        """The env as CPU tensors and plain numbers: the handle's blob (`save_state`, copied to the host), both observation buffers and which one is current,
+        the last reward / done / info rows and the host counters.  `load_state_dict` of it into an env built with the same arguments continues bit for bit."""
+        blob = self.save_state()
+        sd = dict(n_envs=self.n_envs, precision=self.precision, blob=blob.cpu(), obs_bufs=[b.cpu() for b in self._obs_bufs], cur=int(self._cur),
+                  reward=self.reward.cpu(), done=self.done.cpu(), info=self.info.cpu(),
+                  terminal_obs=None if self._terminal_obs is None else self._terminal_obs.cpu(),
+                  reset_launches=list(self.reset_launches), resets_owed=int(self.resets_owed), reset_under_act_max=int(self.reset_under_act_max),
+                  reset_owed_max_rows=int(self.reset_owed_max_rows))
+        return sd
+
+    def load_state_dict(self, sd):
+        if int(sd["n_envs"]) != self.n_envs or sd["precision"] != self.precision:
+            raise _capi.MarineNavHipError(f"load_state_dict: the state is of {sd['n_envs']} envs in precision {sd['precision']!r}, this env has {self.n_envs} in "
+                                          f"{self.precision!r}")
+        self.load_state(sd["blob"])      # first: a refused blob leaves this object as it was
+        for dst, src in zip(self._obs_bufs, sd["obs_bufs"]):
+            dst.copy_(src)
+        self._cur = int(sd["cur"])
+        self.obs = self._obs_bufs[self._cur]
+        self.reward.copy_(sd["reward"]); self.done.copy_(sd["done"]); self.info.copy_(sd["info"])
+        if sd.get("terminal_obs") is not None:
+            if self._terminal_obs is None:
+                self._terminal_obs = torch.empty_like(self.obs)
+            self._terminal_obs.copy_(sd["terminal_obs"])
+        self.reset_launches = list(sd["reset_launches"])
+        self.resets_owed = int(sd["resets_owed"])
+        self.reset_under_act_max = int(sd["reset_under_act_max"])      # (the handle's own copies of the two thresholds came with the blob)
+        self.reset_owed_max_rows = int(sd["reset_owed_max_rows"])
+        torch.cuda.synchronize(self.device)
+
     def enable_obs64(self, on=True):
         """Keep float64 copies of every later step's / reset's observation rows and rewards (`get_obs64`, `get_reward64`; f64 handles).
         Off by default: the training loop never reads them (C-ABI mn_enable_obs64)."""

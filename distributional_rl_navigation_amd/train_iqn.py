@@ -3,11 +3,13 @@
 Same JSON config (`config/config_IQN.json` schema: agent, seed (list -> grid), total_timesteps,
 eval_freq, save_dir), same per-trial outputs (`trial_config.json`, `training_schedule.json`,
 `eval_config.json`, `greedy_evaluations.npz`, `adaptive_evaluations.npz`, `network_params.pth`,
-`constructor_params.json`).  One process per GPU: launch with torch.distributed.run for several
+`constructor_params.json`; `completed.json` last, the marker `--resume` skips a finished seed by).  One process per GPU: launch with torch.distributed.run for several
 GPUs (independent learners per rank by default, `--shared-learner` for one IQN with an RCCL
 gradient all-reduce).
 
     python -m distributional_rl_navigation_amd.train_iqn -C config_IQN.json [--n-envs 4096] [--env-budget reference] [--episode-log [full]] [--together [--stack-envs]] [--dry-run]
+    python -m distributional_rl_navigation_amd.train_iqn -C config_IQN.json ... [--checkpoint-every K] [--stop-after K]      # checkpoint.pt per seed; end behind vector step K
+    python -m distributional_rl_navigation_amd.train_iqn -C config_IQN.json ... --resume SAVE_DIR/training_<time> [--dry-run]   # continue in a fresh process, bit for bit
 
 Cadence.  The reference does one batch-32 gradient step per 4 env steps (replay ratio 8 sampled per generated
 transition).  Two modes (`--env-budget`):
@@ -200,6 +202,37 @@ def make_episode_log(option, env_budget, n_envs, eval_every_vector_steps, discou
     return EpisodeLog(n_envs, n_envs * steps, discount, device, full=option == "full")
 
 
+def trial_dir(params, rank=0, world=1, shared=False):
+    """The directory of one trial: save_dir/training_<time>/seed_<seed> (train_IQN_model.py:76-78), one per rank for independent learners."""
+    exp_dir = os.path.join(params["save_dir"], "training_" + params["training_time"], "seed_" + str(params["seed"]))
+    return os.path.join(exp_dir, f"rank_{rank}") if world > 1 and not shared else exp_dir
+
+
+def plan_trial(params, n_envs, world=1, shared=False, batch=None, replay=None, grad_steps=None, total_grad_steps=None, n_evals=None, env_budget="learner",
+               reference=None):
+    """(n_envs, batch, replay, plan) of one trial: the budget's defaults filled in, `plan_cadence`, and the checks every trial passes before anything is
+    written or allocated.  No GPU needed: `--dry-run` and `--resume` plan with it as `TrialRun` does."""
+    ref_mode = env_budget == "reference"
+    if ref_mode and (world > 1 or shared):
+        raise ValueError("env_budget='reference' is the reference's single-learner experiment: one process, one GPU")
+    n_envs, batch, replay = resolve_budget_args(env_budget, n_envs, batch, replay)
+    plan = plan_cadence(params["total_timesteps"], params["eval_freq"], n_envs * world, batch,
+                        grad_steps_per_vector_step=grad_steps, total_grad_steps=total_grad_steps, n_evals=n_evals, budget=env_budget, reference=reference)
+    if ref_mode:
+        if replay is not None and replay != plan["replay"]:
+            raise ValueError(f"env_budget='reference' keeps the reference's replay ring ({plan['replay']} rows); {replay} contradicts it")
+        replay = plan["replay"]
+    if plan["total_grad_steps"] * batch < 0.1 * plan["reference_samples"]:
+        raise ValueError(f"planned learner budget ({plan['total_grad_steps']} grad steps x {batch}) is more than 10x below the "
+                         f"reference's ({plan['reference_grad_steps']} x 32): raise --total-grad-steps")
+    return n_envs, batch, replay, plan
+
+
+def trial_shape(plan, n_envs, world, batch, replay):
+    """The plan and the sizes it was made for, as trial_config.json records them under "batched": what a checkpoint keeps and `--resume` compares."""
+    return dict(plan, n_envs=n_envs, world=world, batch=batch, replay=replay)
+
+
 class TrialRun:
     """One trial of `run_trial` in the parts a lockstep driver needs (`run_trials_together`): the constructor does everything in front of the loop -- plan,
     directory and its JSON files, envs, agent, episode log -- and leaves `learn_args`, the arguments of `IQNAgent.learn_vec` (or of its loop in parts,
@@ -209,33 +242,22 @@ class TrialRun:
                  grad_steps=None, torch_train=False, total_grad_steps=None, n_evals=None, cvar=1.0, precision="f64",
                  exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1,
                  eval_one_launch=False, eval_deferred=False, env_budget="learner", reference=None, episode_log=None, eval_config=None, max_eval_steps=1000,
-                 on_step=None, train_env=None):
+                 on_step=None, train_env=None, eval_worlds=None):
         import torch
         from .iqn.agent import IQNAgent
         from .marinenav_env.vec_env import VecMarineNavEnv
 
-        exp_dir = os.path.join(params["save_dir"], "training_" + params["training_time"], "seed_" + str(params["seed"]))
-        if world > 1 and not shared:
-            exp_dir = os.path.join(exp_dir, f"rank_{rank}")
+        exp_dir = trial_dir(params, rank, world, shared)
         writer = rank == 0 or not shared
         ref_mode = env_budget == "reference"
-        if ref_mode and (world > 1 or shared):
-            raise ValueError("env_budget='reference' is the reference's single-learner experiment: one process, one GPU")
-        n_envs, batch, replay = resolve_budget_args(env_budget, n_envs, batch, replay)
+        n_envs, batch, replay, plan = plan_trial(params, n_envs, world=world, shared=shared, batch=batch, replay=replay, grad_steps=grad_steps,
+                                                 total_grad_steps=total_grad_steps, n_evals=n_evals, env_budget=env_budget, reference=reference)
         total = n_envs * world
-        plan = plan_cadence(params["total_timesteps"], params["eval_freq"], total, batch,
-                            grad_steps_per_vector_step=grad_steps, total_grad_steps=total_grad_steps, n_evals=n_evals, budget=env_budget, reference=reference)
-        if ref_mode:
-            if replay is not None and replay != plan["replay"]:
-                raise ValueError(f"env_budget='reference' keeps the reference's replay ring ({plan['replay']} rows); {replay} contradicts it")
-            replay = plan["replay"]
-        if plan["total_grad_steps"] * batch < 0.1 * plan["reference_samples"]:
-            raise ValueError(f"planned learner budget ({plan['total_grad_steps']} grad steps x {batch}) is more than 10x below the "
-                             f"reference's ({plan['reference_grad_steps']} x 32): raise --total-grad-steps")
+        self.shape = trial_shape(plan, n_envs, world, batch, replay)
         if writer:
             os.makedirs(exp_dir, exist_ok=True)
             with open(os.path.join(exp_dir, "trial_config.json"), "w+") as f:
-                json.dump(dict(params, batched=dict(plan, n_envs=n_envs, world=world, batch=batch, replay=replay)), f)
+                json.dump(dict(params, batched=self.shape), f)
             with open(os.path.join(exp_dir, "training_schedule.json"), "w+") as f:
                 json.dump(TRAINING_SCHEDULE, f)
             if verbose:
@@ -252,6 +274,8 @@ class TrialRun:
             raise ValueError(f"the train env given holds {train_env.n_envs} rows; the plan is for {n_envs}")
         if eval_config is None:
             eval_config = create_eval_configs(device)
+        if eval_worlds is not None:      # (a run at toy size: the first few of the evaluation worlds)
+            eval_config = {k: eval_config[k] for k in list(eval_config)[:int(eval_worlds)]}
         if writer:
             with open(os.path.join(exp_dir, "eval_config.json"), "w+") as f:
                 json.dump(eval_config, f)
@@ -279,6 +303,7 @@ class TrialRun:
                                eval_one_launch=eval_one_launch, eval_deferred=eval_deferred, on_step=on_step, episode_log=log, max_eval_steps=max_eval_steps,
                                eval_points=plan_eval_points(plan, total) if ref_mode else None)
         self.exp_dir, self.writer, self.plan, self.agent, self.train_env, self.eval_env, self.log = exp_dir, writer, plan, agent, train_env, eval_env, log
+        self.params = params
 
     def conclude(self):
         import torch
@@ -287,20 +312,169 @@ class TrialRun:
             agent.qnetwork_local.save(exp_dir)
             if log is not None:
                 log.save(exp_dir)
-        train_env.close()
-        if eval_env is not None:
-            eval_env.close()
-        torch.cuda.synchronize()
+        self.release()
+        if writer:      # last: the marker says every file of the trial is there (`--resume` skips the seed)
+            with open(os.path.join(exp_dir, COMPLETED_FILE), "w") as f:
+                json.dump(dict(vector_steps=self.plan["vector_steps"], grad_steps=int(agent.grad_steps)), f)
         return exp_dir
 
+    def release(self):
+        """Close the envs and wait for the device; writes nothing (`conclude` without its files: a run that stopped at a checkpoint)."""
+        import torch
+        self.train_env.close()
+        if self.eval_env is not None:
+            self.eval_env.close()
+        torch.cuda.synchronize()
 
+    # ---- checkpoints (--checkpoint-every, --stop-after, --resume) -------------------------------------------------------------------
+    def checkpoint_state(self, loop, next_step, run_args=None):
+        """The whole trial behind vector step `next_step - 1` as one dict of CPU tensors and plain values.  Order matters: the env first (its save launches an
+        owed reset and joins one under the act kernel, so the observation rows the loop saves are final), then the loop (which flushes the deferred
+        evaluations -- that logs into the agent), then the ring and the agent."""
+        env = self.train_env.state_dict()      # (the evaluation env is not state: every evaluation loads its worlds afresh and draws nothing from its streams)
+        lp = loop.state_dict(next_step)
+        return dict(format=CHECKPOINT_FORMAT, vector_step=int(next_step), params=dict(self.params), plan=dict(self.shape), args=dict(run_args or {}),
+                    env=env, loop=lp, ring=self.agent.memory.state_dict(), agent=self.agent.state_dict())
+
+    def restore(self, loop, state):
+        """`checkpoint_state` back into this (freshly built) trial and its fresh `loop`.  Returns the vector step to continue with.  The agent comes last: its
+        state holds torch's generator states, which nothing behind it may move."""
+        self.train_env.load_state_dict(state["env"])
+        self.agent.memory.load_state_dict(state["ring"])
+        next_step = loop.load_state_dict(state["loop"])
+        self.agent.load_state_dict(state["agent"])
+        assert next_step == int(state["vector_step"])
+        return next_step
+
+
+CHECKPOINT_FORMAT = 1
+CHECKPOINT_FILE, CHECKPOINT_PREV_FILE, COMPLETED_FILE = "checkpoint.pt", "checkpoint.prev.pt", "completed.json"
+CHECKPOINT_REFUSALS = dict(
+    together="--checkpoint-every, --stop-after and --resume save and restore one trial's loop; the lockstep loop of --together (with or without --stack-envs) has no "
+             "checkpoint yet: run the seeds one after the other, or with -P",
+    shared="--checkpoint-every, --stop-after and --resume save and restore one process's learner; a shared learner (--shared-learner) would need every rank's "
+           "state from the same vector step, which has no checkpoint yet",
+    world="--checkpoint-every, --stop-after and --resume are the single-process form; they are not combinable with torch.distributed.run (WORLD_SIZE > 1)")
+SHAPE_KEYS_FIRST = ("n_envs", "batch", "replay", "world")      # (named before the plan's own keys, which follow from them)
+
+
+def write_checkpoint(exp_dir, state):
+    """checkpoint.pt in the trial directory `exp_dir`, atomically: written under a temporary name in the same directory and synced, the previous checkpoint
+    kept as checkpoint.prev.pt, then renamed into place.  Whatever interrupts this leaves a readable checkpoint.pt or a readable checkpoint.prev.pt."""
+    import torch
+    path, prev, tmp = (os.path.join(exp_dir, n) for n in (CHECKPOINT_FILE, CHECKPOINT_PREV_FILE, CHECKPOINT_FILE + ".tmp"))
+    with open(tmp, "wb") as f:
+        torch.save(state, f)
+        f.flush()
+        os.fsync(f.fileno())
+    if os.path.exists(path):
+        os.replace(path, prev)
+    os.replace(tmp, path)
+    return path
+
+
+def run_shaping_args(env_budget="learner", precision="f64", n_step=1, shared_taus=False, cvar=1.0, eval_adaptive=True, eval_deferred=False, eval_one_launch=False,
+                     episode_log=None, max_eval_steps=1000, reference=None, target_sync_mult=1.0, final_eps=0.05, eval_worlds=None, **_):
+    """The arguments of `run_trial` that shape a run beside its plan, normalised: what a checkpoint records and `--resume` compares (`check_resumable`).  ONE
+    place builds it, for the run itself and for `--dry-run --resume`; the defaults are `run_trial`'s.  (`torch_train` is recorded by the checkpoint but not
+    compared: a checkpoint of one gradient-step path continues on the other.)"""
+    return dict(env_budget=env_budget, precision=precision, n_step=int(n_step), shared_taus=bool(shared_taus), cvar=float(cvar), eval_adaptive=bool(eval_adaptive),
+                eval_deferred=bool(eval_deferred), eval_one_launch=bool(eval_one_launch), episode_log=episode_log, max_eval_steps=int(max_eval_steps),
+                reference=dict(reference or {}), target_sync_mult=float(target_sync_mult), final_eps=float(final_eps), eval_worlds=eval_worlds)
+
+
+def first_difference(saved, now, first=()):
+    """(key, saved value, value now) of the first key in which two dicts differ -- `first`, then the others in sorted order -- or None."""
+    keys = [k for k in first if k in saved or k in now] + sorted((set(saved) | set(now)) - set(first))
+    for k in keys:
+        if k not in saved or k not in now or saved[k] != now[k]:
+            return k, saved.get(k, "<absent>"), now.get(k, "<absent>")
+    return None
+
+
+def load_checkpoint(seed_dir, log=print):
+    """The checkpoint of a trial directory: checkpoint.pt, or -- where that is missing or unreadable while checkpoint.prev.pt is there -- the previous one, with one
+    log line saying so.  Returns (state, file name), or (None, None) for a directory without a checkpoint."""
+    import torch
+    path, prev = os.path.join(seed_dir, CHECKPOINT_FILE), os.path.join(seed_dir, CHECKPOINT_PREV_FILE)
+    why = None
+    if os.path.exists(path):
+        try:
+            state = torch.load(path, map_location="cpu", weights_only=False)
+            if not isinstance(state, dict) or state.get("format") != CHECKPOINT_FORMAT:
+                raise ValueError(f"format {state.get('format') if isinstance(state, dict) else type(state).__name__!r}, this version reads {CHECKPOINT_FORMAT}")
+            return state, CHECKPOINT_FILE
+        except Exception as e:
+            why = f"unreadable ({type(e).__name__}: {e})"
+    elif os.path.exists(prev):
+        why = "missing"
+    if why is None:
+        return None, None
+    if not os.path.exists(prev):
+        raise ValueError(f"{path} is {why} and there is no {CHECKPOINT_PREV_FILE} beside it")
+    state = torch.load(prev, map_location="cpu", weights_only=False)
+    if not isinstance(state, dict) or state.get("format") != CHECKPOINT_FORMAT:
+        raise ValueError(f"{prev}: not a checkpoint of format {CHECKPOINT_FORMAT}")
+    log(f"[train_iqn] {path} is {why}: continuing from {CHECKPOINT_PREV_FILE} (vector step {state['vector_step']})")
+    return state, CHECKPOINT_PREV_FILE
+
+
+def check_resumable(state, shape, run_args=None):
+    """A checkpoint continues only the run it was taken from: the plan recomputed from the command line must equal the saved one, and so must the arguments
+    that shape the run.  ValueError names the first key that differs and both values."""
+    d = first_difference(state["plan"], shape, SHAPE_KEYS_FIRST)
+    if d is not None:
+        raise ValueError(f"--resume: the checkpoint was written by a run with another plan: {d[0]} was {d[1]!r} there and is {d[2]!r} on this command line")
+    if run_args is not None and state.get("args"):
+        d = first_difference({k: v for k, v in state["args"].items() if k in run_args}, {k: v for k, v in run_args.items() if k in state["args"]})
+        if d is not None:
+            raise ValueError(f"--resume: the checkpoint was written by a run with other arguments: {d[0]} was {d[1]!r} there and is {d[2]!r} on this command line")
+
+
+def resume_point(seed_dir, shape, run_args=None, log=print):
+    """What `--resume` does with one trial directory: ("completed", None, None), ("start", None, None) or ("checkpoint", state, file name) -- checked."""
+    if os.path.exists(os.path.join(seed_dir, COMPLETED_FILE)):
+        return "completed", None, None
+    state, name = load_checkpoint(seed_dir, log)
+    if state is None:
+        return "start", None, None
+    check_resumable(state, shape, run_args)
+    return "checkpoint", state, name
+
+
+def run_loop_with_checkpoints(run, state=None, checkpoint_every=None, stop_after=None, run_args=None):
+    """`IQNAgent.learn_vec` for the trial `run`, in its parts (`iqn.agent.VecLoop`), continued from `state` and with a checkpoint behind every
+    `checkpoint_every`-th vector step and behind vector step `stop_after`, where the loop then ends.  Returns the number of vector steps done if it
+    stopped there, None if it ran to its end."""
+    from .iqn.agent import VecLoop
+    agent, total = run.agent, run.learn_args["total_vector_steps"]
+    loop = VecLoop(agent, **run.learn_args)
+    stopped = None
+    try:
+        first = run.restore(loop, state) if state is not None else 0
+        for it in range(first, total):
+            due = loop.collect(it)
+            loss = agent.train_steps_from_memory(agent.grad_steps_per_update) if due.train else None
+            loop.finish(it, loss)
+            done = it + 1
+            stop = stop_after is not None and done == stop_after and done < total
+            if stop or (checkpoint_every and done % checkpoint_every == 0):
+                write_checkpoint(run.exp_dir, run.checkpoint_state(loop, done, run_args))
+            if stop:
+                stopped = done
+                break
+        if stopped is None:
+            loop.end()
+    finally:
+        loop.close()
+    return stopped
 
 
 def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None, replay=None, verbose=True,
               grad_steps=None, torch_train=False, total_grad_steps=None, n_evals=None, cvar=1.0, precision="f64",
               exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1,
               eval_one_launch=False, eval_deferred=False, env_budget="learner", reference=None, episode_log=None, eval_config=None, max_eval_steps=1000,
-              on_step=None, return_agent=False):
+              on_step=None, return_agent=False, eval_worlds=None, checkpoint_every=None, stop_after=None, resume=False, dump_final_state=None):
     """train_IQN_model.py:74-121 on the vector env.  `params` is one trial of the reference's config grid
     (seed, total_timesteps, eval_freq, save_dir); see `plan_cadence` for how its env-step cadences map to vector steps.
     `precision`: the env kernels' arithmetic.  "f64" (default: every float32 output within 1e-5 of the reference, no
@@ -319,13 +493,50 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None,
     deferred evaluations at every eval_freq.  `episode_log`: None (on with "reference", off otherwise), True or "full" -- training_log.npz with one
     summary row of the training episodes per evaluation interval, "full": training_episodes.npz with every episode's record (episode_log.py).
     `eval_config`: the evaluation worlds (default: the 30 of create_eval_configs); `max_eval_steps`: the step limit of an evaluation episode;
-    `on_step`: learn_vec's hook; `return_agent`: return (directory, agent)."""
+    `on_step`: learn_vec's hook; `return_agent`: return (directory, agent); `eval_worlds`: evaluate on the first so many evaluation worlds only.
+    `checkpoint_every` = K: behind every K-th vector step the whole trial -- env handle, ring, agent, loop, evaluations, episode log -- goes into
+    checkpoint.pt of the trial's directory (`TrialRun.write_checkpoint`); `stop_after` = K: a checkpoint behind vector step K, where the trial then ends without
+    its final files; `resume`: skip the trial if its directory holds the completion marker, continue from its checkpoint if it holds one (refused if that was
+    written under another plan or other run-shaping arguments), start from the beginning otherwise.  A run stopped and resumed writes, byte for byte, the files
+    of the uninterrupted run.  Single process, single learner.  Without the three the loop is `IQNAgent.learn_vec` as ever.
+    `dump_final_state`: a file for torch.save(dict(agent=, ring=, env=)) of the `state_dict()`s behind the last vector step (tests)."""
+    checkpointing = checkpoint_every is not None or stop_after is not None or resume
+    if checkpointing and (shared or world > 1):
+        raise ValueError(CHECKPOINT_REFUSALS["shared" if shared else "world"])
+    if checkpoint_every is not None and int(checkpoint_every) < 1 or stop_after is not None and int(stop_after) < 1:
+        raise ValueError("checkpoint_every and stop_after count vector steps: at least 1")
+    run_args = run_shaping_args(env_budget=env_budget, precision=precision, n_step=n_step, shared_taus=shared_taus, cvar=cvar, eval_adaptive=eval_adaptive,
+                                eval_deferred=eval_deferred, eval_one_launch=eval_one_launch, episode_log=episode_log, max_eval_steps=max_eval_steps, reference=reference,
+                                target_sync_mult=target_sync_mult, final_eps=final_eps, eval_worlds=eval_worlds)
+    state = None
+    if resume:      # (looked at before anything is built or written: a finished seed is left alone, a foreign checkpoint refused)
+        exp_dir = trial_dir(params, rank, world, shared)
+        ne, b, r, plan = plan_trial(params, n_envs, world=world, shared=shared, batch=batch, replay=replay, grad_steps=grad_steps, total_grad_steps=total_grad_steps,
+                                    n_evals=n_evals, env_budget=env_budget, reference=reference)
+        what, state, name = resume_point(exp_dir, trial_shape(plan, ne, world, b, r), run_args)
+        if what == "completed":
+            print(f"[train_iqn] seed {params['seed']}: {exp_dir} holds {COMPLETED_FILE}, nothing to do", flush=True)
+            return (exp_dir, None) if return_agent else exp_dir
+        if verbose:
+            print(f"[train_iqn] seed {params['seed']}: " + (f"continuing from vector step {state['vector_step']} ({name})" if state is not None
+                                                            else "no checkpoint, starting from the beginning"), flush=True)
     run = TrialRun(device, params, n_envs, rank=rank, world=world, shared=shared, batch=batch, replay=replay, verbose=verbose, grad_steps=grad_steps,
                    torch_train=torch_train, total_grad_steps=total_grad_steps, n_evals=n_evals, cvar=cvar, precision=precision, exchange=exchange,
                    shared_taus=shared_taus, target_sync_mult=target_sync_mult, final_eps=final_eps, eval_adaptive=eval_adaptive, n_step=n_step,
                    eval_one_launch=eval_one_launch, eval_deferred=eval_deferred, env_budget=env_budget, reference=reference, episode_log=episode_log,
-                   eval_config=eval_config, max_eval_steps=max_eval_steps, on_step=on_step)
-    run.agent.learn_vec(**run.learn_args)
+                   eval_config=eval_config, max_eval_steps=max_eval_steps, on_step=on_step, eval_worlds=eval_worlds)
+    if checkpoint_every is None and stop_after is None and state is None:
+        run.agent.learn_vec(**run.learn_args)
+    else:
+        stopped = run_loop_with_checkpoints(run, state, checkpoint_every, stop_after, dict(run_args, torch_train=bool(torch_train)))
+        if stopped is not None:
+            run.release()
+            print(f"[train_iqn] seed {params['seed']}: stopped after vector step {stopped} of {run.plan['vector_steps']}; checkpoint in "
+                  f"{os.path.join(run.exp_dir, CHECKPOINT_FILE)} (continue with --resume {os.path.dirname(run.exp_dir)})", flush=True)
+            return (run.exp_dir, run.agent) if return_agent else run.exp_dir
+    if dump_final_state is not None:
+        import torch
+        torch.save(dict(env=run.train_env.state_dict(), ring=run.agent.memory.state_dict(), agent=run.agent.state_dict()), dump_final_state)
     exp_dir = run.conclude()
     return (exp_dir, run.agent) if return_agent else exp_dir
 
@@ -522,7 +733,45 @@ def main(argv=None):
                     help="with --together: the seeds' envs are the rows of ONE env handle and a vector step is one act launch, one env step, one replay append and one "
                          "reset launch for all of them (mn_iqn_actor_group_act / _append) instead of one of each per seed; every seed's files stay equal to the "
                          "sequential run's.  Not with --shared-taus")
+    ap.add_argument("--checkpoint-every", type=int, default=None, metavar="K",
+                    help="behind every K-th vector step write checkpoint.pt into the trial's directory (atomically; the previous one is kept as checkpoint.prev.pt): the "
+                         "env handle's snapshot (mn_state_save), the replay ring, the agent, the loop, the evaluations and the episode log.  Off by default: the loop "
+                         "then does nothing it did not do before")
+    ap.add_argument("--stop-after", type=int, default=None, metavar="K",
+                    help="end every trial behind vector step K with a checkpoint written at that step; exit status 0 (a time-limited session: continue with --resume).  With "
+                         "several seeds EVERY seed runs to its vector step K, one after the other (or in its -P worker), before the process ends.  A K at or beyond the "
+                         "plan's vector steps stops nothing: the trial completes")
+    ap.add_argument("--resume", default=None, metavar="TRAINING_DIR",
+                    help="continue the run in save_dir/training_<time>: per seed, skip it if it is complete, continue from its checkpoint.pt (checkpoint.prev.pt if that "
+                         "is unreadable) or start it if it has none.  Give the command line of the original run: another plan is refused.  The files written equal "
+                         "those of the uninterrupted run byte for byte.  With --dry-run: print where every seed would continue")
+    ap.add_argument("--run-name", default=None, metavar="NAME", help="name the run directory training_NAME instead of training_<start time>")
+    ap.add_argument("--reference", nargs="*", default=None, metavar="KEY=VALUE",
+                    help="with --env-budget reference: overrides of the reference's constants (learning_starts, target_update_interval, exploration_fraction, replay) "
+                         "for runs at toy size")
+    ap.add_argument("--max-eval-steps", type=int, default=1000, help="step limit of an evaluation episode (default 1000, the reference's)")
+    ap.add_argument("--eval-worlds", type=int, default=None, metavar="N", help="evaluate on the first N of the 30 evaluation worlds (runs at toy size)")
+    ap.add_argument("--n-step", type=int, default=1, help="the agent's n-step returns (default 1, the reference's scripts)")
+    ap.add_argument("--dump-final-state", default=None, metavar="FILE",
+                    help="behind the last vector step, torch.save the state_dict()s of the agent, its replay ring and the train env of the LAST trial run to FILE (tests)")
     args = ap.parse_args(argv)
+    checkpointing = args.checkpoint_every is not None or args.stop_after is not None or args.resume is not None
+    if checkpointing:
+        refused = [k for k, on in (("together", args.together or args.stack_envs), ("shared", args.shared_learner), ("world", int(os.environ.get("WORLD_SIZE", "1")) > 1)) if on]
+        if refused:
+            raise SystemExit("train_iqn: " + CHECKPOINT_REFUSALS[refused[0]])
+        if (args.checkpoint_every is not None and args.checkpoint_every < 1) or (args.stop_after is not None and args.stop_after < 1):
+            raise SystemExit("train_iqn: --checkpoint-every and --stop-after count vector steps: at least 1")
+    reference = None
+    if args.reference is not None:
+        if args.env_budget != "reference":
+            raise SystemExit("train_iqn: --reference overrides belong to --env-budget reference")
+        try:
+            reference = {k: (float(v) if k == "exploration_fraction" else int(v)) for k, v in (kv.split("=", 1) for kv in args.reference)}
+        except ValueError:
+            raise SystemExit("train_iqn: --reference takes KEY=VALUE pairs with numeric values")
+    if args.dump_final_state is not None and args.together:
+        raise SystemExit("train_iqn: --dump-final-state dumps one trial's state; the lockstep loop of --together has none to dump")
     if args.stack_envs and not args.together:
         raise SystemExit("train_iqn: " + TOGETHER_REFUSALS["stack_envs"])
     if args.stack_envs and args.shared_taus:
@@ -533,12 +782,40 @@ def main(argv=None):
         if refused:
             raise SystemExit("train_iqn: " + TOGETHER_REFUSALS[refused[0]])
     params = json.load(args.config_file)
+    stamp = args.run_name
+    if args.resume is not None:
+        rdir = os.path.abspath(args.resume)
+        if not os.path.isdir(rdir) or not os.path.basename(rdir).startswith("training_"):
+            raise SystemExit(f"train_iqn: --resume takes a run directory, save_dir/training_<time>; {args.resume!r} is none")
+        stamp = os.path.basename(rdir)[len("training_"):]
+        for p in trial_params(params):
+            if os.path.realpath(os.path.join(p["save_dir"], "training_" + stamp)) != os.path.realpath(rdir):
+                raise SystemExit(f"train_iqn: --resume {args.resume}: the config's save_dir ({p['save_dir']!r}) does not lead to that directory")
+    # run_trial's keyword arguments, built here so that --dry-run --resume checks a checkpoint against exactly what the run itself would be given
+    kw = dict(batch=args.batch, replay=args.replay, grad_steps=args.grad_steps, torch_train=args.torch_train,
+              total_grad_steps=args.total_grad_steps, n_evals=args.n_evals, cvar=args.cvar, precision=args.precision,
+              exchange=args.exchange, shared_taus=args.shared_taus, eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred,
+              env_budget=args.env_budget, episode_log=args.episode_log)
+    # (only what was asked for is passed on: without these options run_trial is called as ever)
+    if reference is not None:
+        kw["reference"] = reference
+    if args.max_eval_steps != 1000:
+        kw["max_eval_steps"] = args.max_eval_steps
+    if args.eval_worlds is not None:
+        kw["eval_worlds"] = args.eval_worlds
+    if args.n_step != 1:
+        kw["n_step"] = args.n_step
+    if checkpointing:
+        kw.update(checkpoint_every=args.checkpoint_every, stop_after=args.stop_after, resume=args.resume is not None)
+    if args.dump_final_state is not None:
+        kw["dump_final_state"] = args.dump_final_state
+    run_args = run_shaping_args(**kw)
     if args.dry_run:
         n_envs, batch, replay = resolve_budget_args(args.env_budget, args.n_envs, args.batch, args.replay)
         for p in trial_params(params):
             try:
                 plan = plan_cadence(p["total_timesteps"], p["eval_freq"], n_envs, batch, grad_steps_per_vector_step=args.grad_steps,
-                                    total_grad_steps=args.total_grad_steps, n_evals=args.n_evals, budget=args.env_budget)
+                                    total_grad_steps=args.total_grad_steps, n_evals=args.n_evals, budget=args.env_budget, reference=reference)
                 if args.env_budget == "reference" and replay is not None and replay != plan["replay"]:
                     raise ValueError(f"env_budget='reference' keeps the reference's replay ring ({plan['replay']} rows); {replay} contradicts it")
             except ValueError as e:
@@ -546,6 +823,14 @@ def main(argv=None):
             print(json.dumps(dict(seed=p["seed"], n_envs=n_envs, batch=batch, replay=plan.get("replay", replay), env_budget=args.env_budget,
                                   eval_deferred=args.eval_deferred or args.env_budget == "reference",
                                   episode_log=(args.env_budget == "reference") if args.episode_log is None else args.episode_log, plan=plan)))
+            if args.resume is not None:      # where this seed would continue (reads its checkpoint on the host; the same checks as the run itself)
+                try:
+                    shape = trial_shape(plan, n_envs, 1, batch, plan.get("replay", replay))
+                    what, state, name = resume_point(trial_dir(dict(p, training_time=stamp)), shape, run_args)
+                except ValueError as e:
+                    raise SystemExit(f"train_iqn: {e}")
+                print(json.dumps(dict(seed=p["seed"], resume=what, vector_step=None if state is None else int(state["vector_step"]), checkpoint=name,
+                                      vector_steps=plan["vector_steps"])))
         if args.together:
             trials = trial_params(params)
             stacked = lambda g: dict(stacked_env_rows=len(g) * n_envs, rows_per_seed=n_envs) if args.stack_envs and len(g) > 1 else {}
@@ -563,14 +848,11 @@ def main(argv=None):
     if world > 1:
         import torch.distributed as dist
         dist.init_process_group("nccl", device_id=torch.device(device))
-    stamp = datetime.now().strftime("%Y-%m-%d-%H-%M-%S")
+    if stamp is None:
+        stamp = datetime.now().strftime("%Y-%m-%d-%H-%M-%S")
     trials = trial_params(params)
     for p in trials:
         p["training_time"] = stamp
-    kw = dict(batch=args.batch, replay=args.replay, grad_steps=args.grad_steps, torch_train=args.torch_train,
-              total_grad_steps=args.total_grad_steps, n_evals=args.n_evals, cvar=args.cvar, precision=args.precision,
-              exchange=args.exchange, shared_taus=args.shared_taus, eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred,
-              env_budget=args.env_budget, episode_log=args.episode_log)
     if args.num_procs > 1:
         # train_IQN_model.py:173-179: a Pool of workers, one trial each.  `spawn`: every worker gets its own HIP context
         if world > 1:

@@ -316,6 +316,31 @@ int mn_get_state(mn_handle *h, int32_t first_env, int32_t count, double *state, 
 int mn_set_state(mn_handle *h, int32_t first_env, int32_t count, const double *state,
                  const int32_t *episode_timesteps, const int64_t *total_timesteps);
 
+/* Snapshot and restore of a whole handle, device to device: mark a point, go on, come back -- or carry the blob to the host and into another
+ * process (VecMarineNavEnv.state_dict).  After mn_state_load the handle behaves exactly as the saved one would have: every later mn_step*,
+ * mn_reset*, mn_rollout* and accessor gives the same bits.
+ *   mn_state_bytes  the size of the handle's blob (a function of n_envs only), or MN_ERR_INVALID for a NULL handle.
+ *   mn_state_save   first does what every state-reading entry point does (an owed reset of mn_reset_done_next_act is launched on `stream`, a
+ *                   pending mn_reset_done_async joined), then packs the state in ONE launch on `stream` into blob_dev (16-byte aligned, at least
+ *                   mn_state_bytes(h) bytes).  Nothing else of the handle is written; no allocation, no host synchronisation.
+ *   mn_state_load   reads the blob's header (one small copy, waits for `stream`), validates it, then unpacks in ONE launch on `stream`.
+ * The blob is self-describing: a header (magic word, format version, n_envs, precision, byte count, the handle's mn_params and schedule, and the
+ * handle's host-side words: done-queue parity, reset tick, the decaying episode peak, the two reset-placement thresholds) followed by, compact
+ * over n_envs (not the padded rows of the handle): every env's MT19937 row and position, both halves of the done-queue (counters and lists), pose
+ * and velocity, the per-env episode constants (start, goal, init_theta, init_speed), episode / total timesteps, the world sizes, the float64
+ * world tables and the compact tables of the mixed-precision step kernel (carried, not re-derived: bit-equal to what the reset kernel wrote).
+ * The done-queue's lists are saved in a canonical form (per shard the live entries in ascending order, zeros behind them): the order in which the step
+ * kernel's wavefronts appended them is timing, not state, so two handles with the same history give the same blob, byte for byte.
+ * NOT state, and not carried: the last-step outputs kept only for parity reads (mn_get_obs64, mn_get_reward64, mn_get_trajectory) and whether
+ * they are enabled, an attached trajectory trace, profiling windows, mn_debug_side_delay_us.  The caller's own buffers (observations, rewards,
+ * done flags) are the caller's to keep.
+ * MN_ERR_INVALID, with a message in mn_last_error and the handle untouched: a NULL or misaligned argument, `bytes` below mn_state_bytes(h), a wrong
+ * magic word or version, a blob of another n_envs or precision, or of a handle with other params (step_lanes / rollout_lanes aside: results do not
+ * depend on them) or another schedule -- the message names the first field that differs. */
+int64_t mn_state_bytes(const mn_handle *h);
+int mn_state_save(mn_handle *h, void *blob_dev, int64_t bytes, void *stream);
+int mn_state_load(mn_handle *h, const void *blob_dev, int64_t bytes, void *stream);
+
 /* Float64 copy of the last observation each env produced (the reference returns float64,
  * marinenav_env.py:326).  Only kept when precision == MN_PRECISION_F64; out[count][26]. */
 /* Float64 copies of the last observation rows / rewards (what the reference's float64 step returns before the agent's .float()),
