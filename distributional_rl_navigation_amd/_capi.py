@@ -138,6 +138,8 @@ SIGNATURES = [
     ("mn_iqn_weights_changed", C.c_int, [_vp]),
     ("mn_iqn_set_variant", C.c_int, [_vp, _i32]),
     ("mn_iqn_set_greedy_rows", C.c_int, [_vp, _i32]),
+    ("mn_iqn_set_few_rows_max", C.c_int, [_vp, _i32]),
+    ("mn_iqn_few_rows_launches", C.c_int, [_vp, C.POINTER(C.c_int64)]),
     ("mn_iqn_set_grid", C.c_int, [_vp, _i32]),
     ("mn_iqn_set_tau_mode", C.c_int, [_vp, _i32]),
     ("mn_iqn_set_late_rows", C.c_int, [_vp, _vp, _vp, C.c_uint32, _i32]),

@@ -38,6 +38,7 @@ namespace {
 #include "iqn_act_common.h"
 #include "iqn_act_exact.h"
 #include "iqn_act_split.h"
+#include "iqn_act_few.h"
 #include "iqn_act_tiled.h"
 #include "iqn_act_group.h"
 
@@ -110,6 +111,8 @@ struct mn_iqn_ctx {
     bool greedy_rows = true;                // mn_iqn_set_greedy_rows
     uint32_t *rows_buf = nullptr;           // GreedyRows of the act launches: 4 words, then the list [rows_cap]
     int rows_cap = 0;
+    int few_rows_max = MN_IQN_FEW_ROWS_MAX_DEFAULT;      // mn_iqn_set_few_rows_max
+    int64_t few_launches = 0;               // act launches that ran as the few-rows kernel (mn_iqn_few_rows_launches)
 };
 
 extern "C" int mn_iqn_set_grid(mn_iqn_ctx *c, int32_t max_workgroups) {
@@ -173,6 +176,21 @@ extern "C" int mn_iqn_set_variant(mn_iqn_ctx *c, int32_t variant) {
 extern "C" int mn_iqn_set_greedy_rows(mn_iqn_ctx *c, int32_t on) {
     if (!c) return MN_ERR_INVALID;
     c->greedy_rows = on != 0;
+    return MN_OK;
+}
+
+// The listed-rows launch (F_SPLIT_ROWS) runs as sp::iqn_act_few_kernel (iqn_act_few.h: no LDS image, two wavefronts per row) while the list is expected
+// to hold at most `rows` rows, (1 - eps) n: negative = never, 0x7fffffff = always.  Same actions, draws and call counter either way.
+extern "C" int mn_iqn_set_few_rows_max(mn_iqn_ctx *c, int32_t rows) {
+    if (!c) return MN_ERR_INVALID;
+    c->few_rows_max = rows;
+    return MN_OK;
+}
+
+// Act launches of this context that ran as the few-rows kernel so far (test hook: which kernel a call took is not visible in its results)
+extern "C" int mn_iqn_few_rows_launches(mn_iqn_ctx *c, int64_t *out) {
+    if (!c || !out) return MN_ERR_INVALID;
+    *out = c->few_launches;
     return MN_OK;
 }
 
@@ -245,6 +263,20 @@ extern "C" int mn_iqn_profile_end(mn_iqn_ctx *c, void *stream, double *mean_ms, 
 static int act_grid(const mn_iqn_ctx *c, int n) {
     const int blocks = (n + 7) / 8, cap = c->max_blocks > 0 ? c->max_blocks : c->n_cu;
     return blocks < cap ? blocks : cap;
+}
+
+// Whether a launch of `n` rows at `eps` in form `f` runs as the few-rows kernel (mn_iqn_set_few_rows_max): the rule reads the EXPECTED length of the list, as
+// mn_reset_placement does -- the host does not know the count
+static bool few_rows(const mn_iqn_ctx *c, const Form &f, int n, float eps) {
+    if (&f != &FORMS[F_SPLIT_ROWS] || c->few_rows_max < 0) return false;
+    return (1.0 - (eps < 1.f ? (double)eps : 1.0)) * (double)n <= (double)c->few_rows_max;
+}
+
+// Its workgroups, one list position each at a time: as many as the threshold lets the list be long, capped like act_grid (a longer list loops)
+static int few_grid(const mn_iqn_ctx *c, int n) {
+    const int cap = c->max_blocks > 0 ? c->max_blocks : c->n_cu, want = c->few_rows_max < 1 ? 1 : c->few_rows_max;
+    const int blocks = want < cap ? want : cap;
+    return blocks < n ? blocks : n;
 }
 
 // Blocks of 256 threads that make a launch's `items` draws beside the pack blocks of a prep kernel
@@ -406,7 +438,11 @@ static int launch_act(mn_iqn_ctx *c, const float *obs_dev, const float *taus_dev
 
     // ---- launch
     const dim3 grid(act_grid(c, n)), block(f.threads);
-    if (f.tiled)
+    if (few_rows(c, f, n, eps)) {
+        ++c->few_launches;
+        hipLaunchKernelGGL(sp::iqn_act_few_kernel, dim3(few_grid(c, n)), dim3(64 * sp::FEW_WAVES), 0, s, obs_dev, taus_dev, (const uint32_t *)c->packed_sp, actions_dev,
+                           n, rng_state_dev, rows);
+    } else if (f.tiled)
         hipLaunchKernelGGL(f.tiled, dim3((n + 255) / 256), block, f.lds_bytes(), s, obs_dev, (const uint32_t *)c->packed_sp, (const uint32_t *)c->timg,
                            (const float *)c->taux, qvals_dev, explore_u_dev, eps, actions_dev, n, rng_state_dev);
     else if (f.split)

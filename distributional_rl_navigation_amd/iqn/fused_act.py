@@ -45,6 +45,7 @@ class ActContext:
         self.variant = self.DEFAULT_VARIANT
         self.tau_mode = 0
         self.greedy_rows = True
+        self.few_rows_max = self.FEW_ROWS_MAX_DEFAULT
         self._ptrs = (C.c_void_p * 14)()
         self._fin = weakref.finalize(self, _capi.lib().mn_iqn_destroy, h)
 
@@ -90,6 +91,27 @@ class ActContext:
         if rc:
             raise _capi.MarineNavHipError(f"mn_iqn_set_greedy_rows failed ({rc})")
         self.greedy_rows = bool(on)
+
+    FEW_ROWS_MAX_DEFAULT = 256      # = MN_IQN_FEW_ROWS_MAX_DEFAULT (include/marinenav_hip.h)
+    FEW_ROWS_ALWAYS = 2 ** 31 - 1
+
+    def set_few_rows_max(self, rows=None):
+        """The act launch of the listed rows runs as the few-rows kernel (csrc/iqn_act_few.h: no LDS weight image, two wavefronts per row) while the
+        list is expected to hold at most `rows` rows, (1 - eps) n (C-ABI mn_iqn_set_few_rows_max).  None: the library's default; negative: never;
+        FEW_ROWS_ALWAYS: always.  Same actions, draws and call counter either way."""
+        rows = self.FEW_ROWS_MAX_DEFAULT if rows is None else int(rows)
+        rc = _capi.lib().mn_iqn_set_few_rows_max(self.h, rows)
+        if rc:
+            raise _capi.MarineNavHipError(f"mn_iqn_set_few_rows_max failed ({rc})")
+        self.few_rows_max = rows
+
+    def few_rows_launches(self):
+        """Act launches of this context that ran as the few-rows kernel so far (C-ABI mn_iqn_few_rows_launches)."""
+        out = C.c_int64()
+        rc = _capi.lib().mn_iqn_few_rows_launches(self.h, C.byref(out))
+        if rc:
+            raise _capi.MarineNavHipError(f"mn_iqn_few_rows_launches failed ({rc})")
+        return out.value
 
     def set_tau_mode(self, mode):
         """0 = every observation row its own 32 taus (default, the reference's per-call draw); 1 = one set of 32 taus per launch:

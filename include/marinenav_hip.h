@@ -411,6 +411,21 @@ int mn_iqn_set_variant(mn_iqn_ctx *c, int32_t variant);
  * other call evaluates every row as before.  Actions, draws and the call counter are bit for bit those of `on` == 0; the list lives in the context
  * (int32 [n], allocated on the first launch of a size; that launch synchronises the device once). */
 int mn_iqn_set_greedy_rows(mn_iqn_ctx *c, int32_t on);
+/* A SHORT list of greedy rows runs in a kernel of its own (csrc/iqn_act_few.h): workgroups of two wavefronts, one per 16-tau column tile of a row, that read
+ * the weight image straight from global memory instead of copying its 154 KB into LDS first.  The launch that would run the listed form without late rows
+ * takes it while the list is EXPECTED to hold at most `rows` rows, (1 - eps) n <= rows (the host does not know the count; a longer list is still
+ * evaluated correctly, a workgroup loops over its positions).  rows < 0: never; 0x7fffffff: always (tests, A / B measurements).  Actions, draws and the
+ * call counter are bit for bit those of the listed form.
+ * MN_IQN_FEW_ROWS_MAX_DEFAULT = 256 rows: at 65 536 envs the few-rows kernel wins 7.0 / 6.6 / 6.4 / 6.4 us per vector step at ~20 / 100 / 150 / 200 listed
+ * rows, 2.1 us at 300 and 400 (more than those blocks' own spread, less than the 2.3 us sessions on this hardware have differed by), ties at 500 and loses
+ * 18 us at 2 000 and 89 us at 8 000 (profiles/act_few_rows.txt).  256 is just above the last length that is clearly won, and the length at which a chip
+ * of 256 CUs still gives every listed row a workgroup of its own. */
+#ifndef MN_IQN_FEW_ROWS_MAX_DEFAULT
+#define MN_IQN_FEW_ROWS_MAX_DEFAULT 256
+#endif
+int mn_iqn_set_few_rows_max(mn_iqn_ctx *c, int32_t rows);
+/* Test hook: the context's act launches that ran as the few-rows kernel so far (host counter; nothing synchronises). */
+int mn_iqn_few_rows_launches(mn_iqn_ctx *c, int64_t *out);
 /* How an act launch's quantile fractions are drawn (round 4).
  *   0 (default): every observation row gets its own 32 taus -- what a batch of independent calls of the reference's batch-1
  *      IQNAgent.act (agent.py:186-205 -> model.py:149-153) would draw.  mn_iqn_act takes taus [n][32]; mn_iqn_act_rng writes
