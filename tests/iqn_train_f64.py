@@ -288,10 +288,11 @@ def _errs(x, ref):
     return float(d.max()), float(np.sqrt(np.mean(d * d)))
 
 
-def compare_step(ref, fused, eager, label="", rows=None):
+def compare_step(ref, fused, eager, label="", rows=None, max_norm=MAX_NORM, lr=LR):
     """A float32 step `fused` and the float32 yardstick `eager` (namespaces: loss, grad, m, v, params, t) against the float64 step `ref` -- the bars of a
     case; raises AssertionError.  Eager PyTorch says how large float32 error is on this input; `fused` is never its own yardstick.  Appends one table line per
-    quantity to `rows` (fused error, eager error, ratio) and returns the bars of the loss and of the gradient's largest error."""
+    quantity to `rows` (fused error, eager error, ratio) and returns the bars of the loss and of the gradient's largest error.  `max_norm`, `lr`: the clip norm and
+    learning rate of the step (the IQN step's by default; tests/dqn_train_f64.py passes the DQN step's)."""
     rows = [] if rows is None else rows
     fails = []
 
@@ -314,7 +315,7 @@ def compare_step(ref, fused, eager, label="", rows=None):
     # side of a ReLU that float64 takes the other side of; a single (row, tau) flip is worth ~1 / (8 B) of an activation.  Their own distance shows they agree)
     rows.append(f"{label:34s} {'fused-eager':14s} grad max {_errs(fused.grad, np.asarray(eager.grad))[0]:10.3e}  of max |g64| {float(np.abs(ref.grad).max()):10.3e}  (not asserted)")
     # the clip: the branch float64 dictates.  Unclipped: p.grad IS the raw gradient, its norm the norm before the clip; clipped: ||p.grad|| = 0.5 norm / (norm + 1e-6)
-    want = ref.norm * min(1.0, MAX_NORM / (ref.norm + 1e-6))
+    want = ref.norm * min(1.0, max_norm / (ref.norm + 1e-6))
     nf, ne = float(np.linalg.norm(fused.grad)), float(np.linalg.norm(eager.grad))
     line("||grad||", abs(nf - want), abs(ne - want), MAX_FACTOR * abs(ne - want) + FLOOR * want)
     # parameters: where the gradient is well above its own error the update is well conditioned: fused within 2e-6 of eager (the tolerance of
@@ -324,7 +325,7 @@ def compare_step(ref, fused, eager, label="", rows=None):
     d = np.abs(pf - pe)
     line("param big", float(d[big].max(initial=0.0)), float(np.abs(pe - ref.params)[big].max(initial=0.0)), 2e-6)
     # (first step: m = v = 0, |update| <= lr; with history |update| can reach lr (1 - b1) / sqrt(1 - b2) ~ 3.2 lr: the moves of the two yardsticks instead)
-    rest_bar = np.full_like(d, 2 * LR) if ref.t == 1 else np.abs(ref.params - ref.p0) + np.abs(pe - ref.p0)
+    rest_bar = np.full_like(d, 2 * lr) if ref.t == 1 else np.abs(ref.params - ref.p0) + np.abs(pe - ref.p0)
     rest = ~big
     rel = lambda x: float((x[rest] / np.maximum(rest_bar[rest], 1e-300)).max(initial=0.0))
     line("param rest", rel(d), rel(np.abs(pe - ref.params)), 1.0)
