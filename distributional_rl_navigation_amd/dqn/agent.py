@@ -227,6 +227,98 @@ class DQNAgent:
         sd.update({"q_net_target." + k: v.detach().clone() for k, v in self.q_net_target.state_dict().items()})
         return sd
 
+    # ---- checkpoints of a training run (train_dqn --checkpoint-every / --stop-after / --resume) --------------------
+    def _owned_trainer(self):
+        return self._fused if self._fused is not None and self._fused.owns(self) else None
+
+    def _adam_state(self):
+        """(exp_avg [P], exp_avg_sq [P], step) of the ONE Adam state both gradient-step paths update, from whichever path holds it: the fused trainer's
+        flat buffers and device counter, or torch.optim.Adam's per-parameter state (zeros and 0 before the first step)."""
+        params = list(self.q_net.parameters())
+        ft = self._owned_trainer()
+        st0 = self.optimizer.state.get(params[0], None)
+        opt_step = int(float(st0["step"])) if st0 is not None and "step" in st0 else 0
+        if ft is not None:      # (the optimizer's moments are views of these)
+            return ft.exp_avg.detach().cpu().clone(), ft.exp_avg_sq.detach().cpu().clone(), int(ft.step_dev.item()) if self._train_path == "hip" else opt_step
+        flat = lambda key: torch.cat([(self.optimizer.state[p][key] if key in self.optimizer.state.get(p, {}) else torch.zeros_like(p)).detach().reshape(-1).cpu()
+                                      for p in params])
+        return flat("exp_avg"), flat("exp_avg_sq"), opt_step
+
+    def _load_adam_state(self, exp_avg, exp_avg_sq, step):
+        """The reverse, IN PLACE: into the fused trainer's flat buffers where there is one (the optimizer's views of them follow), into the optimizer's own
+        tensors otherwise, and the step count into both -- whichever path runs next finds what the saving agent's path left."""
+        ft = self._owned_trainer()
+        if ft is not None:
+            ft.exp_avg.copy_(exp_avg); ft.exp_avg_sq.copy_(exp_avg_sq)
+            ft.step_dev.fill_(int(step))
+        opt = self.optimizer
+        on_dev = any(g.get("fused") or g.get("capturable") for g in opt.param_groups)
+        off = 0
+        with torch.no_grad():
+            for p in self.q_net.parameters():
+                n = p.numel()
+                st = opt.state[p]
+                if "exp_avg" not in st:
+                    st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(p), torch.zeros_like(p)
+                if "step" not in st:
+                    st["step"] = torch.zeros((), dtype=torch.float32, device=p.device if on_dev else "cpu")
+                if ft is None:
+                    st["exp_avg"].copy_(exp_avg[off:off + n].view(p.shape)); st["exp_avg_sq"].copy_(exp_avg_sq[off:off + n].view(p.shape))
+                st["step"].fill_(float(int(step)))
+                off += n
+        self._train_path = None      # both paths hold the same state now: nothing to hand over at the next step
+
+    def global_rng_state(self):
+        """torch's CPU and device global generator states and python's: the agent's constructor seeds them, nothing in the training loop draws from them."""
+        import random
+        return dict(torch_cpu_rng=torch.get_rng_state(), torch_device_rng=torch.cuda.get_rng_state(self.device) if self.device.type == "cuda" else None,
+                    py_random=random.getstate())
+
+    def train_state_dict(self):
+        """Everything of the learner a continued training run depends on, as CPU tensors and plain values (`state_dict()` is the policy.pth of the sb3-style
+        zips and keeps its keys; the replay ring has its own `memory.state_dict()`): both networks, the ONE Adam state from whichever gradient-step path
+        holds it, the fused step's {seed, draw counter} (what a trainer made now would start from, where there is none yet), the update and timestep
+        counts, the fused collect's {seed, calls}, the eager collect's generator, and torch's CPU and device generators and python's.  Not state: the act
+        kernel's weight image, the workspaces, the multi-step buffers and `last_idx` -- the next call that needs them rebuilds them."""
+        ft = self._owned_trainer()
+        m, v, step = self._adam_state()
+        cpu = lambda net: {k: t.detach().cpu().clone() for k, t in net.state_dict().items()}
+        train_rng = (ft.rng_state.cpu() if ft is not None
+                     else torch.tensor([int(self.memory.gen.initial_seed()) & 0x7FFFFFFFFFFFFFFF, 0], dtype=torch.int64))
+        return dict(q_net=cpu(self.q_net), q_net_target=cpu(self.q_net_target), exp_avg=m, exp_avg_sq=v, adam_step=int(step), train_rng=train_rng,
+                    n_updates=int(self.n_updates), num_timesteps=int(self.num_timesteps), act_seed=int(self.act_seed), act_calls=int(self.act_calls),
+                    gen=self.gen.get_state(), **self.global_rng_state())
+
+    def load_train_state_dict(self, sd):
+        """Continue where `train_state_dict()` was taken, on either gradient-step path.  Everything is written IN PLACE: where the fused path is in use its
+        trainer is made first, and the networks, the moments, the step and the draw counter go into its existing flat buffers -- their addresses are what a
+        `LearnerGroup`'s device table holds.  Load the agent LAST: the state holds torch's generator states, which nothing behind it may move."""
+        import random
+        if self._uses_fused():
+            self._fused_trainer()
+        ft = self._owned_trainer()
+        with torch.no_grad():
+            for net, key in ((self.q_net, "q_net"), (self.q_net_target, "q_net_target")):
+                own = net.state_dict()
+                if own.keys() != sd[key].keys():
+                    raise ValueError(f"DQNAgent.load_train_state_dict: the saved {key} has other parameters ({sorted(set(own) ^ set(sd[key]))})")
+                for k, t in own.items():
+                    t.copy_(sd[key][k])
+        self._load_adam_state(sd["exp_avg"], sd["exp_avg_sq"], sd["adam_step"])
+        if ft is not None:
+            ft.rng_state.copy_(sd["train_rng"])
+            ft.point_grads()
+            ft._ws, ft._idx_out, ft._multi = {}, {}, {}      # caches: rebuilt by the next call of their shape
+            ft.__dict__.pop("last_idx", None)
+        self.n_updates, self.num_timesteps = int(sd["n_updates"]), int(sd["num_timesteps"])
+        self.act_seed, self.act_calls = int(sd["act_seed"]), int(sd["act_calls"])
+        self.policy.weights_changed()      # the act kernel's weight image repacks on the next act
+        self.gen.set_state(sd["gen"])
+        torch.set_rng_state(sd["torch_cpu_rng"])
+        if sd["torch_device_rng"] is not None and self.device.type == "cuda":
+            torch.cuda.set_rng_state(sd["torch_device_rng"], self.device)
+        random.setstate(sd["py_random"])
+
     def save(self, directory):
         os.makedirs(directory, exist_ok=True)
         torch.save(self.state_dict(), os.path.join(directory, "policy.pth"))

@@ -137,6 +137,24 @@ class DeferredEvaluations:
             self._envs.close()
             self._envs = None
 
+    # ---- checkpoints ---------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """What a continued run needs of the deferred evaluations once nothing is pending: `flush()` runs first -- legal at any point, because every group of
+        a grouped launch is bit for bit a launch of its own and the greedy DQN draws nothing -- and then the record logged so far, the best mean reward and
+        the counts (`n_taken`: snapshots taken, all logged by now) are all there is.  Numpy arrays and plain values; no wall-clock value."""
+        import copy
+        self.flush()
+        return dict(log=copy.deepcopy(self.log), best=float(self.best), n_taken=len(self.log["timesteps"]), launches=int(self.launches),
+                    steps_run=[int(s) for s in self.steps_run])
+
+    def load_state_dict(self, sd):
+        import copy
+        assert not self.pending, "load_state_dict into DeferredEvaluations with pending snapshots"
+        if int(sd["n_taken"]) != len(sd["log"]["timesteps"]):
+            raise ValueError("DeferredEvaluations.load_state_dict: the state counts other snapshots than its record holds")
+        self.log, self.best = copy.deepcopy(sd["log"]), float(sd["best"])
+        self.launches, self.steps_run = int(sd["launches"]), [int(s) for s in sd["steps_run"]]
+
     # ---- host half -----------------------------------------------------------------------------------------------------
     def log_traces(self, traces, timesteps, local, target, discount):
         """Log the checkpoints reported at `timesteps` from the numpy traces [T][len(timesteps) * R] of their launch, in order, as `run_trial` logs an

@@ -4,6 +4,7 @@ path, with the interface of train_iqn.
     python -m distributional_rl_navigation_amd.train_dqn -C config_DQN.json [--n-envs 4096] [--batch 256] [--replay N]
         [--grad-steps G] [--total-grad-steps N] [--n-evals K] [--torch-train] [--eval-one-launch] [--eval-deferred] [--dry-run]
         [--env-budget reference] [--episode-log [full]] [--train-steps-per-call {auto,1,K,multi}] [--fused-collect] [--together [--stack-envs]]
+        [--checkpoint-every K] [--stop-after K] [--resume TRAINING_DIR] [--run-name NAME]
 
 Same JSON schema as train_iqn (agent, seed (list -> grid), total_timesteps, eval_freq, save_dir); the trials run one after another
 on one device, or -- `--together` -- the seeds of a config in lockstep with ONE launch per gradient step for all of them (`run_trials_together`,
@@ -31,6 +32,12 @@ the seeds' envs are the rows of ONE handle and each vector step is one act, one 
 `--eval-deferred`: an evaluation point only keeps the policy of the moment (a weight image and the parameters, device copies on the training
 stream); the episodes of all pending points run later as ONE mn_rollout_dqn_groups launch (dqn/deferred_eval.py) and are logged as above -- the same
 files, bit for bit, without a host round trip per point: `--n-evals 300` logs the reference's evaluation density.
+
+`--checkpoint-every K`, `--stop-after K`, `--resume TRAINING_DIR`: as train_iqn's, with its helpers -- behind every K-th vector step the whole trial (env snapshot,
+replay ring, the learner's full state, the evaluations, the episode log, `TrialRun`'s own words) goes into checkpoint.pt of the seed's directory; a stopped run
+continues in a fresh process and, on the same gradient-step path, writes the files of the uninterrupted run.  Also under `--together` (per-seed envs): every
+seed writes its own checkpoint, the one its sequential run writes, so a run stopped in lockstep resumes sequentially and the other way round.  Not with
+`--stack-envs` (CHECKPOINT_REFUSALS).  Every trial directory ends with completed.json, written last.
 """
 import argparse
 import io
@@ -42,7 +49,9 @@ from datetime import datetime
 
 import numpy as np
 
-from .train_iqn import TRAINING_SCHEDULE, create_eval_configs, make_episode_log, plan_cadence, plan_eval_points, resolve_budget_args, trial_params
+from .train_iqn import (CHECKPOINT_FILE, CHECKPOINT_FORMAT, CHECKPOINT_PREV_FILE, COMPLETED_FILE, TRAINING_SCHEDULE, check_resumable, create_eval_configs,
+                        first_difference, load_checkpoint, make_episode_log, plan_cadence, plan_eval_points, resolve_budget_args, resume_point, trial_dir,
+                        trial_params, trial_shape, write_checkpoint)
 
 REF_BATCH, REF_UPDATE_EVERY, REF_TARGET_INTERVAL, REF_LEARNING_STARTS = 32, 1, 10_000, 10_000      # config_DQN.json / sb3 DQN defaults
 EXPLORATION_FRACTION, EPS_INITIAL, EPS_FINAL = 0.1, 1.0, 0.05
@@ -78,6 +87,50 @@ def make_plan(params, n_envs, batch, grad_steps=None, total_grad_steps=None, n_e
         plan["learning_starts_vector_steps"] = -(-REF_LEARNING_STARTS // n_envs)
     plan["exploration_vector_steps"] = EXPLORATION_FRACTION * plan["vector_steps"]
     return plan
+
+
+def plan_trial(params, n_envs, batch=None, replay=None, grad_steps=None, total_grad_steps=None, n_evals=None, env_budget="learner", reference=None):
+    """(n_envs, batch, replay, plan) of one trial: the budget's defaults filled in, `make_plan`, and the check every trial passes before anything is written or
+    allocated.  No GPU needed: `--resume` and `--dry-run --resume` plan with it as `TrialRun` does."""
+    n_envs, batch, replay = resolve_budget_args(env_budget, n_envs, batch, replay)
+    plan = make_plan(params, n_envs, batch, grad_steps, total_grad_steps, n_evals, budget=env_budget, reference=reference)
+    if env_budget == "reference":
+        if replay is not None and replay != plan["replay"]:
+            raise ValueError(f"env_budget='reference' keeps the reference's replay ring ({plan['replay']} rows); {replay} contradicts it")
+        replay = plan["replay"]
+    return n_envs, batch, replay, plan
+
+
+def run_shaping_args(env_budget="learner", fused_collect=False, eval_deferred=False, eval_one_launch=False, episode_log=None, max_eval_steps=1000, reference=None,
+                     eval_worlds=None, **_):
+    """The arguments of `run_trial` that shape a run beside its plan, normalised: what a checkpoint records and `--resume` compares (`train_iqn.check_resumable`).
+    ONE place builds it, for the run, the lockstep run and `--dry-run --resume`; the defaults are `run_trial`'s.  (`torch_train` and `train_steps_per_call` are
+    recorded by the checkpoint but not compared: the multi-step call is bit-identical to the loop, and a checkpoint of one gradient-step path continues on the
+    other as a valid run.)"""
+    return dict(env_budget=env_budget, fused_collect=bool(fused_collect), eval_deferred=bool(eval_deferred) or env_budget == "reference",
+                eval_one_launch=bool(eval_one_launch), episode_log=episode_log, max_eval_steps=int(max_eval_steps), reference=dict(reference or {}),
+                eval_worlds=eval_worlds)
+
+
+CHECKPOINT_REFUSALS = dict(
+    stack_envs="--checkpoint-every, --stop-after and --resume keep one checkpoint per seed; with --stack-envs the seeds share ONE env handle, whose snapshot is one "
+               "blob for all rows, which a seed's checkpoint cannot hold: use --together without --stack-envs")
+
+
+def _log(line):
+    print(line.replace("[train_iqn]", "[train_dqn]", 1), flush=True)
+
+
+def check_lockstep(points):
+    """`points`: (seed, what, state) of the seeds that are left of a group (`train_iqn.resume_point`; none "completed").  The lockstep loop continues them only
+    from ONE vector step: all at "start", or all with checkpoints of the same step.  Returns that step (0: the start); ValueError names every seed with its
+    step."""
+    steps = [0 if state is None else int(state["vector_step"]) for _, _, state in points]
+    if len(set(steps)) > 1:
+        where = ", ".join(f"seed {seed} at vector step {k}" + (" (no checkpoint)" if state is None else "") for (seed, _, state), k in zip(points, steps))
+        raise ValueError(f"--resume --together: the seeds of a group continue in lockstep from one vector step, but {where}; resume without --together (the "
+                         "seeds one after the other), which always works")
+    return steps[0] if steps else 0
 
 
 def exploration_rate(it, plan):
@@ -144,24 +197,21 @@ class TrialRun:
 
     def __init__(self, device, params, n_envs, batch=None, replay=None, grad_steps=None, total_grad_steps=None, n_evals=None, torch_train=False,
                  verbose=True, eval_one_launch=False, eval_deferred=False, eval_config=None, max_eval_steps=1000, env_budget="learner",
-                 reference=None, episode_log=None, on_step=None, fused_collect=False, train_env=None):
+                 reference=None, episode_log=None, on_step=None, fused_collect=False, train_env=None, eval_worlds=None):
         from .dqn.agent import DQNAgent
         from .marinenav_env.vec_env import VecMarineNavEnv
         self.params, self.verbose, self.on_step, self.eval_one_launch, self.max_eval_steps = params, verbose, on_step, eval_one_launch, max_eval_steps
-        self.exp_dir = exp_dir = os.path.join(params["save_dir"], "training_" + params["training_time"], "seed_" + str(params["seed"]))
+        self.exp_dir = exp_dir = trial_dir(params)
         ref_mode = env_budget == "reference"
-        n_envs, batch, replay = resolve_budget_args(env_budget, n_envs, batch, replay)
-        self.n_envs, self.batch = n_envs, batch
-        self.plan = plan = make_plan(params, n_envs, batch, grad_steps, total_grad_steps, n_evals, budget=env_budget, reference=reference)
+        n_envs, batch, replay, plan = plan_trial(params, n_envs, batch, replay, grad_steps, total_grad_steps, n_evals, env_budget, reference)
+        self.n_envs, self.batch, self.plan = n_envs, batch, plan
+        self.shape = trial_shape(plan, n_envs, 1, batch, replay)      # (what a checkpoint keeps and `--resume` compares)
         if ref_mode:
-            if replay is not None and replay != plan["replay"]:
-                raise ValueError(f"env_budget='reference' keeps the reference's replay ring ({plan['replay']} rows); {replay} contradicts it")
-            replay = plan["replay"]
             eval_deferred = eval_deferred or True      # (300 evaluation points: each only keeps the policy of the moment)
         self.eval_points = plan_eval_points(plan, n_envs) if ref_mode else None
         os.makedirs(exp_dir, exist_ok=True)
         with open(os.path.join(exp_dir, "trial_config.json"), "w+") as f:
-            json.dump(dict(params, batched=dict(plan, n_envs=n_envs, world=1, batch=batch, replay=replay)), f)
+            json.dump(dict(params, batched=self.shape), f)
         with open(os.path.join(exp_dir, "training_schedule.json"), "w+") as f:
             json.dump(TRAINING_SCHEDULE, f)
         if verbose:
@@ -175,6 +225,8 @@ class TrialRun:
         self.train_env = train_env
         if eval_config is None:
             eval_config = create_eval_configs(device)
+        if eval_worlds is not None:      # (a run at toy size: the first few of the evaluation worlds)
+            eval_config = {k: eval_config[k] for k in list(eval_config)[:int(eval_worlds)]}
         self.eval_config = eval_config
         self.eval_env = VecMarineNavEnv(len(eval_config), device=device, precision="f64")
         self.agent = agent = DQNAgent(26, 9, buffer_size=replay, batch_size=batch, learning_starts=0, device=device, seed=params["seed"] + 100,
@@ -196,6 +248,9 @@ class TrialRun:
         self.n_points = 0
         self.obs = self.train_env.reset()
         self.grad_steps_done = 0
+        # run_trials_together with checkpoints: the process's global generators belong to no single seed there, so a seed's checkpoint records them as they
+        # stood behind THIS seed's constructor -- where its sequential run, whose loop draws nothing from them, still finds them at every checkpoint
+        self.global_rng = None
 
     def collect(self, it):
         """Act, step the envs, log, append the transitions to the replay ring, reset the finished envs."""
@@ -278,12 +333,66 @@ class TrialRun:
         torch.cuda.synchronize()
         self.train_env.close()
         self.eval_env.close()
+        with open(os.path.join(self.exp_dir, COMPLETED_FILE), "w") as f:      # last: the marker says every file of the trial is there (`--resume` skips the seed)
+            json.dump(dict(vector_steps=int(self.plan["vector_steps"]), grad_steps=int(self.grad_steps_done)), f)
         return self.exp_dir
+
+    def release(self):
+        """Close the envs and wait for the device; writes nothing (`finish` without its files: a run that stopped at a checkpoint, whose deferred evaluations
+        the checkpoint flushed)."""
+        import torch
+        if self.deferred is not None:
+            self.deferred.close()
+        self.train_env.close()
+        self.eval_env.close()
+        torch.cuda.synchronize()
+
+    # ---- checkpoints (--checkpoint-every, --stop-after, --resume) -------------------------------------------------------------------
+    def own_state(self):
+        """TrialRun's own words behind a finished vector step: the observation rows the next act reads, the gradient steps done, the evaluation points
+        taken, and the inline evaluations' record and best mean reward.  CPU tensors, numpy arrays and plain values."""
+        import copy
+        return dict(obs=self.obs.detach().cpu().clone(), grad_steps_done=int(self.grad_steps_done), n_points=int(self.n_points), log=copy.deepcopy(self.log),
+                    best=float(self.best))
+
+    def load_own_state(self, sd):
+        import copy
+        self.obs.copy_(sd["obs"])
+        self.grad_steps_done, self.n_points = int(sd["grad_steps_done"]), int(sd["n_points"])
+        self.log, self.best = copy.deepcopy(sd["log"]), float(sd["best"])
+
+    def checkpoint_state(self, next_step, run_args=None):
+        """The whole trial behind vector step `next_step - 1` as one dict of CPU tensors and plain values.  Order matters: the env first (its save settles an
+        owed reset, so the observation rows saved are final), then the deferred evaluations (flushed: that writes their files) and the episode log, then
+        the ring, the agent last."""
+        env = self.train_env.state_dict()      # (the evaluation env is not state: every evaluation loads its worlds afresh and draws nothing)
+        deferred = None if self.deferred is None else self.deferred.state_dict()
+        ep_log = None if self.ep_log is None else self.ep_log.state_dict()
+        return dict(format=CHECKPOINT_FORMAT, vector_step=int(next_step), params=dict(self.params), plan=dict(self.shape), args=dict(run_args or {}),
+                    env=env, deferred=deferred, episode_log=ep_log, run=self.own_state(), ring=self.agent.memory.state_dict(),
+                    agent=dict(self.agent.train_state_dict(), **(self.global_rng or {})))
+
+    def restore(self, state):
+        """`checkpoint_state` back into this (freshly built) trial.  Returns the vector step to continue with.  The agent comes last: its state holds torch's
+        generator states, which nothing behind it may move."""
+        if (state["deferred"] is None) != (self.deferred is None) or (state["episode_log"] is None) != (self.ep_log is None):
+            raise ValueError("TrialRun.restore: the saved trial and this one differ in their deferred evaluations or their episode log")
+        self.train_env.load_state_dict(state["env"])
+        if self.deferred is not None:
+            self.deferred.load_state_dict(state["deferred"])
+        if self.ep_log is not None:
+            self.ep_log.load_state_dict(state["episode_log"])
+        self.agent.memory.load_state_dict(state["ring"])
+        self.obs = self.train_env.obs
+        self.load_own_state(state["run"])
+        self.agent.load_train_state_dict(state["agent"])
+        return int(state["vector_step"])
 
 
 def run_trial(device, params, n_envs, batch=None, replay=None, grad_steps=None, total_grad_steps=None, n_evals=None, torch_train=False,
               verbose=True, eval_one_launch=False, eval_deferred=False, eval_config=None, max_eval_steps=1000, return_agent=False, env_budget="learner",
-              reference=None, episode_log=None, on_step=None, train_steps_per_call="auto", fused_collect=False):
+              reference=None, episode_log=None, on_step=None, train_steps_per_call="auto", fused_collect=False, eval_worlds=None, checkpoint_every=None,
+              stop_after=None, resume=False, dump_final_state=None):
     """train_sb3_model.py on the vector env for one trial of the config grid; returns the trial directory (`return_agent`: and the agent).
     `eval_one_launch`: each evaluation as one mn_rollout_dqn launch instead of one Python iteration per env step (same results).
     `eval_deferred` (True, or a dict of DeferredEvaluations arguments such as max_pending): an evaluation point keeps the policy of the moment and the
@@ -297,16 +406,43 @@ def run_trial(device, params, n_envs, batch=None, replay=None, grad_steps=None, 
     calls (`DQNAgent.train_many`), one per stretch between target copies (at batch <= 32 on the fused path one HIP call each, elsewhere the loop); K > 1 -- the
     same with at most K steps per call; "auto" -- AUTO_TRAIN_STEPS_PER_CALL.  The same files either way.
     `fused_collect`: the collect phase on the device (`DQNAgent(fused_collect=True)`): one exploring act launch with the library's draws, the append inside
-    the env step.  Other exploration draws than the default's, so other files."""
+    the env step.  Other exploration draws than the default's, so other files.
+    `eval_worlds`: evaluate on the first so many evaluation worlds only (runs at toy size).
+    `checkpoint_every` = K: behind every K-th vector step -- behind its evaluation points -- the whole trial goes into checkpoint.pt of the trial's directory
+    (`TrialRun.checkpoint_state`, `train_iqn.write_checkpoint`: atomically, the previous one kept as checkpoint.prev.pt); `stop_after` = K: a checkpoint behind
+    vector step K, where the trial then ends without its final files and without completed.json; `resume`: skip the trial if its directory holds
+    completed.json, continue from its checkpoint if it holds one (refused if that was written under another plan or other run-shaping arguments,
+    `run_shaping_args`), start from the beginning otherwise.  A run stopped and resumed on the same gradient-step path writes the files of the
+    uninterrupted run; a checkpoint of one path continues on the other as a valid run (eager Adam and the fused step differ in the last bits).  Without the
+    three the loop does nothing it did not do before.
+    `dump_final_state`: a file for torch.save(dict(env=, ring=, agent=)) of the states behind the last vector step (tests)."""
     from .dqn.agent import split_at_target_sync
     per_call = steps_per_call(train_steps_per_call)
+    checkpointing = checkpoint_every is not None or stop_after is not None or resume
+    if checkpoint_every is not None and int(checkpoint_every) < 1 or stop_after is not None and int(stop_after) < 1:
+        raise ValueError("checkpoint_every and stop_after count vector steps: at least 1")
+    run_args = run_shaping_args(env_budget=env_budget, fused_collect=fused_collect, eval_deferred=eval_deferred, eval_one_launch=eval_one_launch,
+                                episode_log=episode_log, max_eval_steps=max_eval_steps, reference=reference, eval_worlds=eval_worlds)
+    state = None
+    if resume:      # (looked at before anything is built or written: a finished seed is left alone, a foreign checkpoint refused)
+        exp_dir = trial_dir(params)
+        ne, b, r, plan = plan_trial(params, n_envs, batch, replay, grad_steps, total_grad_steps, n_evals, env_budget, reference)
+        what, state, name = resume_point(exp_dir, trial_shape(plan, ne, 1, b, r), run_args, log=_log)
+        if what == "completed":
+            print(f"[train_dqn] seed {params['seed']}: {exp_dir} holds {COMPLETED_FILE}, nothing to do", flush=True)
+            return (exp_dir, None) if return_agent else exp_dir
+        if verbose:
+            print(f"[train_dqn] seed {params['seed']}: " + (f"continuing from vector step {state['vector_step']} ({name})" if state is not None
+                                                            else "no checkpoint, starting from the beginning"), flush=True)
     run = TrialRun(device, params, n_envs, batch=batch, replay=replay, grad_steps=grad_steps, total_grad_steps=total_grad_steps, n_evals=n_evals,
                    torch_train=torch_train, verbose=verbose, eval_one_launch=eval_one_launch, eval_deferred=eval_deferred, eval_config=eval_config,
                    max_eval_steps=max_eval_steps, env_budget=env_budget, reference=reference, episode_log=episode_log, on_step=on_step,
-                   fused_collect=fused_collect)
+                   fused_collect=fused_collect, eval_worlds=eval_worlds)
     agent, plan = run.agent, run.plan
     G, sync_every = plan["grad_steps_per_vector_step"], plan["target_sync_grad_steps"]
-    for it in range(plan["vector_steps"]):
+    first = run.restore(state) if state is not None else 0
+    saved_args = dict(run_args, torch_train=bool(torch_train), train_steps_per_call=str(train_steps_per_call))
+    for it in range(first, plan["vector_steps"]):
         run.collect(it)
         if run.trains_after(it):
             for steps, sync_after in split_at_target_sync(run.grad_steps_done, G, sync_every):
@@ -320,8 +456,29 @@ def run_trial(device, params, n_envs, batch=None, replay=None, grad_steps=None, 
                 if sync_after:
                     agent.sync_target()
         run.evaluate_points(it)
+        if checkpointing and checkpoint_behind(run, it + 1, checkpoint_every, stop_after, saved_args):
+            run.release()
+            print(stopped_line(run, it + 1), flush=True)
+            return (run.exp_dir, agent) if return_agent else run.exp_dir
+    if dump_final_state is not None:
+        import torch
+        torch.save(dict(env=run.train_env.state_dict(), ring=agent.memory.state_dict(), agent=agent.train_state_dict()), dump_final_state)
     exp_dir = run.finish()
     return (exp_dir, agent) if return_agent else exp_dir
+
+
+def checkpoint_behind(run, done, checkpoint_every, stop_after, saved_args):
+    """Behind vector step `done` (1-based count) of `run`: write its checkpoint if `checkpoint_every` or `stop_after` asks for one.  Returns whether the
+    run stops here (`stop_after` = `done`, short of the plan's last vector step: a K at or beyond it stops nothing)."""
+    stop = stop_after is not None and done == int(stop_after) and done < run.plan["vector_steps"]
+    if stop or (checkpoint_every and done % int(checkpoint_every) == 0):
+        write_checkpoint(run.exp_dir, run.checkpoint_state(done, saved_args))
+    return stop
+
+
+def stopped_line(run, done):
+    return (f"[train_dqn] seed {run.params['seed']}: stopped after vector step {done} of {run.plan['vector_steps']}; checkpoint in "
+            f"{os.path.join(run.exp_dir, CHECKPOINT_FILE)} (continue with --resume {os.path.dirname(run.exp_dir)})")
 
 
 def group_trials(trials, limit=None):
@@ -353,7 +510,7 @@ def stacked_train_env(device, trials, n_envs, env_budget="learner", batch=None, 
 
 
 def run_trials_together(device, trials, n_envs, torch_train=False, on_step=None, return_agents=False, train_steps_per_call="auto", stack_envs=False,
-                        **kwargs):
+                        checkpoint_every=None, stop_after=None, resume=False, **kwargs):
     """`run_trial` for several trials that differ only in their seed (one list of `group_trials`), in LOCKSTEP: per vector step every trial collects as it
     does alone -- its own envs, agent, exploration, generator, replay ring, episode log and hook -- then the gradient steps behind that vector step run for
     ALL trials through one `LearnerGroup` (dqn/group_train.py): one launch per gradient step, or one multi-step call per stretch between target copies,
@@ -363,12 +520,22 @@ def run_trials_together(device, trials, n_envs, torch_train=False, on_step=None,
     `stack_envs` (implies `fused_collect`): the collect phase is shared too -- the seeds' envs are the rows of ONE handle (`stacked_train_env`) and per vector
     step there is one act launch at the common exploration rate, one env step, one append into all rings and one reset launch (dqn/group_collect.py:
     `CollectorGroup`) instead of one chain per seed; every seed then finishes the step on its own rows (`TrialRun.collect_given`).  Every seed's files are
-    what `run_trial(fused_collect=True)` writes."""
+    what `run_trial(fused_collect=True)` writes.
+    `checkpoint_every`, `stop_after`, `resume` (per-seed envs only: refused with `stack_envs`, CHECKPOINT_REFUSALS): every learner and every env is bit for
+    bit what it is alone, so behind lockstep vector step k every seed writes ITS OWN checkpoint.pt into its own directory -- the dict the sequential run
+    writes at k -- and a run stopped here resumes sequentially, and the other way round.  `resume`: completed seeds leave the group (a group of one runs as
+    `run_trial`); the others must all be at the start or all hold checkpoints of ONE vector step (`check_lockstep`), which is refused before anything is
+    built or written otherwise.  A stopped run returns the trial directories as a finished one does."""
     import torch
     from .dqn.agent import split_at_target_sync
     from .dqn.group_train import LearnerGroup
     if torch_train:
         raise ValueError("training trials together needs the fused gradient step: there is no grouped form of the eager PyTorch step (torch_train)")
+    checkpointing = checkpoint_every is not None or stop_after is not None or resume
+    if checkpointing and stack_envs:
+        raise ValueError(CHECKPOINT_REFUSALS["stack_envs"])
+    if checkpoint_every is not None and int(checkpoint_every) < 1 or stop_after is not None and int(stop_after) < 1:
+        raise ValueError("checkpoint_every and stop_after count vector steps: at least 1")
     if stack_envs and torch.device(device).type != "cuda":
         raise ValueError(f"stack_envs: the stacked collect runs on HIP kernels; device {device} has none")
     trials = list(trials)
@@ -376,6 +543,34 @@ def run_trials_together(device, trials, n_envs, torch_train=False, on_step=None,
         raise ValueError("trials that train together differ only in their seed, and are at most 64 (group_trials)")
     per_call = steps_per_call(train_steps_per_call)
     hooks = list(on_step) if on_step is not None else [None] * len(trials)
+    run_args = run_shaping_args(**kwargs)
+    states, all_dirs, all_agents = [None] * len(trials), [trial_dir(p) for p in trials], [None] * len(trials)
+    if resume:      # (looked at before anything is built or written)
+        plan_kw = {k: kwargs.get(k) for k in ("batch", "replay", "grad_steps", "total_grad_steps", "n_evals", "reference")}
+        ne, b, r, plan = plan_trial(trials[0], n_envs, env_budget=kwargs.get("env_budget", "learner"), **plan_kw)
+        shape = trial_shape(plan, ne, 1, b, r)
+        points = [(p["seed"],) + resume_point(d, shape, run_args, log=_log)[:2] for p, d in zip(trials, all_dirs)]
+        left = [i for i, pt in enumerate(points) if pt[1] != "completed"]
+        for i, pt in enumerate(points):
+            if pt[1] == "completed":
+                print(f"[train_dqn] seed {pt[0]}: {all_dirs[i]} holds {COMPLETED_FILE}, nothing to do", flush=True)
+        first = check_lockstep([points[i] for i in left])
+        if len(left) <= 1:      # a group of one runs as run_trial (which looks at its directory again)
+            for i in left:
+                out = run_trial(device, trials[i], n_envs, on_step=hooks[i], return_agent=True, train_steps_per_call=train_steps_per_call,
+                                checkpoint_every=checkpoint_every, stop_after=stop_after, resume=True, **kwargs)
+                all_agents[i] = out[1]
+            return (all_dirs, all_agents) if return_agents else all_dirs
+        if kwargs.get("verbose", True):
+            seeds = [points[i][0] for i in left]
+            print(f"[train_dqn] seeds {seeds}: " + (f"continuing from vector step {first} (their checkpoints)" if first else "no checkpoints, starting from the beginning"),
+                  flush=True)
+        states = [points[i][2] for i in left]
+        keep = left
+        trials, hooks = [trials[i] for i in keep], [hooks[i] for i in keep]
+    else:
+        keep = list(range(len(trials)))
+    saved_args = dict(run_args, torch_train=False, train_steps_per_call=str(train_steps_per_call))
     stacked, views, collectors = None, [None] * len(trials), None
     if stack_envs:
         from .dqn.group_collect import CollectorGroup
@@ -384,7 +579,11 @@ def run_trials_together(device, trials, n_envs, torch_train=False, on_step=None,
         env_kw = {k: kwargs[k] for k in ("env_budget", "batch", "replay", "grad_steps", "total_grad_steps", "n_evals", "reference") if k in kwargs}
         stacked, n_rows = stacked_train_env(device, trials, n_envs, **env_kw)
         views = [StackedRows(stacked, g, n_rows) for g in range(len(trials))]
-    runs = [TrialRun(device, p, n_envs, on_step=h, train_env=v, **kwargs) for p, h, v in zip(trials, hooks, views)]
+    runs = []
+    for p, h, v in zip(trials, hooks, views):
+        runs.append(TrialRun(device, p, n_envs, on_step=h, train_env=v, **kwargs))
+        if checkpointing:
+            runs[-1].global_rng = runs[-1].agent.global_rng_state()
     plan = runs[0].plan
     assert all(r.plan == plan for r in runs)
     group = LearnerGroup([r.agent for r in runs])
@@ -392,8 +591,14 @@ def run_trials_together(device, trials, n_envs, torch_train=False, on_step=None,
         collectors = CollectorGroup([r.agent for r in runs], stacked)
         obs = stacked.obs
     G, sync_every = plan["grad_steps_per_vector_step"], plan["target_sync_grad_steps"]
-    done = 0
-    for it in range(plan["vector_steps"]):
+    done, first = 0, 0
+    if any(st is not None for st in states):      # (behind the LearnerGroup: every learner's state goes IN PLACE into the buffers its device table names)
+        firsts = [r.restore(st) for r, st in zip(runs, states)]
+        for r, st in zip(runs, states):
+            r.global_rng = {k: st["agent"][k] for k in ("torch_cpu_rng", "torch_device_rng", "py_random")}
+        first, done = firsts[0], runs[0].grad_steps_done
+        assert all(f == first for f in firsts) and all(r.grad_steps_done == done for r in runs), (firsts, [r.grad_steps_done for r in runs])
+    for it in range(first, plan["vector_steps"]):
         if stack_envs:
             actions = collectors.act(obs, exploration_rate(it, plan))
             next_obs, reward, ended, info = stacked.step(actions)
@@ -421,12 +626,24 @@ def run_trials_together(device, trials, n_envs, torch_train=False, on_step=None,
                 r.grad_steps_done = done
         for r in runs:
             r.evaluate_points(it)
+        if checkpointing:
+            stops = [checkpoint_behind(r, it + 1, checkpoint_every, stop_after, saved_args) for r in runs]
+            if stops[0]:
+                for r in runs:
+                    r.release()
+                    print(stopped_line(r, it + 1), flush=True)
+                group.close()
+                for i, r in zip(keep, runs):
+                    all_agents[i] = r.agent
+                return (all_dirs, all_agents) if return_agents else all_dirs
     dirs = [r.finish() for r in runs]
     group.close()
     if collectors is not None:
         collectors.close()
         stacked.close()
-    return (dirs, [r.agent for r in runs]) if return_agents else dirs
+    for i, r, d in zip(keep, runs, dirs):
+        all_dirs[i], all_agents[i] = d, r.agent
+    return (all_dirs, all_agents) if return_agents else all_dirs
 
 
 def main(argv=None):
@@ -469,27 +686,101 @@ def main(argv=None):
                          "append and one reset launch for all of them; implies --fused-collect, and every seed's files equal its own --fused-collect run's")
     ap.add_argument("--dry-run", action="store_true", help="print the plan of every trial as JSON and exit (no GPU needed); with --together also which trials "
                                                            "would share a group")
+    ap.add_argument("--checkpoint-every", type=int, default=None, metavar="K",
+                    help="behind every K-th vector step write checkpoint.pt into the trial's directory (atomically; the previous one is kept as checkpoint.prev.pt): the "
+                         "env handle's snapshot (mn_state_save), the replay ring, the learner (both networks, Adam, the draw counters, the generators), the "
+                         "evaluations and the episode log.  With --together every seed writes its own.  Off by default: the loop then does nothing it did not do before")
+    ap.add_argument("--stop-after", type=int, default=None, metavar="K",
+                    help="end every trial behind vector step K with a checkpoint written at that step; exit status 0 (a time-limited session: continue with --resume).  A K "
+                         "at or beyond the plan's vector steps stops nothing: the trial completes")
+    ap.add_argument("--resume", default=None, metavar="TRAINING_DIR",
+                    help="continue the run in save_dir/training_<time>: per seed, skip it if it holds completed.json, continue from its checkpoint.pt (checkpoint.prev.pt if "
+                         "that is unreadable) or start it if it has none.  Give the command line of the original run: another plan is refused.  On the same gradient-step "
+                         "path the files written equal those of the uninterrupted run.  A run stopped under --together resumes with or without it; with --together the "
+                         "seeds left of a group must be at one vector step.  With --dry-run: print where every seed would continue")
+    ap.add_argument("--run-name", default=None, metavar="NAME", help="name the run directory training_NAME instead of training_<start time>")
+    ap.add_argument("--reference", nargs="*", default=None, metavar="KEY=VALUE",
+                    help="with --env-budget reference: overrides of the reference's constants (learning_starts, target_update_interval, exploration_fraction, replay) "
+                         "for runs at toy size")
+    ap.add_argument("--max-eval-steps", type=int, default=1000, help="step limit of an evaluation episode (default 1000, the reference's)")
+    ap.add_argument("--eval-worlds", type=int, default=None, metavar="N", help="evaluate on the first N of the 30 evaluation worlds (runs at toy size)")
+    ap.add_argument("--dump-final-state", default=None, metavar="FILE",
+                    help="behind the last vector step, torch.save the agent's train_state_dict() and the state_dict()s of its replay ring and the train env of the LAST "
+                         "trial run to FILE (tests)")
     args = ap.parse_args(argv)
     if args.together and args.torch_train:
         raise SystemExit("train_dqn: " + TOGETHER_REFUSALS["torch_train"])
     if args.stack_envs and not args.together:
         raise SystemExit("train_dqn: " + TOGETHER_REFUSALS["stack_envs"])
+    checkpointing = args.checkpoint_every is not None or args.stop_after is not None or args.resume is not None
+    if checkpointing:
+        if args.stack_envs:
+            raise SystemExit("train_dqn: " + CHECKPOINT_REFUSALS["stack_envs"])
+        if (args.checkpoint_every is not None and args.checkpoint_every < 1) or (args.stop_after is not None and args.stop_after < 1):
+            raise SystemExit("train_dqn: --checkpoint-every and --stop-after count vector steps: at least 1")
+    reference = None
+    if args.reference is not None:
+        if args.env_budget != "reference":
+            raise SystemExit("train_dqn: --reference overrides belong to --env-budget reference")
+        try:
+            reference = {k: (float(v) if k == "exploration_fraction" else int(v)) for k, v in (kv.split("=", 1) for kv in args.reference)}
+        except ValueError:
+            raise SystemExit("train_dqn: --reference takes KEY=VALUE pairs with numeric values")
+    if args.dump_final_state is not None and args.together:
+        raise SystemExit("train_dqn: --dump-final-state dumps one trial's state; the lockstep loop of --together has none to dump")
     fused_collect = args.fused_collect or args.stack_envs
     try:
         steps_per_call(args.train_steps_per_call)
     except ValueError as e:
         raise SystemExit(f"train_dqn: {e}")
     params = json.load(args.config_file)
-    stamp = datetime.now().strftime("%Y-%m-%d-%H-%M-%S")
+    stamp = args.run_name if args.run_name is not None else datetime.now().strftime("%Y-%m-%d-%H-%M-%S")
+    if args.resume is not None:
+        rdir = os.path.abspath(args.resume)
+        if not os.path.isdir(rdir) or not os.path.basename(rdir).startswith("training_"):
+            raise SystemExit(f"train_dqn: --resume takes a run directory, save_dir/training_<time>; {args.resume!r} is none")
+        stamp = os.path.basename(rdir)[len("training_"):]
+        for p in trial_params(params):
+            if os.path.realpath(os.path.join(p["save_dir"], "training_" + stamp)) != os.path.realpath(rdir):
+                raise SystemExit(f"train_dqn: --resume {args.resume}: the config's save_dir ({p['save_dir']!r}) does not lead to that directory")
+    # (only what was asked for is passed on: without these options run_trial and run_trials_together are called as ever)
+    more = {}
+    if reference is not None:
+        more["reference"] = reference
+    if args.max_eval_steps != 1000:
+        more["max_eval_steps"] = args.max_eval_steps
+    if args.eval_worlds is not None:
+        more["eval_worlds"] = args.eval_worlds
+    if checkpointing:
+        more.update(checkpoint_every=args.checkpoint_every, stop_after=args.stop_after, resume=args.resume is not None)
     trials = trial_params(params)
     for p in trials:
         p["training_time"] = stamp
     groups = group_trials(trials) if args.together else [[i] for i in range(len(trials))]
+
+    def where_to_continue(emit):
+        """`--resume`: every seed's resume point, checked as the run checks it -- a foreign checkpoint and, under --together, seeds of a group at different
+        vector steps end the command here, before anything is built or written."""
+        run_args = run_shaping_args(env_budget=args.env_budget, fused_collect=fused_collect, eval_deferred=args.eval_deferred, eval_one_launch=args.eval_one_launch,
+                                    episode_log=args.episode_log, **more)
+        try:
+            points = []
+            for p in trials:
+                ne, b, r, plan = plan_trial(p, args.n_envs, args.batch, args.replay, args.grad_steps, args.total_grad_steps, args.n_evals, args.env_budget, reference)
+                what, state, name = resume_point(trial_dir(p), trial_shape(plan, ne, 1, b, r), run_args, log=_log if emit is not None else (lambda line: None))
+                points.append((p["seed"], what, state))
+                if emit is not None:
+                    emit(dict(seed=p["seed"], resume=what, vector_step=None if state is None else int(state["vector_step"]), checkpoint=name))
+            for g in groups:      # (--together: the seeds left of a group continue from one vector step)
+                check_lockstep([points[i] for i in g if points[i][1] != "completed"])
+        except ValueError as e:
+            raise SystemExit(f"train_dqn: {e}")
+
     if args.dry_run:
         n_envs, batch, replay = resolve_budget_args(args.env_budget, args.n_envs, args.batch, args.replay)
         for p in trials:
             try:
-                plan = make_plan(p, n_envs, batch, args.grad_steps, args.total_grad_steps, args.n_evals, budget=args.env_budget)
+                plan = make_plan(p, n_envs, batch, args.grad_steps, args.total_grad_steps, args.n_evals, budget=args.env_budget, reference=reference)
                 if args.env_budget == "reference" and replay is not None and replay != plan["replay"]:
                     raise ValueError(f"env_budget='reference' keeps the reference's replay ring ({plan['replay']} rows); {replay} contradicts it")
             except ValueError as e:
@@ -498,17 +789,21 @@ def main(argv=None):
             print(json.dumps(dict(seed=p["seed"], n_envs=n_envs, batch=batch, replay=plan.get("replay", replay), fused=not args.torch_train,
                                   eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred or args.env_budget == "reference", **extra, **(dict(fused_collect=True) if fused_collect else {}), eps_start=exploration_rate(0, plan), eps_end=exploration_rate(int(np.ceil(plan["exploration_vector_steps"])), plan),
                                   plan=plan)))
+        if args.resume is not None:      # where every seed would continue (reads its checkpoint on the host; the same checks as the run itself)
+            where_to_continue(lambda line: print(json.dumps(line), flush=True))
         if args.together:
             stacked = lambda g: dict(stacked_env_rows=len(g) * n_envs, rows_per_seed=n_envs) if args.stack_envs and len(g) > 1 else {}
             print(json.dumps(dict(together=[dict(group=k, seeds=[trials[i]["seed"] for i in g], one_launch_per_gradient_step=len(g) > 1, **stacked(g))
                                             for k, g in enumerate(groups)])))
         return
+    if args.resume is not None:
+        where_to_continue(None)
     import torch
     device = "cuda:0" if args.device in (None, "cuda") else args.device
     torch.cuda.set_device(torch.device(device))
     common = dict(batch=args.batch, replay=args.replay, grad_steps=args.grad_steps, total_grad_steps=args.total_grad_steps, n_evals=args.n_evals,
                   torch_train=args.torch_train, eval_one_launch=args.eval_one_launch, eval_deferred=args.eval_deferred, env_budget=args.env_budget,
-                  episode_log=args.episode_log, train_steps_per_call=args.train_steps_per_call, fused_collect=fused_collect)
+                  episode_log=args.episode_log, train_steps_per_call=args.train_steps_per_call, fused_collect=fused_collect, **more)
     for g in groups:
         t0 = time.time()
         if len(g) > 1:
@@ -519,7 +814,7 @@ def main(argv=None):
             print(f"[train_dqn] seeds {seeds}: {time.time() - t0:.1f} s -> {os.path.dirname(dirs[0])}", flush=True)
             continue
         p = trials[g[0]]
-        d = run_trial(device, p, args.n_envs, **common)
+        d = run_trial(device, p, args.n_envs, **common, **(dict(dump_final_state=args.dump_final_state) if args.dump_final_state is not None else {}))
         print(f"[train_dqn] seed {p['seed']}: {time.time() - t0:.1f} s -> {d}", flush=True)
 
 

@@ -10,6 +10,7 @@ bench       `python bench.py` (plain and `--eps 0.05`) in this tree against `--p
             `--reps` runs each: the options are off there, so the two must agree within the run-to-run spread the README records for that line.
 
     python scripts/resume_bench.py [--parts checkpoint,interval,bench] [--parent DIR] [--reps 3] [--out profiles/resume_bench.txt]
+    python scripts/resume_bench.py --agent dqn --out profiles/dqn_resume_bench.txt      # the `checkpoint` part for a train_dqn checkpoint
 """
 import argparse
 import json
@@ -80,6 +81,52 @@ def part_checkpoint(reps, device):
         torch.cuda.empty_cache()
 
 
+DQN_SIZES = (("reference DQN shape, ring full", 80, 1_000_000, 32), ("learner default", 4096, 100_000, 256))
+
+
+def part_checkpoint_dqn(reps, device):
+    """`--agent dqn`: one train_dqn checkpoint in its parts -- the env's, the ring's and the learner's state (`DQNAgent.train_state_dict`: both networks, the
+    one Adam state, the draw counters, the generators) and the file -- at the reference DQN shape with its 1 M-row ring full, and at the learner default."""
+    import torch
+    from distributional_rl_navigation_amd.dqn.agent import DQNAgent
+    from distributional_rl_navigation_amd.marinenav_env.vec_env import VecMarineNavEnv
+    from distributional_rl_navigation_amd.train_iqn import TRAINING_SCHEDULE, write_checkpoint
+    say("== one train_dqn checkpoint, in its parts (medians [min .. max])")
+    for name, n, ring, batch in DQN_SIZES:
+        env = VecMarineNavEnv(n, seed=3, schedule=TRAINING_SCHEDULE, device=device, precision="f64")
+        agent = DQNAgent(26, 9, buffer_size=ring, batch_size=batch, learning_starts=0, train_freq=1, device=device, seed=103, fused_train=True)
+        agent.learn_vec(total_vector_steps=max(16, 2 * batch // n + 2), train_env=env)      # (a few real steps: trainer, ring rows, Adam history)
+        agent.memory.size = agent.memory.capacity      # the ring counted as full: every row is copied
+        blob = torch.empty(env.state_bytes(), dtype=torch.uint8, device=device)
+        t = dict(launch=[], env=[], ring=[], agent=[], write=[])
+        nbytes = 0
+        with tempfile.TemporaryDirectory() as tmp:
+            for r in range(reps + 1):
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); env.save_state(blob); e1.record(); torch.cuda.synchronize()
+                t0 = time.perf_counter(); sd_env = env.state_dict(); t1 = time.perf_counter()
+                sd_ring = agent.memory.state_dict(); t2 = time.perf_counter()
+                sd_agent = agent.train_state_dict(); t3 = time.perf_counter()
+                path = write_checkpoint(tmp, dict(format=1, vector_step=r, env=sd_env, ring=sd_ring, agent=sd_agent)); t4 = time.perf_counter()
+                nbytes = os.path.getsize(path)
+                if r:      # (the first pass warms the allocators up)
+                    for k, v in (("launch", e0.elapsed_time(e1)), ("env", 1e3 * (t1 - t0)), ("ring", 1e3 * (t2 - t1)), ("agent", 1e3 * (t3 - t2)), ("write", 1e3 * (t4 - t3))):
+                        t[k].append(v)
+        say(f"-- {name}: {n} envs, ring {ring} rows, batch {batch}; blob {env.state_bytes() / 1e6:.2f} MB, checkpoint.pt {nbytes / 1e6:.1f} MB")
+        say(f"   snapshot launch (device)         {fmt(t['launch'])}")
+        say(f"   env.state_dict()                 {fmt(t['env'])}")
+        say(f"   ring.state_dict()                {fmt(t['ring'])}")
+        say(f"   agent.train_state_dict()         {fmt(t['agent'])}")
+        say(f"   torch.save + fsync + rename      {fmt(t['write'])}")
+        sums = [sum(x) for x in zip(t['env'], t['ring'], t['agent'], t['write'])]
+        say(f"   sum                              {fmt(sums)}")
+        env.close()
+        del agent, env, blob
+        torch.cuda.empty_cache()
+    say("   (the run between two checkpoints, `interval`, and the lockstep loop's per-seed checkpoints: not measured)")
+
+
 def _train(cwd, args, timeout=3000):
     env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
     t0 = time.perf_counter()
@@ -126,6 +173,9 @@ def part_bench(reps, parent, steps, warmup):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="checkpoint")
+    ap.add_argument("--agent", default="iqn", choices=["iqn", "dqn"],
+                    help="dqn: the `checkpoint` part for a train_dqn checkpoint (the reference DQN shape with its ring full, the learner default); write it with "
+                         "--out profiles/dqn_resume_bench.txt")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--seconds", type=float, default=30.0)
     ap.add_argument("--total-timesteps", type=int, default=3_000_000)
@@ -137,8 +187,10 @@ def main():
     args = ap.parse_args()
     parts = args.parts.split(",")
     say("# scripts/resume_bench.py " + " ".join(sys.argv[1:]))
+    if args.agent == "dqn" and parts != ["checkpoint"]:
+        raise SystemExit("resume_bench: --agent dqn measures the `checkpoint` part only")
     if "checkpoint" in parts:
-        part_checkpoint(args.reps, args.device)
+        (part_checkpoint_dqn if args.agent == "dqn" else part_checkpoint)(args.reps, args.device)
     if "interval" in parts:
         part_interval(args.reps, args.seconds, args.total_timesteps)
     if "bench" in parts:
