@@ -18,9 +18,13 @@ __global__ __launch_bounds__(MN_STEP_BLOCK, 2) void mn_step_kernel(MnArrays A, M
 
     if (tid < MN_QSHARDS) A.queue_count[(parity ^ 1) * MN_QWORDS + tid * MN_QSTRIDE] = 0u;  // counters the NEXT step will fill
 
+    // Loads in the order of first use (MnLane::load_head): what the sub-steps need -- pose, goal, counters, cores, the action -- first, then
+    // everything that is first read behind them; the scheduler may not mix the two groups.
     Lane ln;
-    ln.load(A, e, q);
+    ln.load_head(A, e, q);
     const int action = ln.active ? actions[e] : 0;
+    __builtin_amdgcn_sched_barrier(0);
+    ln.load_obstacles(A);
     // Fused replay append (mn_step_append): this lane's share of the obs_t row -- the same float2 columns it will
     // write of obs_t+1 -- is loaded here with everything else, so the transition leaves in this launch instead of a
     // separate append kernel that re-reads both observation tiles.
@@ -34,8 +38,10 @@ __global__ __launch_bounds__(MN_STEP_BLOCK, 2) void mn_step_kernel(MnArrays A, M
             prev_beam[j] = prow[2 + (b < MN_NUM_BEAMS ? b : MN_NUM_BEAMS - 1)];
         }
     }
+    ln.load_tables(P);
+    __builtin_amdgcn_sched_barrier(0);
 
-    const MnStepOut o = ln.template step<APPEND>(A, P, action, obs_out + (size_t)e * MN_OBS_DIM,
+    const MnStepOut o = ln.template step<APPEND, true>(A, P, action, obs_out + (size_t)e * MN_OBS_DIM,
                                                  (PARITY && A.obs64) ? A.obs64 + (size_t)e * MN_OBS_DIM : nullptr, R, prev_head, prev_beam);
     ln.store(A);
     if (ln.active && q == 0) {

@@ -44,6 +44,8 @@
 // Put inside a wave-uniform `if`: keeps hipcc from if-converting it (it would evaluate the guarded float64 square root on every
 // step and select afterwards, which is exactly what the guard is there to avoid).
 #define MN_REAL_BRANCH() asm volatile("" ::: "memory")
+// A wave-uniform value in scalar registers whose origin the optimiser does not know from here on.
+#define MN_UNIFORM(v) asm("" : "+s"(v))
 
 #ifndef MN_STEP_BLOCK
 #define MN_STEP_BLOCK 64    // threads per workgroup (npad is a multiple of 256, so 64 / 128 / 256 all tile it); measured: same at 65 536 envs, 64 is 4 % faster at 1 M
@@ -131,8 +133,84 @@ struct MnLane {
     M cgs[CPL];
     double obx[OPL], oby[OPL], obr[OPL];
 
-    // Every load is UNCONDITIONAL (rows beyond the placed count hold zeros), so all ~40-70 loads of a lane are in flight
-    // together and the kernel pays one memory latency, not a counts -> tables dependent chain.
+    // Obstacle rows as loaded (compact tables: fixed-point positions, float32 radius), until finish_obstacles() has turned them into obx / oby / obr
+    int opx[OPL], opy[OPL];
+    float opr[OPL];
+    // MnDev's beam tables as a register bank (L > 1): lane i < 33 of the wavefront holds double i of {beam_rel, beam_cos, beam_sin}, see load_tables()
+    double tab;
+
+    // Every load is UNCONDITIONAL (rows beyond the placed count hold zeros), so all ~30-70 loads of a lane are in flight together -- no
+    // counts -> tables dependent chain -- and they are issued in the order of first use: pose, goal, counters and cores here (what the sub-steps
+    // need), the caller's action, then load_obstacles() and whatever else is first read behind the sub-step loop.  The vector-memory counter
+    // counts in order, so the wait in front of the sub-steps leaves everything issued after the action outstanding.
+    __device__ __forceinline__ void load_head(const MnArrays &A, int env, int lane_in_group) {
+        e = env; q = lane_in_group;
+        active = e < A.n;
+        dis_c = 0.0; dis_ok = false;
+        const int np = A.npad;
+        x = A.x[e]; y = A.y[e]; theta = A.theta[e]; speed = A.speed[e];
+        velx = (M)A.vx[e]; vely = (M)A.vy[e];
+        gx = A.goal_x[e]; gy = A.goal_y[e];
+        const int cnt = A.counts[e];
+        ep_t = A.ep_t[e];
+        tot_t = A.tot_t[e];
+        double ccg[CPL];
+        if (PARITY) {   // float64 master tables
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) {
+                const int k = (q & (MN_MAX_CORES - 1)) * CPL + j;
+                ccx[j] = A.cx[k * np + e]; ccy[j] = A.cy[k * np + e]; ccg[j] = A.cg[k * np + e];
+            }
+        } else {        // compact tables: int32 fixed-point positions (2^-24 m), float32 Gamma / radius
+            int qx[CPL], qy[CPL];
+            float qg[CPL];
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) {
+                const int k = (q & (MN_MAX_CORES - 1)) * CPL + j;
+                qx[j] = A.qcx[k * np + e]; qy[j] = A.qcy[k * np + e]; qg[j] = A.qcg[k * np + e];
+            }
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) {
+                ccx[j] = (double)qx[j] * MN_FIX_INV; ccy[j] = (double)qy[j] * MN_FIX_INV; ccg[j] = (double)qg[j];
+            }
+        }
+        nc = cnt & 0xff; no = (cnt >> 8) & 0xff;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+            const bool v = (q & (MN_MAX_CORES - 1)) * CPL + j < nc;
+            ccx[j] = v ? ccx[j] : 1.0e6;   // padding: far away, zero circulation
+            ccy[j] = v ? ccy[j] : 1.0e6;
+            cgs[j] = v ? (M)ccg[j] : M(0);
+        }
+    }
+
+    // This lane's share of the obstacle rows: issued only.  Nothing here reads a loaded value, so no wait follows.
+    __device__ __forceinline__ void load_obstacles(const MnArrays &A) {
+        const int np = A.npad;
+#pragma unroll
+        for (int j = 0; j < OPL; ++j) {
+            const int k = min(q + L * j, MN_MAX_OBS - 1);
+            if (PARITY) { obx[j] = A.ox[k * np + e]; oby[j] = A.oy[k * np + e]; obr[j] = A.orad[k * np + e]; }
+            else { opx[j] = A.qox[k * np + e]; opy[j] = A.qoy[k * np + e]; opr[j] = A.qor[k * np + e]; }
+        }
+    }
+
+    // ... and their first use: conversion of the compact rows, padding.  Once per load_obstacles().
+    __device__ __forceinline__ void finish_obstacles() {
+#pragma unroll
+        for (int j = 0; j < OPL; ++j) {
+            if (!PARITY) { obx[j] = (double)opx[j] * MN_FIX_INV; oby[j] = (double)opy[j] * MN_FIX_INV; obr[j] = (double)opr[j]; }
+            const bool v = q + L * j < no; // padding: far away, r = 0 -> never relevant, never the nearest
+            obx[j] = v ? obx[j] : 1.0e6;
+            oby[j] = v ? oby[j] : 1.0e6;
+            obr[j] = v ? obr[j] : 0.0;
+        }
+    }
+
+    // Everything at once, every first use included, for a caller that runs many steps on the registers (the rollout and episode kernels): the same loads,
+    // conversions and padding as load_head() + load_obstacles() + finish_obstacles(), in the statement order those kernels have been measured with.  They
+    // sit at the limit of both register files and compile to different code (other spills) when this is written as the three calls; that form has not
+    // been measured there, so this one stays (profiles/step_kernel_loads.txt (c): what a few more live registers cost in those kernels).
     __device__ __forceinline__ void load(const MnArrays &A, int env, int lane_in_group) {
         e = env; q = lane_in_group;
         active = e < A.n;
@@ -195,6 +273,26 @@ struct MnLane {
         }
     }
 
+    // MnDev's per-lane indexed tables.  A lane's beams are b = q + L j, so beam_rel[b], beam_cos[b] and beam_sin[b] are indexed by a lane constant; read
+    // where they are used they compile to vector loads from the kernel-argument segment BEHIND the sub-step loop, one more memory round trip on the
+    // step's dependent chain.  Instead lane i < 33 of the wavefront fetches double i of the three (contiguous) tables here, with the other loads, and
+    // table() reads an entry from the lane that holds it (ds_bpermute: no memory access, no LDS allocation).  For step<., ONE_STEP = true> only; call it
+    // with all 64 lanes of the wavefront active -- as step() must be called, for the same reason.  L = 1: every index is a constant and the reads are scalar loads.
+    static_assert(offsetof(MnDev, beam_cos) == offsetof(MnDev, beam_rel) + MN_NUM_BEAMS * sizeof(double) &&
+                  offsetof(MnDev, beam_sin) == offsetof(MnDev, beam_cos) + MN_NUM_BEAMS * sizeof(double) && 3 * MN_NUM_BEAMS <= MN_WAVE, "one bank: 33 consecutive doubles");
+    __device__ __forceinline__ void load_tables(const MnDev &P) {
+        if constexpr (L > 1) {
+            const int lane = threadIdx.x & (MN_WAVE - 1);
+            tab = (&P.beam_rel[0])[lane < 3 * MN_NUM_BEAMS ? lane : 3 * MN_NUM_BEAMS - 1];
+        }
+    }
+    __device__ __forceinline__ double table(int i) const {      // double i of the bank
+        const long long b = __builtin_bit_cast(long long, tab);
+        const int lo = __builtin_amdgcn_ds_bpermute(i << 2, (int)(b & 0xffffffffll));
+        const int hi = __builtin_amdgcn_ds_bpermute(i << 2, (int)(b >> 32));
+        return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned int)lo);
+    }
+
     // pose + counters back to the handle's arrays (lane 0 of the group)
     __device__ __forceinline__ void store(const MnArrays &A) const {
         if (active && q == 0) {
@@ -209,7 +307,12 @@ struct MnLane {
     // ([26] floats of THIS env; float64 copy to obs_row64 in parity precision) and, with APPEND, the transition to the
     // replay ring R (prev_head / prev_beam = this lane's share of obs_t, loaded by the caller).
     // obs_row_b: optional second destination of the same row (the rollout kernel's trace), or nullptr.
-    template <bool APPEND>
+    // ONE_STEP: the single-step kernels (mn_step.hip), where the step's dependent chain starts at the kernel's loads.  The caller has issued load_head(),
+    // load_obstacles() and load_tables() but not finish_obstacles(): the step does that behind its sub-steps, which then run while those rows are still in
+    // flight, and it takes MnDev's per-lane indexed tables in the forms that cost no further memory round trip (below).  A kernel that steps many times on the
+    // registers (rollouts, episodes) finishes the obstacles once, in load(), and reads the tables as written: there hipcc hoists those reads in front of
+    // its step loop, and the forms below only add to a scalar register file that is already full (measured slower: profiles/step_kernel_loads.txt).
+    template <bool APPEND, bool ONE_STEP = false>
     __device__ __forceinline__ MnStepOut step(const MnArrays &A, const MnDev &P, int action_raw, float *__restrict__ obs_row,
                                               double *__restrict__ obs_row64, const MnRing &R, const float2 *prev_head,
                                               const float2 *prev_beam, float *__restrict__ obs_row_b = nullptr) {
@@ -226,14 +329,29 @@ struct MnLane {
 
         // robot.py:55-56: actions[i] = (a[i // 3], w[i % 3])
         const int ai = action / 3, wi = action - 3 * ai;
-        const double acc = ai == 0 ? P.a[0] : (ai == 1 ? P.a[1] : P.a[2]);
-        const double wdt = (wi == 0 ? P.w[0] : (wi == 1 ? P.w[1] : P.w[2])) * P.dt;
-        const double rot_c = wi == 0 ? P.rot_c[0] : (wi == 1 ? P.rot_c[1] : P.rot_c[2]);   // cos(w*dt)
-        const double rot_s = wi == 0 ? P.rot_s[0] : (wi == 1 ? P.rot_s[1] : P.rot_s[2]);   // sin(w*dt)
+        // The twelve action constants as wave-uniform values the optimiser cannot see through: scalar registers and v_cndmask, as written.  (Left to
+        // itself hipcc folds each select of three kernel-argument fields into a select of three OFFSETS and a vector load from the kernel-argument
+        // segment, issued only once the action has arrived: a second dependent memory round trip in front of the sub-steps.)
+        double acc, wdt, rot_c, rot_s;      // a[ai], w[wi] * dt, cos(w*dt), sin(w*dt)
+        if constexpr (ONE_STEP) {
+            double a0 = P.a[0], a1 = P.a[1], a2 = P.a[2], w0 = P.w[0], w1 = P.w[1], w2 = P.w[2];
+            double rc0 = P.rot_c[0], rc1 = P.rot_c[1], rc2 = P.rot_c[2], rs0 = P.rot_s[0], rs1 = P.rot_s[1], rs2 = P.rot_s[2];
+            MN_UNIFORM(a0); MN_UNIFORM(a1); MN_UNIFORM(a2); MN_UNIFORM(w0); MN_UNIFORM(w1); MN_UNIFORM(w2);
+            MN_UNIFORM(rc0); MN_UNIFORM(rc1); MN_UNIFORM(rc2); MN_UNIFORM(rs0); MN_UNIFORM(rs1); MN_UNIFORM(rs2);
+            acc = ai == 0 ? a0 : (ai == 1 ? a1 : a2);
+            wdt = (wi == 0 ? w0 : (wi == 1 ? w1 : w2)) * P.dt;
+            rot_c = wi == 0 ? rc0 : (wi == 1 ? rc1 : rc2);
+            rot_s = wi == 0 ? rs0 : (wi == 1 ? rs1 : rs2);
+        } else {
+            acc = ai == 0 ? P.a[0] : (ai == 1 ? P.a[1] : P.a[2]);
+            wdt = (wi == 0 ? P.w[0] : (wi == 1 ? P.w[1] : P.w[2])) * P.dt;
+            rot_c = wi == 0 ? P.rot_c[0] : (wi == 1 ? P.rot_c[1] : P.rot_c[2]);
+            rot_s = wi == 0 ? P.rot_s[0] : (wi == 1 ? P.rot_s[1] : P.rot_s[2]);
+        }
         const double dt = P.dt, two_pi = P.two_pi;
 
-        const double inv_two_pi_r2 = 1.0 / P.two_pi_r_r;
-        const double inv_two_pi = 1.0 / P.two_pi;
+        const double inv_two_pi_r2 = P.inv_two_pi_r2;      // 1 / two_pi_r_r and 1 / two_pi: the host's correctly rounded quotients (mn_capi.hip)
+        const double inv_two_pi = P.inv_two_pi;
 
         // heading: wrap once on entry (state may have been set from outside), one sincos per step
         while (theta < 0.0) theta += two_pi;
@@ -349,6 +467,7 @@ struct MnLane {
         }
 
         MN_TICK(1);      // N sub-steps (current field + integration)
+        if constexpr (ONE_STEP) finish_obstacles();      // first read of the obstacle rows
         // marinenav_env.py:214 dis_after
         const double dax = gx - x, day = gy - y;
         const double dis_after = sqrt(fma(dax, dax, day * day));
@@ -412,12 +531,13 @@ struct MnLane {
         for (int j = 0; j < BPL; ++j) {
             const int b = q + L * j;
             const int bb = b < MN_NUM_BEAMS ? b : MN_NUM_BEAMS - 1;
-            const double angle = theta + P.beam_rel[bb];  // robot.py:134, not wrapped
+            const double angle = theta + (ONE_STEP && L > 1 ? table(bb) : P.beam_rel[bb]);  // robot.py:134, not wrapped
             const bool up = fabs(angle - half_pi) < 1e-03;
             const bool down = fabs(angle - three_half_pi) < 1e-03;
             // beam direction in the robot frame: the constant (cos rel, sin rel); a snapped beam points
             // along world (0,+-1), i.e. R^T (0,+-1) = +-(sin theta, cos theta)
-            bdx[j] = P.beam_cos[bb]; bdy[j] = P.beam_sin[bb];
+            bdx[j] = ONE_STEP && L > 1 ? table(MN_NUM_BEAMS + bb) : P.beam_cos[bb];
+            bdy[j] = ONE_STEP && L > 1 ? table(2 * MN_NUM_BEAMS + bb) : P.beam_sin[bb];
             if (up || down) {
                 const double sg = up ? 1.0 : -1.0;
                 bdx[j] = sg * sn; bdy[j] = sg * cs;
