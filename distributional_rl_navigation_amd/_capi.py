@@ -15,6 +15,8 @@ PRECISION_F64, PRECISION_MIXED = 0, 1
 RESET_IN_FRONT, RESET_UNDER_ACT, RESET_OWED = 0, 1, 2      # mn_reset_placement / mn_reset_done_next_act (include/marinenav_hip.h)
 QUERY_VELOCITY_GIVEN, QUERY_VELOCITY_FROM_CURRENT = 0, 1
 QUERY_FLAG_COLLISION, QUERY_FLAG_OUTSIDE, QUERY_FLAG_GOAL, QUERY_FLAG_BAD_ENV = 1, 2, 4, 128
+QUERY_ACTIONS_SHARED, QUERY_ACTIONS_CONSTANT, QUERY_ACTIONS_PER_QUERY = 0, 1, 2      # mn_query_rollout
+QUERY_INFO_BAD_STATE, QUERY_MAX_STEPS = 64, 65536
 INFO_STRINGS = ("normal", "out of boundary", "too long episode", "collision", "reach goal")
 
 
@@ -117,6 +119,7 @@ SIGNATURES = [
     ("mn_get_worlds", C.c_int, [_vp, _i32, _i32, _pi32, _pd, _pi32, _pd, _pi32, _pd, _pd, _pd, _pd, _pd, _pd]),
     ("mn_query_velocity", C.c_int, [_vp, _vp, _i32, _vp, _i64, _vp, _vp]),
     ("mn_query_observation", C.c_int, [_vp, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
+    ("mn_query_rollout", C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i64] + [_vp] * 14),
     ("mn_get_state", C.c_int, [_vp, _i32, _i32, _pd, _pi32, _pi64]),
     ("mn_set_state", C.c_int, [_vp, _i32, _i32, _pd, _pi32, _pi64]),
     ("mn_state_bytes", _i64, [_vp]),

@@ -934,6 +934,34 @@ extern "C" int mn_query_observation(mn_handle *h, const int32_t *env_of_query_de
     return MN_OK;
 }
 
+extern "C" int mn_query_rollout(mn_handle *h, const int32_t *env_of_query_dev, int32_t env0, const double *state_dev, const int32_t *episode_timesteps_dev,
+                                int32_t action_mode, const int32_t *actions_dev, int32_t n_steps, const int32_t *n_steps_of_query_dev, int64_t n_queries,
+                                double *state_out_dev, float *obs_dev, double *obs64_dev, double *reward_dev, uint8_t *done_dev, uint8_t *info_dev,
+                                int32_t *steps_dev, double *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev,
+                                double *state_trace_dev, double *traj_trace_dev, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (h && action_mode != MN_QUERY_ACTIONS_SHARED && action_mode != MN_QUERY_ACTIONS_CONSTANT && action_mode != MN_QUERY_ACTIONS_PER_QUERY)
+        return fail(h, MN_ERR_INVALID, "mn_query_rollout: action_mode is none of MN_QUERY_ACTIONS_SHARED, _CONSTANT, _PER_QUERY");
+    if (h && (n_steps < 0 || n_steps > MN_QUERY_MAX_STEPS)) {
+        char b[128];
+        snprintf(b, sizeof(b), "mn_query_rollout: n_steps = %d is outside [0, %d]", n_steps, MN_QUERY_MAX_STEPS);
+        return fail(h, MN_ERR_INVALID, b);
+    }
+    const int rc = query_common(h, env_of_query_dev, env0, state_dev, n_queries, s);
+    if (rc) return rc;
+    if (n_queries == 0) return MN_OK;
+    if (n_steps > 0 && !actions_dev) return fail(h, MN_ERR_INVALID, "mn_query_rollout: actions_dev is NULL");
+    if (!state_out_dev && !obs_dev && !obs64_dev && !reward_dev && !done_dev && !info_dev && !steps_dev && !reward_trace_dev && !done_trace_dev &&
+        !info_trace_dev && !action_trace_dev && !state_trace_dev && !traj_trace_dev)
+        return fail(h, MN_ERR_INVALID, "mn_query_rollout: every output is NULL");
+    if ((uintptr_t)obs_dev & 7) return fail(h, MN_ERR_INVALID, "mn_query_rollout: obs_dev must be 8-byte aligned (rows leave as float pairs)");
+    mn_launch_query_rollout(h->A, h->P, env_of_query_dev, env0, state_dev, episode_timesteps_dev, action_mode, actions_dev, n_steps, n_steps_of_query_dev,
+                            n_queries, state_out_dev, obs_dev, obs64_dev, reward_dev, done_dev, info_dev, steps_dev, reward_trace_dev, done_trace_dev,
+                            info_trace_dev, action_trace_dev, state_trace_dev, traj_trace_dev, s);
+    MN_HIP(h, hipGetLastError());
+    return MN_OK;
+}
+
 extern "C" int mn_get_state(mn_handle *h, int32_t first, int32_t count, double *state, int32_t *ep_t, int64_t *tot_t) {
     int rc = range_ok(h, first, count);
     if (rc) return rc;

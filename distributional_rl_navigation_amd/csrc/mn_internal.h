@@ -225,3 +225,8 @@ void mn_launch_sleep(uint32_t us, hipStream_t s);
 void mn_launch_query_velocity(const MnArrays &A, const MnDev &P, const int32_t *env_of, int env0, const double *xy, int64_t nq, double *v, hipStream_t s);
 void mn_launch_query_observation(const MnArrays &A, const MnDev &P, const int32_t *env_of, int env0, const double *state, int from_current, int64_t nq,
                                  float *obs, double *obs64, uint8_t *flags, hipStream_t s);
+// what-if steps / open-loop rollouts (mn_query_step.hip): read-only on A; the arguments of mn_query_rollout
+void mn_launch_query_rollout(const MnArrays &A, const MnDev &P, const int32_t *env_of, int env0, const double *state, const int32_t *ep_t, int action_mode,
+                             const int32_t *actions, int n_steps, const int32_t *n_steps_of, int64_t nq, double *state_out, float *obs, double *obs64,
+                             double *reward, uint8_t *done, uint8_t *info, int32_t *steps, double *reward_tr, uint8_t *done_tr, uint8_t *info_tr,
+                             int32_t *action_tr, double *state_tr, double *traj_tr, hipStream_t s);

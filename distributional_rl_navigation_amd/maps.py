@@ -3,7 +3,8 @@
 The reference's visualiser asks its environment two things besides replaying episodes: the current at a point
 (`env_visualizer.plot_graph` evaluates `get_velocity` on a 100 x 100 grid) and the observation of a robot placed by hand.  Here both
 are queries of `VecMarineNavEnv` (`velocity_at`, `observation_at`: one HIP launch for the whole grid, nothing in the env changes), and
-a policy map is the observation query followed by the policy's own act call on the rows it returns.  Nothing here plots.
+a policy map is the observation query followed by the policy's own act call on the rows it returns.  `action_fan` and `lookahead_map` add
+the other half -- what happens if the robot placed there takes an action (`step_at`, `constant_rollout_at`: the what-if step).  Nothing here plots.
 """
 import numpy as np
 import torch
@@ -60,6 +61,72 @@ def policy_map(policy, env, env_index, xs, ys, thetas, speed, chunk=65536, obser
     return res
 
 
+def action_fan(env, env_index, state, horizon, episode_timesteps=0):
+    """Where each of the nine actions leads from `state` ([4] or [6]: x, y, theta, speed[, velocity]) in world `env_index`: nine open-loop rollouts
+    of `horizon` steps, rollout a holding action a (`VecMarineNavEnv.constant_rollout_at`, one launch).  Returns a dict of arrays: `trajectory`
+    [9][horizon * N][2] (the sub-step positions in order, NaN behind a rollout's end), `steps` [9], `state` [9][6], `done`, `info` [9], `reward`
+    [9][horizon] (per step, undiscounted; 0 behind the end)."""
+    st = np.asarray(state, dtype=np.float64).reshape(1, -1).repeat(9, axis=0)
+    out = env.constant_rollout_at(st, np.arange(9, dtype=np.int32), int(horizon), env=env_index, episode_timesteps=int(episode_timesteps),
+                                  trace=("traj", "reward"))
+    traj = _host(out["traj_trace"])      # [H][9][N][2]
+    return dict(trajectory=np.ascontiguousarray(traj.transpose(1, 0, 2, 3)).reshape(9, -1, 2), steps=_host(out["steps"]), state=_host(out["state"]),
+                done=_host(out["done"]), info=_host(out["info"]), reward=np.ascontiguousarray(_host(out["reward_trace"]).T))
+
+
+def lookahead_map(policy, env, env_index, xs, ys, thetas, speed, gamma=None, chunk=65536, observe=None, step=None):
+    """A critic against the simulator at every pose of policy_map's grid (same order, same chunks): the one-step Bellman backup of each of the nine
+    actions, backup[a] = r + gamma (1 - done) max Q(s', .), where (s', r, done) is the what-if step of the placed robot under action a
+    (`VecMarineNavEnv.step_at`), beside the critic's own Q(s, .).
+
+    `policy`: a map policy whose output has `q` [m][9] (`iqn_policy`, `dqn_policy(dqn, q=True)`); one without (the planners) is refused with
+    ValueError.  Per chunk it is called once on the poses' observations and then once per action on the next observations, m rows each.
+    `gamma`: default `env.discount`.  `observe` as in policy_map; `step`: (states [m][4] float64, actions [m] int32) -> dict with obs [m][26]
+    float32, reward [m] float64, done [m], info [m]; default `env.step_at(states, actions, env=env_index)` -- stand-ins make the function run
+    without a GPU.
+    Returns arrays shaped [len(thetas)][len(ys)][len(xs)] + tail: `q` [9] (as the policy gives it), `action`, `backup` [9] float64, `residual` [9]
+    = backup - q, `lookahead_action` = argmax backup (int32), `reward_next` [9] float64, `done_next` [9], `info_next` [9] uint8, `flags`."""
+    if observe is None:
+        observe = lambda st: env.observation_at(st, env=env_index, velocity="current", return_flags=True)
+    if step is None:
+        step = lambda st, a: env.step_at(st, a, env=env_index)
+    if gamma is None:
+        gamma = env.discount
+    gamma = float(gamma)
+    device = env.device if env is not None and hasattr(env, "device") else "cpu"
+    poses = pose_grid(xs, ys, thetas, speed, device)
+    shape = (len(thetas), len(ys), len(xs))
+    parts = {k: [] for k in ("q", "action", "backup", "reward_next", "done_next", "info_next", "flags")}
+
+    def q_of(out, m):
+        if "q" not in out:
+            raise ValueError("lookahead_map needs a policy whose output has 'q' [m][9] (a critic); this one gives " + str(sorted(out)))
+        q = out["q"]
+        if tuple(q.shape) != (m, 9):
+            raise ValueError(f"policy output 'q' has shape {tuple(q.shape)} for {m} poses; expected ({m}, 9)")
+        return q
+    width = max(1, int(chunk))
+    for lo in range(0, poses.shape[0], width):
+        st = poses[lo:lo + width]
+        m = st.shape[0]
+        obs, fl = observe(st)
+        out = policy(obs)
+        parts["q"].append(_host(q_of(out, m)))
+        parts["action"].append(_host(out["action"]).astype(np.int32))
+        parts["flags"].append(_host(fl))
+        backup, rew, done, info = (np.empty((m, 9), dtype=d) for d in (np.float64, np.float64, np.uint8, np.uint8))
+        for a in range(9):
+            nxt = step(st, torch.full((m,), a, dtype=torch.int32, device=st.device))
+            qn = _host(q_of(policy(nxt["obs"]), m)).astype(np.float64)
+            rew[:, a], done[:, a], info[:, a] = _host(nxt["reward"]), _host(nxt["done"]), _host(nxt["info"])
+            backup[:, a] = rew[:, a] + gamma * (1.0 - done[:, a].astype(np.float64)) * qn.max(axis=1)
+        parts["backup"].append(backup); parts["reward_next"].append(rew); parts["done_next"].append(done); parts["info_next"].append(info)
+    res = {k: np.concatenate(v).reshape(shape + v[0].shape[1:]) for k, v in parts.items()}
+    res["residual"] = res["backup"] - res["q"].astype(np.float64)
+    res["lookahead_action"] = res["backup"].argmax(axis=-1).astype(np.int32)
+    return res
+
+
 def iqn_policy(agent, cvar=1.0, adaptive=False, quantiles=False):
     """An IQNAgent as a map policy: action [m], the CVaR level used `cvar` [m] (`adaptive`: agent.adjust_cvar_batch per row, else the constant), `q` [m][9]
     = mean over the 32 quantile samples and, with `quantiles`, `quantiles` [m][32][9] and `taus` [m][32].  It acts through adjust_cvar_batch and
@@ -76,8 +143,10 @@ def iqn_policy(agent, cvar=1.0, adaptive=False, quantiles=False):
     return policy
 
 
-def dqn_policy(dqn):
-    """A dqn.policy.DQNPolicy as a map policy: action [m]."""
+def dqn_policy(dqn, q=False):
+    """A dqn.policy.DQNPolicy as a map policy: action [m] and, with `q`, its Q-values `q` [m][9] (what lookahead_map needs)."""
+    if q:
+        return lambda obs: dict(action=dqn.act_batch(obs), q=dqn.q_values(obs))
     return lambda obs: dict(action=dqn.act_batch(obs))
 
 

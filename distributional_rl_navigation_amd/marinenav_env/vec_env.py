@@ -516,6 +516,92 @@ class VecMarineNavEnv:
                                                 _ptr(flags) if flags is not None else None, self._stream()))
         return (obs, flags) if return_flags else obs
 
+    ROLLOUT_TRACES = ("reward", "done", "info", "action", "state", "traj")
+
+    def rollout_at(self, states, actions, lengths=None, env=0, episode_timesteps=None, trace=(), dtype=torch.float32):
+        """Open-loop rollouts of robots placed by hand (C-ABI mn_query_rollout: one HIP launch, float64 in the reference's own arithmetic
+        whatever the env's precision; nothing in the env changes, no random number is drawn).  `states` [Q, 6] or [Q, 4] as in observation_at (a
+        step ignores the velocity columns), in world `env` (an int, or one index per query).  `actions` (int): [H] -- one sequence shared by every
+        query --, or [Q, H] -- a sequence per query; for one action per query held over H steps use `actions[:, None].expand(Q, H)` or
+        `constant_rollout_at`.  `lengths` [Q]: query q runs at most lengths[q] <= H steps (default H); every query stops at the step that ends its
+        episode.  `episode_timesteps` [Q] or an int: the counter before the first step (default 0).
+        Returns a dict of device tensors: `state` [Q, 6] float64, `obs` [Q, 26] `dtype`, `reward` [Q] float64 (the last step's), `done`, `info` [Q]
+        uint8, `steps` [Q] int32, and per name in `trace` (ROLLOUT_TRACES) `<name>_trace` in the episode launches' [H][Q] layout (reward float64,
+        undiscounted; state [H][Q][6]; traj [H][Q][N][2]) -- episodes.tally takes reward / done / info / action as they are.  Behind a query's last
+        step the rows hold reward 0, done 1, the last info code, action -1.  A query with an index that is no env, a non-finite state or
+        |theta| >= 1e6, or an action outside [0, 9) is poisoned alone: NaN floats, done 1, info _capi.QUERY_FLAG_BAD_ENV / QUERY_INFO_BAD_STATE."""
+        act = torch.as_tensor(actions).to(device=self.device, dtype=torch.int32)
+        if act.dim() not in (1, 2):
+            raise ValueError(f"actions must be [H] or [Q, H], got {tuple(act.shape)}")
+        mode = _capi.QUERY_ACTIONS_SHARED if act.dim() == 1 else _capi.QUERY_ACTIONS_PER_QUERY
+        return self._rollout_query(states, act.contiguous(), mode, int(act.shape[-1]), lengths, env, episode_timesteps, trace, dtype)
+
+    def constant_rollout_at(self, states, actions, horizon, lengths=None, env=0, episode_timesteps=None, trace=(), dtype=torch.float32):
+        """rollout_at with ONE action per query, `actions` [Q], held for `horizon` steps (an action fan)."""
+        act = torch.as_tensor(actions).to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        return self._rollout_query(states, act, _capi.QUERY_ACTIONS_CONSTANT, int(horizon), lengths, env, episode_timesteps, trace, dtype)
+
+    def step_at(self, states, actions, env=0, episode_timesteps=None, dtype=torch.float32):
+        """The what-if step: MarineNavEnv.step (marinenav_env.py:199-262) of a robot in `states` [Q, 6] or [Q, 4] taking `actions` [Q] (or one int
+        for all) in world `env`, as rollout_at with H = 1.  Returns dict(state [Q, 6] float64, obs [Q, 26] `dtype`, reward [Q] float64, done,
+        info [Q] uint8)."""
+        if isinstance(actions, (int, np.integer)):
+            act = torch.tensor([int(actions)], dtype=torch.int32, device=self.device)
+            out = self._rollout_query(states, act, _capi.QUERY_ACTIONS_SHARED, 1, None, env, episode_timesteps, (), dtype)
+        else:
+            act = torch.as_tensor(actions).to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+            out = self._rollout_query(states, act, _capi.QUERY_ACTIONS_CONSTANT, 1, None, env, episode_timesteps, (), dtype)
+        del out["steps"]
+        return out
+
+    def _rollout_query(self, states, act, mode, horizon, lengths, env, episode_timesteps, trace, dtype):
+        st = torch.as_tensor(states).to(device=self.device, dtype=torch.float64)
+        if st.dim() != 2 or st.shape[1] not in (4, 6):
+            raise ValueError(f"states must be [Q, 4] or [Q, 6], got {tuple(st.shape)}")
+        if st.shape[1] == 4:
+            st = torch.cat([st, st.new_zeros(st.shape[0], 2)], dim=1)
+        st = st.contiguous()
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("dtype must be torch.float32 or torch.float64")
+        q, dev = st.shape[0], self.device
+        if horizon < 0 or horizon > _capi.QUERY_MAX_STEPS:
+            raise ValueError(f"the horizon must be in [0, {_capi.QUERY_MAX_STEPS}], got {horizon}")
+        want = {_capi.QUERY_ACTIONS_SHARED: (horizon,), _capi.QUERY_ACTIONS_CONSTANT: (q,), _capi.QUERY_ACTIONS_PER_QUERY: (q, horizon)}[mode]
+        if tuple(act.shape) != want:
+            raise ValueError(f"actions must have shape {want} for {q} states, got {tuple(act.shape)}")
+        unknown = [k for k in trace if k not in self.ROLLOUT_TRACES]
+        if unknown:
+            raise ValueError(f"unknown trace {unknown}: rollout_at traces are {self.ROLLOUT_TRACES}")
+        idx, env0 = self._query_env(env, q)
+
+        def per_query(v, name):
+            if v is None:
+                return None
+            if isinstance(v, (int, np.integer)):
+                return torch.full((q,), int(v), dtype=torch.int32, device=dev)
+            t = torch.as_tensor(v).to(device=dev, dtype=torch.int32).contiguous()
+            if t.shape != (q,):
+                raise ValueError(f"{name} must hold one value per query ({q}), got shape {tuple(t.shape)}")
+            return t
+        ep = per_query(episode_timesteps, "episode_timesteps")
+        ln = per_query(lengths, "lengths")
+        out = dict(state=torch.empty(q, 6, dtype=torch.float64, device=dev), obs=torch.empty(q, OBS_DIM, dtype=dtype, device=dev),
+                   reward=torch.empty(q, dtype=torch.float64, device=dev), done=torch.empty(q, dtype=torch.uint8, device=dev),
+                   info=torch.empty(q, dtype=torch.uint8, device=dev), steps=torch.empty(q, dtype=torch.int32, device=dev))
+        n_sub = int(self.params.N)
+        shapes = dict(reward=((horizon, q), torch.float64), done=((horizon, q), torch.uint8), info=((horizon, q), torch.uint8),
+                      action=((horizon, q), torch.int32), state=((horizon, q, 6), torch.float64), traj=((horizon, q, n_sub, 2), torch.float64))
+        tr = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in trace}
+        p = lambda t: _ptr(t) if t is not None else None
+        self._check(self.L.mn_query_rollout(
+            self.h, p(idx), env0, _ptr(st), p(ep), mode, _ptr(act), horizon, p(ln), q, _ptr(out["state"]),
+            _ptr(out["obs"]) if dtype == torch.float32 else None, _ptr(out["obs"]) if dtype == torch.float64 else None, _ptr(out["reward"]),
+            _ptr(out["done"]), _ptr(out["info"]), _ptr(out["steps"]), p(tr.get("reward")), p(tr.get("done")), p(tr.get("info")), p(tr.get("action")),
+            p(tr.get("state")), p(tr.get("traj")), self._stream()))
+        for k, v in tr.items():
+            out[k + "_trace"] = v
+        return out
+
     # ---- state accessors (tests, checkpoints) ------------------------------------------------
     def get_state(self, first_env=0, count=None):
         cnt = self.n_envs - first_env if count is None else count

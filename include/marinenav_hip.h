@@ -309,6 +309,42 @@ int mn_query_observation(mn_handle *h, const int32_t *env_of_query_dev, int32_t 
                          int32_t velocity_mode, int64_t n_queries, float *obs_dev, double *obs64_dev,
                          uint8_t *flags_dev, void *stream);
 
+/* What-if steps and open-loop rollouts: MarineNavEnv.step (marinenav_env.py:199-262 with robot.py:102-123) of a robot placed by hand, n_steps
+ * times, under actions the caller names -- env_visualizer.one_step / visualize_control(action_sequence), a stored episode of
+ * *_evaluations.npz, the nine-action fan of a pose.  A query like the two above: it reads the float64 master tables only, computes in
+ * float64 in the reference's own order of operations whatever the handle's precision, writes NOTHING into the handle, draws no random
+ * number and runs no policy; world selection (env_of_query_dev / env0), n_queries = 0 and the joined mn_reset_done_async are as above.
+ * n_steps = 1 is the what-if step.
+ *   state_dev [n_queries][6] f64 = x, y, theta, speed, velocity_x, velocity_y: the start of query q.  A step ignores columns 4-5 (it
+ *     overwrites the velocity before it reads it); a query that runs no step reports them as they are.
+ *   episode_timesteps_dev [n_queries] i32: the counter before the first step (NULL = 0); step t of a query sees it + t.
+ *   actions_dev (i32), by action_mode: MN_QUERY_ACTIONS_SHARED [n_steps], one sequence for every query; MN_QUERY_ACTIONS_CONSTANT
+ *     [n_queries], query q holds actions_dev[q] for all its steps; MN_QUERY_ACTIONS_PER_QUERY [n_queries][n_steps].
+ *   n_steps_of_query_dev [n_queries] i32 (NULL = n_steps): query q runs min(max(it, 0), n_steps) steps, fewer if a step ends its
+ *     episode (done).  0 <= n_steps <= MN_QUERY_MAX_STEPS.
+ * Outputs per query, each may be NULL: state_out_dev [n_queries][6] f64 (columns 4-5: the velocity the last sub-step moved with),
+ * obs_dev [n_queries][26] f32 (8-byte aligned) / obs64_dev f64: the observation of that state, reward_dev [n_queries] f64: the last
+ * step's reward (0 if no step ran), done_dev / info_dev [n_queries] u8 (MN_INFO_*), steps_dev [n_queries] i32: steps run.
+ * Traces, each may be NULL, [n_steps][n_queries] as the episode launches lay theirs out: reward_trace_dev f64, done_trace_dev u8,
+ * info_trace_dev u8, action_trace_dev i32, state_trace_dev [n_steps][n_queries][6] f64 (the state after the step),
+ * traj_trace_dev [n_steps][n_queries][N][2] f64 (the position after each sub-step, marinenav_env.py:211-212).  Every row is written:
+ * behind a query's last step reward 0, done 1, its last info code, action -1, its last state, NaN positions.  Rewards are not
+ * discounted.
+ * Not visible to the host, and confined to their own query (the call returns MN_OK): an index outside [0, n_envs) inside
+ * env_of_query_dev -- no table is read, no step runs (steps 0), float outputs NaN, done 1, info MN_QUERY_FLAG_BAD_ENV; a state about to
+ * be stepped with a non-finite x, y, theta or speed or |theta| >= 1e6 (the reference wraps the heading in a loop), or an action outside
+ * [0, 9) -- that step counts as run, float outputs NaN, done 1, info MN_QUERY_INFO_BAD_STATE.
+ * MN_ERR_INVALID: as above, an unknown action_mode, n_steps outside [0, MN_QUERY_MAX_STEPS], n_steps > 0 with actions_dev NULL. */
+enum { MN_QUERY_ACTIONS_SHARED = 0, MN_QUERY_ACTIONS_CONSTANT = 1, MN_QUERY_ACTIONS_PER_QUERY = 2 };
+enum { MN_QUERY_INFO_BAD_STATE = 64 };
+#define MN_QUERY_MAX_STEPS 65536
+int mn_query_rollout(mn_handle *h, const int32_t *env_of_query_dev, int32_t env0, const double *state_dev,
+                     const int32_t *episode_timesteps_dev, int32_t action_mode, const int32_t *actions_dev, int32_t n_steps,
+                     const int32_t *n_steps_of_query_dev, int64_t n_queries, double *state_out_dev, float *obs_dev,
+                     double *obs64_dev, double *reward_dev, uint8_t *done_dev, uint8_t *info_dev, int32_t *steps_dev,
+                     double *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev,
+                     double *state_trace_dev, double *traj_trace_dev, void *stream);
+
 /* Robot pose and counters (robot.py:40-44, marinenav_env.py:70-71).  state[count][6] =
  * x, y, theta, speed, velocity_x, velocity_y (float64).  NULL pointers are skipped. */
 int mn_get_state(mn_handle *h, int32_t first_env, int32_t count, double *state, int32_t *episode_timesteps,
