@@ -17,6 +17,8 @@ QUERY_VELOCITY_GIVEN, QUERY_VELOCITY_FROM_CURRENT = 0, 1
 QUERY_FLAG_COLLISION, QUERY_FLAG_OUTSIDE, QUERY_FLAG_GOAL, QUERY_FLAG_BAD_ENV = 1, 2, 4, 128
 QUERY_ACTIONS_SHARED, QUERY_ACTIONS_CONSTANT, QUERY_ACTIONS_PER_QUERY = 0, 1, 2      # mn_query_rollout
 QUERY_INFO_BAD_STATE, QUERY_MAX_STEPS = 64, 65536
+RENDER_MAX_LEVELS, RENDER_MAX_LIC_STEPS, RENDER_MAX_HALF_WIDTH = 32, 64, 8      # mn_render_worlds / mn_render_draw
+RENDER_SEGMENT, RENDER_DISC, RENDER_RING = 0, 1, 2
 INFO_STRINGS = ("normal", "out of boundary", "too long episode", "collision", "reach goal")
 
 
@@ -42,6 +44,19 @@ class MnDqnLearner(C.Structure):
 
 
 DQN_MAX_LEARNERS = 64      # MN_DQN_MAX_LEARNERS
+
+
+class MnRenderStyle(C.Structure):
+    """mn_render_style: how mn_render_worlds colours a world (include/marinenav_hip.h); colours are r << 16 | g << 8 | b."""
+    _fields_ = [("v_max", C.c_double), ("hpx", C.c_double), ("marker_r", C.c_double), ("n_levels", C.c_int32), ("lic", C.c_int32),
+                ("lic_steps", C.c_int32), ("lic_floor", C.c_int32), ("seed", C.c_uint32), ("outside", C.c_uint32), ("obstacle", C.c_uint32),
+                ("marker", C.c_uint32), ("max_workgroups", C.c_int32), ("reserved", C.c_int32), ("palette", C.c_uint32 * 32)]
+
+
+class MnRenderPrim(C.Structure):
+    """mn_render_prim: one primitive of mn_render_draw, 48 bytes."""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("x1", C.c_double), ("y1", C.c_double), ("image_first", C.c_int32), ("image_last", C.c_int32),
+                ("color_z", C.c_uint32), ("kind", C.c_uint16), ("half_width_px", C.c_uint16)]
 
 
 class MnIqnLearner(C.Structure):
@@ -120,6 +135,8 @@ SIGNATURES = [
     ("mn_query_velocity", C.c_int, [_vp, _vp, _i32, _vp, _i64, _vp, _vp]),
     ("mn_query_observation", C.c_int, [_vp, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
     ("mn_query_rollout", C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i64] + [_vp] * 14),
+    ("mn_render_worlds", C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _pd, C.POINTER(MnRenderStyle), _vp, _vp]),
+    ("mn_render_draw", C.c_int, [_vp, _i32, _i32, _i32, _pd, _vp, _i64, _vp]),
     ("mn_get_state", C.c_int, [_vp, _i32, _i32, _pd, _pi32, _pi64]),
     ("mn_set_state", C.c_int, [_vp, _i32, _i32, _pd, _pi32, _pi64]),
     ("mn_state_bytes", _i64, [_vp]),

@@ -962,6 +962,52 @@ extern "C" int mn_query_rollout(mn_handle *h, const int32_t *env_of_query_dev, i
     return MN_OK;
 }
 
+// ---- pictures: nothing in the handle is written (mn_render.hip) -----------------------------------------------------------------------------------
+static const char *render_canvas_error(const void *pixels_dev, int32_t n_images, int32_t width, int32_t height, const double *view) {
+    if (!pixels_dev) return "render: pixels_dev is NULL";
+    if (!view) return "render: view is NULL";
+    if (n_images < 1 || width < 1 || height < 1) return "render: n_images, width and height must be at least 1";
+    if ((int64_t)width * height * n_images >= ((int64_t)1 << 31)) return "render: width * height * n_images must stay below 2^31";
+    for (int i = 0; i < 4; ++i) if (!(view[i] - view[i] == 0.0)) return "render: the view has a non-finite entry";
+    if (!(view[2] > view[0]) || !(view[3] > view[1])) return "render: the view needs x1 > x0 and y1 > y0";
+    return nullptr;
+}
+
+extern "C" int mn_render_worlds(mn_handle *h, const int32_t *env_of_image_dev, int32_t env0, int32_t n_images, int32_t width, int32_t height,
+                                const double view[4], const mn_render_style *style, uint32_t *pixels_dev, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!h) return fail(nullptr, MN_ERR_INVALID, "mn_render_worlds: NULL handle");
+    if (!style) return fail(h, MN_ERR_INVALID, "mn_render_worlds: style is NULL");
+    if (const char *e = render_canvas_error(pixels_dev, n_images, width, height, view)) return fail(h, MN_ERR_INVALID, e);
+    if (style->n_levels < 1 || style->n_levels > MN_RENDER_MAX_LEVELS) return fail(h, MN_ERR_INVALID, "mn_render_worlds: n_levels outside [1, 32]");
+    if (style->lic_steps < 0 || style->lic_steps > MN_RENDER_MAX_LIC_STEPS) return fail(h, MN_ERR_INVALID, "mn_render_worlds: lic_steps outside [0, 64]");
+    if (style->lic_floor < 0 || style->lic_floor > 255) return fail(h, MN_ERR_INVALID, "mn_render_worlds: lic_floor outside [0, 255]");
+    if (!(style->v_max > 0.0)) return fail(h, MN_ERR_INVALID, "mn_render_worlds: v_max must be above 0");
+    if (style->max_workgroups < 0) return fail(h, MN_ERR_INVALID, "mn_render_worlds: max_workgroups is negative");
+    if (!env_of_image_dev && (env0 < 0 || env0 >= h->A.n)) {
+        char b[128];
+        snprintf(b, sizeof(b), "mn_render_worlds: env0 = %d is outside [0, %d) and no env_of_image array is given", env0, h->A.n);
+        return fail(h, MN_ERR_INVALID, b);
+    }
+    join_reset(h, s);
+    MN_ON_DEVICE(h);
+    mn_launch_render_worlds(h->A, h->P, env_of_image_dev, env0, n_images, width, height, view, *style, pixels_dev, s);
+    MN_HIP(h, hipGetLastError());
+    return MN_OK;
+}
+
+extern "C" int mn_render_draw(uint32_t *pixels_dev, int32_t n_images, int32_t width, int32_t height, const double view[4], const mn_render_prim *prims_dev,
+                              int64_t n_prims, void *stream) {
+    mn_handle *none = nullptr;
+    if (const char *e = render_canvas_error(pixels_dev, n_images, width, height, view)) return fail(none, MN_ERR_INVALID, e);
+    if (n_prims < 0) return fail(none, MN_ERR_INVALID, "mn_render_draw: n_prims is negative");
+    if (n_prims == 0) return MN_OK;
+    if (!prims_dev) return fail(none, MN_ERR_INVALID, "mn_render_draw: prims_dev is NULL");
+    mn_launch_render_draw(pixels_dev, n_images, width, height, view, prims_dev, n_prims, (hipStream_t)stream);
+    MN_HIP(none, hipGetLastError());
+    return MN_OK;
+}
+
 extern "C" int mn_get_state(mn_handle *h, int32_t first, int32_t count, double *state, int32_t *ep_t, int64_t *tot_t) {
     int rc = range_ok(h, first, count);
     if (rc) return rc;

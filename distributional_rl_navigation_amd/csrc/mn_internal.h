@@ -230,3 +230,8 @@ void mn_launch_query_rollout(const MnArrays &A, const MnDev &P, const int32_t *e
                              const int32_t *actions, int n_steps, const int32_t *n_steps_of, int64_t nq, double *state_out, float *obs, double *obs64,
                              double *reward, uint8_t *done, uint8_t *info, int32_t *steps, double *reward_tr, uint8_t *done_tr, uint8_t *info_tr,
                              int32_t *action_tr, double *state_tr, double *traj_tr, hipStream_t s);
+// pictures (mn_render.hip): read-only on A; env_of = NULL: every image shows world env0.  The arguments of mn_render_worlds / mn_render_draw, validated
+void mn_launch_render_worlds(const MnArrays &A, const MnDev &P, const int32_t *env_of, int env0, int n_images, int width, int height, const double view[4],
+                             const mn_render_style &style, uint32_t *pixels, hipStream_t s);
+void mn_launch_render_draw(uint32_t *pixels, int n_images, int width, int height, const double view[4], const mn_render_prim *prims, int64_t n_prims,
+                           hipStream_t s);

@@ -345,6 +345,81 @@ int mn_query_rollout(mn_handle *h, const int32_t *env_of_query_dev, int32_t env0
                      double *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev,
                      double *state_trace_dev, double *traj_trace_dev, void *stream);
 
+/* Pictures on the device: flow images of worlds the handle holds, and primitives (trails, discs, rings) drawn over them.  The rules below are
+ * csrc/mn_render_body.h's, a __host__ __device__ body on top of the query body: every operation is an IEEE float64 add, multiply, divide, square
+ * root, floor or comparison, or integer arithmetic (no trigonometric function, contraction off), so host and device give the same pixel words.
+ *
+ * Pixel word and view.  A pixel is a uint32 z << 24 | r << 16 | g << 8 | b; z is the draw order, the larger z wins, and every write that may be
+ * contested is an integer atomic max on the word: the result does not depend on the order of arrival.  view = {x0, y0, x1, y1} in world units over
+ * an image of width x height pixels ([n_images][height][width] words), sx = (x1 - x0) / width, sy = (y1 - y0) / height; the centre of pixel (row r,
+ * column c) is x = x0 + (c + 0.5) sx, y = y1 - (r + 0.5) sy: row 0 is the top.
+ *
+ * mn_render_worlds: image i shows world env_of_image_dev[i] ([n_images] i32 on the device), or every image world env0 if that is NULL.  It reads only
+ * the float64 master tables (cores, obstacles, start, goal, the placed counts) and the parameters, like the queries, computes in float64 whatever the
+ * handle's precision and writes NOTHING into the handle.  The launch owns every pixel: whole words, plain stores.  Per pixel, by the pixel's centre:
+ *   field (z = 0): outside [0, width] x [0, height] of the params: style.outside.  Otherwise (vx, vy) = get_velocity at the centre (the arithmetic of
+ *     mn_query_velocity), speed = sqrt(vx vx + vy vy), t = speed / v_max * n_levels, level = n_levels - 1 if t is not finite or t >= n_levels, else
+ *     (int)floor(t); the colour is palette[level].
+ *   LIC (style.lic != 0): noise of pixel (c, r): h = c * 0x9E3779B1 ^ r * 0x85EBCA77 ^ seed * 0xC2B2AE3D (uint32); h ^= h >> 15; h *= 0x2C1B3C6D;
+ *     h ^= h >> 12; h *= 0x297A2D39; h ^= h >> 15; noise = h >> 24.  The streamline starts at the centre in continuous pixel coordinates
+ *     (u, v) = (c + 0.5, r + 0.5); the first sample is the pixel's own noise; then up to lic_steps Euler steps with sign s = +1 and, from the centre
+ *     again, up to lic_steps with s = -1.  A step: the velocity at the world point (x0 + u sx, y1 - v sy); stop this direction if the speed is not a
+ *     finite number above zero; u = u + s (hpx vx / speed), v = v - s (hpx vy / speed); stop if floor(u) is outside [0, width) or floor(v) outside
+ *     [0, height), else add the noise of pixel (floor(u), floor(v)).  g = (2 sum + count) / (2 count) in integers over the count samples taken; each
+ *     colour channel c becomes c * (lic_floor + (255 - lic_floor) * g / 255) / 255, in integers, in this order.
+ *   obstacles (z = 1): obstacle k covers a centre with dx dx + dy dy <= r r (dx = x - ox): style.obstacle.
+ *   markers (z = 2, style.marker_r > 0): the start is the disc of marker_r world units; the goal is that disc plus the ring rin^2 <= d^2 <= goal_dis^2,
+ *     rin = goal_dis - max(sx, sy), one pixel wide (rin <= 0: the whole disc of goal_dis): style.marker.
+ * A world index outside [0, n_envs) inside env_of_image_dev is not visible to the host: that image is style.outside everywhere, the others are
+ * unaffected and the call returns MN_OK.  style.max_workgroups bounds the grid (0: 2048); more tiles than that take the stride loop.
+ *
+ * mn_render_draw takes no handle.  It draws prims_dev [n_prims] into every image of each record's inclusive range [image_first, image_last], cut to
+ * [0, n_images), with atomic max of color_z (the whole word: z << 24 | rgb).  Primitives that share a z have the colours the caller gave them, and
+ * max still decides.  half_width_px above MN_RENDER_MAX_HALF_WIDTH counts as that.  A record with a non-finite number where its kind reads one, an
+ * empty image range or an unknown kind draws nothing; nothing a record holds makes the kernel read or write outside the images.
+ *   MN_RENDER_SEGMENT: endpoints (x0, y0), (x1, y1) in world units; in pixel units a = ((x0 - view.x0) / sx, (view.y1 - y0) / sy), b alike, d = b - a
+ *     (a, b or d not finite: nothing -- a NaN row is how a polyline breaks).  The segment is clipped (Liang-Barsky, t0 = 0, t1 = 1, the edges in the
+ *     order u-low, u-high, v-low, v-high: p = -du, du, -dv, dv; q = au - lo, hi - au, ...; p == 0: q < 0 rejects; r = q / p; p < 0: r > t1 rejects,
+ *     r > t0 sets t0; p > 0: r < t0 rejects, r < t1 sets t1) to the image rectangle grown by m = half_width_px + 1 on every side, and its new ends
+ *     a + t0 d, a + t1 d are clamped into that rectangle, component by component, so a coordinate of 1e300 cannot spin a lane:
+ *     n = (int)ceil(max(|du|, |dv|)) of the clipped segment is at most max(width, height) + 2 m.  Samples p_k = a + (d k) / n, k = 0..n (n = 0: a
+ *     alone); each stamps the (2 half_width_px + 1)^2 pixels around (floor(p_k.u), floor(p_k.v)) that lie inside the image.
+ *   MN_RENDER_DISC: every pixel whose centre has dx dx + dy dy <= x1 x1 around (x0, y0) (x1 < 0: nothing).
+ *   MN_RENDER_RING: every pixel whose centre has x1 x1 <= dx dx + dy dy <= y1 y1 (x1 < 0 or y1 < x1: nothing).
+ *
+ * Both calls make ONE launch on `stream`, allocate nothing and never wait on the host.  MN_ERR_INVALID, without a launch: a NULL handle, style,
+ * view, pixel or primitive pointer (prims_dev may be NULL when n_prims is 0, which returns MN_OK at once); n_prims < 0; n_images, width or height < 1 or
+ * width * height * n_images >= 2^31; a view with x1 <= x0, y1 <= y0 or a non-finite entry; n_levels outside [1, MN_RENDER_MAX_LEVELS]; lic_steps outside
+ * [0, MN_RENDER_MAX_LIC_STEPS]; lic_floor outside [0, 255]; v_max <= 0 or NaN; max_workgroups < 0; env0 outside [0, n_envs) without an index array. */
+#define MN_RENDER_MAX_LEVELS 32
+#define MN_RENDER_MAX_LIC_STEPS 64
+#define MN_RENDER_MAX_HALF_WIDTH 8
+enum { MN_RENDER_SEGMENT = 0, MN_RENDER_DISC = 1, MN_RENDER_RING = 2 };
+typedef struct mn_render_style {
+    double v_max;            /* the speed of the top level */
+    double hpx;              /* LIC step in pixels */
+    double marker_r;         /* world units; <= 0: no markers */
+    int32_t n_levels;        /* 1 .. MN_RENDER_MAX_LEVELS */
+    int32_t lic;             /* 0: the plain field colour */
+    int32_t lic_steps;       /* 0 .. MN_RENDER_MAX_LIC_STEPS, each way */
+    int32_t lic_floor;       /* 0 .. 255: the brightness of noise 0 */
+    uint32_t seed;
+    uint32_t outside, obstacle, marker;      /* r << 16 | g << 8 | b */
+    int32_t max_workgroups;  /* 0: the default grid bound */
+    int32_t reserved;
+    uint32_t palette[MN_RENDER_MAX_LEVELS];  /* r << 16 | g << 8 | b per level, by value */
+} mn_render_style;           /* 192 bytes */
+typedef struct mn_render_prim {
+    double x0, y0, x1, y1;
+    int32_t image_first, image_last;
+    uint32_t color_z;
+    uint16_t kind, half_width_px;
+} mn_render_prim;            /* 48 bytes */
+int mn_render_worlds(mn_handle *h, const int32_t *env_of_image_dev, int32_t env0, int32_t n_images, int32_t width, int32_t height,
+                     const double view[4], const mn_render_style *style, uint32_t *pixels_dev, void *stream);
+int mn_render_draw(uint32_t *pixels_dev, int32_t n_images, int32_t width, int32_t height, const double view[4],
+                   const mn_render_prim *prims_dev, int64_t n_prims, void *stream);
+
 /* Robot pose and counters (robot.py:40-44, marinenav_env.py:70-71).  state[count][6] =
  * x, y, theta, speed, velocity_x, velocity_y (float64).  NULL pointers are skipped. */
 int mn_get_state(mn_handle *h, int32_t first_env, int32_t count, double *state, int32_t *episode_timesteps,
