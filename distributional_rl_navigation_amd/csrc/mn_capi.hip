@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "mn_internal.h"
+#include "mn_render_font.h"
 
 struct mn_handle {
     MnArrays A;
@@ -1005,6 +1006,13 @@ extern "C" int mn_render_draw(uint32_t *pixels_dev, int32_t n_images, int32_t wi
     if (!prims_dev) return fail(none, MN_ERR_INVALID, "mn_render_draw: prims_dev is NULL");
     mn_launch_render_draw(pixels_dev, n_images, width, height, view, prims_dev, n_prims, (hipStream_t)stream);
     MN_HIP(none, hipGetLastError());
+    return MN_OK;
+}
+
+extern "C" int mn_render_font(uint8_t *out) {
+    mn_handle *none = nullptr;
+    if (!out) return fail(none, MN_ERR_INVALID, "mn_render_font: out is NULL");
+    memcpy(out, MNR_FONT, sizeof(MNR_FONT));
     return MN_OK;
 }
 

@@ -8,6 +8,7 @@
 // palette is asked of the caller (`pal(level)`: LDS on the device), the obstacles of its `World` (`w.obstacle(k, ox, oy, r)`: a table read).
 #pragma once
 #include "mn_query_body.h"
+#include "mn_render_font.h"
 
 #define MNR_HD __host__ __device__ __forceinline__
 
@@ -100,13 +101,16 @@ MNR_HD uint32_t mnr_world_pixel(const MnqCores &C, const World &w, int no, doubl
 // (mnr_item): the items of one (primitive, image) pair are independent of each other, so the caller may hand them to lanes in any order.
 struct MnrPlan {
     int kind, i0, i1;        // images [i0, i1]
-    long long per_image;     // items per image: samples of a segment, pixels of a disc's / ring's bounding box
-    double au, av, du, dv;   // SEGMENT: the clipped start and extent, pixel units
-    int n, hw;
-    int c_lo, r_lo, bw;      // DISC / RING: the box
-    double cx, cy, rin2, rout2;
+    long long per_image;     // items per image: samples of a segment, pixels of a box (DISC, RING, RECT, SECTOR), of a marker's square, of a glyph's cell
+    double au, av, du, dv;   // SEGMENT: the clipped start and extent, pixel units.  SECTOR: (du, dv) = m, au = sqrt(m.m), av = the cosine c
+    int n, hw;               // MARKER: n = shape, hw = arm.  GLYPH: hw = scale
+    int c_lo, r_lo, bw;      // DISC / RING / RECT / SECTOR: the box.  MARKER: the square's top-left pixel and side.  GLYPH: the cell's top-left and width
+    double cx, cy, rin2, rout2;      // RECT: the closed rectangle [cx, rin2] x [cy, rout2]
+    int t;                   // MARKER: the stroke
+    unsigned long long bits; // GLYPH: the 35 pixels of the character, bit 5 j + i = row j, column i
     uint32_t word;
 };
+#define MNR_ANCHOR_MAX 1048576.0      // 2^20: an anchor (MARKER, GLYPH) or a glyph offset farther out than this draws nothing
 
 MNR_HD double mnr_clamp(double a, double lo, double hi) { return a < lo ? lo : (a > hi ? hi : a); }
 
@@ -168,6 +172,54 @@ MNR_HD bool mnr_plan(const mn_render_prim &p, const MnrView &V, int n_images, Mn
         out.per_image = (long long)out.bw * (r_hi - r_lo + 1);
         return true;
     }
+    if (p.kind == MN_RENDER_RECT || p.kind == MN_RENDER_SECTOR) {
+        if (!(mnr_finite(p.x0) && mnr_finite(p.y0) && mnr_finite(p.x1) && mnr_finite(p.y1))) return false;
+        // both kinds fill the same fields below, each once, whatever the kind: a store that is in one branch only keeps the plan in memory
+        const bool rect = p.kind == MN_RENDER_RECT;
+        const double mx = p.x1 - p.x0, my = p.y1 - p.y0, mm = mx * mx + my * my;
+        if (!rect && (p.half_width_px > 32768 || !mnr_finite(mm) || mm == 0.0)) return false;
+        const double rad = rect ? 0.0 : sqrt(mm);
+        const double xa = rect ? p.x0 : p.x0 - rad, xb = rect ? p.x1 : p.x0 + rad, ya = rect ? p.y0 : p.y0 - rad, yb = rect ? p.y1 : p.y0 + rad;
+        const double xl = xa < xb ? xa : xb, xh = xa < xb ? xb : xa, yl = ya < yb ? ya : yb, yh = ya < yb ? yb : ya;
+        out.cx = rect ? xl : p.x0; out.cy = rect ? yl : p.y0; out.rin2 = rect ? xh : 0.0; out.rout2 = rect ? yh : mm;
+        out.du = mx; out.dv = my; out.au = rad; out.av = p.half_width_px / 16384.0 - 1.0;
+        // the box of DISC: one pixel of slack each way, cut to the image in float64 before any conversion to an integer
+        const double cl = floor((xl - V.x0) / V.sx) - 1.0, ch = floor((xh - V.x0) / V.sx) + 1.0;
+        const double rl = floor((V.y1 - yh) / V.sy) - 1.0, rh = floor((V.y1 - yl) / V.sy) + 1.0;
+        if (!(mnr_finite(cl) && mnr_finite(ch) && mnr_finite(rl) && mnr_finite(rh))) return false;
+        if (ch < 0.0 || cl > V.W - 1.0 || rh < 0.0 || rl > V.H - 1.0) return false;
+        const int c_lo = (int)mnr_clamp(cl, 0.0, V.W - 1.0), c_hi = (int)mnr_clamp(ch, 0.0, V.W - 1.0);
+        const int r_lo = (int)mnr_clamp(rl, 0.0, V.H - 1.0), r_hi = (int)mnr_clamp(rh, 0.0, V.H - 1.0);
+        out.c_lo = c_lo; out.r_lo = r_lo; out.bw = c_hi - c_lo + 1;
+        out.per_image = (long long)out.bw * (r_hi - r_lo + 1);
+        return true;
+    }
+    if (p.kind == MN_RENDER_MARKER || p.kind == MN_RENDER_GLYPH) {
+        const double au = (p.x0 - V.x0) / V.sx, av = (V.y1 - p.y0) / V.sy;
+        if (!(fabs(au) <= MNR_ANCHOR_MAX && fabs(av) <= MNR_ANCHOR_MAX)) return false;      // (a NaN fails the comparison)
+        const int cu = (int)floor(au), cv = (int)floor(av);
+        if (p.kind == MN_RENDER_MARKER) {
+            const int h = p.half_width_px < MN_RENDER_MAX_HALF_WIDTH ? p.half_width_px : MN_RENDER_MAX_HALF_WIDTH;
+            if (!(p.x1 == 0.0 || p.x1 == 1.0 || p.x1 == 2.0) || !mnr_finite(p.y1)) return false;
+            out.n = (int)p.x1; out.hw = h; out.t = (int)mnr_clamp(p.y1, 0.0, (double)h);
+            out.c_lo = cu - h; out.r_lo = cv - h; out.bw = 2 * h + 1;
+            out.per_image = (long long)out.bw * out.bw;
+            return true;
+        }
+        const int code = p.half_width_px & 255, scale = p.half_width_px >> 8;
+        if (code <= MNR_FONT_FIRST || code >= MNR_FONT_FIRST + MNR_FONT_COUNT || scale < 1 || scale > 8) return false;
+        const double ox = floor(p.x1), oy = floor(p.y1);
+        if (!(fabs(ox) <= MNR_ANCHOR_MAX && fabs(oy) <= MNR_ANCHOR_MAX)) return false;
+        unsigned long long bits = 0;      // the code is the same in all lanes: seven byte reads at a uniform address, no indexed private copy
+        for (int j = 0; j < MNR_FONT_ROWS; ++j) {
+            const unsigned row = MNR_FONT[code - MNR_FONT_FIRST][j];
+            for (int i = 0; i < MNR_FONT_COLS; ++i) bits |= (unsigned long long)(row >> (MNR_FONT_COLS - 1 - i) & 1u) << (MNR_FONT_COLS * j + i);
+        }
+        out.bits = bits; out.hw = scale;
+        out.c_lo = cu + (int)ox; out.r_lo = cv + (int)oy; out.bw = MNR_FONT_COLS * scale;
+        out.per_image = (long long)out.bw * (MNR_FONT_ROWS * scale);
+        return true;
+    }
     return false;
 }
 
@@ -181,11 +233,27 @@ MNR_HD void mnr_item(const MnrPlan &L, const MnrView &V, long long j, Put &put) 
         const int r0 = cr - L.hw > 0 ? cr - L.hw : 0, r1 = cr + L.hw < V.H - 1 ? cr + L.hw : V.H - 1;
         for (int r = r0; r <= r1; ++r)
             for (int c = c0; c <= c1; ++c) put(c, r);
-    } else {
-        const int c = L.c_lo + (int)(j % L.bw), r = L.r_lo + (int)(j / L.bw);
+    } else {      // a box, a square or a cell: item j is one of its pixels
+        const int pc = (int)(j % L.bw), pr = (int)(j / L.bw);
+        const int c = L.c_lo + pc, r = L.r_lo + pr;
         if (c < 0 || c >= V.W || r < 0 || r >= V.H) return;
-        const double dx = (V.x0 + (c + 0.5) * V.sx) - L.cx, dy = (V.y1 - (r + 0.5) * V.sy) - L.cy;
-        const double d2 = dx * dx + dy * dy;
-        if (d2 <= L.rout2 && d2 >= L.rin2) put(c, r);
+        if (L.kind == MN_RENDER_MARKER) {
+            const int du = pc < L.hw ? L.hw - pc : pc - L.hw, dv = pr < L.hw ? L.hw - pr : pr - L.hw;      // |du|, |dv|
+            const int dd = du < dv ? dv - du : du - dv;
+            if (L.n == 0 || (L.n == 1 && (du <= L.t || dv <= L.t)) || (L.n == 2 && dd <= L.t)) put(c, r);
+        } else if (L.kind == MN_RENDER_GLYPH) {
+            if (L.bits >> (MNR_FONT_COLS * (pr / L.hw) + pc / L.hw) & 1ull) put(c, r);
+        } else {
+            const double x = V.x0 + (c + 0.5) * V.sx, y = V.y1 - (r + 0.5) * V.sy;
+            if (L.kind == MN_RENDER_RECT) {
+                if (x >= L.cx && x <= L.rin2 && y >= L.cy && y <= L.rout2) put(c, r);
+            } else {
+                const double dx = x - L.cx, dy = y - L.cy;
+                const double d2 = dx * dx + dy * dy;
+                if (L.kind == MN_RENDER_SECTOR) {
+                    if (d2 <= L.rout2 && (d2 == 0.0 || dx * L.du + dy * L.dv >= L.av * sqrt(d2) * L.au)) put(c, r);
+                } else if (d2 <= L.rout2 && d2 >= L.rin2) put(c, r);
+            }
+        }
     }
 }

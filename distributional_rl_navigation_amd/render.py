@@ -1,8 +1,9 @@
 """Pictures of worlds and episodes, made where the data is: flow images (speed levels, optionally line integral convolution for the direction),
 obstacles and start / goal markers by `mn_render_worlds`, trails, robots and sonar beams by `mn_render_draw` (include/marinenav_hip.h states the
 raster rules; csrc/mn_render.hip holds the kernels).  A trajectory trace of an episode launch, `[T][n][N][2]` on the device, becomes a sheet of
-one image per world (`episode_sheet`: the reference's `draw_trajectory` figure) or the frames of a video (`episode_frames`: `draw_video_plots`
-without its side panels) without leaving the device; only finished RGB images are copied to the host, by `save_png` (zlib and struct, no
+one image per world (`episode_sheet`: the reference's `draw_trajectory` figure) or the frames of a video (`episode_frames`: the map of
+`draw_video_plots`; render_panels.py draws its side panels and the whole frame from the plot primitives here: `rects`, `markers`, `sectors`,
+`arrows`, `text`, `numbers`, `choose_text`) without leaving the device; only finished RGB images are copied to the host, by `save_png` (zlib and struct, no
 plotting library).
 
 A pixel is a uint32 word `z << 24 | r << 16 | g << 8 | b`; the larger word wins wherever two things meet, so the draw order `z` decides first and
@@ -77,7 +78,7 @@ def _ptr(t):
 
 class Canvas:
     """`pixels`: the packed [I][H][W] uint32 images on the device, `view` = (x0, y0, x1, y1) in world units.  `draw(prims)` draws a primitive buffer
-    (`segments`, `polylines`, `discs`, `rings`; `torch.cat` joins buffers) into them in ONE launch and returns the canvas; `rgb()` drops the z byte."""
+    (`segments`, `polylines`, `discs`, `rings`, `rects`, `markers`, `sectors`, `arrows`, `text`, `numbers`; `torch.cat` joins buffers) into them in ONE launch and returns the canvas; `rgb()` drops the z byte."""
 
     def __init__(self, pixels, view):
         assert pixels.dim() == 3 and pixels.dtype == torch.uint32 and pixels.is_contiguous()
@@ -191,6 +192,209 @@ def rings(centres, r_in, r_out, color_z, image_first=0, image_last=None):
     c = torch.as_tensor(centres).to(torch.float64).reshape(-1, 2)
     ri, ro = _per_prim(r_in, c.shape[0], torch.float64, c.device), _per_prim(r_out, c.shape[0], torch.float64, c.device)
     return pack_prims(torch.stack((c[:, 0], c[:, 1], ri, ro), dim=1), _capi.RENDER_RING, color_z, image_first, image_last)
+
+
+# ---- the kinds a plot needs: rectangles, pixel-sized marks, sectors, arrows, text --------------------------------------------------------------------
+MARKER_SHAPES = {"square": _capi.RENDER_MARKER_SQUARE, "plus": _capi.RENDER_MARKER_PLUS, "cross": _capi.RENDER_MARKER_CROSS}
+GLYPH_ADVANCE, GLYPH_LINE = 6, 9      # pixels per character and per line at scale 1 (the cell is 5 x 7)
+NUMBERS_MAX_DECIMALS = 3              # |v| < 1e15 times 10^3 stays an exact int64
+
+
+def _pack16(coords, kind, color_z, image_first, image_last, param):
+    """pack_prims with the record's 16-bit parameter as it is (0..65535): GLYPH's code | scale << 8, SECTOR's quantised cosine."""
+    xy = torch.as_tensor(coords).to(torch.float64).reshape(-1, 4).contiguous()
+    n, dev = xy.shape[0], xy.device
+    first = _per_prim(image_first, n, torch.int32, dev)
+    last = first if image_last is None else _per_prim(image_last, n, torch.int32, dev)
+    cz = _per_prim(color_z, n, torch.int64, dev)
+    cz = torch.where(cz >= 1 << 31, cz - (1 << 32), cz).to(torch.int32)
+    w = _per_prim(param, n, torch.int64, dev).clamp(0, 0xFFFF) << 16 | int(kind)
+    w = torch.where(w >= 1 << 31, w - (1 << 32), w).to(torch.int32)
+    tail = torch.stack((first, last, cz, w), dim=1).contiguous()
+    return torch.cat((xy.view(torch.uint8).reshape(n, 32), tail.view(torch.uint8).reshape(n, 16)), dim=1)
+
+
+def rects(a, b, color_z, image_first=0, image_last=None):
+    """Filled axis-aligned rectangles with corners `a` [P][2] and `b` [P][2] (any order), world units: every pixel whose centre lies inside, the
+    edges included.  A NaN coordinate skips the rectangle."""
+    a, b = torch.as_tensor(a).to(torch.float64).reshape(-1, 2), torch.as_tensor(b).to(torch.float64).reshape(-1, 2)
+    return pack_prims(torch.cat((a, b.to(a.device)), dim=1), _capi.RENDER_RECT, color_z, image_first, image_last)
+
+
+def markers(points, shape, arm, stroke, color_z, image_first=0, image_last=None):
+    """Pixel-sized marks at `points` [P][2]: `shape` "square", "plus" or "cross" (or 0, 1, 2; one for all or [P]), `arm` pixels each way from the
+    anchor pixel (at most 8), `stroke` the half thickness of a plus's or a cross's bars in pixels.  The size does not follow the view."""
+    p = torch.as_tensor(points).to(torch.float64).reshape(-1, 2)
+    n, dev = p.shape[0], p.device
+    sh = MARKER_SHAPES[shape] if isinstance(shape, str) else shape
+    return pack_prims(torch.stack((p[:, 0], p[:, 1], _per_prim(sh, n, torch.float64, dev), _per_prim(stroke, n, torch.float64, dev)), dim=1),
+                      _capi.RENDER_MARKER, color_z, image_first, image_last, arm)
+
+
+def sector_cosine(half_angle):
+    """The 16-bit parameter of a SECTOR record for a half angle in radians (a host float): q with cos = q / 16384 - 1, quantised once."""
+    import math
+    return min(32768, max(0, int(round((math.cos(float(half_angle)) + 1.0) * 16384.0))))
+
+
+def sectors(centres, mid_points, half_angle, color_z, image_first=0, image_last=None, device=None):
+    """Wedges of discs: centre [P][2], `mid_points` [P][2] the point of the arc on the middle direction (so the radius is their distance), and the
+    half angle in radians, one host float for all.  Built on the centres' device, or on `device`."""
+    c, m = torch.as_tensor(centres, device=device).to(torch.float64).reshape(-1, 2), torch.as_tensor(mid_points).to(torch.float64).reshape(-1, 2)
+    return _pack16(torch.cat((c, m.to(c.device)), dim=1), _capi.RENDER_SECTOR, color_z, image_first, image_last, sector_cosine(half_angle))
+
+
+def arrows(a, b, head_px, color_z, view, size, image_first=0, image_last=None, half_width=0):
+    """Arrows from `a` [P][2] to `b` [P][2]: the shaft and two head strokes of `head_px` pixels, 3 SEGMENT records each ([P][3] in this order).  The
+    head is built in pixel units of `view` over `size` = (width, height), at atan(1 / 2) to the shaft; an arrow of no length has no head (its
+    strokes are NaN)."""
+    a, b = torch.as_tensor(a).to(torch.float64).reshape(-1, 2), torch.as_tensor(b).to(torch.float64).reshape(-1, 2)
+    b = b.to(a.device)
+    sx, sy = (float(view[2]) - float(view[0])) / int(size[0]), (float(view[3]) - float(view[1])) / int(size[1])
+    du, dv = (b[:, 0] - a[:, 0]) / sx, -(b[:, 1] - a[:, 1]) / sy
+    norm = torch.sqrt(du * du + dv * dv)
+    uu, uv = du / norm, dv / norm      # (0 / 0 = NaN: no head)
+    c, s = 2.0 / 5.0 ** 0.5, 1.0 / 5.0 ** 0.5
+    tips = []
+    for sign in (1.0, -1.0):
+        pu, pv = -(c * uu) + sign * s * -uv, -(c * uv) + sign * s * uu
+        tips.append(torch.stack((b[:, 0] + float(head_px) * pu * sx, b[:, 1] - float(head_px) * pv * sy), dim=1))
+    n = a.shape[0]
+    start = torch.stack((a, b, b), dim=1).reshape(3 * n, 2)
+    end = torch.stack((b, tips[0], tips[1]), dim=1).reshape(3 * n, 2)
+    def per_record(v, dtype):      # one value per arrow -> one per record
+        return None if v is None else _per_prim(v, n, dtype, a.device)[:, None].expand(n, 3).reshape(-1)
+    return segments(start, end, per_record(color_z, torch.int64), per_record(image_first, torch.int32), per_record(image_last, torch.int32), half_width)
+
+
+def _align_shift(align, n_chars, scale):
+    """Pixels from the anchor to the left edge of a line of `n_chars` characters."""
+    width = max(GLYPH_ADVANCE * scale * n_chars - scale, 0)      # without the gap behind the last character
+    if align == "left":
+        return 0
+    if align == "right":
+        return -width
+    if align == "centre" or align == "center":
+        return -(width // 2)
+    raise ValueError(f"align is 'left', 'right' or 'centre', got {align!r}")
+
+
+def _glyphs(codes, anchor, cell_dx, cell_dy, color_z, scale, image_first, image_last):
+    """GLYPH records of `codes` [P][L] (int tensor) at `anchor` [P][2] (or [2]): cell l of every row at pixel offset (cell_dx[l], cell_dy[l]) from the
+    anchor's pixel, down positive.  Per-primitive values are one for all or [P]."""
+    scale = int(scale)
+    if not 1 <= scale <= 8:
+        raise ValueError(f"a glyph's scale is 1..8, got {scale}")
+    P, L = int(codes.shape[0]), int(codes.shape[1])
+    dev = codes.device
+    anchor = torch.as_tensor(anchor).to(device=dev, dtype=torch.float64).reshape(-1, 2)
+    if anchor.shape[0] == 1:
+        anchor = anchor.expand(P, 2)
+    if anchor.shape[0] != P:
+        raise ValueError(f"{anchor.shape[0]} anchors for {P} rows of text")
+    off = torch.stack((torch.as_tensor(cell_dx, dtype=torch.float64, device=dev).reshape(L), torch.as_tensor(cell_dy, dtype=torch.float64, device=dev).reshape(L)), dim=1)
+    coords = torch.cat((anchor[:, None, :].expand(P, L, 2), off[None].expand(P, L, 2)), dim=2).reshape(P * L, 4)
+
+    def per_row(v, dtype):
+        if v is None:
+            return None
+        return _per_prim(v, P, dtype, dev)[:, None].expand(P, L).reshape(-1)
+    return _pack16(coords, _capi.RENDER_GLYPH, per_row(color_z, torch.int64), per_row(image_first, torch.int32), per_row(image_last, torch.int32),
+                   (codes.to(torch.int64).clamp(0, 255) | scale << 8).reshape(-1))
+
+
+def _text_cells(string, scale, align, dx, dy):
+    """(codes [L], cell_dx [L], cell_dy [L]) of a string with "\\n": every character but the line breaks is one cell."""
+    codes, xs, ys = [], [], []
+    for k, line in enumerate(str(string).split("\n")):
+        left = int(dx) + _align_shift(align, len(line), scale)
+        for i, ch in enumerate(line):
+            codes.append(ord(ch) if 32 <= ord(ch) <= 126 else ord("?"))
+            xs.append(left + GLYPH_ADVANCE * scale * i)
+            ys.append(int(dy) + GLYPH_LINE * scale * k)
+    return codes, xs, ys
+
+
+def text(string, anchor, color_z, scale=1, align="left", dx=0, dy=0, image_first=0, image_last=None, device=None):
+    """`string` in the 5 x 7 font at `anchor` (world units; [2], or [P][2] for the same string at P anchors): one GLYPH record per character, the
+    spaces included ([P][len]), each character `6 scale` pixels right of the one before, "\\n" `9 scale` pixels down.  (dx, dy) moves the text in
+    pixels, dy down; the cell of the first line's first character has its top-left pixel at the anchor's pixel plus (dx, dy) for align "left";
+    "right" ends every line there, "centre" centres it.  A character outside 32..126 becomes '?'.  An empty string gives 0 records.  The records
+    are built on the anchor's device, or on `device` (a host anchor for a picture on the GPU)."""
+    anchor = torch.as_tensor(anchor, device=device).to(torch.float64).reshape(-1, 2)
+    codes, xs, ys = _text_cells(string, int(scale), align, dx, dy)
+    P = anchor.shape[0]
+    table = torch.tensor(codes, dtype=torch.int64, device=anchor.device).reshape(1, -1).expand(P, -1)
+    return _glyphs(table, anchor, xs, ys, color_z, scale, image_first, image_last)
+
+
+def number_codes(values, decimals, width, justify="right"):
+    """[P][width] int64 character codes of `values` [P] in fixed notation on the device of `values`, the text at the right end of the cells or
+    (`justify` "left") at their left end; see `numbers`."""
+    if justify not in ("right", "left"):
+        raise ValueError(f"justify is 'right' or 'left', got {justify!r}")
+    d, width = int(decimals), int(width)
+    if not 0 <= d <= NUMBERS_MAX_DECIMALS or width < 1:
+        raise ValueError(f"numbers: decimals is 0..{NUMBERS_MAX_DECIMALS} and width at least 1, got {d} and {width}")
+    v = torch.as_tensor(values).to(torch.float64).reshape(-1)
+    dev = v.device
+    bad = ~torch.isfinite(v) | (v.abs() >= 1e15)
+    n = torch.floor(torch.where(bad, torch.zeros_like(v), v.abs()) * float(10 ** d) + 0.5).to(torch.int64)
+    pow10 = torch.tensor([10 ** j for j in range(19)], dtype=torch.int64, device=dev)
+    n_digits = (n[:, None] >= pow10[None, :]).sum(dim=1)                      # 0 for n = 0
+    shown = torch.clamp(n_digits, min=d + 1)                                  # at least one digit before the point
+    neg = (v < 0) & (n > 0)
+    point = 1 if d > 0 else 0
+    length = shown + point + neg.to(torch.int64)
+    k = torch.arange(width - 1, -1, -1, device=dev, dtype=torch.int64)[None, :]      # cell -> its place counted from the right
+    place = torch.where(k > d, k - point, k) if d > 0 else k                     # the decimal place of the digit in that cell
+    digit = (n[:, None] // pow10[place.clamp(0, 18)]) % 10
+    codes = torch.where(place < shown[:, None], 48 + digit, torch.full_like(digit, 32))
+    if d > 0:
+        codes = torch.where(k == d, torch.full_like(codes, 46), codes)
+    codes = torch.where(neg[:, None] & (k == (shown + point)[:, None]), torch.full_like(codes, 45), codes)
+    if justify == "left":      # cell i takes what stands (width - length) cells further right; the cells behind the text are spaces
+        i = torch.arange(width, device=dev, dtype=torch.int64)[None, :]
+        src = (i + (width - length)[:, None]).clamp(0, width - 1)
+        codes = torch.where(i < length[:, None], torch.gather(codes, 1, src), torch.full_like(codes, 32))
+    return torch.where((bad | (length > width))[:, None], torch.full_like(codes, 35), codes)
+
+
+def numbers(values, decimals, width, anchor, color_z, scale=1, align="right", dx=0, dy=0, image_first=0, image_last=None, justify="right"):
+    """`values` [P] (a device tensor, never read back) as text, value p at anchor p: exactly `width` GLYPH records per value ([P][width]), whatever
+    the values.  n = floor(|v| 10^decimals + 0.5) as int64; its digits get a point before the last `decimals` digits and at least one digit before
+    the point; '-' goes in front if v < 0 and n > 0; the text is right-justified in the `width` cells (`justify` "left": left-justified) and the unused cells hold a space.  A text
+    longer than `width`, a non-finite v or |v| >= 1e15 fills every cell with '#'.  This is Python's f"{v:.{decimals}f}" except at ties, which that
+    rounds to even on the exact decimal value and this rounds up on the float64 product, and except that a value that rounds to zero loses its
+    sign.  `decimals` is 0..3.  The cells lie as a `text` of `width` characters does under `align`."""
+    codes = number_codes(values, decimals, width, justify)
+    _, xs, ys = _text_cells("0" * int(width), int(scale), align, dx, dy)
+    return _glyphs(codes, anchor, xs, ys, color_z, scale, image_first, image_last)
+
+
+def choose_text(strings, index, anchor, color_z, scale=1, align="left", dx=0, dy=0, image_first=0, image_last=None):
+    """One of the host strings `strings` per anchor, chosen on the device: row index[p] (`index` [P], a device int tensor) of the code table goes at
+    anchor p.  The strings are padded with spaces to the longest; every anchor gets that many GLYPH records.  An index outside the list writes
+    spaces."""
+    strings = [str(s) for s in strings]
+    if not strings or any("\n" in s for s in strings):
+        raise ValueError("choose_text takes a non-empty list of one-line strings")
+    L = max(len(s) for s in strings)
+    index = torch.as_tensor(index).reshape(-1)
+    dev = index.device
+    rows = [[ord(c) if 32 <= ord(c) <= 126 else ord("?") for c in s.ljust(L)] for s in strings] + [[32] * L]
+    table = torch.tensor(rows, dtype=torch.int64, device=dev).reshape(len(rows), L)
+    idx = index.to(torch.int64)
+    idx = torch.where((idx >= 0) & (idx < len(strings)), idx, torch.full_like(idx, len(strings)))
+    _, xs, ys = _text_cells("0" * L, int(scale), align, dx, dy)
+    return _glyphs(table[idx], anchor, xs, ys, color_z, scale, image_first, image_last)
+
+
+def font():
+    """The 5 x 7 font as uint8 [95][7] (numpy): row byte j of code 32 + k, bit 4 the leftmost column (C-ABI mn_render_font)."""
+    buf = (C.c_uint8 * (95 * 7))()
+    _capi.check(_capi.lib().mn_render_font(C.cast(buf, C.c_void_p)))
+    return np.frombuffer(bytes(buf), dtype=np.uint8).reshape(95, 7).copy()
 
 
 def prims_to_numpy(prims):

@@ -376,7 +376,7 @@ int mn_query_rollout(mn_handle *h, const int32_t *env_of_query_dev, int32_t env0
  * mn_render_draw takes no handle.  It draws prims_dev [n_prims] into every image of each record's inclusive range [image_first, image_last], cut to
  * [0, n_images), with atomic max of color_z (the whole word: z << 24 | rgb).  Primitives that share a z have the colours the caller gave them, and
  * max still decides.  half_width_px above MN_RENDER_MAX_HALF_WIDTH counts as that.  A record with a non-finite number where its kind reads one, an
- * empty image range or an unknown kind draws nothing; nothing a record holds makes the kernel read or write outside the images.
+ * empty image range, an out-of-range parameter or an unknown kind draws nothing; nothing a record holds makes the kernel read or write outside the images.
  *   MN_RENDER_SEGMENT: endpoints (x0, y0), (x1, y1) in world units; in pixel units a = ((x0 - view.x0) / sx, (view.y1 - y0) / sy), b alike, d = b - a
  *     (a, b or d not finite: nothing -- a NaN row is how a polyline breaks).  The segment is clipped (Liang-Barsky, t0 = 0, t1 = 1, the edges in the
  *     order u-low, u-high, v-low, v-high: p = -du, du, -dv, dv; q = au - lo, hi - au, ...; p == 0: q < 0 rejects; r = q / p; p < 0: r > t1 rejects,
@@ -386,6 +386,24 @@ int mn_query_rollout(mn_handle *h, const int32_t *env_of_query_dev, int32_t env0
  *     alone); each stamps the (2 half_width_px + 1)^2 pixels around (floor(p_k.u), floor(p_k.v)) that lie inside the image.
  *   MN_RENDER_DISC: every pixel whose centre has dx dx + dy dy <= x1 x1 around (x0, y0) (x1 < 0: nothing).
  *   MN_RENDER_RING: every pixel whose centre has x1 x1 <= dx dx + dy dy <= y1 y1 (x1 < 0 or y1 < x1: nothing).
+ *   MN_RENDER_RECT: the filled axis-aligned rectangle with corners (x0, y0), (x1, y1) in world units, in any order: every pixel whose centre lies in
+ *     the closed rectangle [min x, max x] x [min y, max y].  The pixels are looked for in a box cut to the image in float64 before any conversion to
+ *     an integer, as for a disc: a corner at 1e300 is fine.
+ *   MN_RENDER_MARKER: a pixel-sized mark at the world point (x0, y0).  With a as for a segment, the anchor pixel is (cu, cv) = (floor(a.u),
+ *     floor(a.v)); |a.u| or |a.v| above 2^20 (tested in float64; a NaN too): nothing.  half_width_px is the arm h (above MN_RENDER_MAX_HALF_WIDTH
+ *     counts as that), x1 the shape: 0 square, 1 plus, 2 cross, any other value nothing; y1 the stroke t = (int)y1 clamped to [0, h] (not finite:
+ *     nothing).  Pixel (cu + du, cv + dv) with |du|, |dv| <= h is taken if: square, always; plus, |du| <= t or |dv| <= t; cross,
+ *     ||du| - |dv|| <= t.  Cut to the image.
+ *   MN_RENDER_GLYPH: one character of the fixed 5 x 7 font (csrc/mn_render_font.h; mn_render_font copies it out), pixel-sized, anchored at the world
+ *     point (x0, y0) by the MARKER rules.  (floor(x1), floor(y1)) is the offset in pixels of the cell's top-left pixel (L, T) from the anchor pixel;
+ *     each must be finite and within +-2^20, else nothing.  half_width_px = code | scale << 8: code 33..126 (anything else, the space 32 included,
+ *     draws nothing), scale 1..8 (anything else: nothing).  Bit (i, j) of the glyph -- column i = 0..4 from the left, row j = 0..6 from the top; bit
+ *     4 - i of row byte j of the font -- covers the scale x scale block of columns [L + i scale, L + (i + 1) scale) and rows [T + j scale,
+ *     T + (j + 1) scale), cut to the image.
+ *   MN_RENDER_SECTOR: a wedge of a disc (the sonar's field of view).  Centre (x0, y0); (x1, y1) is the point of the arc on the sector's middle
+ *     direction, m = (x1 - x0, y1 - y0); half_width_px = q gives the cosine of the half angle, c = q / 16384 - 1 (q above 32768: nothing).  A pixel
+ *     centre with d = centre - (x0, y0) is inside if d.d <= m.m and (d.d == 0 or d.m >= (c sqrt(d.d)) sqrt(m.m)), in world units, with
+ *     d.d = dx dx + dy dy and d.m = dx mx + dy my.  m.m == 0 or not finite (also by overflow): nothing.  The box is the disc's of radius sqrt(m.m).
  *
  * Both calls make ONE launch on `stream`, allocate nothing and never wait on the host.  MN_ERR_INVALID, without a launch: a NULL handle, style,
  * view, pixel or primitive pointer (prims_dev may be NULL when n_prims is 0, which returns MN_OK at once); n_prims < 0; n_images, width or height < 1 or
@@ -394,7 +412,8 @@ int mn_query_rollout(mn_handle *h, const int32_t *env_of_query_dev, int32_t env0
 #define MN_RENDER_MAX_LEVELS 32
 #define MN_RENDER_MAX_LIC_STEPS 64
 #define MN_RENDER_MAX_HALF_WIDTH 8
-enum { MN_RENDER_SEGMENT = 0, MN_RENDER_DISC = 1, MN_RENDER_RING = 2 };
+enum { MN_RENDER_SEGMENT = 0, MN_RENDER_DISC = 1, MN_RENDER_RING = 2, MN_RENDER_RECT = 4, MN_RENDER_MARKER = 5, MN_RENDER_GLYPH = 6,
+       MN_RENDER_SECTOR = 7 };      /* 3 is unassigned and draws nothing */
 typedef struct mn_render_style {
     double v_max;            /* the speed of the top level */
     double hpx;              /* LIC step in pixels */
@@ -419,6 +438,8 @@ int mn_render_worlds(mn_handle *h, const int32_t *env_of_image_dev, int32_t env0
                      const double view[4], const mn_render_style *style, uint32_t *pixels_dev, void *stream);
 int mn_render_draw(uint32_t *pixels_dev, int32_t n_images, int32_t width, int32_t height, const double view[4],
                    const mn_render_prim *prims_dev, int64_t n_prims, void *stream);
+/* The font of MN_RENDER_GLYPH into out [95][7] (host memory, 665 bytes): row byte j of code 32 + k at out[7 k + j].  MN_ERR_INVALID: out is NULL. */
+int mn_render_font(uint8_t *out);
 
 /* Robot pose and counters (robot.py:40-44, marinenav_env.py:70-71).  state[count][6] =
  * x, y, theta, speed, velocity_x, velocity_y (float64).  NULL pointers are skipped. */
