@@ -963,6 +963,43 @@ extern "C" int mn_query_rollout(mn_handle *h, const int32_t *env_of_query_dev, i
     return MN_OK;
 }
 
+// ---- minimum-time-to-goal fields: nothing in the handle is written (mn_time_field.hip) ------------------------------------------------------------
+static bool time_field_grid_ok(int32_t nx, int32_t ny) { return nx >= 1 && ny >= 1 && (int64_t)nx * ny <= MN_TIME_FIELD_MAX_CELLS; }
+
+extern "C" int64_t mn_time_field_workspace_bytes(int32_t nx, int32_t ny, int64_t n_fields) {
+    if (!time_field_grid_ok(nx, ny) || n_fields < 0) return (int64_t)MN_ERR_INVALID;
+    return mn_time_field_planes_bytes(nx, ny, n_fields);
+}
+
+extern "C" int mn_time_field(mn_handle *h, const int32_t *env_of_field_dev, int32_t env0, const double *goal_xy_dev, int64_t n_fields, int32_t nx,
+                             int32_t ny, double speed, double clearance, int32_t max_sweeps, double *T_dev, uint8_t *dir_dev, int32_t *status_dev,
+                             int32_t *sweeps_dev, void *workspace_dev, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!h) return fail(nullptr, MN_ERR_INVALID, "mn_time_field: NULL handle");
+    if (n_fields < 0 || n_fields >= ((int64_t)1 << 31)) return fail(h, MN_ERR_INVALID, "mn_time_field: n_fields is negative or not below 2^31");
+    if (!time_field_grid_ok(nx, ny)) {
+        char b[160];
+        snprintf(b, sizeof(b), "mn_time_field: a grid of %d x %d cells is outside 1 <= nx, ny and nx * ny <= %d", nx, ny, MN_TIME_FIELD_MAX_CELLS);
+        return fail(h, MN_ERR_INVALID, b);
+    }
+    if (!(clearance >= 0.0) || !(clearance - clearance == 0.0)) return fail(h, MN_ERR_INVALID, "mn_time_field: clearance is negative or not finite");
+    if (max_sweeps < 1) return fail(h, MN_ERR_INVALID, "mn_time_field: max_sweeps < 1");
+    if (!env_of_field_dev && (env0 < 0 || env0 >= h->A.n)) {
+        char b[128];
+        snprintf(b, sizeof(b), "mn_time_field: env0 = %d is outside [0, %d) and no env_of_field array is given", env0, h->A.n);
+        return fail(h, MN_ERR_INVALID, b);
+    }
+    if (n_fields > 0 && (!T_dev || !status_dev || !workspace_dev)) return fail(h, MN_ERR_INVALID, "mn_time_field: T_dev, status_dev or workspace_dev is NULL");
+    join_reset(h, s);
+    MN_ON_DEVICE(h);
+    if (n_fields == 0) return MN_OK;
+    if (mn_launch_time_field(h->A, h->P, env_of_field_dev, env0, goal_xy_dev, n_fields, nx, ny, speed, clearance, max_sweeps, T_dev, dir_dev, status_dev,
+                             sweeps_dev, workspace_dev, s) != MN_OK)
+        return fail(h, MN_ERR_HIP, "mn_time_field: raising the kernel's dynamic LDS limit failed");
+    MN_HIP(h, hipGetLastError());
+    return MN_OK;
+}
+
 // ---- pictures: nothing in the handle is written (mn_render.hip) -----------------------------------------------------------------------------------
 static const char *render_canvas_error(const void *pixels_dev, int32_t n_images, int32_t width, int32_t height, const double *view) {
     if (!pixels_dev) return "render: pixels_dev is NULL";

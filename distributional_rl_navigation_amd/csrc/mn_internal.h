@@ -230,6 +230,11 @@ void mn_launch_query_rollout(const MnArrays &A, const MnDev &P, const int32_t *e
                              const int32_t *actions, int n_steps, const int32_t *n_steps_of, int64_t nq, double *state_out, float *obs, double *obs64,
                              double *reward, uint8_t *done, uint8_t *info, int32_t *steps, double *reward_tr, uint8_t *done_tr, uint8_t *info_tr,
                              int32_t *action_tr, double *state_tr, double *traj_tr, hipStream_t s);
+// minimum-time-to-goal fields (mn_time_field.hip): read-only on A; the arguments of mn_time_field, validated.  MN_OK or MN_ERR_HIP
+int64_t mn_time_field_planes_bytes(int nx, int ny, int64_t n_fields);
+int mn_launch_time_field(const MnArrays &A, const MnDev &P, const int32_t *env_of, int env0, const double *goal_xy, int64_t n_fields, int nx, int ny,
+                         double speed, double clearance, int max_sweeps, double *T, uint8_t *dir, int32_t *status, int32_t *sweeps, void *workspace,
+                         hipStream_t s);
 // pictures (mn_render.hip): read-only on A; env_of = NULL: every image shows world env0.  The arguments of mn_render_worlds / mn_render_draw, validated
 void mn_launch_render_worlds(const MnArrays &A, const MnDev &P, const int32_t *env_of, int env0, int n_images, int width, int height, const double view[4],
                              const mn_render_style &style, uint32_t *pixels, hipStream_t s);

@@ -158,3 +158,98 @@ def planner_policy(kind, params):
         raise ValueError(f"planner_policy: kind must be 'APF' or 'BA', got {kind!r}")
     a, w = [float(v) for v in params.a], [float(v) for v in params.w]
     return lambda obs: dict(action=planner_act_batch(obs, kind, a, w))
+
+
+# ---- minimum-time-to-goal fields (VecMarineNavEnv.time_field, C-ABI mn_time_field) -------------------------------------------------------------------
+# offset of stencil direction k, as include/marinenav_hip.h lists them
+TIME_FIELD_DX = (1, 0, -1, 0, 1, -1, -1, 1, 2, 1, -1, -2, -2, -1, 1, 2)
+TIME_FIELD_DY = (0, 1, 0, -1, 1, 1, -1, -1, 1, 2, 2, 1, -1, -2, -2, -1)
+TIME_FIELD_NO_DIR = 255
+
+
+def time_field(env, env_index, nx=128, ny=128, speed=None, clearance=0.0, goal=None, max_sweeps=None):
+    """The minimum-time-to-goal field of world `env_index` on an nx x ny grid (`VecMarineNavEnv.time_field`: one launch).  Returns a dict of device
+    tensors: `T` [ny][nx] float64 (seconds; +inf where the goal cannot be reached), `dir` [ny][nx] uint8 (the stencil direction of the first move,
+    TIME_FIELD_DX / _DY; 255: none), `free` [ny][nx] bool (T finite: the cell is free and the goal reachable from it), `xs` [nx], `ys` [ny] (the
+    cell centres), and `status`, `sweeps` (ints), `hx`, `hy` (floats: the cell size).  A status of _capi.TIME_FIELD_NOT_CONVERGED means max_sweeps
+    (default 4 (nx + ny)) was too small: call again with more."""
+    T, d, status, sweeps = env.time_field(int(env_index), nx, ny, speed=speed, clearance=clearance, max_sweeps=max_sweeps,
+                                          goals=None if goal is None else torch.as_tensor(goal, dtype=torch.float64).reshape(1, 2))
+    return field_dict(T[0], d[0], float(env.params.width), float(env.params.height), int(status[0]), int(sweeps[0]))
+
+
+def field_dict(T, d, width, height, status=0, sweeps=0):
+    """The dict of `time_field` from a field's tensors T, dir [ny][nx] (on any device) and the map's size."""
+    ny, nx = T.shape
+    hx, hy = float(width) / nx, float(height) / ny
+    xs = (torch.arange(nx, dtype=torch.float64, device=T.device) + 0.5) * hx
+    ys = (torch.arange(ny, dtype=torch.float64, device=T.device) + 0.5) * hy
+    return dict(T=T, dir=d, free=torch.isfinite(T), xs=xs, ys=ys, status=status, sweeps=sweeps, hx=hx, hy=hy)
+
+
+def _cells_of(field, xy):
+    """(cell index [Q] int64, inside [Q] bool) of the points xy [Q][2]: cell (i, j) = (floor(x / hx), floor(y / hy)); a point on the map's far edge
+    belongs to the last cell, a point outside the map (or NaN) to none (index 0, inside False)."""
+    T = field["T"]
+    ny, nx = T.shape
+    if not torch.is_tensor(xy):
+        xy = np.asarray(xy, dtype=np.float64)      # (a list would pass through float32)
+    p = torch.as_tensor(xy).to(device=T.device, dtype=torch.float64).reshape(-1, 2)
+    x, y = p[:, 0], p[:, 1]
+    inside = (x >= 0.0) & (x <= nx * field["hx"]) & (y >= 0.0) & (y <= ny * field["hy"])
+    i = torch.floor(torch.where(inside, x, torch.zeros_like(x)) / field["hx"]).long().clamp_(0, nx - 1)
+    j = torch.floor(torch.where(inside, y, torch.zeros_like(y)) / field["hy"]).long().clamp_(0, ny - 1)
+    return torch.where(inside, j * nx + i, torch.zeros_like(i)), inside
+
+
+def time_at(field, xy):
+    """T of the cell that contains each point of xy [Q][2]: float64 [Q] on the field's device, an exact lookup (no interpolation); NaN for a point
+    outside the map."""
+    c, inside = _cells_of(field, xy)
+    t = field["T"].reshape(-1)[c]
+    return torch.where(inside, t, torch.full_like(t, float("nan")))
+
+
+def time_path(field, xy0):
+    """The route the field gives from each start of xy0 [Q][2]: the centres of the cells that following `dir` visits, from the start's own cell to a
+    source.  A bounded loop of torch gathers on the field's device, at most nx ny hops.  Returns (path [Q][L][2] float64, NaN behind each route's
+    end; lengths [Q] int64, the points of each route): a start outside the map, in a blocked cell or in one the goal cannot be reached from has
+    length 0, a start in a source cell length 1.  L is the longest route of the call."""
+    T, d = field["T"], field["dir"]
+    ny, nx = T.shape
+    flat_t, flat_d = T.reshape(-1), d.reshape(-1).long()
+    dx = torch.tensor(TIME_FIELD_DX + (0,), dtype=torch.int64, device=T.device)
+    dy = torch.tensor(TIME_FIELD_DY + (0,), dtype=torch.int64, device=T.device)
+    cur, inside = _cells_of(field, xy0)
+    alive = inside & torch.isfinite(flat_t[cur])
+    lengths = torch.zeros_like(cur)
+    pts = []
+    for _ in range(nx * ny):
+        if not bool(alive.any()):
+            break
+        centre = torch.stack((field["xs"][cur % nx], field["ys"][cur // nx]), dim=-1)
+        pts.append(torch.where(alive[:, None], centre, torch.full_like(centre, float("nan"))))
+        lengths = lengths + alive.long()
+        k = flat_d[cur]
+        alive = alive & (k != TIME_FIELD_NO_DIR)
+        k = torch.where(alive, k, torch.full_like(k, 16))
+        cur = cur + dy[k] * nx + dx[k]
+    path = torch.stack(pts, dim=1) if pts else torch.zeros(cur.shape[0], 0, 2, dtype=torch.float64, device=T.device)
+    return path, lengths
+
+
+def reference_times(env, envs=None, nx=128, ny=128, speed=None, clearance=0.0, max_sweeps=None):
+    """The yardstick of an episode: T at each env's own start, on its own world's field (one launch for all of `envs`; default: every env).  float64
+    [len(envs)] on the device; +inf where the start's cell is blocked on this grid or the goal cannot be reached from it.  A field that did not
+    converge in max_sweeps raises RuntimeError."""
+    from . import _capi
+    idx = np.arange(env.n_envs, dtype=np.int32) if envs is None else np.asarray(_host(envs), dtype=np.int32).reshape(-1)
+    worlds = env.get_worlds()
+    starts = torch.as_tensor(np.array([worlds[int(e)]["start"] for e in idx], dtype=np.float64).reshape(-1, 2), device=env.device)
+    T, _, status, _ = env.time_field(idx, nx, ny, speed=speed, clearance=clearance, max_sweeps=max_sweeps, want_dir=False, want_sweeps=False)
+    if bool((status == _capi.TIME_FIELD_NOT_CONVERGED).any()):
+        raise RuntimeError("reference_times: a field did not converge; raise max_sweeps")
+    hx, hy = float(env.params.width) / int(nx), float(env.params.height) / int(ny)
+    c, inside = _cells_of(dict(T=T[0], hx=hx, hy=hy), starts)      # (a field per start: time_at's lookup, row f in field f)
+    t = T.reshape(len(idx), -1)[torch.arange(len(idx), device=T.device), c]
+    return torch.where(inside, t, torch.full_like(t, float("nan")))

@@ -602,6 +602,41 @@ class VecMarineNavEnv:
             out[k + "_trace"] = v
         return out
 
+    def time_field(self, envs, nx, ny, speed=None, clearance=0.0, goals=None, max_sweeps=None, want_dir=True, want_sweeps=True):
+        """Minimum-time-to-goal fields (C-ABI mn_time_field: one HIP launch, one workgroup per field; float64 on the master tables whatever the env's
+        precision; nothing in the env changes).  `envs`: one world index (int: one field) or an int tensor / array [F], one world per field.  For every
+        cell of the nx x ny grid over the map -- centre ((i + 0.5) width / nx, (j + 0.5) height / ny) -- the least travel time to the goal of a
+        vehicle of constant speed `speed` through the water (default: the parameters' max_speed), carried by the current and kept
+        r + robot_r + `clearance` away from every obstacle's centre, over the 16-direction stencil of include/marinenav_hip.h.  `goals` [F, 2]:
+        another goal per field than the world's own.  `max_sweeps`: default 4 (nx + ny); raise it if a status says TIME_FIELD_NOT_CONVERGED.
+        Returns device tensors (T [F, ny, nx] float64 -- +inf where the goal cannot be reached, NaN for a field whose world index or goal is bad --,
+        dir [F, ny, nx] uint8 -- the stencil direction of the first move, 255 at sources, blocked and unreachable cells --, status [F] int32
+        (_capi.TIME_FIELD_*), sweeps [F] int32); dir / sweeps are None with want_dir / want_sweeps off."""
+        nx, ny = int(nx), int(ny)
+        if isinstance(envs, (int, np.integer)):
+            idx, env0, n = None, int(envs), 1
+        else:
+            idx = torch.as_tensor(envs).to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+            env0, n = 0, idx.shape[0]
+        g = None
+        if goals is not None:
+            g = goals if torch.is_tensor(goals) else torch.from_numpy(np.array(goals, dtype=np.float64))      # (a list would pass through float32)
+            g = g.to(device=self.device, dtype=torch.float64).contiguous()
+            if g.shape != (n, 2):
+                raise ValueError(f"goals must be [{n}, 2] (one goal per field), got {tuple(g.shape)}")
+        nb = int(self.L.mn_time_field_workspace_bytes(nx, ny, n))
+        cells = nx * ny if nb >= 0 else 0      # (a refused grid: the call below says why, and nothing is allocated for it)
+        T = torch.empty(n, ny if cells else 0, nx if cells else 0, dtype=torch.float64, device=self.device)
+        d = torch.empty(T.shape, dtype=torch.uint8, device=self.device) if want_dir else None
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        sweeps = torch.empty(n, dtype=torch.int32, device=self.device) if want_sweeps else None
+        ws = torch.empty(max(nb, 0) // 8, dtype=torch.float64, device=self.device)
+        p = lambda t: _ptr(t) if t is not None and t.numel() else None
+        self._check(self.L.mn_time_field(self.h, p(idx), env0, p(g), n, nx, ny, float(speed) if speed is not None else 0.0, float(clearance),
+                                         int(max_sweeps) if max_sweeps is not None else 4 * (nx + ny), p(T), p(d), p(status), p(sweeps), p(ws),
+                                         self._stream()))
+        return T, d, status, sweeps
+
     # ---- state accessors (tests, checkpoints) ------------------------------------------------
     def get_state(self, first_env=0, count=None):
         cnt = self.n_envs - first_env if count is None else count

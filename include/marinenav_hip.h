@@ -441,6 +441,56 @@ int mn_render_draw(uint32_t *pixels_dev, int32_t n_images, int32_t width, int32_
 /* The font of MN_RENDER_GLYPH into out [95][7] (host memory, 665 bytes): row byte j of code 32 + k at out[7 k + j].  MN_ERR_INVALID: out is NULL. */
 int mn_render_font(uint8_t *out);
 
+/* Minimum-time-to-goal fields (Zermelo navigation on a grid): for every cell of an nx x ny grid over a world the handle holds, the least travel time
+ * to the goal of a vehicle of constant speed s through the water, carried by the current and kept out of the obstacles, and the first move of a path
+ * that attains it.  A query like those above: it reads the float64 master tables only (cores, obstacles, goal, the placed counts) and the parameters,
+ * computes in float64 whatever the handle's precision and writes NOTHING into the handle.  The rules are csrc/mn_time_field_body.h's, a
+ * __host__ __device__ body on top of the query body: every operation is an IEEE float64 add, multiply, divide, square root or comparison
+ * (contraction off), in the order written here, so host and device give the same words.
+ *
+ * Grid.  1 <= nx, ny and nx * ny <= MN_TIME_FIELD_MAX_CELLS (one workgroup's LDS holds the field).  hx = width / nx, hy = height / ny; cell (i, j),
+ *   i = 0..nx-1, j = 0..ny-1, index c = j nx + i, has its centre at x = (i + 0.5) hx, y = (j + 0.5) hy.
+ * Current.  c(i, j) = get_velocity at the centre (the arithmetic of mn_query_velocity).  A centre exactly on a core has a NaN current.
+ * Free cells.  Cell (i, j) is free iff for EVERY placed obstacle sqrt(dx dx + dy dy) > (r + robot_r) + clearance, dx = ox - x, dy = oy - y.
+ * Sources.  A free cell with sqrt(dx dx + dy dy) <= goal_dis, dx = x - gx, dy = y - gy (check_reach_goal); the goal is the world's own or
+ *   goal_xy_dev[field].
+ * Edges.  16 directions, in this order (the order breaks ties):
+ *     k    0  1  2  3    4  5  6  7    8  9 10 11 12 13 14 15
+ *     dx   1  0 -1  0    1 -1 -1  1    2  1 -1 -2 -2 -1  1  2
+ *     dy   0  1  0 -1    1  1 -1 -1    1  2  2  1 -1 -2 -2 -1
+ *   Edge u -> v = u + (dx, dy) exists iff u, v and the two cells the segment crosses are inside the grid and free: a diagonal (dx, dy) crosses
+ *   u + (dx, 0) and u + (0, dy); a knight move (2 sx, sy) crosses u + (sx, 0) and u + (sx, sy); a knight move (sx, 2 sy) crosses u + (0, sy) and
+ *   u + (sx, sy); an axis move crosses none.
+ * Edge time.  s = speed if speed > 0, else the parameters' max_speed.  ex = dx hx, ey = dy hy (dx, dy converted to float64);
+ *   L = sqrt(ex ex + ey ey); ux = ex / L, uy = ey / L; cx = (c_u.x + c_v.x) 0.5, cy = (c_u.y + c_v.y) 0.5; a = cx ux + cy uy;
+ *   disc = (s s - (cx cx + cy cy)) + a a; g = a + sqrt(disc).  The edge is feasible iff disc >= 0.0 && g > 0.0 (a NaN is infeasible); w = L / g.
+ *   An edge that does not exist or is infeasible has w = +inf.
+ * Field.  T(u) = 0 for sources, +inf for blocked cells; otherwise T(u) = min over k of (w_k(u) + T(u + off_k)), the float64 sum as written, +inf
+ *   where no path exists.  Every w exceeds an ulp of every finite T, so w + T > T strictly and the fixed point is unique: what Dijkstra's algorithm
+ *   over the same w with the same float64 w + T settles.  Iteration order, sweep count and work distribution do not show in the result.
+ *   dir(u) = the least k that attains the minimum; 255 for sources, blocked cells and cells with T = +inf.
+ *
+ * mn_time_field: field f is solved in world env_of_field_dev[f] ([n_fields] i32 on the device), or every field in world env0 if that is NULL.
+ *   goal_xy_dev [n_fields][2] f64 or NULL (the world's own goal).  Outputs: T_dev [n_fields][ny][nx] f64; dir_dev [n_fields][ny][nx] u8 or NULL;
+ *   status_dev [n_fields] i32; sweeps_dev [n_fields] i32 (the relaxation sweeps that ran) or NULL.  Status: MN_TIME_FIELD_OK; _NOT_CONVERGED: the
+ *   max_sweeps-th sweep still lowered a cell -- T and dir are then unspecified upper bounds, call again with more; _NO_SOURCE: no free cell within
+ *   goal_dis of the goal (T is +inf everywhere, dir 255); _BAD_ENV: the field's world index is outside [0, n_envs), or its goal is not finite: no
+ *   table is read, T is NaN, dir 255, sweeps 0, and the other fields are unaffected (the queries' poison rule; the call returns MN_OK).
+ *   workspace_dev: mn_time_field_workspace_bytes(nx, ny, n_fields) bytes, 8-byte aligned, contents arbitrary before and after ([n_fields][18][ny nx]
+ *   f64: the 16 edge-time planes and the currents); one workspace per concurrently running call.
+ * ONE launch on `stream` (one workgroup per field), no allocation, no host synchronisation; a pending mn_reset_done_async is joined on `stream`.
+ * n_fields = 0 returns MN_OK without a launch.  MN_ERR_INVALID (message in mn_last_error), without a launch: a NULL handle; n_fields < 0 or >= 2^31;
+ * nx or ny < 1 or nx * ny > MN_TIME_FIELD_MAX_CELLS; clearance < 0 or not finite; max_sweeps < 1; env0 outside [0, n_envs) without an index array;
+ * and with n_fields > 0 a NULL T_dev, status_dev or workspace_dev.  mn_time_field_workspace_bytes returns MN_ERR_INVALID for a grid outside the
+ * limit or n_fields < 0. */
+#define MN_TIME_FIELD_MAX_CELLS 16384
+#define MN_TIME_FIELD_NO_DIR 255
+enum { MN_TIME_FIELD_OK = 0, MN_TIME_FIELD_NOT_CONVERGED = 1, MN_TIME_FIELD_NO_SOURCE = 2, MN_TIME_FIELD_BAD_ENV = 3 };
+int64_t mn_time_field_workspace_bytes(int32_t nx, int32_t ny, int64_t n_fields);
+int mn_time_field(mn_handle *h, const int32_t *env_of_field_dev, int32_t env0, const double *goal_xy_dev, int64_t n_fields, int32_t nx, int32_t ny,
+                  double speed, double clearance, int32_t max_sweeps, double *T_dev, uint8_t *dir_dev, int32_t *status_dev, int32_t *sweeps_dev,
+                  void *workspace_dev, void *stream);
+
 /* Robot pose and counters (robot.py:40-44, marinenav_env.py:70-71).  state[count][6] =
  * x, y, theta, speed, velocity_x, velocity_y (float64).  NULL pointers are skipped. */
 int mn_get_state(mn_handle *h, int32_t first_env, int32_t count, double *state, int32_t *episode_timesteps,
