@@ -590,6 +590,7 @@ extern "C" int mn_rollout_dqn_groups(mn_handle *h, const float *images_dev, int6
 
 extern "C" int mn_planner_act(const float *obs_dev, int32_t n, int32_t policy, const double *a, const double *w, int32_t *actions_dev, void *stream) {
     if (!obs_dev || !actions_dev || !a || !w || n <= 0 || (policy != MN_POLICY_APF && policy != MN_POLICY_BA)) return MN_ERR_INVALID;
+    if ((uintptr_t)obs_dev % 8 != 0 || (uintptr_t)actions_dev % 4 != 0) return MN_ERR_INVALID;      // the kernel loads the rows as float2
     mn_launch_planner_act(obs_dev, n, policy, a, w, actions_dev, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
 }

@@ -6,6 +6,8 @@
 // call, no loops over python objects; used by mn_planner_act (one launch per policy step for a whole vector of observations) and by the
 // episode rollout kernel (mn_rollout.hip), where the policy runs on the observation the step just produced, in the same launch.
 // The observation arrives as the float32 row the step kernels write (what the batched planners of planners.py are fed as well).
+// The functions are __host__ __device__: tests/planners_host.hip compiles the same text for the CPU, where it is held to the reference's
+// recorded actions branch by branch (golden G19).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -19,7 +21,7 @@ struct MnPlanTabs {
 
 // BA.py:157-162 / APF.py:55-59.  The arguments are differences of two atan2 values or one +- a margin, i.e. inside (-3 pi, 3 pi): two
 // conditional shifts are the reference's while loops, and values already in range pass through unchanged
-__device__ __forceinline__ double mn_wrap_pi(double a) {
+__host__ __device__ __forceinline__ double mn_wrap_pi(double a) {
     const double PI = 3.141592653589793;
 #pragma unroll
     for (int i = 0; i < 2; ++i) a = a < -PI ? a + 2.0 * PI : (a >= PI ? a - 2.0 * PI : a);
@@ -27,7 +29,7 @@ __device__ __forceinline__ double mn_wrap_pi(double a) {
 }
 
 // index of the first minimum of |t[k] - x| over the three table entries (np.argmin)
-__device__ __forceinline__ int mn_nearest3(const double (&t)[3], double x) {
+__host__ __device__ __forceinline__ int mn_nearest3(const double (&t)[3], double x) {
     const double d0 = fabs(t[0] - x), d1 = fabs(t[1] - x), d2 = fabs(t[2] - x);
     int k = 0;
     double best = d0;
@@ -35,11 +37,11 @@ __device__ __forceinline__ int mn_nearest3(const double (&t)[3], double x) {
     if (d2 < best) { k = 2; }
     return k;
 }
-__device__ __forceinline__ int mn_argmax3(const double (&t)[3]) { int k = 0; if (t[1] > t[k]) k = 1; if (t[2] > t[k]) k = 2; return k; }
-__device__ __forceinline__ int mn_argmin3(const double (&t)[3]) { int k = 0; if (t[1] < t[k]) k = 1; if (t[2] < t[k]) k = 2; return k; }
+__host__ __device__ __forceinline__ int mn_argmax3(const double (&t)[3]) { int k = 0; if (t[1] > t[k]) k = 1; if (t[2] > t[k]) k = 2; return k; }
+__host__ __device__ __forceinline__ int mn_argmin3(const double (&t)[3]) { int k = 0; if (t[1] < t[k]) k = 1; if (t[2] < t[k]) k = 2; return k; }
 
 // APF_agent.act (APF.py:17-78)
-__device__ __forceinline__ int mn_apf_act(const float *__restrict__ o, const MnPlanTabs &T) {
+__host__ __device__ __forceinline__ int mn_apf_act(const float *__restrict__ o, const MnPlanTabs &T) {
     const double k_att = 50.0, k_rep = 500.0, mass = 500.0, d0 = 10.0, min_vel = 1.0;      // APF.py:7-12 (n = 2)
     const double vx = o[0], vy = o[1], gx = o[2], gy = o[3];
     const double d_goal = sqrt(gx * gx + gy * gy);
@@ -68,7 +70,7 @@ __device__ __forceinline__ int mn_apf_act(const float *__restrict__ o, const MnP
 }
 
 // BA_agent.act (BA.py:14-155)
-__device__ __forceinline__ int mn_ba_act(const float *__restrict__ o, const MnPlanTabs &T) {
+__host__ __device__ __forceinline__ int mn_ba_act(const float *__restrict__ o, const MnPlanTabs &T) {
     const double PI = 3.141592653589793;
     const double follow_dist = 5.0, detect_angle = 2.0 * PI / 3.0, margin = 10.0 * PI / 180.0, min_vel = 1.0;      // BA.py:7-12
     const double vx = o[0], vy = o[1], gx = o[2], gy = o[3];
@@ -138,6 +140,6 @@ __device__ __forceinline__ int mn_ba_act(const float *__restrict__ o, const MnPl
     return a_idx * 3 + w_idx;
 }
 
-__device__ __forceinline__ int mn_policy_act(int policy, const float *__restrict__ o, const MnPlanTabs &T) {
+__host__ __device__ __forceinline__ int mn_policy_act(int policy, const float *__restrict__ o, const MnPlanTabs &T) {
     return policy == MN_POLICY_APF ? mn_apf_act(o, T) : mn_ba_act(o, T);
 }

@@ -19,6 +19,8 @@ def planner_act_batch(obs, kind, a, w):
     from . import _capi
     assert obs.is_cuda and obs.dtype == torch.float32
     obs = obs.contiguous()
+    if obs.data_ptr() % 8:      # the kernel loads rows as float2: a view at an odd float offset is copied, not passed on (mn_planner_act refuses it)
+        obs = obs.clone()
     n = obs.shape[0]
     out = torch.empty(n, dtype=torch.int32, device=obs.device)
     if n == 0:

@@ -184,7 +184,8 @@ int mn_rollout(mn_handle *h, int32_t n_steps, const int32_t *actions_dev, uint64
 int mn_rollout_policy(mn_handle *h, int32_t n_steps, int32_t policy, float *obs_dev, float *obs_trace_dev, float *reward_trace_dev,
                       uint8_t *done_trace_dev, uint8_t *info_trace_dev, int32_t *action_trace_dev, void *stream);
 /* One policy step of the same device functions for n observation rows [n][26] f32 -> actions [n] i32; a[3], w[3]: HOST arrays, the
- * robot's acceleration / angular-velocity tables (robot.py:35-36). */
+ * robot's acceleration / angular-velocity tables (robot.py:35-36).  MN_ERR_INVALID, without a launch: a NULL argument, n <= 0, an unknown
+ * policy, an obs_dev that is not 8-byte aligned (the rows are loaded as float2) or an actions_dev that is not 4-byte aligned. */
 int mn_planner_act(const float *obs_dev, int32_t n, int32_t policy, const double *a, const double *w, int32_t *actions_dev, void *stream);
 /* The action draws of mn_rollout for one step: actions_dev[i] = action of env (first_env_index + i) at step step_index. */
 int mn_random_actions(uint64_t action_seed, uint64_t step_index, uint64_t first_env_index, int32_t n, int32_t *actions_dev,
