@@ -457,7 +457,14 @@ class IQNAgent(ReferenceLoopMixin):
         """Batched adjust_cvar on device: states [n, 26] -> cvar [n]."""
         p = states[:, 4:].view(states.shape[0], -1, 2)
         skip = (p[:, :, 0].abs() < 1e-3) & (p[:, :, 1].abs() < 1e-3)
-        d = torch.linalg.vector_norm(p, dim=2).masked_fill(skip, float("inf"))
+        if states.is_cuda:
+            d = torch.linalg.vector_norm(p, dim=2)
+        else:
+            # on the CPU vector_norm rounds x^2 + y^2 once; written out, the norm is the device's (and adjust_cvar_row's, csrc/mn_rollout_iqn_body.h):
+            # the two squares rounded separately, their sum, a correctly rounded root
+            sq = p * p
+            d = (sq[:, :, 0] + sq[:, :, 1]).sqrt()
+        d = d.masked_fill(skip, float("inf"))
         closest = d.min(dim=1).values
         return torch.where(closest < 10.0, closest / 10.0, torch.ones_like(closest))
 
