@@ -159,19 +159,19 @@ MNQ_HD unsigned mnq_observe(const World &w, int no, double gx, double gy, const 
     //    so leaving it out of the scan changes nothing.  The 0.05 m margin covers the slope form's own error (1e-7 m at the
     //    steepest slope outside the snap window).
     unsigned reach_mask = 0;
-    double bd = (double)INFINITY, br = 0.0;
+    // (nearest by the SQUARED distance, as the KD-tree and MnLane::step find it: two d2 one ulp apart can share a rounded root)
+    double bd2 = (double)INFINITY, br = 0.0;
     const double reach0 = P.sonar_range + 0.05;
     no = no < MN_MAX_OBS ? no : MN_MAX_OBS;
     for (int k = 0; k < no; ++k) {
         double ox, oy, orad;
         w.obstacle(k, ox, oy, orad);
         const double dx = ox - x, dy = oy - y, d2 = dx * dx + dy * dy, reach = reach0 + orad;
-        const double d = sqrt(d2);
-        if (d < bd) { bd = d; br = orad; }
+        if (d2 < bd2) { bd2 = d2; br = orad; }
         if (d2 <= reach * reach) reach_mask |= 1u << k;
     }
     unsigned flags = 0;
-    if (no > 0 && bd <= br + P.robot_r) flags |= MN_QUERY_FLAG_COLLISION;
+    if (no > 0 && sqrt(bd2) <= br + P.robot_r) flags |= MN_QUERY_FLAG_COLLISION;
     if ((x < 0.0 || x > P.width) || (y < 0.0 || y > P.height)) flags |= MN_QUERY_FLAG_OUTSIDE;
     const double gdx = x - gx, gdy = y - gy;
     if (sqrt(gdx * gdx + gdy * gdy) <= P.goal_dis) flags |= MN_QUERY_FLAG_GOAL;      // check_reach_goal (:338-342)

@@ -29,17 +29,17 @@ MNQ_HD bool mnq_state_ok(const MnqRobot &r) {
 // with the NEAREST CENTRE is tested, first of equals; out_of_boundary; check_reach_goal :338-342), operation for operation.
 template <class World>
 MNQ_HD unsigned mnq_flags(const World &w, int no, double gx, double gy, const MnDev &P, double x, double y) {
-    double bd = (double)INFINITY, br = 0.0;
+    double bd2 = (double)INFINITY, br = 0.0;      // (nearest by the SQUARED distance: see mnq_observe)
     no = no < MN_MAX_OBS ? no : MN_MAX_OBS;
     for (int k = 0; k < no; ++k) {
         double ox, oy, orad;
         w.obstacle(k, ox, oy, orad);
         const double dx = ox - x, dy = oy - y;
-        const double d = sqrt(dx * dx + dy * dy);
-        if (d < bd) { bd = d; br = orad; }
+        const double d2 = dx * dx + dy * dy;
+        if (d2 < bd2) { bd2 = d2; br = orad; }
     }
     unsigned flags = 0;
-    if (no > 0 && bd <= br + P.robot_r) flags |= MN_QUERY_FLAG_COLLISION;
+    if (no > 0 && sqrt(bd2) <= br + P.robot_r) flags |= MN_QUERY_FLAG_COLLISION;
     if ((x < 0.0 || x > P.width) || (y < 0.0 || y > P.height)) flags |= MN_QUERY_FLAG_OUTSIDE;
     const double gdx = x - gx, gdy = y - gy;
     if (sqrt(gdx * gdx + gdy * gdy) <= P.goal_dis) flags |= MN_QUERY_FLAG_GOAL;

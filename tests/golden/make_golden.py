@@ -34,6 +34,8 @@ Outputs (all small, committed):
                         behind the robot, span edges, vertical / near-vertical / sloped walls near and far, two-return tangents, APF's d0,
                         extremes and near-cancellation, hand-written exact rows) under five (a, w) tables, with `stable` = the action
                         survives 8 copies of the row perturbed by 1e-9 relative
+  g20_ladder_edges.npz  the case table of tests/ladder_edges.py (stationary robots on the termination ladder's thresholds, ties, coinciding rungs)
+                        through MarineNavEnv.step; written without time stamps, so it regenerates byte for byte
   (g10 / g11: make_golden_dqn.py)
 """
 import contextlib
@@ -1301,8 +1303,66 @@ def g18_sonar_params_edge():
         vel=np.array([c["vel"] for c in cases]), obs=obs, obs_ld=obs_ld)
 
 
+# ---- g20: the termination ladder on its thresholds, ties and coinciding rungs ---------------------------------------------------
+def _savez_fixed(path, arrays):
+    """np.savez_compressed without the clock: every member stamped 1980-01-01, members in the order given, so the same arrays give the same bytes."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue(), compresslevel=9)
+
+
+def g20_ladder_edges():
+    """tests/ladder_edges.py's case table through MarineNavEnv.step: obstacle list + KD-tree, goal, pose, episode_timesteps and the set's parameters
+    written into a fresh env, one step.  `ref_ok`: the reference can express the case (its ladder holds 1000 for the episode limit; the other rows stay
+    zero).  On a TIE case the nearest obstacle is whatever scipy's KD-tree answers: kept apart (`tie_ref_nearest`, `tie_ref_info`), for the record only."""
+    import scipy.spatial
+    import ladder_edges as LE
+    cases = LE.table()
+    inp, ok = LE.arrays(), LE.expressible()
+    n = len(cases)
+    ref = dict(ref_obs=np.zeros((n, 26)), ref_reward=np.zeros(n), ref_done=np.zeros(n, bool), ref_info=np.zeros(n, np.uint8), ref_state=np.zeros((n, 6)),
+               ref_ep_t=np.zeros(n, np.int64), ref_tot_t=np.zeros(n, np.int64), tie_ref_nearest=np.full(n, -1, np.int32), tie_ref_info=np.zeros(n, np.uint8))
+    for i, c in enumerate(cases):
+        if not ok[i]:
+            continue
+        env = MarineNavEnv(seed=0)
+        apply_set(env, LE.pset_spec(c.pset))
+        env.cores.clear()
+        env.obstacles.clear()
+        for (ox, oy, r) in c.obstacles:
+            env.obstacles.append(Obstacle(ox, oy, r))
+        if c.obstacles:
+            env.obs_centers = scipy.spatial.KDTree(np.array([[o[0], o[1]] for o in c.obstacles]))
+        env.goal = np.array(c.goal)
+        env.total_timesteps = c.tot_t
+        ob, r, d, info, sout = _eval_step(env, c.pose, c.action, c.ep_t)
+        if c.tie:
+            ref["tie_ref_nearest"][i] = env.obs_centers.query(np.array([env.robot.x, env.robot.y]))[1]
+            ref["tie_ref_info"][i] = info
+        ref["ref_obs"][i], ref["ref_reward"][i], ref["ref_done"][i], ref["ref_info"][i], ref["ref_state"][i] = ob, r, d, info, sout
+        ref["ref_ep_t"][i], ref["ref_tot_t"][i] = env.episode_timesteps, env.total_timesteps
+    exp = LE.expected()
+    tie = inp["tie"]
+    agree = ok & ~tie & (ref["ref_info"] == exp["info"])
+    print(f"  g20: {n} cases, {int(ok.sum())} the reference can express; info equal to exact arithmetic on {int(agree.sum())} of {int((ok & ~tie).sum())} "
+          f"untied ones; KD-tree = first in generation order on {int((ref['tie_ref_info'][tie] == exp['info'][tie]).sum())} of {int(tie.sum())} ties")
+    out = dict(inp)
+    out["ref_ok"] = ok
+    out["set_names"] = np.array(LE.PSET_NAMES)
+    out.update(ref)
+    _savez_fixed(os.path.join(OUT, "g20_ladder_edges.npz"), out)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20"]
+    if "g20" in which:
+        g20_ladder_edges()
     if "g16" in which:
         g16_reset_params()
     if "g17" in which:
