@@ -23,6 +23,7 @@ struct mn_handle {
     int32_t *list_scratch = nullptr;
     double *peek_scratch = nullptr;
     double *obs64_buf = nullptr, *rew64_buf = nullptr;      // mn_enable_obs64: A.obs64 / A.rew64 point here while enabled
+    MnArrays *A_mem = nullptr;                              // device copy of A (sync_arrays): the preparation launch's reset blocks read their store pointers from it
     double *traj_trace = nullptr;                           // mn_set_trajectory_trace: the caller's [traj_trace_steps][n][N][2] buffer, until the next episode launch takes it
     int32_t traj_trace_steps = 0, traj_trace_sub = 0;
     int device = -1;      // HIP device the handle's memory lives on (the caller's current device at mn_create)
@@ -208,6 +209,16 @@ static int dev_alloc(mn_handle *h, T **out, size_t count, bool zero = true) {
     return MN_OK;
 }
 
+// h->A as the device sees it (MnOwedReset::A_mem; mn_reset_env's TAIL_MEM): rewritten wherever a pointer of A changes.  The callers have synchronised the device.
+static int sync_arrays(mn_handle *h) {
+    if (!h->A_mem) {
+        const int rc = dev_alloc(h, &h->A_mem, 1, false);
+        if (rc) return rc;
+    }
+    MN_HIP(h, hipMemcpy(h->A_mem, &h->A, sizeof(MnArrays), hipMemcpyHostToDevice));
+    return MN_OK;
+}
+
 extern "C" int mn_destroy(mn_handle *h) {
     if (!h) return MN_ERR_INVALID;
     int cur = -1;
@@ -280,6 +291,7 @@ extern "C" int mn_create(int32_t n_envs, const mn_params *p, mn_handle **out) {
         hipError_t e = hipDeviceSynchronize();
         if (e != hipSuccess) { g_create_err = hipGetErrorString(e); mn_destroy(h); return MN_ERR_HIP; }
     }
+    if ((rc = sync_arrays(h)) != MN_OK) { g_create_err = h->err; mn_destroy(h); return rc; }
     *out = h;
     return MN_OK;
 }
@@ -732,7 +744,7 @@ bool mn_owed_reset_take(mn_handle *h, hipStream_t s, MnOwedReset *out) {
     if (s != h->owed_stream) (void)hipStreamSynchronize(h->owed_stream);
     // (inside a profiling window the launch that runs the reset is timed as the handle's reset launch of this step, as mn_reset_done's is)
     const bool prof = h->prof_reset_n < h->prof_max;
-    *out = MnOwedReset{&h->A, &h->P, h->params.precision, h->A.queue_count + h->last_parity * MN_QWORDS, h->A.queue, h->owed_obs, h->peak_dev, h->seen_dev,
+    *out = MnOwedReset{&h->A, h->A_mem, &h->P, h->params.precision, h->A.queue_count + h->last_parity * MN_QWORDS, h->A.queue, h->owed_obs, h->peak_dev, h->seen_dev,
                        mn_prep_reset_blocks(*h->seen_host, h->A.n), prof ? h->ev_reset[2 * h->prof_reset_n] : nullptr,
                        prof ? h->ev_reset[2 * h->prof_reset_n + 1] : nullptr};
     if (prof) h->prof_reset_n++;
@@ -1244,14 +1256,14 @@ extern "C" int mn_enable_obs64(mn_handle *h, int32_t on) {
     MN_ON_DEVICE(h);
     if (h->params.precision != MN_PRECISION_F64) return fail(h, MN_ERR_INVALID, "float64 observation copies exist only with MN_PRECISION_F64");
     MN_HIP(h, hipDeviceSynchronize());
-    if (!on) { h->A.obs64 = nullptr; h->A.rew64 = nullptr; return MN_OK; }      // the buffers stay owned by the handle
+    if (!on) { h->A.obs64 = nullptr; h->A.rew64 = nullptr; return sync_arrays(h); }      // the buffers stay owned by the handle
     if (!h->obs64_buf) {
         int rc = dev_alloc(h, &h->obs64_buf, (size_t)h->A.npad * MN_OBS_DIM);
         if (rc == MN_OK) rc = dev_alloc(h, &h->rew64_buf, (size_t)h->A.npad);
         if (rc) return rc;
     }
     h->A.obs64 = h->obs64_buf; h->A.rew64 = h->rew64_buf;
-    return MN_OK;
+    return sync_arrays(h);
 }
 
 extern "C" int mn_enable_trajectory(mn_handle *h, int32_t max_substeps) {
@@ -1263,7 +1275,7 @@ extern "C" int mn_enable_trajectory(mn_handle *h, int32_t max_substeps) {
     int rc = dev_alloc(h, &h->A.traj, (size_t)h->A.npad * max_substeps * 2);   // an earlier, smaller buffer stays owned by the handle
     if (rc) return rc;
     h->A.traj_n = max_substeps;
-    return MN_OK;
+    return sync_arrays(h);
 }
 
 extern "C" int mn_get_trajectory(mn_handle *h, int32_t first, int32_t count, int32_t n_substeps, double *out) {

@@ -187,6 +187,7 @@ void mn_launch_reset(const MnArrays &A, const MnDev &P, int precision, const uin
 #define MN_PREP_RESET_MAX_BLOCKS 8192
 struct MnOwedReset {
     const MnArrays *A;
+    const MnArrays *A_mem;            // the handle's DEVICE copy of *A (mn_reset_env's TAIL_MEM)
     const MnDev *P;
     int precision;
     const uint32_t *count_dev;

@@ -8,12 +8,13 @@
 // No side stream, no events, no `ready` words; the blocks of the launch are independent of each other and everything behind it is ordered by the stream.
 //
 //   blocks [0, R)                    one reset wavefront each, queue-driven exactly as mn_reset_kernel with the sharded done-queue (MnDoneQueue, mn_note_count,
-//                                    mn_reset_env<M, PARITY, MtInLds>, ready = NULL); first in the grid, so the long chains start first
+//                                    mn_reset_env<M, PARITY, MtDoubles> in its short-chain form, ready = NULL); first in the grid, so the long chains start first.
+//                                    The array pointers its stores need come from the handle's device copy of MnArrays (A_mem: mn_reset_env's TAIL_MEM)
 //   blocks [R, R + pack)             the weight image when it is stale: one 32-bit word per thread (sp::pack_word, as iqn_split_prep_kernel)
 //   blocks [R + pack, gridDim.x)     draw_block<ROWS, 64>: the call's taus and exploration uniforms, with `rows` the exploring rows' actions and the list of the others
 // The workgroup is ONE wavefront (the reset body's __syncthreads() are wave barriers), so the pack and draw blocks are 64 threads wide; the draws are
-// counter-based and do not depend on the block shape.  Those blocks inherit the reset body's register and LDS allocation (3 136 B; 171 registers with
-// float64 env kernels, 131 mixed: a SIMD holds two or three of them), which costs an otherwise empty chip nothing; no scratch (tests/test_reset_in_prep_cpu.py).
+// counter-based and do not depend on the block shape.  Those blocks inherit the reset body's register and LDS allocation (3 136 B; ~125 registers in both
+// precisions: a SIMD holds four of them), which costs an otherwise empty chip nothing; no scratch (tests/test_reset_in_prep_cpu.py, tests/test_reset_chain_cpu.py).
 //
 // Both roundings in one file, as mn_rollout_iqn.o: built with -ffp-contract=fast-honor-pragmas; the reset body under `#pragma clang fp contract(off)` is
 // mn_reset.o's code (world generation stays bit-identical to numpy), the pack and the draws are iqn_act.o's (contraction allowed).
@@ -51,14 +52,14 @@ struct PrepArgs {      // what sp::iqn_split_prep_kernel takes
 
 template <typename M, bool PARITY>
 __global__ __launch_bounds__(MN_WAVE) void mn_prep_reset_kernel(MnArrays A, MnDev P, const uint32_t *__restrict__ count_dev, const int32_t *__restrict__ list,
-                                                                float *__restrict__ obs_out, const MnSeen seen, int reset_blocks, PrepArgs a) {
-    __shared__ MtLds S;
+                                                                float *__restrict__ obs_out, const MnSeen seen, int reset_blocks, const MnArrays *A_mem, PrepArgs a) {
+    __shared__ MtDblLds S;
     __shared__ WorldLds W;
     if ((int)blockIdx.x < reset_blocks) {
         MnDoneQueue Q;
         const uint32_t count = Q.open(count_dev);
         mn_note_count(seen, count);      // (block 0 is a reset block: reset_blocks >= 1)
-        for (uint32_t qi = blockIdx.x; qi < count; qi += (uint32_t)reset_blocks) mn_reset_env<M, PARITY>(A, P, S, W, Q.at(list, A.qcap, qi), 0, obs_out);
+        for (uint32_t qi = blockIdx.x; qi < count; qi += (uint32_t)reset_blocks) mn_reset_env<M, PARITY, MtDoubles, true, true>(A, P, S, W, Q.at(list, A.qcap, qi), 0, obs_out, nullptr, 0u, A_mem);
         return;
     }
     const int b = (int)blockIdx.x - reset_blocks;
@@ -99,8 +100,8 @@ void mn_launch_prep_reset(const MnOwedReset &o, const MnPrepLaunch &p, hipStream
     const dim3 grid((unsigned)(o.blocks + a.pack_blocks + draw));
     if (o.ev_begin) (void)hipEventRecord(o.ev_begin, s);
     if (o.precision == MN_PRECISION_F64)
-        hipLaunchKernelGGL((mn_prep_reset_kernel<double, true>), grid, dim3(MN_WAVE), 0, s, *o.A, *o.P, o.count_dev, o.list, o.obs, seen, o.blocks, a);
+        hipLaunchKernelGGL((mn_prep_reset_kernel<double, true>), grid, dim3(MN_WAVE), 0, s, *o.A, *o.P, o.count_dev, o.list, o.obs, seen, o.blocks, o.A_mem, a);
     else
-        hipLaunchKernelGGL((mn_prep_reset_kernel<float, false>), grid, dim3(MN_WAVE), 0, s, *o.A, *o.P, o.count_dev, o.list, o.obs, seen, o.blocks, a);
+        hipLaunchKernelGGL((mn_prep_reset_kernel<float, false>), grid, dim3(MN_WAVE), 0, s, *o.A, *o.P, o.count_dev, o.list, o.obs, seen, o.blocks, o.A_mem, a);
     if (o.ev_end) (void)hipEventRecord(o.ev_end, s);
 }

@@ -1,6 +1,11 @@
 // mn_reset.hip -- world generation / episode reset kernel for gfx950 (MI355X): one wavefront per finished environment
 // (mn_reset_env, mn_reset_body.h), env indices pulled from the done-queue the step kernel filled -- plus the small
 // kernels around the RNG streams (seeding, mask -> queue, peek).
+#ifdef MN_ABLATION
+// s_memtime ticks per phase of the reset wavefront of workgroup 0 (MN_RTICK in mn_reset_body.h), slot 7 the number of resets stamped: ablation build only
+__device__ unsigned long long g_reset_phase[8];
+#define MN_RESET_PHASE_VAR g_reset_phase
+#endif
 #include "mn_reset_body.h"
 #include "mn_done_queue.h"
 
@@ -14,13 +19,13 @@ template <typename M, bool PARITY>
 __global__ __launch_bounds__(MN_WAVE) void mn_reset_kernel(MnArrays A, MnDev P, const uint32_t *__restrict__ count_dev,
                                                            uint32_t count_host, const int32_t *__restrict__ list, int mode,
                                                            float *__restrict__ obs_out, const MnSeen seen, int qcap) {
-    __shared__ MtLds S;
+    __shared__ MtDblLds S;
     __shared__ WorldLds W;
     MnDoneQueue Q;
     const uint32_t count = qcap ? Q.open(count_dev) : (count_dev ? *count_dev : count_host);      // qcap != 0: the sharded done-queue
     mn_note_count(seen, count);
     for (uint32_t qi = blockIdx.x; qi < count; qi += gridDim.x)
-        mn_reset_env<M, PARITY>(A, P, S, W, qcap ? Q.at(list, qcap, qi) : (list ? list[qi] : (int)qi), mode, obs_out);
+        mn_reset_env<M, PARITY, MtDoubles>(A, P, S, W, qcap ? Q.at(list, qcap, qi) : (list ? list[qi] : (int)qi), mode, obs_out);
 }
 
 // The same body for mn_reset_done_async: it runs on the handle's side stream UNDER the act kernel of the next vector step, whose 512-thread
@@ -132,3 +137,14 @@ void mn_launch_mask_to_queue(const MnArrays &A, const uint8_t *mask, uint32_t *c
 void mn_launch_peek(const MnArrays &A, int first, int count, double *out_dev, hipStream_t s) {
     hipLaunchKernelGGL(mn_peek_kernel, dim3((count + 255) / 256), dim3(256), 0, s, A, first, count, out_dev);
 }
+
+#ifdef MN_ABLATION
+extern "C" int mn_debug_reset_phases(unsigned long long *out_host, int reset) {
+    if (hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_reset_phase), sizeof(unsigned long long) * 8) != hipSuccess) return MN_ERR_HIP;
+    if (reset) {
+        const unsigned long long z[8] = {0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_reset_phase), z, sizeof(z)) != hipSuccess) return MN_ERR_HIP;
+    }
+    return MN_OK;
+}
+#endif
