@@ -21,6 +21,7 @@ RENDER_MAX_LEVELS, RENDER_MAX_LIC_STEPS, RENDER_MAX_HALF_WIDTH = 32, 64, 8      
 RENDER_SEGMENT, RENDER_DISC, RENDER_RING = 0, 1, 2
 TIME_FIELD_MAX_CELLS, TIME_FIELD_NO_DIR = 16384, 255      # mn_time_field
 TIME_FIELD_OK, TIME_FIELD_NOT_CONVERGED, TIME_FIELD_NO_SOURCE, TIME_FIELD_BAD_ENV = 0, 1, 2, 3
+PILOT_MAX_HORIZON, PILOT_FLAG_BAD_FIELD = 16, 32      # mn_pilot_act / mn_rollout_pilot
 RENDER_RECT, RENDER_MARKER, RENDER_GLYPH, RENDER_SECTOR = 4, 5, 6, 7      # (3 is unassigned)
 RENDER_MARKER_SQUARE, RENDER_MARKER_PLUS, RENDER_MARKER_CROSS = 0, 1, 2
 INFO_STRINGS = ("normal", "out of boundary", "too long episode", "collision", "reach goal")
@@ -144,6 +145,8 @@ SIGNATURES = [
     ("mn_render_font", C.c_int, [_vp]),
     ("mn_time_field_workspace_bytes", _i64, [_i32, _i32, _i64]),
     ("mn_time_field", C.c_int, [_vp, _vp, _i32, _vp, _i64, _i32, _i32, C.c_double, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("mn_pilot_act", C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("mn_rollout_pilot", C.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mn_get_state", C.c_int, [_vp, _i32, _i32, _pd, _pi32, _pi64]),
     ("mn_set_state", C.c_int, [_vp, _i32, _i32, _pd, _pi32, _pi64]),
     ("mn_state_bytes", _i64, [_vp]),

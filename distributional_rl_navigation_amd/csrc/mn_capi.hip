@@ -1013,6 +1013,62 @@ extern "C" int mn_time_field(mn_handle *h, const int32_t *env_of_field_dev, int3
     return MN_OK;
 }
 
+// ---- the field pilot (mn_pilot.hip): mn_pilot_act is a query, mn_rollout_pilot an episode entry point --------------------------------------------
+static int pilot_args_ok(mn_handle *h, const char *who, const double *T_dev, int64_t n_fields, int32_t nx, int32_t ny, int32_t horizon) {
+    char b[192];
+    if (!T_dev) { snprintf(b, sizeof(b), "%s: T_dev is NULL", who); return fail(h, MN_ERR_INVALID, b); }
+    if (n_fields < 1 || n_fields >= ((int64_t)1 << 31)) { snprintf(b, sizeof(b), "%s: n_fields is below 1 or not below 2^31", who); return fail(h, MN_ERR_INVALID, b); }
+    if (!time_field_grid_ok(nx, ny)) {
+        snprintf(b, sizeof(b), "%s: a grid of %d x %d cells is outside 1 <= nx, ny and nx * ny <= %d", who, nx, ny, MN_TIME_FIELD_MAX_CELLS);
+        return fail(h, MN_ERR_INVALID, b);
+    }
+    if (horizon < 1 || horizon > MN_PILOT_MAX_HORIZON) {
+        snprintf(b, sizeof(b), "%s: horizon = %d is outside [1, %d]", who, horizon, MN_PILOT_MAX_HORIZON);
+        return fail(h, MN_ERR_INVALID, b);
+    }
+    return MN_OK;
+}
+
+extern "C" int mn_pilot_act(mn_handle *h, const int32_t *env_of_query_dev, int32_t env0, const double *state_dev, const int32_t *episode_timesteps_dev,
+                            const double *T_dev, const int32_t *field_of_query_dev, int64_t n_fields, int32_t nx, int32_t ny, int32_t horizon,
+                            int64_t n_queries, int32_t *actions_dev, double *scores_dev, int32_t *steps_dev, uint8_t *infos_dev, uint8_t *flags_dev,
+                            void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (h) {
+        const int arc = pilot_args_ok(h, "mn_pilot_act", T_dev, n_fields, nx, ny, horizon);
+        if (arc) return arc;
+    }
+    const int rc = query_common(h, env_of_query_dev, env0, state_dev, n_queries, s);
+    if (rc) return rc;
+    if (n_queries == 0) return MN_OK;
+    if (!actions_dev && !scores_dev && !steps_dev && !infos_dev && !flags_dev) return fail(h, MN_ERR_INVALID, "mn_pilot_act: every output is NULL");
+    mn_launch_pilot_act(h->A, h->P, env_of_query_dev, env0, state_dev, episode_timesteps_dev, T_dev, field_of_query_dev, n_fields, nx, ny, horizon,
+                        n_queries, actions_dev, scores_dev, steps_dev, infos_dev, flags_dev, s);
+    MN_HIP(h, hipGetLastError());
+    return MN_OK;
+}
+
+extern "C" int mn_rollout_pilot(mn_handle *h, int32_t n_steps, const double *T_dev, const int32_t *field_of_env_dev, int64_t n_fields, int32_t nx,
+                                int32_t ny, int32_t horizon, float *obs_dev, float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev,
+                                uint8_t *info_trace_dev, int32_t *action_trace_dev, void *stream) {
+    if (!h) return MN_ERR_INVALID;
+    double *traj = nullptr;
+    const int trc = take_traj_trace(h, n_steps, &traj);      // first: the attachment is consumed even by a call refused below
+    if (!obs_dev || n_steps < 1) return fail(h, MN_ERR_INVALID, "mn_rollout_pilot: obs_dev is NULL or n_steps < 1");
+    if (h->params.precision != MN_PRECISION_F64)
+        return fail(h, MN_ERR_INVALID, "mn_rollout_pilot: the pilot's episodes run only with MN_PRECISION_F64 (its candidates start from the float64 state)");
+    const int arc = pilot_args_ok(h, "mn_rollout_pilot", T_dev, n_fields, nx, ny, horizon);
+    if (arc) return arc;
+    if (!field_of_env_dev && n_fields != h->A.n)
+        return fail(h, MN_ERR_INVALID, "mn_rollout_pilot: without field_of_env_dev env i follows field i, so n_fields must equal the number of envs");
+    if (trc) return trc;
+    hipStream_t s = (hipStream_t)stream;
+    return launch_episodes(h, s, [&] {
+        mn_launch_rollout_pilot(h->A, h->P, n_steps, T_dev, field_of_env_dev, n_fields, nx, ny, horizon, obs_dev, obs_trace_dev, reward_trace_dev,
+                                done_trace_dev, info_trace_dev, action_trace_dev, traj, s);
+    });
+}
+
 // ---- pictures: nothing in the handle is written (mn_render.hip) -----------------------------------------------------------------------------------
 static const char *render_canvas_error(const void *pixels_dev, int32_t n_images, int32_t width, int32_t height, const double *view) {
     if (!pixels_dev) return "render: pixels_dev is NULL";

@@ -236,6 +236,13 @@ int64_t mn_time_field_planes_bytes(int nx, int ny, int64_t n_fields);
 int mn_launch_time_field(const MnArrays &A, const MnDev &P, const int32_t *env_of, int env0, const double *goal_xy, int64_t n_fields, int nx, int ny,
                          double speed, double clearance, int max_sweeps, double *T, uint8_t *dir, int32_t *status, int32_t *sweeps, void *workspace,
                          hipStream_t s);
+// the field pilot (mn_pilot.hip): mn_pilot_act is read-only on A, mn_rollout_pilot steps the envs; the arguments of the entry points, validated
+void mn_launch_pilot_act(const MnArrays &A, const MnDev &P, const int32_t *env_of, int env0, const double *state, const int32_t *ep_t, const double *T,
+                         const int32_t *field_of, int64_t n_fields, int nx, int ny, int horizon, int64_t nq, int32_t *actions, double *scores,
+                         int32_t *steps, uint8_t *infos, uint8_t *flags, hipStream_t s);
+void mn_launch_rollout_pilot(const MnArrays &A, const MnDev &P, int n_steps, const double *T, const int32_t *field_of, int64_t n_fields, int nx, int ny,
+                             int horizon, float *obs_io, float *obs_trace, float *reward_trace, uint8_t *done_trace, uint8_t *info_trace,
+                             int32_t *action_trace, double *traj_trace, hipStream_t s);
 // pictures (mn_render.hip): read-only on A; env_of = NULL: every image shows world env0.  The arguments of mn_render_worlds / mn_render_draw, validated
 void mn_launch_render_worlds(const MnArrays &A, const MnDev &P, const int32_t *env_of, int env0, int n_images, int width, int height, const double view[4],
                              const mn_render_style &style, uint32_t *pixels, hipStream_t s);

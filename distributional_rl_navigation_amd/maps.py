@@ -184,7 +184,7 @@ def field_dict(T, d, width, height, status=0, sweeps=0):
     hx, hy = float(width) / nx, float(height) / ny
     xs = (torch.arange(nx, dtype=torch.float64, device=T.device) + 0.5) * hx
     ys = (torch.arange(ny, dtype=torch.float64, device=T.device) + 0.5) * hy
-    return dict(T=T, dir=d, free=torch.isfinite(T), xs=xs, ys=ys, status=status, sweeps=sweeps, hx=hx, hy=hy)
+    return dict(T=T, dir=d, free=torch.isfinite(T), xs=xs, ys=ys, status=status, sweeps=sweeps, hx=hx, hy=hy, width=float(width), height=float(height))
 
 
 def _cells_of(field, xy):
@@ -253,3 +253,84 @@ def reference_times(env, envs=None, nx=128, ny=128, speed=None, clearance=0.0, m
     c, inside = _cells_of(dict(T=T[0], hx=hx, hy=hy), starts)      # (a field per start: time_at's lookup, row f in field f)
     t = T.reshape(len(idx), -1)[torch.arange(len(idx), device=T.device), c]
     return torch.where(inside, t, torch.full_like(t, float("nan")))
+
+
+# ---- the field pilot (VecMarineNavEnv.pilot_act / rollout_pilot, C-ABI mn_pilot_act / mn_rollout_pilot) -------------------------------------------------
+def time_interp(field, xy):
+    """Tint of include/marinenav_hip.h ("Field pilot") at the points xy [Q][2], operation for operation: the bilinear value of T between the four
+    cell centres around the point where all four are finite, else T of the containing cell (`_cells_of`); +inf outside the map and for a NaN.
+    float64 [Q] on the field's device -- the words the pilot's kernels and tests/pilot_host.hip form."""
+    T = field["T"]
+    ny, nx = T.shape
+    hx, hy = float(field["hx"]), float(field["hy"])
+    width, height = float(field.get("width", nx * hx)), float(field.get("height", ny * hy))
+    if not torch.is_tensor(xy):
+        xy = np.asarray(xy, dtype=np.float64)
+    p = torch.as_tensor(xy).to(device=T.device, dtype=torch.float64).reshape(-1, 2)
+    x, y = p[:, 0], p[:, 1]
+    inside = (x >= 0.0) & (x <= width) & (y >= 0.0) & (y <= height)
+    xs, ys = torch.where(inside, x, torch.zeros_like(x)), torch.where(inside, y, torch.zeros_like(y))
+    flat = T.reshape(-1)
+    # (divisors as tensors on the field's device: a device tensor divided by a Python number is multiplied by its reciprocal, which is another word)
+    hx, hy = torch.full((), hx, dtype=torch.float64, device=T.device), torch.full((), hy, dtype=torch.float64, device=T.device)
+    i = torch.floor(xs / hx).long().clamp_(0, nx - 1)
+    j = torch.floor(ys / hy).long().clamp_(0, ny - 1)
+    v = flat[j * nx + i]
+    if nx > 1 and ny > 1:
+        u, w = xs / hx - 0.5, ys / hy - 0.5
+        i0 = torch.floor(u).long().clamp_(0, nx - 2)
+        j0 = torch.floor(w).long().clamp_(0, ny - 2)
+        fx = (u - i0.to(torch.float64)).clamp_(0.0, 1.0)
+        fy = (w - j0.to(torch.float64)).clamp_(0.0, 1.0)
+        T00, T10, T01, T11 = flat[j0 * nx + i0], flat[j0 * nx + i0 + 1], flat[(j0 + 1) * nx + i0], flat[(j0 + 1) * nx + i0 + 1]
+        ok = torch.isfinite(T00) & torch.isfinite(T10) & torch.isfinite(T01) & torch.isfinite(T11)
+        z = torch.zeros_like(T00)
+        a00, a10, a01, a11 = (torch.where(ok, t, z) for t in (T00, T10, T01, T11))
+        bil = (a00 * (1.0 - fx) + a10 * fx) * (1.0 - fy) + (a01 * (1.0 - fx) + a11 * fx) * fy
+        v = torch.where(ok, bil, v)
+    inf = torch.full_like(v, float("inf"))
+    return torch.where(inside & ~torch.isnan(v), v, inf)
+
+
+def pilot_map(env, env_index, xs, ys, thetas, speed, field, horizon=2):
+    """The field pilot's action and nine scores at every pose of policy_map's grid (same order), for a robot placed there with forward speed `speed`
+    in world `env_index`; `field`: the dict of `time_field` for that world (or its T).  One launch (`VecMarineNavEnv.pilot_act`).  Returns arrays
+    shaped [len(thetas)][len(ys)][len(xs)] + tail: `action` (int32; -1: poisoned), `scores` [9] float64, `steps` [9], `infos` [9], `flags`."""
+    poses = pose_grid(xs, ys, thetas, speed, env.device)
+    shape = (len(thetas), len(ys), len(xs))
+    out = env.pilot_act(poses, field["T"] if isinstance(field, dict) else field, env=int(env_index), horizon=horizon,
+                        want=("action", "scores", "steps", "infos", "flags"))
+    return {k: _host(v).reshape(shape + tuple(v.shape[1:])) for k, v in out.items()}
+
+
+def pilot_times(env, envs=None, nx=128, ny=128, horizon=2, clearance=0.0, n_steps=None, speed=None, max_sweeps=None):
+    """The field pilot as a yardstick: solve the fields of the worlds `envs` (default: every env) and run their current episodes under the pilot --
+    two launches (`time_field`, `rollout_pilot`).  An env outside `envs` is given no field and ends at once.  `n_steps`: default the parameters'
+    max_episode_steps.  Returns a dict of device tensors over `envs`: `success` [E] bool (the episode reached the goal), `steps` [E] int64 (the
+    steps it ran), `time` [E] float64 = steps * step_time, `T_start` [E] float64 (reference_times' lookup on the same fields) and `ratio` = time /
+    T_start (NaN without success)."""
+    from . import _capi
+    n = env.n_envs
+    idx = np.arange(n, dtype=np.int32) if envs is None else np.asarray(_host(envs), dtype=np.int32).reshape(-1)
+    T, _, status, _ = env.time_field(idx, nx, ny, speed=speed, clearance=clearance, max_sweeps=max_sweeps, want_dir=False, want_sweeps=False)
+    field_of_env = np.full(n, -1, dtype=np.int32)
+    field_of_env[idx] = np.arange(len(idx), dtype=np.int32)
+    steps_max = int(env.params.max_episode_steps) if n_steps is None else int(n_steps)
+    tr = env.rollout_pilot(steps_max, T, field_of_env=field_of_env, horizon=horizon, trace=("done", "info"))
+    if bool((status == _capi.TIME_FIELD_NOT_CONVERGED).any()):
+        raise RuntimeError("pilot_times: a field did not converge; raise max_sweeps")
+    sel = torch.as_tensor(idx.astype(np.int64), device=env.device)
+    done, info = tr["done"][:, sel].bool(), tr["info"][:, sel]
+    ended = done.any(dim=0)
+    first = torch.where(ended, done.to(torch.uint8).argmax(dim=0), torch.full_like(sel, steps_max - 1))
+    steps = torch.where(ended, first + 1, torch.full_like(sel, steps_max))
+    success = ended & (info.gather(0, first[None, :])[0] == 4)      # MN_INFO_REACH_GOAL
+    worlds = env.get_worlds()
+    starts = torch.as_tensor(np.array([worlds[int(e)]["start"] for e in idx], dtype=np.float64).reshape(-1, 2), device=env.device)
+    hx, hy = float(env.params.width) / int(nx), float(env.params.height) / int(ny)
+    c, inside = _cells_of(dict(T=T[0], hx=hx, hy=hy), starts)
+    t0 = T.reshape(len(idx), -1)[torch.arange(len(idx), device=T.device), c]
+    t0 = torch.where(inside, t0, torch.full_like(t0, float("nan")))
+    time = steps.to(torch.float64) * (float(env.params.N) * float(env.params.dt))
+    ratio = torch.where(success, time / t0, torch.full_like(time, float("nan")))
+    return dict(success=success, steps=steps, time=time, T_start=t0, ratio=ratio)

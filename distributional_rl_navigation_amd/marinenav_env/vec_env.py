@@ -637,6 +637,82 @@ class VecMarineNavEnv:
                                          self._stream()))
         return T, d, status, sweeps
 
+    # ---- the field pilot: follow a time field under the real dynamics -------------------------
+    PILOT_WANTS = ("action", "scores", "steps", "infos", "flags")
+
+    def _pilot_fields(self, fields, horizon):
+        T = fields["T"] if isinstance(fields, dict) else fields
+        T = torch.as_tensor(T).to(device=self.device, dtype=torch.float64)
+        if T.dim() == 2:
+            T = T[None]
+        if T.dim() != 3:
+            raise ValueError(f"fields must be [ny, nx] or [F, ny, nx], got {tuple(T.shape)}")
+        return T.contiguous(), int(horizon)
+
+    def pilot_act(self, states, fields, env=0, field_of_query=None, horizon=2, episode_timesteps=None, want=("action", "scores")):
+        """The field pilot's action for robots placed by hand (C-ABI mn_pilot_act: one HIP launch, a row of 16 lanes per query; float64 in the
+        what-if step's arithmetic whatever the env's precision; nothing in the env changes).  `states` [Q, 6] or [Q, 4] as in rollout_at, in world
+        `env` (an int, or one index per query); `fields`: T [F, ny, nx] (or [ny, nx]) float64 as `time_field` returns it, query q on field
+        `field_of_query[q]` (default: field 0); `episode_timesteps` [Q] or an int (default 0).  For each of the nine actions the robot is stepped up
+        to `horizon` (1..16) times and its landing point scored with the interpolated field (include/marinenav_hip.h, "Field pilot"); the least
+        (score, horizon - steps, action) wins.  Returns a dict with the names in `want` (PILOT_WANTS): action [Q] int32, scores [Q, 9] float64, steps
+        [Q, 9] int32, infos [Q, 9] uint8, flags [Q] uint8.  A poisoned query (world or field index out of range, a BAD_ENV field, a state that is
+        not finite) gets action -1, NaN scores and its flag (_capi.QUERY_FLAG_BAD_ENV, PILOT_FLAG_BAD_FIELD, QUERY_INFO_BAD_STATE)."""
+        st = torch.as_tensor(states).to(device=self.device, dtype=torch.float64)
+        if st.dim() != 2 or st.shape[1] not in (4, 6):
+            raise ValueError(f"states must be [Q, 4] or [Q, 6], got {tuple(st.shape)}")
+        if st.shape[1] == 4:
+            st = torch.cat([st, st.new_zeros(st.shape[0], 2)], dim=1)
+        st = st.contiguous()
+        unknown = [k for k in want if k not in self.PILOT_WANTS]
+        if unknown or not want:
+            raise ValueError(f"want must name some of {self.PILOT_WANTS}, got {tuple(want)}")
+        T, H = self._pilot_fields(fields, horizon)
+        q, dev = st.shape[0], self.device
+        idx, env0 = self._query_env(env, q)
+
+        def per_query(v, name):
+            if v is None:
+                return None
+            if isinstance(v, (int, np.integer)):
+                return torch.full((q,), int(v), dtype=torch.int32, device=dev)
+            t = torch.as_tensor(v).to(device=dev, dtype=torch.int32).contiguous()
+            if t.shape != (q,):
+                raise ValueError(f"{name} must hold one value per query ({q}), got shape {tuple(t.shape)}")
+            return t
+        ep = per_query(episode_timesteps, "episode_timesteps")
+        fq = per_query(field_of_query, "field_of_query")
+        shapes = dict(action=((q,), torch.int32), scores=((q, 9), torch.float64), steps=((q, 9), torch.int32), infos=((q, 9), torch.uint8),
+                      flags=((q,), torch.uint8))
+        out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in want}
+        p = lambda t: _ptr(t) if t is not None else None
+        self._check(self.L.mn_pilot_act(self.h, p(idx), env0, _ptr(st), p(ep), _ptr(T), p(fq), T.shape[0], T.shape[2], T.shape[1], H, q,
+                                        p(out.get("action")), p(out.get("scores")), p(out.get("steps")), p(out.get("infos")), p(out.get("flags")),
+                                        self._stream()))
+        return out
+
+    def rollout_pilot(self, n_steps, fields, field_of_env=None, horizon=2, trace=("reward", "done", "info", "action")):
+        """Every env's CURRENT episode under the field pilot for up to `n_steps` steps in ONE launch (C-ABI mn_rollout_pilot; float64 envs only):
+        rollout_policy's contract -- no resets, a finished env idles (reward 0, done 1, terminal info, action -1), "traj" among the traces records
+        the sub-step positions -- with the pilot of `pilot_act` as the policy.  `fields`: T [F, ny, nx]; env i follows field `field_of_env[i]`, or
+        field i by default (then F must be the number of envs).  Bit for bit the loop (get_state, pilot_act, step).  Returns the requested traces
+        + `final_obs`."""
+        T, n, dev = int(n_steps), self.n_envs, self.device
+        F, H = self._pilot_fields(fields, horizon)
+        fe = None
+        if field_of_env is not None:
+            fe = torch.as_tensor(field_of_env).to(device=dev, dtype=torch.int32).contiguous()
+            if fe.shape != (n,):
+                raise ValueError(f"field_of_env must hold one field index per env ({n}), got shape {tuple(fe.shape)}")
+        tr = trace_buffers(T, n, dev, trace, n_substeps=int(self.params.N))
+        p = lambda k: _ptr(tr[k]) if k in tr else None
+        self.set_trajectory_trace(tr.get("traj"))
+        self._check(self.L.mn_rollout_pilot(self.h, T, _ptr(F), _ptr(fe) if fe is not None else None, F.shape[0], F.shape[2], F.shape[1], H,
+                                            _ptr(self.obs), p("obs"), p("reward"), p("done"), p("info"), p("action"), self._stream()))
+        out = dict(tr)
+        out["final_obs"] = self.obs
+        return out
+
     # ---- state accessors (tests, checkpoints) ------------------------------------------------
     def get_state(self, first_env=0, count=None):
         cnt = self.n_envs - first_env if count is None else count

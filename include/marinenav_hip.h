@@ -492,6 +492,57 @@ int mn_time_field(mn_handle *h, const int32_t *env_of_field_dev, int32_t env0, c
                   double speed, double clearance, int32_t max_sweeps, double *T_dev, uint8_t *dir_dev, int32_t *status_dev, int32_t *sweeps_dev,
                   void *workspace_dev, void *stream);
 
+/* Field pilot: a pilot with full knowledge of the map that drives the real 9-action robot by looking a few steps ahead with each action and scoring
+ * the landing point with the world's minimum-time field T (the global dynamic-window approach).  The upper baseline beside the sonar-only planners,
+ * and a per-pose expert action.  The rule is csrc/mn_pilot_body.h's, a __host__ __device__ body on top of the what-if step (mn_query_rollout's
+ * arithmetic, csrc/mn_query_step_body.h): float64 whatever the handle's precision, every operation an IEEE float64 add, multiply, divide, floor or
+ * comparison in the order written here (contraction off), so host and device give the same words.
+ *
+ * Inputs.  A world; a robot state [6] (the columns of mn_get_state; the velocity columns are not read) and its episode counter t; a field
+ *   T [ny][nx] of that world as mn_time_field writes it (hx = width / nx, hy = height / ny); a horizon H, 1 <= H <= MN_PILOT_MAX_HORIZON.
+ * Candidates.  For a = 0..8: copy the state; run the what-if step with action a and the counters t, t + 1, ... up to H times; stop behind the first
+ *   step whose info is not MN_INFO_NORMAL.  n_a = the steps run, info_a = the last info, (x_a, y_a) = the end position.  This is mn_query_rollout
+ *   with MN_QUERY_ACTIONS_CONSTANT, its rule for a state that leaves the finite numbers on the way included (that step counts, info_a =
+ *   MN_QUERY_INFO_BAD_STATE).
+ * Score.  step_time = (double)N * dt.  REACH_GOAL: score_a = n_a step_time.  COLLISION, OUT_OF_BOUNDARY (and BAD_STATE): score_a = +inf.
+ *   NORMAL, TOO_LONG: score_a = n_a step_time + Tint(x_a, y_a), n_a converted to float64, the product first.
+ * Tint(x, y).  +inf unless 0 <= x <= width and 0 <= y <= height.  Tc = T of the containing cell: i = (int)floor(x / hx), j = (int)floor(y / hy),
+ *   each clamped to the grid (the far edge belongs to the last cell).  If nx == 1 or ny == 1: Tc.  Otherwise u = x / hx - 0.5, v = y / hy - 0.5;
+ *   i0 = (int)floor(u) clamped to [0, nx - 2], j0 = (int)floor(v) clamped to [0, ny - 2]; fx = u - i0 clamped to [0, 1], fy = v - j0 likewise;
+ *   T00 = T[j0][i0], T10 = T[j0][i0 + 1], T01 = T[j0 + 1][i0], T11 = T[j0 + 1][i0 + 1].  If all four are finite:
+ *   (T00 (1 - fx) + T10 fx) (1 - fy) + (T01 (1 - fx) + T11 fx) fy, in exactly this order; otherwise Tc.  A NaN result counts as +inf.
+ * Choice.  The action a with the least key (score_a, H - n_a, a) in lexicographic order: the first minimum wins, and if all nine scores are +inf
+ *   the action that survives longest.
+ * Poison (the queries' rule: the call returns MN_OK, the trouble stays with its own query).  A world index outside [0, n_envs): flag
+ *   MN_QUERY_FLAG_BAD_ENV; a field index outside [0, n_fields): MN_PILOT_FLAG_BAD_FIELD; a state that is not finite or has |theta| >= 1e6:
+ *   MN_QUERY_INFO_BAD_STATE; a field whose T[0] is NaN (a MN_TIME_FIELD_BAD_ENV field): MN_PILOT_FLAG_BAD_FIELD -- tested in this order, the first
+ *   that holds names the flag.  Such a query gets action -1, NaN scores, 0 steps, its flag in every info and in flags_dev; every other query has
+ *   flag 0.
+ *
+ * mn_pilot_act: a query.  Query q is a robot in state_dev[q] with counter episode_timesteps_dev[q] (NULL: 0) in world env_of_query_dev[q] (NULL:
+ *   every query in env0), on field field_of_query_dev[q] (NULL: field 0) of T_dev [n_fields][ny][nx].  Outputs, each NULL or: actions_dev [Q] i32,
+ *   scores_dev [Q][9] f64, steps_dev [Q][9] i32 (n_a), infos_dev [Q][9] u8 (info_a), flags_dev [Q] u8.  Nothing in the handle is written; ONE launch
+ *   on `stream` (a row of 16 lanes per query), no allocation, no host synchronisation; a pending mn_reset_done_async is joined on `stream`.
+ *   n_queries = 0 returns MN_OK without a launch.  MN_ERR_INVALID (message in mn_last_error), without a launch: a NULL handle; n_queries < 0; env0
+ *   outside [0, n_envs) without an index array; a NULL state_dev or T_dev; n_fields < 1; a grid outside mn_time_field's; horizon outside
+ *   [1, MN_PILOT_MAX_HORIZON]; every output NULL.
+ *
+ * mn_rollout_pilot: mn_rollout_policy's contract with the pilot as the policy -- every env runs its CURRENT episode for up to n_steps steps, a
+ *   finished env idles (reward 0, done 1, its terminal info, action -1), no resets, an attached mn_set_trajectory_trace is honoured -- on
+ *   MN_PRECISION_F64 handles only.  Env i follows field field_of_env_dev[i] ([n_envs] i32), or field i if that is NULL (then n_fields must equal
+ *   n_envs).  Each step: the nine candidates from the env's own float64 state and counter, the choice, then the real step (mn_step's arithmetic)
+ *   -- bit for bit the loop (mn_get_state, mn_pilot_act, mn_step).  A poisoned env (bad field index, BAD_ENV field, a state that is not finite)
+ *   ends at once: reward 0, done 1, info MN_QUERY_INFO_BAD_STATE, action -1, and is not stepped.  ONE launch (a row of 16 lanes per env).
+ *   MN_ERR_INVALID: a NULL handle, obs_dev or T_dev; n_steps < 1; a mixed-precision handle; the grid, horizon and n_fields errors above. */
+#define MN_PILOT_MAX_HORIZON 16
+enum { MN_PILOT_FLAG_BAD_FIELD = 32 };
+int mn_pilot_act(mn_handle *h, const int32_t *env_of_query_dev, int32_t env0, const double *state_dev, const int32_t *episode_timesteps_dev,
+                 const double *T_dev, const int32_t *field_of_query_dev, int64_t n_fields, int32_t nx, int32_t ny, int32_t horizon, int64_t n_queries,
+                 int32_t *actions_dev, double *scores_dev, int32_t *steps_dev, uint8_t *infos_dev, uint8_t *flags_dev, void *stream);
+int mn_rollout_pilot(mn_handle *h, int32_t n_steps, const double *T_dev, const int32_t *field_of_env_dev, int64_t n_fields, int32_t nx, int32_t ny,
+                     int32_t horizon, float *obs_dev, float *obs_trace_dev, float *reward_trace_dev, uint8_t *done_trace_dev,
+                     uint8_t *info_trace_dev, int32_t *action_trace_dev, void *stream);
+
 /* Robot pose and counters (robot.py:40-44, marinenav_env.py:70-71).  state[count][6] =
  * x, y, theta, speed, velocity_x, velocity_y (float64).  NULL pointers are skipped. */
 int mn_get_state(mn_handle *h, int32_t first_env, int32_t count, double *state, int32_t *episode_timesteps,

@@ -14,7 +14,9 @@ indexing, cells the goal cannot be reached from in grey, and the field's own rou
 --compare: the named policies' episodes on the same worlds through the existing one-launch functions; per policy the success count, and the median
 and range of time / T(start) over its successful episodes from starts the grid reaches the goal from.  T is the time of a vehicle that turns and
 accelerates at once and always runs at --speed, over-estimated by the 16-direction stencil (up to 2.75 % in still water) and by averaging the
-current per edge: a ratio slightly below 1 is possible."""
+current per edge: a ratio slightly below 1 is possible.  PILOT among --compare is the upper baseline: it knows the whole map and follows the field
+under the real dynamics, so a policy's ratio divided by the pilot's median is its time against what the real robot can do.
+    python scripts/time_field.py --eval-config tests/golden/eval_config_seed3.json --compare APF BA PILOT --pilot-horizon 2"""
 import argparse
 import json
 import os
@@ -29,18 +31,22 @@ ROUTE = 0xE8590C
 
 
 def _policies(args):
-    """[(label, run)]: run(env, T) -> the traces "done" and "info" of every env's episode, by the policy's one-launch function."""
+    """[(label, run)]: run(env, T, fields) -> the traces "done" and "info" of every env's episode, by the policy's one-launch function (`fields`: the
+    worlds' time fields, which only the field pilot reads)."""
     trace = ("reward", "done", "info", "action")
     out = []
     for name in args.compare or ():
-        out.append((name, lambda env, T, name=name: env.rollout_policy(T, name, trace=trace)))
+        if name == "PILOT":
+            out.append((f"PILOT horizon {args.pilot_horizon}", lambda env, T, fields: env.rollout_pilot(T, fields, horizon=args.pilot_horizon, trace=trace)))
+        else:
+            out.append((name, lambda env, T, fields, name=name: env.rollout_policy(T, name, trace=trace)))
     for path in args.iqn or ():
         from distributional_rl_navigation_amd.iqn.agent import IQNAgent
         from distributional_rl_navigation_amd.iqn.fused_act import ActRng, rollout_iqn
         agent = IQNAgent(26, 9, device=args.device, seed=args.seed, BUFFER_SIZE=1024)
         agent.load_model(path, args.device)
 
-        def run(env, T, agent=agent):
+        def run(env, T, fields, agent=agent):
             tr = rollout_iqn(agent.qnetwork_local, env, T, ActRng(args.seed, env.device), cvar=args.cvar, adaptive=args.adaptive, trace=trace)
             if tr is None:
                 raise SystemExit("the IQN episode launch refused this form")
@@ -50,7 +56,7 @@ def _policies(args):
         from distributional_rl_navigation_amd.dqn import DQNPolicy
         pol = DQNPolicy.load(path, device=args.device)
 
-        def run(env, T, pol=pol):
+        def run(env, T, fields, pol=pol):
             tr = pol.rollout(env, T, trace=trace)
             if tr is None:
                 raise SystemExit("the DQN episode launch does not run this network")
@@ -101,7 +107,9 @@ def main(argv=None):
     ap.add_argument("--band", type=float, default=2.0, help="seconds per isochrone band of --png")
     ap.add_argument("--cols", type=int, default=0)
     ap.add_argument("--v-max", type=float, default=4.0)
-    ap.add_argument("--compare", nargs="*", choices=("APF", "BA"), metavar="PLANNER", help="APF and / or BA; --iqn / --dqn add learned policies")
+    ap.add_argument("--compare", nargs="*", choices=("APF", "BA", "PILOT"), metavar="POLICY",
+                    help="APF, BA and / or PILOT (the field pilot on these very fields: VecMarineNavEnv.rollout_pilot); --iqn / --dqn add learned policies")
+    ap.add_argument("--pilot-horizon", type=int, default=2, help="the look-ahead of PILOT in steps (1..16)")
     ap.add_argument("--iqn", action="append", metavar="DIR")
     ap.add_argument("--adaptive", action="store_true")
     ap.add_argument("--cvar", type=float, default=1.0)
@@ -157,7 +165,7 @@ def main(argv=None):
         print(f"{args.png}: {rgb.shape[0]} tiles of {rgb.shape[2]} x {rgb.shape[1]}, {cols} per row; bands of {args.band:g} s, {len(prims)} routes")
     for label, run in _policies(args):
         env.load_worlds(worlds)
-        tr = run(env, args.max_steps)
+        tr = run(env, args.max_steps, T)
         done = tr["done"].bool()
         last = done.to(torch.uint8).argmax(dim=0)
         success = done.any(dim=0) & (tr["info"][last, torch.arange(len(worlds), device=env.device)] == 4)
