@@ -89,6 +89,13 @@ class MnDqnActor(C.Structure):
 
 DQN_MAX_ACTORS = 64      # MN_DQN_MAX_ACTORS
 
+NSTEP_MAX, NSTEP_REFERENCE, NSTEP_EPISODE = 16, 0, 1      # MN_NSTEP_MAX, MN_NSTEP_REFERENCE, MN_NSTEP_EPISODE (mn_replay_append_nstep)
+
+
+class MnNstepGamma(C.Structure):
+    """mn_nstep_gamma: float32(gamma ** a) for a = 0 .. MN_NSTEP_MAX - 1, passed to mn_replay_append_nstep by value."""
+    _fields_ = [("g", C.c_float * NSTEP_MAX)]
+
 
 class MarineNavHipError(RuntimeError):
     pass
@@ -236,6 +243,7 @@ SIGNATURES = [
     ("mn_iqn_last_greedy_rows", C.c_int, [_vp, _vp, _pi32, _i32, _pi32]),
     ("mn_iqn_act_rng_env", C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_void_p), _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _i32, _i32, _vp]),
     ("mn_replay_append", C.c_int, [_vp] * 10 + [_i64, _i64, _i64, _vp]),
+    ("mn_replay_append_nstep", C.c_int, [_vp] * 10 + [_i64, _i32, MnNstepGamma, _i32] + [_vp] * 5 + [_i64, _i64, _i64, _vp]),
     ("mn_episode_log", C.c_int, [_vp, _vp, _vp, _i32, _dbl, _i64, C.c_float] + [_vp] * 9 + [_i64, _vp, _vp]),
     ("mn_iqn_train_workspace_floats", C.c_int64, [_i32]),
     ("mn_iqn_train_workspace_misplaced_word", C.c_int64, [_i32]),

@@ -269,7 +269,7 @@ class IQNAgent(ReferenceLoopMixin):
     def __init__(self, state_size, action_size, layer_size=64, n_step=1, BATCH_SIZE=32, BUFFER_SIZE=1_000_000,
                  LR=1e-4, TAU=1.0, GAMMA=0.99, UPDATE_EVERY=4, learning_starts=10000, target_update_interval=10000,
                  exploration_fraction=0.1, initial_eps=1.0, final_eps=0.05, device="cpu", seed=0,
-                 distributed=False, act_chunk=8192, rank=0):
+                 distributed=False, act_chunk=8192, rank=0, n_step_mode="reference"):
         self.state_size = state_size
         self.action_size = action_size
         self.device = torch.device(device)
@@ -277,6 +277,7 @@ class IQNAgent(ReferenceLoopMixin):
         self.UPDATE_EVERY = UPDATE_EVERY
         self.BATCH_SIZE = BATCH_SIZE
         self.n_step = n_step
+        self.n_step_mode = n_step_mode               # n_step > 1: "reference" (the reference's window, sliding across episode ends) or "episode" (cut at the first done): replay_buffer.py
         self.learning_starts = learning_starts
         self.target_update_interval = target_update_interval
         self.exploration_fraction = exploration_fraction
@@ -310,7 +311,7 @@ class IQNAgent(ReferenceLoopMixin):
         self.qnetwork_local = ObsEncoder(state_size, action_size, seed, device)
         self.qnetwork_target = ObsEncoder(state_size, action_size, seed, device)   # identical init (App. A A1)
         self.optimizer = self._make_adam()
-        self.memory = ReplayBuffer(BUFFER_SIZE, BATCH_SIZE, device, seed, GAMMA, n_step, state_size)
+        self.memory = ReplayBuffer(BUFFER_SIZE, BATCH_SIZE, device, seed, GAMMA, n_step, state_size, nstep_mode=n_step_mode)
         random.seed(seed)                            # replay_buffer.py:21 seeds python `random` (eps-greedy)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(int(seed) + 12345 + 7919 * self.rank)

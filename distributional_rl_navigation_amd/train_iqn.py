@@ -8,6 +8,7 @@ GPUs (independent learners per rank by default, `--shared-learner` for one IQN w
 gradient all-reduce).
 
     python -m distributional_rl_navigation_amd.train_iqn -C config_IQN.json [--n-envs 4096] [--env-budget reference] [--episode-log [full]] [--together [--stack-envs]] [--dry-run]
+    python -m distributional_rl_navigation_amd.train_iqn -C config_IQN.json ... [--n-step N [--n-step-mode episode]]        # N-step returns; episode: windows cut at episode ends
     python -m distributional_rl_navigation_amd.train_iqn -C config_IQN.json ... [--checkpoint-every K] [--stop-after K]      # checkpoint.pt per seed; end behind vector step K
     python -m distributional_rl_navigation_amd.train_iqn -C config_IQN.json ... --resume SAVE_DIR/training_<time> [--dry-run]   # continue in a fresh process, bit for bit
 
@@ -240,7 +241,7 @@ class TrialRun:
 
     def __init__(self, device, params, n_envs, rank=0, world=1, shared=False, batch=None, replay=None, verbose=True,
                  grad_steps=None, torch_train=False, total_grad_steps=None, n_evals=None, cvar=1.0, precision="f64",
-                 exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1,
+                 exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1, n_step_mode="reference",
                  eval_one_launch=False, eval_deferred=False, env_budget="learner", reference=None, episode_log=None, eval_config=None, max_eval_steps=1000,
                  on_step=None, train_env=None, eval_worlds=None):
         import torch
@@ -281,7 +282,7 @@ class TrialRun:
                 json.dump(eval_config, f)
         eval_env = VecMarineNavEnv(len(eval_config), device=device, precision=precision) if writer else None
 
-        agent = IQNAgent(26, 9, n_step=n_step, BATCH_SIZE=batch, BUFFER_SIZE=replay, device=device,
+        agent = IQNAgent(26, 9, n_step=n_step, n_step_mode=n_step_mode, BATCH_SIZE=batch, BUFFER_SIZE=replay, device=device,
                          seed=params["seed"] + 100 + (0 if shared else rank), distributed=shared and world > 1,
                          UPDATE_EVERY=1, learning_starts=plan["learning_starts"] if ref_mode else 0, rank=rank if shared else 0, final_eps=final_eps,
                          **(dict(exploration_fraction=plan["exploration_fraction"]) if ref_mode else {}))
@@ -373,12 +374,12 @@ def write_checkpoint(exp_dir, state):
     return path
 
 
-def run_shaping_args(env_budget="learner", precision="f64", n_step=1, shared_taus=False, cvar=1.0, eval_adaptive=True, eval_deferred=False, eval_one_launch=False,
+def run_shaping_args(env_budget="learner", precision="f64", n_step=1, n_step_mode="reference", shared_taus=False, cvar=1.0, eval_adaptive=True, eval_deferred=False, eval_one_launch=False,
                      episode_log=None, max_eval_steps=1000, reference=None, target_sync_mult=1.0, final_eps=0.05, eval_worlds=None, **_):
     """The arguments of `run_trial` that shape a run beside its plan, normalised: what a checkpoint records and `--resume` compares (`check_resumable`).  ONE
     place builds it, for the run itself and for `--dry-run --resume`; the defaults are `run_trial`'s.  (`torch_train` is recorded by the checkpoint but not
     compared: a checkpoint of one gradient-step path continues on the other.)"""
-    return dict(env_budget=env_budget, precision=precision, n_step=int(n_step), shared_taus=bool(shared_taus), cvar=float(cvar), eval_adaptive=bool(eval_adaptive),
+    return dict(env_budget=env_budget, precision=precision, n_step=int(n_step), n_step_mode=str(n_step_mode), shared_taus=bool(shared_taus), cvar=float(cvar), eval_adaptive=bool(eval_adaptive),
                 eval_deferred=bool(eval_deferred), eval_one_launch=bool(eval_one_launch), episode_log=episode_log, max_eval_steps=int(max_eval_steps),
                 reference=dict(reference or {}), target_sync_mult=float(target_sync_mult), final_eps=float(final_eps), eval_worlds=eval_worlds)
 
@@ -472,7 +473,7 @@ def run_loop_with_checkpoints(run, state=None, checkpoint_every=None, stop_after
 
 def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None, replay=None, verbose=True,
               grad_steps=None, torch_train=False, total_grad_steps=None, n_evals=None, cvar=1.0, precision="f64",
-              exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1,
+              exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1, n_step_mode="reference",
               eval_one_launch=False, eval_deferred=False, env_budget="learner", reference=None, episode_log=None, eval_config=None, max_eval_steps=1000,
               on_step=None, return_agent=False, eval_worlds=None, checkpoint_every=None, stop_after=None, resume=False, dump_final_state=None):
     """train_IQN_model.py:74-121 on the vector env.  `params` is one trial of the reference's config grid
@@ -484,7 +485,8 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None,
     reference's per-call draw, model.py:149; A/B on learning in profiles/; the learner's taus are untouched).
     `target_sync_mult`, `final_eps`: study knobs (scripts/learning_curve.py) -- the target network is copied every target_sync_mult x the planned number of gradient
     steps; the exploration floor (agent.py: 0.05); `n_step`: the agent's n-step returns (agent.py:12-29; the reference's scripts use 1; > 1 takes the step + append launch pair
-    instead of the fused mn_step_append).  `eval_adaptive` = False skips the adaptive-CVaR evaluation at the evaluation points (the reference runs both).
+    instead of the fused mn_step_append: mn_step, then the window append mn_replay_append_nstep); `n_step_mode`: "reference" (the reference's window, which slides across
+    episode ends) or "episode" (the window cut at its first episode end: iqn/replay_buffer.py).  `eval_adaptive` = False skips the adaptive-CVaR evaluation at the evaluation points (the reference runs both).
     `eval_one_launch`: each evaluation as one mn_rollout_iqn launch instead of one Python iteration per env step (same results).
     `eval_deferred`: an evaluation point keeps the policy of the moment and the episodes of all pending points run as one mn_rollout_iqn_groups launch
     (iqn/deferred_eval.py) -- with `n_evals=300` the reference's evaluation density.
@@ -505,7 +507,7 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None,
         raise ValueError(CHECKPOINT_REFUSALS["shared" if shared else "world"])
     if checkpoint_every is not None and int(checkpoint_every) < 1 or stop_after is not None and int(stop_after) < 1:
         raise ValueError("checkpoint_every and stop_after count vector steps: at least 1")
-    run_args = run_shaping_args(env_budget=env_budget, precision=precision, n_step=n_step, shared_taus=shared_taus, cvar=cvar, eval_adaptive=eval_adaptive,
+    run_args = run_shaping_args(env_budget=env_budget, precision=precision, n_step=n_step, n_step_mode=n_step_mode, shared_taus=shared_taus, cvar=cvar, eval_adaptive=eval_adaptive,
                                 eval_deferred=eval_deferred, eval_one_launch=eval_one_launch, episode_log=episode_log, max_eval_steps=max_eval_steps, reference=reference,
                                 target_sync_mult=target_sync_mult, final_eps=final_eps, eval_worlds=eval_worlds)
     state = None
@@ -522,7 +524,7 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None,
                                                             else "no checkpoint, starting from the beginning"), flush=True)
     run = TrialRun(device, params, n_envs, rank=rank, world=world, shared=shared, batch=batch, replay=replay, verbose=verbose, grad_steps=grad_steps,
                    torch_train=torch_train, total_grad_steps=total_grad_steps, n_evals=n_evals, cvar=cvar, precision=precision, exchange=exchange,
-                   shared_taus=shared_taus, target_sync_mult=target_sync_mult, final_eps=final_eps, eval_adaptive=eval_adaptive, n_step=n_step,
+                   shared_taus=shared_taus, target_sync_mult=target_sync_mult, final_eps=final_eps, eval_adaptive=eval_adaptive, n_step=n_step, n_step_mode=n_step_mode,
                    eval_one_launch=eval_one_launch, eval_deferred=eval_deferred, env_budget=env_budget, reference=reference, episode_log=episode_log,
                    eval_config=eval_config, max_eval_steps=max_eval_steps, on_step=on_step, eval_worlds=eval_worlds)
     if checkpoint_every is None and stop_after is None and state is None:
@@ -752,6 +754,9 @@ def main(argv=None):
     ap.add_argument("--max-eval-steps", type=int, default=1000, help="step limit of an evaluation episode (default 1000, the reference's)")
     ap.add_argument("--eval-worlds", type=int, default=None, metavar="N", help="evaluate on the first N of the 30 evaluation worlds (runs at toy size)")
     ap.add_argument("--n-step", type=int, default=1, help="the agent's n-step returns (default 1, the reference's scripts)")
+    ap.add_argument("--n-step-mode", choices=("reference", "episode"), default="reference",
+                    help="with --n-step > 1: 'reference' = the reference's sliding window, which does not restart at episode ends (default); 'episode' = the standard "
+                         "n-step transition, cut at the window's first episode end (return up to it, its next state, done = 1)")
     ap.add_argument("--dump-final-state", default=None, metavar="FILE",
                     help="behind the last vector step, torch.save the state_dict()s of the agent, its replay ring and the train env of the LAST trial run to FILE (tests)")
     args = ap.parse_args(argv)
@@ -805,6 +810,8 @@ def main(argv=None):
         kw["eval_worlds"] = args.eval_worlds
     if args.n_step != 1:
         kw["n_step"] = args.n_step
+    if args.n_step_mode != "reference":
+        kw["n_step_mode"] = args.n_step_mode
     if checkpointing:
         kw.update(checkpoint_every=args.checkpoint_every, stop_after=args.stop_after, resume=args.resume is not None)
     if args.dump_final_state is not None:

@@ -817,6 +817,46 @@ int mn_replay_append(const float *obs_dev, const int32_t *actions_dev, const flo
                      const uint8_t *done_dev, float *ring_states, float *ring_next_states, int64_t *ring_actions,
                      float *ring_rewards, float *ring_dones, int64_t n, int64_t ptr, int64_t capacity, void *stream);
 
+/* ---- n-step window ------------------------------------------------------------------------------
+ * ReplayBuffer.add with n_step > 1 (thirdparty/IQN/replay_buffer.py:26-41) for k parallel streams in ONE launch: row i of every call
+ * is the next transition of stream i.  Each stream keeps its last n = n_step transitions in a caller-owned window (device):
+ *     hist_states [n][k][26] f32, hist_actions [n][k] i64, hist_rewards [n][k] f32,
+ *     and in MN_NSTEP_EPISODE only: hist_next_states [n][k][26] f32, hist_dones [n][k] u8 (both may be NULL in MN_NSTEP_REFERENCE).
+ * `count` is the number of calls the window has taken so far; the caller adds 1 after every call.  The call stores its transition
+ * (obs, (i64) action, reward, and in episode mode next_obs and done ? 1 : 0) into window slot count % n.  If count + 1 >= n the
+ * window is full and the call emits ONE transition per stream into ring slot (ptr + i - first) mod capacity, first = max(0, k -
+ * capacity) (rows below `first` are stored in the window but not emitted: only the newest `capacity` rows of a call survive, as in
+ * mn_replay_append); the caller then advances ptr by min(k, capacity).  Earlier calls emit nothing and leave the ring untouched.
+ * Slots in AGE order: slot a = 0 .. n-1 is window slot (count + 1 + a) % n; slot n-1 is this call's.  s[a], act[a], r[a], ns[a], d[a]
+ * are the slot's state, action, reward, next state and done; those of slot n-1 are this call's inputs.  gamma_pow.g[a] is the caller's
+ * float32 table of gamma ** a (Python's double power rounded to float32 once), passed by value.
+ *   MN_NSTEP_REFERENCE -- the reference's sliding window, which does not restart at episode ends:
+ *     state = s[0], action = act[0]
+ *     ret = 0.0f;  for a = 0 .. n-1:  ret = ret + g[a] * r[a]       float32; the product rounds, then the sum (no fused multiply-add);
+ *                                                                  the first term is 0.0f + g[0] * r[0] (so -0.0f becomes +0.0f)
+ *     next_state = ns[n-1] (this call's next_obs),  done = d[n-1] ? 1.0f : 0.0f
+ *   MN_NSTEP_EPISODE -- the window is cut at its first episode end: j = the first a with d[a] set, or n-1 if none is set
+ *     state = s[0], action = act[0]
+ *     ret = 0.0f;  for a = 0 .. j:    ret = ret + g[a] * r[a]       as above
+ *     next_state = ns[j],  done = (any d[a] set) ? 1.0f : 0.0f
+ *   Every transition is still the head of exactly one emitted window; the step right behind an episode end heads a clean window,
+ *   because the windows in front of it were cut at that end.  The learner's bootstrap discount stays gamma ** n: a cut window has done
+ *   = 1, which switches the bootstrap off.
+ * The slot a launch writes (count % n) is never the head it reads ((count + 1) % n), and nothing of the newest step is read back from
+ * the window.  Two calls on one window must be ordered (one stream).  No allocation, no host synchronisation.
+ * MN_ERR_INVALID, without a launch: a NULL among the batch, hist_states / hist_actions / hist_rewards or ring pointers; episode mode
+ * without hist_next_states or hist_dones; an unknown mode; n_step outside 2..MN_NSTEP_MAX; count < 0; k <= 0; capacity <= 0; ptr
+ * outside [0, capacity). */
+#define MN_NSTEP_MAX 16
+#define MN_NSTEP_REFERENCE 0
+#define MN_NSTEP_EPISODE 1
+typedef struct { float g[MN_NSTEP_MAX]; } mn_nstep_gamma;
+int mn_replay_append_nstep(const float *obs_dev, const int32_t *actions_dev, const float *reward_dev, const float *next_obs_dev,
+                           const uint8_t *done_dev, float *hist_states, int64_t *hist_actions, float *hist_rewards, float *hist_next_states,
+                           uint8_t *hist_dones, int64_t count, int32_t n_step, mn_nstep_gamma gamma_pow, int32_t mode, float *ring_states,
+                           float *ring_next_states, int64_t *ring_actions, float *ring_rewards, float *ring_dones, int64_t k, int64_t ptr,
+                           int64_t capacity, void *stream);
+
 /* ---- training episode log ----------------------------------------------------------------------
  * The record the reference prints at every training episode end (thirdparty/IQN/agent.py:118-119, 152-168) for the n envs of a
  * vector step, in one launch that needs no env handle and no host look.  reward_dev [n] f32, done_dev / info_dev [n] u8 are a
