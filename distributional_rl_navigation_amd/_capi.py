@@ -89,6 +89,7 @@ class MnDqnActor(C.Structure):
 
 DQN_MAX_ACTORS = 64      # MN_DQN_MAX_ACTORS
 
+PER_MASS_ONE, PER_BLOCK, PER_MAX_CAPACITY, PER_MAX_BATCH = 1 << 16, 1024, 1 << 20, 1024      # MN_PER_* (mn_per_append / _sample / _update)
 NSTEP_MAX, NSTEP_REFERENCE, NSTEP_EPISODE = 16, 0, 1      # MN_NSTEP_MAX, MN_NSTEP_REFERENCE, MN_NSTEP_EPISODE (mn_replay_append_nstep)
 
 
@@ -249,6 +250,10 @@ SIGNATURES = [
     ("mn_iqn_train_workspace_misplaced_word", C.c_int64, [_i32]),
     ("mn_iqn_sample", C.c_int, [_i64, _i32, _vp, _vp, _vp, _i32, _vp]),
     ("mn_iqn_train_grad", C.c_int, [_vp] * 13 + [_i32, _i32, C.c_float, _vp]),
+    ("mn_iqn_train_grad_per", C.c_int, [_vp] * 13 + [_i32, _i32, C.c_float, _vp, _vp, _vp]),
+    ("mn_per_append", C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    ("mn_per_sample", C.c_int, [_vp, _vp, _i64, _i64, _i32, C.c_float] + [_vp] * 5),
+    ("mn_per_update", C.c_int, [_vp] * 5 + [_i32, C.c_float, C.c_float, _i64, _vp]),
     ("mn_iqn_train_grad_sampled", C.c_int, [_vp] * 5 + [_i64] + [_vp] * 8 + [_i32, _i32, C.c_float, _i32, _vp]),
     ("mn_iqn_train_adam", C.c_int, [_vp] * 6 + [_i32] + [C.c_double] * 5 + [C.c_float, _i32, _vp]),
     ("mn_iqn_train_set_mode", C.c_int, [_i32]),

@@ -1187,6 +1187,17 @@ __device__ __forceinline__ StepTail ld_step_tail(TrainArgsK A) {
 // registers instead of 88 / 91 and the one-launch step at batch 256 measured 33.1-33.4 us against 32.6; included, the three instantiations compile as before.)
 template <bool XCHG, bool FUSED>
 __global__ __launch_bounds__(THREADS) void iqn_train_fwdbwd(const TrainArgs args) {
+    constexpr bool PER = false;
+    const float *const per_weights = nullptr;
+    float *const per_absdelta = nullptr;
+#include "iqn_train_fwdbwd_body.h"
+}
+
+// The weighted step of prioritized replay (marinenav_hip.h, mn_iqn_train_grad_per): the body in the grouped kernel's form -- XCHG = FUSED = false, launched with
+// MODE_LOCAL_ONLY, so every workgroup runs the target forward of its own two batch elements and none waits for another -- with PER = true: the elements' importance
+// weights go into the loss scale and their mean |TD error| comes out.
+__global__ __launch_bounds__(THREADS) void iqn_per_fwdbwd_kernel(const TrainArgs args, const float *__restrict__ per_weights, float *__restrict__ per_absdelta) {
+    constexpr bool XCHG = false, FUSED = false, PER = true;
 #include "iqn_train_fwdbwd_body.h"
 }
 
@@ -1534,7 +1545,9 @@ __global__ __launch_bounds__(THREADS) void iqn_group_fwdbwd_kernel(const IqnGrou
     a.batch = ga.batch; a.gamma = ga.gamma;
     a.mode = MODE_LOCAL_ONLY; a.use_staged = 0;
     const TrainArgs args = a;
-    constexpr bool XCHG = false, FUSED = false;
+    constexpr bool XCHG = false, FUSED = false, PER = false;
+    const float *const per_weights = nullptr;
+    float *const per_absdelta = nullptr;
 #include "iqn_train_fwdbwd_body.h"
 }
 

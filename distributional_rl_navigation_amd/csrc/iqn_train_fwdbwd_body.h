@@ -1,6 +1,7 @@
 // iqn_train_fwdbwd_body.h -- the statements of one forward / backward workgroup of the IQN gradient step (csrc/iqn_train.hip), included INSIDE the kernels that
-// run them: iqn_train_fwdbwd<XCHG, FUSED> and iqn_group_fwdbwd_kernel.  Expects in scope: `args` (const TrainArgs: the launch's arguments), the compile-time
-// constants XCHG and FUSED, blockIdx.x = the workgroup's index in its learner's launch, and everything iqn_train.hip defines in front of its kernels.
+// run them: iqn_train_fwdbwd<XCHG, FUSED>, iqn_group_fwdbwd_kernel and iqn_per_fwdbwd_kernel.  Expects in scope: `args` (const TrainArgs: the launch's arguments), the
+// compile-time constants XCHG, FUSED and PER (the weighted step of prioritized replay: `per_weights` [batch] scales each element's loss terms, `per_absdelta` [batch]
+// receives its mean |TD error|; both are named, and NULL, where PER is false), blockIdx.x = the workgroup's index in its learner's launch, and everything iqn_train.hip defines in front of its kernels.
 // No include guard: it is a function body, included once per kernel.
     extern __shared__ __align__(16) float S[];
     __shared__ int s_act[BE];
@@ -151,6 +152,8 @@
 #pragma unroll
         for (int e = 0; e < 2; ++e) w4row[e] = VL.f1(O_W4 + s_act[e] * H + (tid & 63));
     }
+    float per_w[2] = {1.f, 1.f};      // PER: the importance weights of this workgroup's two elements, requested early like the row above
+    if (PER) { per_w[0] = per_weights[b0]; per_w[1] = per_weights[b0 + 1]; }
     const PassBufs Bl = {S + S_C, is_target ? nullptr : S + S_H1, S + S_X, S + S_H2, S + S_H3, S + S_FEAT, S + S_Q};
     BwdWeights bw;
     if (is_target) forward_pass<false>(Bl, w, S + S_OBS, S + S_TAU, nullptr, VL, ph_local);
@@ -267,7 +270,7 @@
     for (int e = 0; e < 2; ++e) {
         const int t = tid + THREADS * e, r = t >> 6, kq = t & 63, be = r >> 3;
         const float qe = S[S_Q + r * 12 + s_act[be]], tau = S[S_TAU + r];
-        float lsum = 0.f, gsum = 0.f;
+        float lsum = 0.f, gsum = 0.f, asum = 0.f;
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
             const float td = S[S_QT + be * NQ + j] - qe, ad = fabsf(td);
@@ -275,12 +278,14 @@
             const float wq = fabsf(tau - (td < 0.f ? 1.f : 0.f));
             lsum = fmaf(wq, hub, lsum);
             gsum = fmaf(wq, fminf(fmaxf(td, -1.f), 1.f), gsum);
+            if (PER) asum = asum + ad;
         }
-        const float scale = 1.f / (float)(batch * NQ);
+        const float scale = PER ? per_w[e] * (1.f / (float)(batch * NQ)) : 1.f / (float)(batch * NQ);      // (row r belongs to element r >> 3 = e)
         const float gr = -gsum * scale;
         if (kq == 0) {
             S[S_G + r] = gr;
             S[S_MISC + 2 * BE + r] = lsum * scale;
+            if (PER) S[T_TAU + r] = asum;      // (the target pass's taus, which nothing reads any more: PER workgroups always run that pass themselves)
         }
         // output layer backward: only the taken action's row carries gradient
         S[S_DH3 + r * LDC + kq] = S[S_H3 + r * LDC + kq] > 0.f ? gr * w4row[e] : 0.f;
@@ -293,6 +298,14 @@
         if (FUSED)      // self-tagged, polled by reduction + Adam block 0
             __hip_atomic_store((gu64 *)(ws + ws_lossq(n_part)) + part, ((uint64_t)tag << 32) | (uint64_t)__float_as_uint(l), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else ws[ws_loss(n_part) + part] = l;
+        if (PER) {      // the elements' new priorities: mean |TD error| over the 8 x 8 tau pairs, the 8 row sums in index order
+#pragma unroll
+            for (int be = 0; be < BE; ++be) {
+                float d = 0.f;
+                for (int q = 0; q < NQ; ++q) d = d + S[T_TAU + be * NQ + q];
+                per_absdelta[b0 + be] = d * (1.f / (float)(NQ * NQ));
+            }
+        }
     }
 
     // ---- backward (all 8 waves)

@@ -269,7 +269,8 @@ class IQNAgent(ReferenceLoopMixin):
     def __init__(self, state_size, action_size, layer_size=64, n_step=1, BATCH_SIZE=32, BUFFER_SIZE=1_000_000,
                  LR=1e-4, TAU=1.0, GAMMA=0.99, UPDATE_EVERY=4, learning_starts=10000, target_update_interval=10000,
                  exploration_fraction=0.1, initial_eps=1.0, final_eps=0.05, device="cpu", seed=0,
-                 distributed=False, act_chunk=8192, rank=0, n_step_mode="reference"):
+                 distributed=False, act_chunk=8192, rank=0, n_step_mode="reference", per=False, per_alpha=0.6, per_beta0=0.4,
+                 per_eps=1e-6):
         self.state_size = state_size
         self.action_size = action_size
         self.device = torch.device(device)
@@ -278,6 +279,15 @@ class IQNAgent(ReferenceLoopMixin):
         self.BATCH_SIZE = BATCH_SIZE
         self.n_step = n_step
         self.n_step_mode = n_step_mode               # n_step > 1: "reference" (the reference's window, sliding across episode ends) or "episode" (cut at the first done): replay_buffer.py
+        # proportional prioritized replay (opt-in; iqn/priority.py; include/marinenav_hip.h, "Prioritized replay"): rows are drawn in proportion to
+        # (mean |TD error| + per_eps) ** per_alpha, the loss is weighted by (size * P(row)) ** -beta over the batch's largest, beta linear from per_beta0 to 1
+        # over `per_beta_steps` gradient steps (None, the default, also under `learn_vec` called directly: constant per_beta0; train_iqn sets the number of gradient steps its plan will take)
+        self.per, self.per_alpha, self.per_beta0, self.per_eps = bool(per), float(per_alpha), float(per_beta0), float(per_eps)
+        self.per_beta_steps = None
+        self._per_step = 0                           # beta's position: prioritized gradient steps so far
+        if self.per and distributed:
+            raise ValueError("prioritized replay (per=True) keeps one learner's priorities next to its own ring; a shared learner (distributed=True), whose ranks "
+                             "average gradients of differently weighted batches, is refused")
         self.learning_starts = learning_starts
         self.target_update_interval = target_update_interval
         self.exploration_fraction = exploration_fraction
@@ -311,7 +321,7 @@ class IQNAgent(ReferenceLoopMixin):
         self.qnetwork_local = ObsEncoder(state_size, action_size, seed, device)
         self.qnetwork_target = ObsEncoder(state_size, action_size, seed, device)   # identical init (App. A A1)
         self.optimizer = self._make_adam()
-        self.memory = ReplayBuffer(BUFFER_SIZE, BATCH_SIZE, device, seed, GAMMA, n_step, state_size, nstep_mode=n_step_mode)
+        self.memory = ReplayBuffer(BUFFER_SIZE, BATCH_SIZE, device, seed, GAMMA, n_step, state_size, nstep_mode=n_step_mode, prioritized=self.per)
         random.seed(seed)                            # replay_buffer.py:21 seeds python `random` (eps-greedy)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(int(seed) + 12345 + 7919 * self.rank)
@@ -409,6 +419,8 @@ class IQNAgent(ReferenceLoopMixin):
                   act_rng=None if self._act_rng is None else self._act_rng.state.cpu(), train_rng=None if ft is None else ft.rng_state.cpu(),
                   gen=self.gen.get_state(), torch_cpu_rng=torch.get_rng_state(),
                   torch_device_rng=torch.cuda.get_rng_state(self.device) if self.device.type == "cuda" else None, py_random=random.getstate())
+        if self.per:      # beta's position (the masses, mmax and the sampler's generator state are the ring's: memory.state_dict())
+            sd["per"] = dict(step=int(self._per_step), beta_steps=self.per_beta_steps)
         return sd
 
     def load_state_dict(self, sd):
@@ -429,6 +441,9 @@ class IQNAgent(ReferenceLoopMixin):
         for k in self._EVAL_LISTS:
             setattr(self, k, copy.deepcopy(sd["eval_lists"][k]))
         self.best_eval = copy.deepcopy(sd["best_eval"])
+        if self.per and sd.get("per") is not None:      # (absent: a state written without prioritized replay -- beta starts over)
+            self._per_step = int(sd["per"]["step"])
+            self.per_beta_steps = sd["per"]["beta_steps"]
         if sd["act_rng"] is not None:
             if self._act_rng is None:
                 from .fused_act import ActRng
@@ -554,8 +569,10 @@ class IQNAgent(ReferenceLoopMixin):
             g.copy_(self._flat[off:off + g.numel()].view_as(g))
             off += g.numel()
 
-    def compute_loss(self, experiences, taus_target=None, taus_local=None):
-        """Quantile-Huber TD loss of agent.py:276-295 (taus can be injected for tests)."""
+    def compute_loss(self, experiences, taus_target=None, taus_local=None, weights=None, want_abs_td=False):
+        """Quantile-Huber TD loss of agent.py:276-295 (taus can be injected for tests).  `weights` [B]: element b's terms scaled by weights[b] (prioritized
+        replay's importance weights; ones give the unweighted loss bit for bit).  `want_abs_td`: return (loss, mean |TD error| per element [B], detached) --
+        the elements' new priorities."""
         states, actions, rewards, next_states, dones = experiences
         B = states.shape[0]
         with torch.no_grad():
@@ -571,7 +588,13 @@ class IQNAgent(ReferenceLoopMixin):
         with torch.no_grad():
             weight = (taus - (qt < qe).to(taus.dtype)).abs()      # |tau - 1[td < 0]|, agent.py:293
         # sum over the local-quantile axis, mean over the target-sample axis, mean over the batch (agent.py:294-295)
-        return (weight * huber_l).sum() / (B * self.N)
+        terms = weight * huber_l
+        if weights is not None:
+            terms = terms * weights.to(terms.dtype).view(B, 1, 1)
+        loss = terms.sum() / (B * self.N)
+        if want_abs_td:
+            return loss, (qt - qe).detach().abs().mean(dim=(1, 2))
+        return loss
 
     def _fused_trainer(self):
         from .fused_train import FusedTrainer
@@ -599,6 +622,9 @@ class IQNAgent(ReferenceLoopMixin):
         vector step need to stay ahead of the GPU.  Same arithmetic, same generator stream: bit-identical to the eager calls."""
         # (while the ring is still filling its row count changes with every vector step and each change would be a re-capture +
         # device synchronisation: the eager steps -- bit-identical -- run until the ring is full)
+        if self.per and self.use_fused_graph:
+            raise ValueError("prioritized replay (per=True) samples, steps and updates priorities as separate launches per gradient step; the captured graph of "
+                             "`use_fused_graph`, which replays in-launch uniform draws, is refused")
         want_graph = self.use_fused_graph and self.use_fused_train and self.device.type == "cuda" and n_steps > 1
         if want_graph and len(self.memory) < self.memory.capacity and not self._graph_bypass_logged:
             self._graph_bypass_logged = True
@@ -617,7 +643,9 @@ class IQNAgent(ReferenceLoopMixin):
 
     def train_from_memory(self):
         """`self.train(self.memory.sample())` (agent.py:131-133).  With `use_fused_train` the HIP step gathers its batch
-        straight from the device ring (no sampled copies)."""
+        straight from the device ring (no sampled copies).  With `per`: `_train_prioritized`."""
+        if self.per:
+            return self._train_prioritized()
         if self.use_fused_train and self.device.type == "cuda":
             m = self.memory
             ft = self._fused_trainer()
@@ -627,6 +655,38 @@ class IQNAgent(ReferenceLoopMixin):
             self.grad_steps += 1
             return loss
         return self.train(self.memory.sample())
+
+    def per_beta(self):
+        """The importance exponent of the next prioritized gradient step."""
+        from .priority import beta_at
+        return beta_at(self.per_beta0, self._per_step, self.per_beta_steps)
+
+    def _train_prioritized(self):
+        """One gradient step of prioritized replay: sample (rows in proportion to their masses, importance weights, the step's taus) -> the weighted step --
+        `FusedTrainer.step_per` (mn_iqn_train_grad_per + mn_iqn_train_adam), or autograd where `use_fused_train` is off and on the CPU -> the batch's mean
+        |TD errors| become its rows' new masses.  On the GPU three small launches around the step's, nothing synchronises with the host."""
+        m = self.memory
+        idx, w, taus = m.priority.sample(m.size, self.BATCH_SIZE, self.per_beta())
+        ring = (m.states, m.actions, m.rewards, m.next_states, m.dones)
+        if self.use_fused_train and self.device.type == "cuda":
+            ft = self._fused_trainer()
+            self._enter_train_path("hip")
+            loss, abs_td = ft.step_per(ring, idx, taus[0], taus[1], w)
+        else:
+            self._enter_train_path("torch")
+            self.optimizer.zero_grad(set_to_none=False)
+            loss, abs_td = self.compute_loss(tuple(t[idx] for t in ring), taus[0], taus[1], weights=w, want_abs_td=True)
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(self.qnetwork_local.parameters(), 0.5)
+            self.optimizer.step()
+            if self.device.type == "cuda":      # (as in `train`: the act path's cached weight image goes by a counter Adam(fused=True) does not bump)
+                from .fused_act import weights_changed
+                weights_changed(self.qnetwork_local)
+            loss, abs_td = loss.detach(), abs_td.contiguous()
+        m.priority.update(idx, abs_td, self.per_alpha, self.per_eps)
+        self._per_step += 1
+        self.grad_steps += 1
+        return loss
 
     def train(self, experiences, taus_target=None, taus_local=None):
         """agent.py:269-304: one optimizer step; returns the loss (device scalar tensor).

@@ -155,6 +155,9 @@ class FusedTrainer:
         has not been written since (MN_TRAIN_USE_STAGED) -- same batch, same result, one memory round trip at the head of the
         launch instead of three."""
         ag = self.agent
+        if getattr(ag, "per", False):
+            raise ValueError("prioritized replay (per=True) draws its batch from the priority store (IQNAgent.train_from_memory); the uniform draw inside the "
+                             "launch and its staged batches are refused")
         states, actions, rewards, next_states, dones = ring
         for t in ring:
             assert t.is_cuda and t.is_contiguous()
@@ -333,6 +336,30 @@ class FusedTrainer:
         if rc:
             raise _capi.MarineNavHipError(f"mn_iqn_train_grad failed ({rc})")
         return self._finish_step(B)
+
+    def step_per(self, ring, idx, taus_target, taus_local, weights):
+        """One optimizer step of prioritized replay on the batch rows `idx` [B] i64 with importance weights `weights` [B] f32 and taus [B, 8] f32 each (what
+        `PriorityStore.sample` returns): mn_iqn_train_grad_per -- element b's loss terms scaled by weights[b], every workgroup its own target forward --
+        then clip + Adam as ever.  Returns (loss, mean |TD error| per element [B] f32); both are views of buffers the next step overwrites."""
+        ag = self.agent
+        states, actions, rewards, next_states, dones = ring
+        for t in ring + (idx, taus_target, taus_local, weights):
+            assert t.is_cuda and t.is_contiguous()
+        assert states.dtype == torch.float32 and actions.dtype == torch.int64 and dones.dtype == torch.float32
+        assert idx.dtype == torch.int64 and weights.dtype == torch.float32 and taus_target.dtype == torch.float32 and taus_local.dtype == torch.float32
+        B = idx.shape[0]
+        assert weights.shape[0] == B and taus_target.numel() == B * ag.N and taus_local.numel() == B * ag.N
+        if not hasattr(self, "_absdelta"):
+            self._absdelta = {}
+        if B not in self._absdelta:
+            self._absdelta[B] = torch.zeros(B, dtype=torch.float32, device=self.device)
+        self._staged_key = None
+        rc = _capi.lib().mn_iqn_train_grad_per(_p(states), _p(next_states), _p(actions), _p(rewards), _p(dones), _p(idx), _p(taus_target), _p(taus_local),
+                                               _p(self.local), _p(self.target), _p(self._workspace(B)), _p(self.grad), _p(self.loss), B, ag.N,
+                                               C.c_float(ag.GAMMA ** ag.n_step), _p(weights), _p(self._absdelta[B]), _capi.stream_ptr(self.device))
+        if rc:
+            raise _capi.MarineNavHipError(f"mn_iqn_train_grad_per failed ({rc}): need an even batch <= 1024")
+        return self._finish_step(B), self._absdelta[B]
 
     def _finish_step(self, B):
         """Gradient in self.grad -> (shared learner: all-reduce) -> clip + Adam -> loss."""

@@ -47,6 +47,9 @@ def check_agents(agents):
             raise ValueError(f"learner group: agent {i} does not use the fused gradient step (use_fused_train): there is no grouped form of the PyTorch step")
         if a.distributed:
             raise ValueError(f"learner group: agent {i} is a distributed (shared) learner: its gradient exchange has no grouped form")
+        if getattr(a, "per", False):
+            raise ValueError(f"learner group: agent {i} uses prioritized replay (per=True): the grouped launches draw uniformly inside the launch and have no "
+                             "prioritized form")
     if first.BATCH_SIZE % 2 or not 2 <= first.BATCH_SIZE <= 1024:
         raise ValueError(f"learner group: batch size {first.BATCH_SIZE}; the fused gradient step takes even batch sizes up to 1024")
     return agents

@@ -15,6 +15,10 @@ by operation: include/marinenav_hip.h, "n-step window".
 The fused `mn_step_append` path stores 1-step transitions only, so the agent uses step + `add_vector_step` when n_step > 1:
 on a CUDA ring with 2 <= n_step <= 16 that is ONE launch (`mn_replay_append_nstep`, csrc/replay.hip; `use_nstep_kernel`),
 otherwise -- the CPU, n_step > 16, `add_batch` -- the torch ops of `_nstep_window`, which the kernel equals bit for bit.
+
+prioritized = True (opt-in): a `PriorityStore` (iqn/priority.py) rides next to the ring -- every row the ring writes, by whichever of the paths above, gets the
+largest mass assigned so far (one small launch in stream order behind the write; with n_step > 1 only when rows were emitted).  `sample()` stays the uniform
+draw; the prioritized draw is `priority.sample` (IQNAgent.train_from_memory with per = True).
 """
 import torch
 
@@ -22,7 +26,7 @@ NSTEP_MODES = ("reference", "episode")
 
 
 class ReplayBuffer:
-    def __init__(self, buffer_size, batch_size, device, seed, gamma, n_step=1, state_size=26, nstep_mode="reference"):
+    def __init__(self, buffer_size, batch_size, device, seed, gamma, n_step=1, state_size=26, nstep_mode="reference", prioritized=False):
         if int(n_step) < 1:
             raise ValueError("n_step must be >= 1")
         if nstep_mode not in NSTEP_MODES:
@@ -46,6 +50,10 @@ class ReplayBuffer:
         self.ptr = 0
         self._hist = None     # n_step > 1: per-stream window of the last n_step transitions
         self._gamma_pow = None   # the kernel's table of float32(gamma ** i), built at its first call
+        self.priority = None  # prioritized: the rows' masses, block sums and sampling state (iqn/priority.py)
+        if prioritized:
+            from .priority import PriorityStore
+            self.priority = PriorityStore(self.capacity, self.device, seed)
         self.version = 0      # bumped by every write to the ring (a batch the gradient kernels staged from it is then stale)
 
     def add(self, state, action, reward, next_state, done):
@@ -148,6 +156,8 @@ class ReplayBuffer:
         if rc:
             raise _capi.MarineNavHipError(f"mn_replay_append failed ({rc})")
         m = min(n, self.capacity)
+        if self.priority is not None:
+            self.priority.append(self.ptr, m)
         self.ptr = (self.ptr + m) % self.capacity
         self.size = min(self.capacity, self.size + m)
         self.version += 1
@@ -178,6 +188,8 @@ class ReplayBuffer:
             finally:
                 self.n_step = n_step
             return
+        if self.priority is not None:
+            self.priority.append(self.ptr, n)
         self.ptr = end % self.capacity
         self.size = min(self.capacity, self.size + n)
         self.version += 1
@@ -185,6 +197,8 @@ class ReplayBuffer:
     def advance(self, n):
         """Ring bookkeeping after `n` transitions were written at `ptr` by a kernel (mn_step_append)."""
         m = min(int(n), self.capacity)
+        if self.priority is not None:
+            self.priority.append(self.ptr, m)
         self.ptr = (self.ptr + m) % self.capacity
         self.size = min(self.capacity, self.size + m)
         self.version += 1
@@ -227,6 +241,8 @@ class ReplayBuffer:
         if self._hist is not None:
             h = self._hist
             sd["hist"] = dict({k: v.cpu() for k, v in h.items() if k != "count"}, count=int(h["count"]))      # (s, a, r; episode mode: ns, d)
+        if self.priority is not None:      # (a uniform ring's state has no such key, as before there were priorities)
+            sd["priority"] = self.priority.state_dict(s)
         return sd
 
     def load_state_dict(self, sd):
@@ -243,6 +259,8 @@ class ReplayBuffer:
         self.gen.set_state(sd["gen"])
         h = sd.get("hist")
         self._hist = None if h is None else dict({k: v.to(self.device).contiguous() for k, v in h.items() if k != "count"}, count=int(h["count"]))
+        if self.priority is not None:      # a state saved by a uniform ring loads as uniform: every row mass 1.0
+            self.priority.load_state_dict(sd.get("priority"), s)
 
     def __len__(self):
         return self.size

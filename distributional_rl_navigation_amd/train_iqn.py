@@ -243,11 +243,13 @@ class TrialRun:
                  grad_steps=None, torch_train=False, total_grad_steps=None, n_evals=None, cvar=1.0, precision="f64",
                  exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1, n_step_mode="reference",
                  eval_one_launch=False, eval_deferred=False, env_budget="learner", reference=None, episode_log=None, eval_config=None, max_eval_steps=1000,
-                 on_step=None, train_env=None, eval_worlds=None):
+                 on_step=None, train_env=None, eval_worlds=None, per=None):
         import torch
         from .iqn.agent import IQNAgent
         from .marinenav_env.vec_env import VecMarineNavEnv
 
+        if per and shared:
+            raise ValueError(PER_REFUSALS["shared"])
         exp_dir = trial_dir(params, rank, world, shared)
         writer = rank == 0 or not shared
         ref_mode = env_budget == "reference"
@@ -285,7 +287,10 @@ class TrialRun:
         agent = IQNAgent(26, 9, n_step=n_step, n_step_mode=n_step_mode, BATCH_SIZE=batch, BUFFER_SIZE=replay, device=device,
                          seed=params["seed"] + 100 + (0 if shared else rank), distributed=shared and world > 1,
                          UPDATE_EVERY=1, learning_starts=plan["learning_starts"] if ref_mode else 0, rank=rank if shared else 0, final_eps=final_eps,
-                         **(dict(exploration_fraction=plan["exploration_fraction"]) if ref_mode else {}))
+                         **(dict(exploration_fraction=plan["exploration_fraction"]) if ref_mode else {}),
+                         **(dict(per=True, per_alpha=per["alpha"], per_beta0=per["beta0"]) if per else {}))
+        if per:      # beta reaches 1 with the run's last gradient step (the reference plan's total already leaves out the vector steps in front of learning_starts)
+            agent.per_beta_steps = int(plan["total_grad_steps"])
         agent.grad_steps_per_update = plan["grad_steps_per_vector_step"]
         agent.target_sync_grad_steps = max(1, int(round(plan["target_sync_grad_steps"] * target_sync_mult)))
         agent.exchange = exchange
@@ -356,6 +361,11 @@ CHECKPOINT_REFUSALS = dict(
     shared="--checkpoint-every, --stop-after and --resume save and restore one process's learner; a shared learner (--shared-learner) would need every rank's "
            "state from the same vector step, which has no checkpoint yet",
     world="--checkpoint-every, --stop-after and --resume are the single-process form; they are not combinable with torch.distributed.run (WORLD_SIZE > 1)")
+PER_REFUSALS = dict(
+    together="--per keeps one learner's priorities next to its own ring and samples, steps and updates them in launches of its own; the grouped gradient launches of "
+             "--together draw uniformly inside the launch and have no prioritized form",
+    shared="--per weights one learner's batch by its own priorities; a shared learner (--shared-learner) averages the gradients of several ranks' batches, which "
+           "has no prioritized form")
 SHAPE_KEYS_FIRST = ("n_envs", "batch", "replay", "world")      # (named before the plan's own keys, which follow from them)
 
 
@@ -375,13 +385,14 @@ def write_checkpoint(exp_dir, state):
 
 
 def run_shaping_args(env_budget="learner", precision="f64", n_step=1, n_step_mode="reference", shared_taus=False, cvar=1.0, eval_adaptive=True, eval_deferred=False, eval_one_launch=False,
-                     episode_log=None, max_eval_steps=1000, reference=None, target_sync_mult=1.0, final_eps=0.05, eval_worlds=None, **_):
+                     episode_log=None, max_eval_steps=1000, reference=None, target_sync_mult=1.0, final_eps=0.05, eval_worlds=None, per=None, **_):
     """The arguments of `run_trial` that shape a run beside its plan, normalised: what a checkpoint records and `--resume` compares (`check_resumable`).  ONE
     place builds it, for the run itself and for `--dry-run --resume`; the defaults are `run_trial`'s.  (`torch_train` is recorded by the checkpoint but not
     compared: a checkpoint of one gradient-step path continues on the other.)"""
     return dict(env_budget=env_budget, precision=precision, n_step=int(n_step), n_step_mode=str(n_step_mode), shared_taus=bool(shared_taus), cvar=float(cvar), eval_adaptive=bool(eval_adaptive),
                 eval_deferred=bool(eval_deferred), eval_one_launch=bool(eval_one_launch), episode_log=episode_log, max_eval_steps=int(max_eval_steps),
-                reference=dict(reference or {}), target_sync_mult=float(target_sync_mult), final_eps=float(final_eps), eval_worlds=eval_worlds)
+                reference=dict(reference or {}), target_sync_mult=float(target_sync_mult), final_eps=float(final_eps), eval_worlds=eval_worlds,
+                **(dict(per=dict(alpha=float(per["alpha"]), beta0=float(per["beta0"]))) if per else {}))      # (a uniform run records no such key, as before there were priorities)
 
 
 def first_difference(saved, now, first=()):
@@ -428,6 +439,8 @@ def check_resumable(state, shape, run_args=None):
         raise ValueError(f"--resume: the checkpoint was written by a run with another plan: {d[0]} was {d[1]!r} there and is {d[2]!r} on this command line")
     if run_args is not None and state.get("args"):
         d = first_difference({k: v for k, v in state["args"].items() if k in run_args}, {k: v for k, v in run_args.items() if k in state["args"]})
+        if d is None and state["args"].get("per") != run_args.get("per"):      # (recorded only by a run with --per: absent on either side means uniform replay)
+            d = ("per", state["args"].get("per"), run_args.get("per"))
         if d is not None:
             raise ValueError(f"--resume: the checkpoint was written by a run with other arguments: {d[0]} was {d[1]!r} there and is {d[2]!r} on this command line")
 
@@ -475,7 +488,7 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None,
               grad_steps=None, torch_train=False, total_grad_steps=None, n_evals=None, cvar=1.0, precision="f64",
               exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1, n_step_mode="reference",
               eval_one_launch=False, eval_deferred=False, env_budget="learner", reference=None, episode_log=None, eval_config=None, max_eval_steps=1000,
-              on_step=None, return_agent=False, eval_worlds=None, checkpoint_every=None, stop_after=None, resume=False, dump_final_state=None):
+              on_step=None, return_agent=False, eval_worlds=None, checkpoint_every=None, stop_after=None, resume=False, dump_final_state=None, per=None):
     """train_IQN_model.py:74-121 on the vector env.  `params` is one trial of the reference's config grid
     (seed, total_timesteps, eval_freq, save_dir); see `plan_cadence` for how its env-step cadences map to vector steps.
     `precision`: the env kernels' arithmetic.  "f64" (default: every float32 output within 1e-5 of the reference, no
@@ -501,6 +514,8 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None,
     its final files; `resume`: skip the trial if its directory holds the completion marker, continue from its checkpoint if it holds one (refused if that was
     written under another plan or other run-shaping arguments), start from the beginning otherwise.  A run stopped and resumed writes, byte for byte, the files
     of the uninterrupted run.  Single process, single learner.  Without the three the loop is `IQNAgent.learn_vec` as ever.
+    `per`: None (uniform replay) or dict(alpha=, beta0=) -- proportional prioritized replay (iqn/priority.py): rows drawn in proportion to (mean |TD error| + 1e-6) ** alpha,
+    the loss weighted by importance weights whose exponent runs linearly from beta0 to 1 over the run's gradient steps; single learner only.
     `dump_final_state`: a file for torch.save(dict(agent=, ring=, env=)) of the `state_dict()`s behind the last vector step (tests)."""
     checkpointing = checkpoint_every is not None or stop_after is not None or resume
     if checkpointing and (shared or world > 1):
@@ -509,7 +524,7 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None,
         raise ValueError("checkpoint_every and stop_after count vector steps: at least 1")
     run_args = run_shaping_args(env_budget=env_budget, precision=precision, n_step=n_step, n_step_mode=n_step_mode, shared_taus=shared_taus, cvar=cvar, eval_adaptive=eval_adaptive,
                                 eval_deferred=eval_deferred, eval_one_launch=eval_one_launch, episode_log=episode_log, max_eval_steps=max_eval_steps, reference=reference,
-                                target_sync_mult=target_sync_mult, final_eps=final_eps, eval_worlds=eval_worlds)
+                                target_sync_mult=target_sync_mult, final_eps=final_eps, eval_worlds=eval_worlds, per=per)
     state = None
     if resume:      # (looked at before anything is built or written: a finished seed is left alone, a foreign checkpoint refused)
         exp_dir = trial_dir(params, rank, world, shared)
@@ -526,7 +541,7 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None,
                    torch_train=torch_train, total_grad_steps=total_grad_steps, n_evals=n_evals, cvar=cvar, precision=precision, exchange=exchange,
                    shared_taus=shared_taus, target_sync_mult=target_sync_mult, final_eps=final_eps, eval_adaptive=eval_adaptive, n_step=n_step, n_step_mode=n_step_mode,
                    eval_one_launch=eval_one_launch, eval_deferred=eval_deferred, env_budget=env_budget, reference=reference, episode_log=episode_log,
-                   eval_config=eval_config, max_eval_steps=max_eval_steps, on_step=on_step, eval_worlds=eval_worlds)
+                   eval_config=eval_config, max_eval_steps=max_eval_steps, on_step=on_step, eval_worlds=eval_worlds, per=per)
     if checkpoint_every is None and stop_after is None and state is None:
         run.agent.learn_vec(**run.learn_args)
     else:
@@ -607,6 +622,8 @@ def run_trials_together(device, trials, n_envs, on_step=None, return_agents=Fals
             raise ValueError(TOGETHER_REFUSALS["stack_n_step"])
         if kwargs.get("shared_taus", False):
             raise ValueError(TOGETHER_REFUSALS["stack_shared_taus"])
+    if kwargs.get("per"):
+        raise ValueError(PER_REFUSALS["together"])
     hooks = list(on_step) if on_step is not None else [None] * len(trials)
     stacked, views = None, [None] * len(trials)
     if stack_envs:
@@ -757,6 +774,12 @@ def main(argv=None):
     ap.add_argument("--n-step-mode", choices=("reference", "episode"), default="reference",
                     help="with --n-step > 1: 'reference' = the reference's sliding window, which does not restart at episode ends (default); 'episode' = the standard "
                          "n-step transition, cut at the window's first episode end (return up to it, its next state, done = 1)")
+    ap.add_argument("--per", action="store_true",
+                    help="proportional prioritized experience replay (opt-in): rows are drawn in proportion to (mean |TD error| + 1e-6) ** alpha by an exact device-side "
+                         "sampler, the loss is weighted by importance weights whose exponent beta runs from --per-beta0 to 1 over the run's gradient steps; "
+                         "single learner (not with --together or --shared-learner)")
+    ap.add_argument("--per-alpha", type=float, default=0.6, help="with --per: the priority exponent (default 0.6)")
+    ap.add_argument("--per-beta0", type=float, default=0.4, help="with --per: the importance exponent at the first gradient step (default 0.4)")
     ap.add_argument("--dump-final-state", default=None, metavar="FILE",
                     help="behind the last vector step, torch.save the state_dict()s of the agent, its replay ring and the train env of the LAST trial run to FILE (tests)")
     args = ap.parse_args(argv)
@@ -767,6 +790,12 @@ def main(argv=None):
             raise SystemExit("train_iqn: " + CHECKPOINT_REFUSALS[refused[0]])
         if (args.checkpoint_every is not None and args.checkpoint_every < 1) or (args.stop_after is not None and args.stop_after < 1):
             raise SystemExit("train_iqn: --checkpoint-every and --stop-after count vector steps: at least 1")
+    if args.per:
+        refused = [k for k, on in (("together", args.together or args.stack_envs), ("shared", args.shared_learner)) if on]
+        if refused:
+            raise SystemExit("train_iqn: " + PER_REFUSALS[refused[0]])
+        if not (args.per_alpha >= 0 and 0 <= args.per_beta0 <= 1):
+            raise SystemExit("train_iqn: --per-alpha is at least 0 and --per-beta0 lies in [0, 1]")
     reference = None
     if args.reference is not None:
         if args.env_budget != "reference":
@@ -812,6 +841,8 @@ def main(argv=None):
         kw["n_step"] = args.n_step
     if args.n_step_mode != "reference":
         kw["n_step_mode"] = args.n_step_mode
+    if args.per:
+        kw["per"] = dict(alpha=args.per_alpha, beta0=args.per_beta0)
     if checkpointing:
         kw.update(checkpoint_every=args.checkpoint_every, stop_after=args.stop_after, resume=args.resume is not None)
     if args.dump_final_state is not None:

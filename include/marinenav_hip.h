@@ -857,6 +857,49 @@ int mn_replay_append_nstep(const float *obs_dev, const int32_t *actions_dev, con
                            float *ring_next_states, int64_t *ring_actions, float *ring_rewards, float *ring_dones, int64_t k, int64_t ptr,
                            int64_t capacity, void *stream);
 
+/* ---- Prioritized replay --------------------------------------------------------------------------
+ * Proportional prioritized experience replay (Schaul et al. 2016) next to the ring, opt-in.  Priorities are INTEGERS, so every sum is
+ * exact and independent of the order in which it was formed; tests/per_twin.py restates all of this in numpy / Python ints.
+ * The store (caller-owned, device, all zero at first except mmax):
+ *     mass [capacity] u32        row i's mass m_i; MN_PER_MASS_ONE = 1 << 16 is priority 1.0; rows never written have mass 0; 16-byte aligned
+ *     block_sums [ceil(capacity / 1024)] u64     bsum[b] = sum of m_i over rows [1024 b, 1024 (b + 1));  total = sum of bsum
+ *     mmax [1] u32               the largest mass ever assigned; starts at MN_PER_MASS_ONE
+ * capacity <= MN_PER_MAX_CAPACITY = 2^20 rows (<= 1 024 block sums: one scan in one workgroup), batch <= MN_PER_MAX_BATCH = 1 024.
+ *
+ * mn_per_append -- whenever the ring writes rows [ptr, ptr + n) mod capacity (1 <= n <= capacity; call it in stream order behind the
+ *   write, before the caller advances ptr): every such row gets mass *mmax (read on the device) and its block's sum moves by the
+ *   integer difference new - old (64-bit atomics, modulo 2^64).
+ *
+ * mn_per_sample -- `batch` = B slots from rows of positive mass, stratified; needs B <= size <= capacity (every written row has mass
+ *   >= 1, so total >= B).  With {seed, ctr} = rng_state_dev (u64[2], the state mn_iqn_sample uses) and
+ *   base = mix64(seed + 0x9E3779B97F4A7C15 (ctr + 1)):
+ *     q = total / B                                   integer division; the top total - B q < B mass units are never drawn
+ *     U_k = mix64(base ^ (0x8CB92BA72F3D8DD7 (k + 1))) >> 40          a 24-bit word; a key of its own, apart from the taus' 0xD1B5...
+ *     target_k = k q + mulhi64(U_k << 40, q)          in [k q, (k + 1) q)
+ *     idx[k] = the least row i whose inclusive prefix sum m_0 + ... + m_i exceeds target_k      (a zero-mass row is never chosen;
+ *                                                      one mass that spans several strata is chosen by all of them: rows repeat)
+ *     w_k = powf((float) size * (float) m_idx[k] / (float) total, -beta)       float32, left to right
+ *     weights[k] = w_k / max_j w_j                    float32 division
+ *   taus_out [2][B][8] f32 are the step's taus exactly as mn_iqn_sample draws them under the same base (target network's first);
+ *   idx_out [B] i64, weights_out [B] f32: the layouts mn_iqn_train_grad_per takes.  The call counter advances by one per call.
+ *
+ * mn_per_update -- after the weighted step: slot k's priority delta_k = absdelta[k] (mn_iqn_train_grad_per) becomes
+ *     m = clamp(floorf(powf(delta_k + eps, alpha) * 65536.0f + 0.5f), 1, 2^31 - 1)      float32, product and sum round separately;
+ *                                                                                      a NaN gives 1
+ *   written to row idx[k]; when several slots name one row the HIGHEST slot wins (one writer per row); block sums move by the integer
+ *   difference; *mmax = max(*mmax, m) over the masses written.  A row index outside [0, capacity) is dropped.
+ * One launch each, no allocation, no host synchronisation.  MN_ERR_INVALID, without a launch: a NULL pointer, capacity outside
+ * 1..2^20, a mass array that is not 16-byte aligned (mn_per_sample), batch outside 1..1024, size outside [batch, capacity], ptr outside [0, capacity), n outside 1..capacity, beta < 0 or NaN. */
+#define MN_PER_MASS_ONE 65536u
+#define MN_PER_BLOCK 1024
+#define MN_PER_MAX_CAPACITY 1048576
+#define MN_PER_MAX_BATCH 1024
+int mn_per_append(uint32_t *mass, uint64_t *block_sums, const uint32_t *mmax, int64_t ptr, int64_t n, int64_t capacity, void *stream);
+int mn_per_sample(const uint32_t *mass, const uint64_t *block_sums, int64_t size, int64_t capacity, int32_t batch, float beta,
+                  uint64_t *rng_state_dev, int64_t *idx_out, float *weights_out, float *taus_out, void *stream);
+int mn_per_update(uint32_t *mass, uint64_t *block_sums, uint32_t *mmax, const int64_t *idx_dev, const float *absdelta_dev, int32_t batch,
+                  float alpha, float eps, int64_t capacity, void *stream);
+
 /* ---- training episode log ----------------------------------------------------------------------
  * The record the reference prints at every training episode end (thirdparty/IQN/agent.py:118-119, 152-168) for the n envs of a
  * vector step, in one launch that needs no env handle and no host look.  reward_dev [n] f32, done_dev / info_dev [n] u8 are a
@@ -1230,6 +1273,18 @@ int mn_iqn_train_grad(const float *ring_states, const float *ring_next_states, c
                       const float *taus_target_dev, const float *taus_local_dev, const float *params_local,
                       const float *params_target, float *workspace, float *grad_out, float *loss_out, int32_t batch,
                       int32_t num_taus, float gamma, void *stream);
+/* mn_iqn_train_grad for prioritized replay ("Prioritized replay" above): element b's loss terms are scaled by weights_dev[b] --
+ * loss = 1 / (B N) sum_b w_b sum_ij rho_ij, in float32 the scale (w_b * (1.0f / (B N))) applied where mn_iqn_train_grad applies 1 / (B N),
+ * so weights of 1.0f give its gradient and loss bit for bit -- and absdelta_out [batch] f32 receives
+ *     delta_b = (1 / N^2) sum_ij |td_ij|      float32: the 8 |td| of a local-tau row i added in order j = 0..7 from 0.0f, the 8 row sums of
+ *                                             an element added in order i = 0..7 from 0.0f, times 1 / 64.
+ * Every workgroup runs the target forward of its own two batch elements (no workgroup waits for another), then the same reduction as
+ * mn_iqn_train_grad; mn_iqn_train_adam follows unchanged. */
+int mn_iqn_train_grad_per(const float *ring_states, const float *ring_next_states, const int64_t *ring_actions,
+                          const float *ring_rewards, const float *ring_dones, const int64_t *idx_dev,
+                          const float *taus_target_dev, const float *taus_local_dev, const float *params_local,
+                          const float *params_target, float *workspace, float *grad_out, float *loss_out, int32_t batch,
+                          int32_t num_taus, float gamma, const float *weights_dev, float *absdelta_out, void *stream);
 /* The same gradient step with the batch drawn inside the launch: every workgroup of the forward / backward kernel evaluates
  * mn_iqn_sample's permutation for its own two slots (and its own taus) from {seed, call counter}, so there is no sampling launch.
  * Bit-identical to mn_iqn_sample followed by mn_iqn_train_grad from the same state; the call counter is advanced once (by the
