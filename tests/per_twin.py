@@ -2,7 +2,7 @@
 and Python ints, built on tests/rng_twin.py: the append, the exact stratified sampler with its importance weights, and the priority update.  Masses are uint32,
 block sums uint64 over blocks of 1 024 rows; every sum is an integer sum.  float32 only where the kernels use float32 (weights, the mass rule); the `*_f64`
 helpers give the same quantities in float64 as a yardstick.  Plain helper module, no fixtures, no torch, no GPU.
-tests/test_per_cpu.py holds this twin to a brute-force restatement; tests/test_per_gpu.py holds the kernels to the twin."""
+tests/test_per_cpu.py holds this twin to a brute-force restatement; tests/test_per_gpu.py and tests/test_per_scale_gpu.py hold the kernels to the twin."""
 import numpy as np
 
 import rng_twin as R
@@ -59,6 +59,60 @@ def hand_made(name, size, capacity=2053):
     st = Store(capacity)
     st.set_masses(m)
     return st
+
+
+LARGE_VECTORS = ("random", "saturated", "ones", "holes_wide", "heavy_far", "young")
+
+
+def hand_made_large(name, size, capacity):
+    """Mass vectors for rings of the sizes training uses (65 blocks and more: the sampler's scan crosses wavefronts), `size` rows in a ring of `capacity`."""
+    g = np.random.default_rng(7)
+    m = np.zeros(size, dtype=np.uint32)
+    if name == "random":
+        m[:] = g.integers(1, MASS_MAX, size, dtype=np.int64) >> g.integers(0, 30, size)
+        m[m == 0] = 1
+    elif name == "saturated":        # the largest total the store admits: just under 2^51 at 2^20 rows
+        m[:] = MASS_MAX
+    elif name == "ones":             # the smallest total: q = size // batch
+        m[:] = 1
+    elif name == "holes_wide":       # zero-mass holes, the first block and the whole of blocks 64..127 -- one wavefront of the scan -- among them
+        m[:] = g.integers(1, MASS_MAX, size, dtype=np.int64) >> g.integers(0, 30, size)
+        m[m == 0] = 1
+        m[g.random(size) < 0.4] = 0
+        m[:1024] = 0
+        m[64 * BLOCK:128 * BLOCK] = 0
+        m[size - 1] = 3
+    elif name == "heavy_far":        # one row of the last non-empty block holds 99 % of the mass: repeats, as far into the ring as its rows go
+        m[:] = 1
+        first = (size - 1) // BLOCK * BLOCK
+        m[first + (size - first) // 3] = 99 * (size - 1)
+    elif name == "young":            # a ring that has just reached its batch size: every later block is empty
+        m[:] = MASS_ONE
+    else:
+        raise KeyError(name)
+    st = Store(capacity)
+    st.set_masses(m)
+    return st
+
+
+# (capacity, size): 64 blocks -- the last size one wavefront scans --, 65, train_iqn --per's default ring full and one row into block 64, a capacity that
+# is no multiple of 4, --env-budget reference's ring, and the most the ABI admits
+LARGE_GRID = [(65_536, 65_536), (66_560, 66_560), (100_000, 100_000), (100_000, 65_537), (99_997, 99_997), (1_000_000, 1_000_000), (1_048_576, 1_048_576)]
+
+
+def large_case(name, capacity, size, batch):
+    """(store, rows in use) of one vector at one place of the grid; `young` holds just `batch` rows, whatever the grid's size."""
+    n = batch if name == "young" else size
+    return hand_made_large(name, n, capacity), n
+
+
+def rows_by_cumsum(mass, targets):
+    """The rule restated without blocks, at sizes where Python ints are too slow: ONE cumulative sum over all rows in uint64 (exact: a total stays below
+    2^51), then for every target the least row whose inclusive prefix exceeds it."""
+    cs = np.cumsum(np.asarray(mass, dtype=np.uint64), dtype=np.uint64)
+    t = np.array([int(x) for x in targets], dtype=np.uint64)
+    assert int(t.max()) < int(cs[-1]), "target beyond the total mass"
+    return np.searchsorted(cs, t, side="right").astype(np.int64)
 
 
 def block_sums(mass):

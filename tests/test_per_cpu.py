@@ -1,7 +1,8 @@
 """Prioritized replay without a GPU: the symbols, the twin of the priority store (tests/per_twin.py) against a brute-force restatement -- one plain
 cumulative sum over all rows in Python ints --, the empirical frequencies of its draws, the CPU path of iqn/priority.py against the twin, the weighted
-loss of IQNAgent.compute_loss, and an agent that trains with priorities on the CPU, stopped and resumed.  (The kernels against the twin:
-tests/test_per_gpu.py.)"""
+loss of IQNAgent.compute_loss, and an agent that trains with priorities on the CPU, stopped and resumed.  At the ring sizes training uses (64 to 1 024
+blocks) the brute force is one uint64 cumulative sum (per_twin.rows_by_cumsum), and the draws are shown to reach the far blocks.  (The kernels against the
+twin: tests/test_per_gpu.py, and tests/test_per_scale_gpu.py at these sizes.)"""
 import ctypes
 import json
 import os
@@ -136,6 +137,115 @@ def test_cpu_store_equals_the_twin_interleaved():
             _same_store(ps, st)
     assert size == cap and it * 150 > cap      # the ring wrapped
     assert st.mmax > T.MASS_ONE and int(ps.rng_state[1]) == ctr
+
+
+# ---- rings of the sizes training uses: 64 to 1 024 blocks -----------------------------------------------------------------------------------
+LARGE_BATCHES = (2, 256, 1024)
+_large_samples = {}
+
+
+def _twin_large(name, capacity, size):
+    """The twin's draws of one vector at one place of the grid -- {(batch, ctr): (idx, w, taus)} --, drawn once for the tests below."""
+    key = (name, capacity, size)
+    if key not in _large_samples:
+        out = {}
+        for batch in LARGE_BATCHES:
+            st, n = T.large_case(name, capacity, size, batch)
+            for ctr in range(3):
+                out[batch, ctr] = T.sample(st, n, batch, 0.4, SEED, ctr)
+        _large_samples[key] = out
+    return _large_samples[key]
+
+
+def _inputs_exercise_the_code(name, capacity, size, batch, idx):
+    """What a case is there for, asserted on the twin's rows: a case that stops reaching the code it was made for fails here."""
+    blocks = idx // T.BLOCK
+    full = name != "young" and size == capacity
+    # holes_wide keeps blocks 64..127 empty and gives the last row mass 3: up to 131 072 rows it has three units of mass beyond row 65 535, no seed changes that
+    if full and capacity > 65_536 and batch >= 256 and not (name == "holes_wide" and size <= 128 * T.BLOCK):
+        assert int(idx.max()) >= 65_536, (name, capacity, batch)      # beyond the first wavefront's 64 block sums
+    if capacity == T.MAX_CAPACITY and batch == 1024 and name in ("random", "saturated", "holes_wide"):
+        assert int(blocks.max()) == 1023, (name, int(blocks.max()))
+    if name == "holes_wide":
+        assert not ((blocks >= 64) & (blocks < 128)).any() and int(idx.min()) >= 1024
+        if size > 128 * T.BLOCK and batch >= 256:
+            assert (blocks < 64).any() and (blocks >= 128).any()      # rows on both sides of the empty wavefront
+    if name == "heavy_far" and batch >= 256:
+        assert len(set(idx.tolist())) < batch
+        if size > 65_536:
+            heavy = np.bincount(idx).argmax()
+            assert heavy >= 65_536 and (idx == heavy).sum() > 1      # the repeats lie beyond block 63
+    if name == "young":
+        assert sorted(idx.tolist()) == list(range(batch))      # every stratum is one row
+
+
+@pytest.mark.parametrize("name", T.LARGE_VECTORS)
+@pytest.mark.parametrize("capacity,size", T.LARGE_GRID)
+def test_twin_equals_one_cumulative_sum_at_scale(capacity, size, name):
+    draws = _twin_large(name, capacity, size)
+    for batch in LARGE_BATCHES:
+        st, n = T.large_case(name, capacity, size, batch)
+        assert np.array_equal(st.bsum, T.block_sums(st.mass)) and st.total == int(st.mass.sum(dtype=np.uint64)) < 1 << 51
+        for ctr in range(3):
+            idx, w, taus = draws[batch, ctr]
+            tg = T.targets(st.total, SEED, ctr, batch)
+            q = st.total // batch
+            assert all(k * q <= t < (k + 1) * q for k, t in enumerate(tg))
+            assert idx.tolist() == T.rows_by_cumsum(st.mass, tg).tolist(), (name, capacity, size, batch, ctr)
+            assert (st.mass[idx] > 0).all() and int(idx.max()) < n
+            assert w.dtype == np.float32 and w.max() == 1.0 and (w > 0).all()
+            np.testing.assert_allclose(w, T.weights_f64(st.mass[idx], n, st.total, 0.4), rtol=1e-5)
+            assert np.array_equal(taus.reshape(-1), R.sample_taus(R.sample_base(SEED, ctr), 2 * batch * 8))
+            _inputs_exercise_the_code(name, capacity, size, batch, idx)
+        blocks = np.unique(np.concatenate([draws[batch, c][0] for c in range(3)]) // T.BLOCK)
+        print(f"capacity {capacity} size {n} {name} batch {batch}: rows in {len(blocks)} distinct blocks, highest {int(blocks.max())}")
+
+
+@pytest.mark.parametrize("name", T.LARGE_VECTORS)
+@pytest.mark.parametrize("capacity,size", T.LARGE_GRID)
+def test_cpu_store_equals_the_twin_at_scale(capacity, size, name):
+    from distributional_rl_navigation_amd.iqn.priority import PriorityStore
+    draws = _twin_large(name, capacity, size)
+    ps = PriorityStore(capacity, "cpu", SEED)
+    for batch in LARGE_BATCHES:
+        st, n = T.large_case(name, capacity, size, batch)
+        ps.mass.copy_(torch.from_numpy(st.mass.view(np.int32).copy()))
+        ps.bsum.copy_(torch.from_numpy(st.bsum.view(np.int64).copy()))
+        ps.rng_state[1] = 0
+        for ctr in range(3):
+            idx, w, taus = ps.sample(n, batch, 0.4)
+            ti, tw, tt = draws[batch, ctr]
+            assert idx.tolist() == ti.tolist(), (name, capacity, size, batch, ctr)
+            assert np.array_equal(w.numpy(), tw) and np.array_equal(taus.numpy(), tt)
+            assert ps.rng_state.tolist() == [SEED, ctr + 1]
+        _same_store(ps, st)      # the sampler writes nothing
+
+
+def test_cpu_store_equals_the_twin_interleaved_at_scale():
+    """train_iqn --per's default ring: 98 blocks, 4 096 rows a vector step, batch 256."""
+    from distributional_rl_navigation_amd.iqn.priority import PriorityStore
+    cap, batch, n = 100_000, 256, 4096
+    ps, st = PriorityStore(cap, "cpu", SEED), T.Store(cap)
+    g = np.random.default_rng(3)
+    ptr = size = ctr = 0
+    beyond = 0
+    for it in range(40):
+        ps.append(ptr, n); T.append(st, ptr, n)
+        ptr, size = (ptr + n) % cap, min(cap, size + n)
+        _same_store(ps, st)
+        idx, w, taus = ps.sample(size, batch, 0.5)
+        ti, tw, tt = T.sample(st, size, batch, 0.5, SEED, ctr)
+        ctr += 1
+        assert idx.tolist() == ti.tolist() and np.array_equal(w.numpy(), tw) and np.array_equal(taus.numpy(), tt)
+        assert ti.tolist() == T.rows_by_cumsum(st.mass, T.targets(st.total, SEED, ctr - 1, batch)).tolist()
+        np.testing.assert_allclose(w.numpy(), T.weights_f64(st.mass[ti], size, st.total, 0.5), rtol=1e-5)
+        beyond += int((ti >= 65_536).sum())
+        d = torch.from_numpy((g.random(batch) * 10 ** g.uniform(-4, 2, batch)).astype(np.float32))
+        ps.update(idx, d, 0.6, 1e-6)
+        T.update(st, ti, T.new_mass_f32(d.numpy(), 0.6, 1e-6))
+        _same_store(ps, st)
+    assert size == cap and 40 * n > cap and ptr == 40 * n % cap      # the ring wrapped
+    assert st.mmax > T.MASS_ONE and int(ps.rng_state[1]) == ctr and beyond > 0
 
 
 def test_update_highest_slot_wins_and_clamps():
