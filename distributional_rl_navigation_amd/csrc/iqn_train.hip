@@ -46,6 +46,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -460,6 +461,59 @@ __device__ __forceinline__ float td_target(const float *q, int row, float rew, f
     for (int a = 1; a < NA; ++a) m = fmaxf(m, q[row * 12 + a]);
     return fmaf(gamma * m, 1.f - done, rew);
 }
+
+// ---- the Munchausen target ("Munchausen target" in marinenav_hip.h states the rule operation by operation) -------------------------------------------------
+// The soft-max policy of batch element `be` over the MEAN of its 8 quantile rows of q [16][12] in LDS: tlp[a] = te * log pi[a] and pi[a], every sum in index order,
+// d / te a division.  Each thread that needs the policy evaluates it itself (72 LDS reads, 9 expf, one logf): one instruction sequence per output.
+__device__ __forceinline__ void munch_policy(const float *q, int be, float te, float (&tlp)[NA], float (&pi)[NA]) {
+    float d[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+        float s = q[be * NQ * 12 + a];
+#pragma unroll
+        for (int j = 1; j < NQ; ++j) s = s + q[(be * NQ + j) * 12 + a];
+        d[a] = 0.125f * s;
+    }
+    float m = d[0];
+#pragma unroll
+    for (int a = 1; a < NA; ++a) m = fmaxf(m, d[a]);
+    float E = 0.f;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+        d[a] = d[a] - m;
+        pi[a] = expf(d[a] / te);
+        E = E + pi[a];
+    }
+    const float tl = te * logf(E);
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+        tlp[a] = d[a] - tl;
+        pi[a] = pi[a] / E;
+    }
+}
+// alpha * clip(tlp[action taken], lo, 0) of batch element `be`, from the target network's quantiles of the CURRENT state
+__device__ __forceinline__ float munch_bonus(const float *q, int be, int act, float alpha, float te, float lo) {
+    float tlp[NA], pi[NA];
+    munch_policy(q, be, te, tlp, pi);
+    float x = tlp[0];      // (selects, not an indexed array, which would live in scratch)
+#pragma unroll
+    for (int a = 1; a < NA; ++a) x = act == a ? tlp[a] : x;
+    return alpha * fminf(fmaxf(x, lo), 0.f);
+}
+// y of row `row`: r + bonus + gamma (1 - done) sum_a pi'[a] (Z'[row][a] - tlp'[a]), from the target network's quantiles of the NEXT state
+__device__ __forceinline__ float munch_target(const float *q, int row, float rew, float done, float gamma, float te, float bonus) {
+    float tlp[NA], pi[NA];
+    munch_policy(q, row >> 3, te, tlp, pi);
+    float v = 0.f;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) v = v + pi[a] * (q[row * 12 + a] - tlp[a]);
+    return fmaf(gamma * v, 1.f - done, rew + bonus);
+}
+struct MunchArgs {
+    const float *taus;      // [batch][8] the third tau set
+    float alpha, entropy_tau, clip_lo;
+    float *targets_out;     // [batch][8] y, or NULL
+};
 
 struct BatchArgs {
     const float *ring_s, *ring_ns, *ring_r, *ring_d;
@@ -1187,9 +1241,10 @@ __device__ __forceinline__ StepTail ld_step_tail(TrainArgsK A) {
 // registers instead of 88 / 91 and the one-launch step at batch 256 measured 33.1-33.4 us against 32.6; included, the three instantiations compile as before.)
 template <bool XCHG, bool FUSED>
 __global__ __launch_bounds__(THREADS) void iqn_train_fwdbwd(const TrainArgs args) {
-    constexpr bool PER = false;
+    constexpr bool PER = false, MUNCH = false;
     const float *const per_weights = nullptr;
     float *const per_absdelta = nullptr;
+    const MunchArgs munch = {};
 #include "iqn_train_fwdbwd_body.h"
 }
 
@@ -1197,7 +1252,18 @@ __global__ __launch_bounds__(THREADS) void iqn_train_fwdbwd(const TrainArgs args
 // MODE_LOCAL_ONLY, so every workgroup runs the target forward of its own two batch elements and none waits for another -- with PER = true: the elements' importance
 // weights go into the loss scale and their mean |TD error| comes out.
 __global__ __launch_bounds__(THREADS) void iqn_per_fwdbwd_kernel(const TrainArgs args, const float *__restrict__ per_weights, float *__restrict__ per_absdelta) {
-    constexpr bool XCHG = false, FUSED = false, PER = true;
+    constexpr bool XCHG = false, FUSED = false, PER = true, MUNCH = false;
+    const MunchArgs munch = {};
+#include "iqn_train_fwdbwd_body.h"
+}
+
+// The step with the Munchausen target (marinenav_hip.h, mn_iqn_train_grad_munch): the body in the same form -- XCHG = FUSED = false, launched with MODE_LOCAL_ONLY and a
+// given batch -- with MUNCH = true: every workgroup runs the target network twice through its T_* buffers, over its two current states (third tau set) and over its two
+// next states, and the soft-max reduction takes td_target's place.  Everything from the loss on is the common body.
+__global__ __launch_bounds__(THREADS) void iqn_munch_fwdbwd_kernel(const TrainArgs args, const MunchArgs munch) {
+    constexpr bool XCHG = false, FUSED = false, PER = false, MUNCH = true;
+    const float *const per_weights = nullptr;
+    float *const per_absdelta = nullptr;
 #include "iqn_train_fwdbwd_body.h"
 }
 
@@ -1545,9 +1611,10 @@ __global__ __launch_bounds__(THREADS) void iqn_group_fwdbwd_kernel(const IqnGrou
     a.batch = ga.batch; a.gamma = ga.gamma;
     a.mode = MODE_LOCAL_ONLY; a.use_staged = 0;
     const TrainArgs args = a;
-    constexpr bool XCHG = false, FUSED = false, PER = false;
+    constexpr bool XCHG = false, FUSED = false, PER = false, MUNCH = false;
     const float *const per_weights = nullptr;
     float *const per_absdelta = nullptr;
+    const MunchArgs munch = {};
 #include "iqn_train_fwdbwd_body.h"
 }
 

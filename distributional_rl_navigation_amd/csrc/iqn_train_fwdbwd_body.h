@@ -1,7 +1,9 @@
 // iqn_train_fwdbwd_body.h -- the statements of one forward / backward workgroup of the IQN gradient step (csrc/iqn_train.hip), included INSIDE the kernels that
-// run them: iqn_train_fwdbwd<XCHG, FUSED>, iqn_group_fwdbwd_kernel and iqn_per_fwdbwd_kernel.  Expects in scope: `args` (const TrainArgs: the launch's arguments), the
-// compile-time constants XCHG, FUSED and PER (the weighted step of prioritized replay: `per_weights` [batch] scales each element's loss terms, `per_absdelta` [batch]
-// receives its mean |TD error|; both are named, and NULL, where PER is false), blockIdx.x = the workgroup's index in its learner's launch, and everything iqn_train.hip defines in front of its kernels.
+// run them: iqn_train_fwdbwd<XCHG, FUSED>, iqn_group_fwdbwd_kernel, iqn_per_fwdbwd_kernel and iqn_munch_fwdbwd_kernel.  Expects in scope: `args` (const TrainArgs: the launch's arguments), the
+// compile-time constants XCHG, FUSED, PER (the weighted step of prioritized replay: `per_weights` [batch] scales each element's loss terms, `per_absdelta` [batch]
+// receives its mean |TD error|; both are named, and NULL, where PER is false) and MUNCH (the Munchausen target, marinenav_hip.h: `munch` -- a MunchArgs: the third tau
+// set [batch][8], alpha, the entropy temperature, the clip bound and the optional targets_out [batch][8] -- is named, and all zero, where MUNCH is false; a MUNCH kernel
+// is launched local-only with a given batch), blockIdx.x = the workgroup's index in its learner's launch, and everything iqn_train.hip defines in front of its kernels.
 // No include guard: it is a function body, included once per kernel.
     extern __shared__ __align__(16) float S[];
     __shared__ int s_act[BE];
@@ -117,6 +119,8 @@
             tau_t = ba.taus_t[e_t];
             tau_l = ba.taus_l[e_t];
         }
+        float tau_m = 0.f;      // MUNCH: the third tau set, for the target network's pass over the CURRENT state
+        if (MUNCH) tau_m = munch.taus[e_t];
         // ---- ... then the transitions, in one straight line without branches (all threads load, clamped -- the few that matter
         // store to LDS below)
         const int g_be = (tid / OBS) & 1, g_k = tid % OBS;
@@ -128,6 +132,7 @@
         if (tid < ROWS) {
             S[S_TAU + tid] = is_target ? tau_t : tau_l;
             if (!two_roles) S[T_TAU + tid] = tau_t;
+            if (MUNCH) S[S_QT + tid] = tau_m;      // (the TD targets' slots, which nothing writes before both target passes are over)
         }
         // gathered transitions -> LDS (replay_buffer.py:42-57)
         if (tid < BE * OBS) {
@@ -229,10 +234,21 @@
         prefetch_forward(wt, VT);
         prefetch_forward_late(wt, VT);
         const PassBufs Bt = {S + T_C, nullptr, S + T_X, S + T_H2, S + T_H3, S + T_FEAT, S + T_Q};
+        if (MUNCH) {
+            // the target network on the CURRENT states (the local role's observations, the third tau set) through the same T_* buffers and weight registers; what
+            // survives into the second pass is the two bonuses, in slots of S_G that the loss phase writes only later
+            forward_pass<false>(Bt, wt, S + S_OBS, S + S_QT, nullptr, VT, -2);
+            if (tid < BE) S[S_G + tid] = munch_bonus(S + T_Q, tid, s_act[tid], munch.alpha, munch.entropy_tau, munch.clip_lo);
+        }
         forward_pass<false>(Bt, wt, S + T_OBS, S + T_TAU, nullptr, VT, -2);
         if (tid < ROWS) {
             const int be = tid >> 3;
-            S[S_QT + tid] = td_target(S + T_Q, tid, S[S_MISC + be], S[S_MISC + BE + be], gamma);
+            if (MUNCH) {
+                const float y = munch_target(S + T_Q, tid, S[S_MISC + be], S[S_MISC + BE + be], gamma, munch.entropy_tau, S[S_G + be]);
+                S[S_QT + tid] = y;
+                if (munch.targets_out) munch.targets_out[b0 * NQ + tid] = y;
+            } else
+                S[S_QT + tid] = td_target(S + T_Q, tid, S[S_MISC + be], S[S_MISC + BE + be], gamma);
         }
         __syncthreads();
     }

@@ -104,7 +104,7 @@ static int dev_info(DevInfo *out) {
         // the forward / backward kernel's dynamic LDS (97 KB) is above the default limit: raised once per device
         const void *kernels[] = {reinterpret_cast<const void *>(iqn_train_fwdbwd<false, false>), reinterpret_cast<const void *>(iqn_train_fwdbwd<false, true>),
                                  reinterpret_cast<const void *>(iqn_train_fwdbwd<true, true>), reinterpret_cast<const void *>(iqn_group_fwdbwd_kernel),
-                                 reinterpret_cast<const void *>(iqn_per_fwdbwd_kernel)};
+                                 reinterpret_cast<const void *>(iqn_per_fwdbwd_kernel), reinterpret_cast<const void *>(iqn_munch_fwdbwd_kernel)};
         for (const void *kf : kernels)
             if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) return MN_ERR_HIP;
         int a = 0, b = 0;
@@ -296,6 +296,33 @@ extern "C" int mn_iqn_train_grad_per(const float *ring_states, const float *ring
     const StepTail no_tail = {};
     hipLaunchKernelGGL(iqn_per_fwdbwd_kernel, dim3(n_part), dim3(THREADS), LDS_BYTES, s,
                        TrainArgs{ba, params_local, params_target, workspace, batch, gamma, MODE_LOCAL_ONLY, 0, no_tail}, weights_dev, absdelta_out);
+    if (hipGetLastError() != hipSuccess) return MN_ERR_HIP;
+    hipLaunchKernelGGL(iqn_grad_reduce, dim3(N_RED), dim3(RED_COLS * RED_SEG), 0, s, workspace, n_part, grad_out, loss_out, (uint64_t *)nullptr, ba, 0, (uint64_t)0);
+    return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
+}
+
+// mn_iqn_train_grad's step with the Munchausen target: the MUNCH forward / backward kernel (every workgroup two target forwards of its own two elements), then the
+// same reduction.  Nothing is launched unless every argument is valid.
+extern "C" int mn_iqn_train_grad_munch(const float *ring_states, const float *ring_next_states, const int64_t *ring_actions,
+                                       const float *ring_rewards, const float *ring_dones, const int64_t *idx_dev,
+                                       const float *taus_target_dev, const float *taus_munch_dev, const float *taus_local_dev,
+                                       const float *params_local, const float *params_target, float *workspace, float *grad_out, float *loss_out,
+                                       int32_t batch, int32_t num_taus, float gamma, float alpha, float entropy_tau, float clip_lo, float *targets_out,
+                                       void *stream) {
+    if (!ring_states || !ring_next_states || !ring_actions || !ring_rewards || !ring_dones || !idx_dev || !taus_target_dev || !taus_munch_dev ||
+        !taus_local_dev || !params_local || !params_target || !workspace || !grad_out || !loss_out)
+        return MN_ERR_INVALID;
+    if (batch <= 0 || batch > MAX_BATCH || batch % BE || num_taus != NQ) return MN_ERR_INVALID;
+    if (!std::isfinite(entropy_tau) || !(entropy_tau > 0.f) || !(clip_lo <= 0.f) || !std::isfinite(alpha) || !(alpha >= 0.f)) return MN_ERR_INVALID;
+    DevInfo dev;
+    if (int rc = dev_info(&dev)) return rc;      // (raises the kernels' dynamic LDS limit once per device)
+    const int n_part = batch / BE;
+    const BatchArgs ba = {ring_states, ring_next_states, ring_rewards, ring_dones, ring_actions, idx_dev, taus_target_dev, taus_local_dev, nullptr, 0, nullptr, nullptr};
+    hipStream_t s = (hipStream_t)stream;
+    const StepTail no_tail = {};
+    hipLaunchKernelGGL(iqn_munch_fwdbwd_kernel, dim3(n_part), dim3(THREADS), LDS_BYTES, s,
+                       TrainArgs{ba, params_local, params_target, workspace, batch, gamma, MODE_LOCAL_ONLY, 0, no_tail},
+                       MunchArgs{taus_munch_dev, alpha, entropy_tau, clip_lo, targets_out});
     if (hipGetLastError() != hipSuccess) return MN_ERR_HIP;
     hipLaunchKernelGGL(iqn_grad_reduce, dim3(N_RED), dim3(RED_COLS * RED_SEG), 0, s, workspace, n_part, grad_out, loss_out, (uint64_t *)nullptr, ba, 0, (uint64_t)0);
     return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;

@@ -8,6 +8,7 @@ the fused / pipelined gradient step.  Optional data-parallel training over RCCL:
 one flat 35 785-float gradient bucket, one all_reduce per grad step.
 """
 import json
+import math
 import os
 import random
 import sys
@@ -270,7 +271,7 @@ class IQNAgent(ReferenceLoopMixin):
                  LR=1e-4, TAU=1.0, GAMMA=0.99, UPDATE_EVERY=4, learning_starts=10000, target_update_interval=10000,
                  exploration_fraction=0.1, initial_eps=1.0, final_eps=0.05, device="cpu", seed=0,
                  distributed=False, act_chunk=8192, rank=0, n_step_mode="reference", per=False, per_alpha=0.6, per_beta0=0.4,
-                 per_eps=1e-6):
+                 per_eps=1e-6, munchausen=False, m_alpha=0.9, m_tau=0.03, m_clip=-1.0):
         self.state_size = state_size
         self.action_size = action_size
         self.device = torch.device(device)
@@ -288,6 +289,19 @@ class IQNAgent(ReferenceLoopMixin):
         if self.per and distributed:
             raise ValueError("prioritized replay (per=True) keeps one learner's priorities next to its own ring; a shared learner (distributed=True), whose ranks "
                              "average gradients of differently weighted batches, is refused")
+        # the Munchausen target (opt-in; Vieillard et al. 2020; include/marinenav_hip.h, "Munchausen target"): a soft-max policy over the target network's mean
+        # quantiles (temperature m_tau) replaces the hard max, its entropy enters the target, and m_alpha x the log-policy of the action taken, clipped to
+        # [m_clip, 0], is added to the reward.  Defaults: the paper's
+        self.munchausen, self.m_alpha, self.m_tau, self.m_clip = bool(munchausen), float(m_alpha), float(m_tau), float(m_clip)
+        if self.munchausen:
+            if not (math.isfinite(self.m_tau) and self.m_tau > 0 and self.m_clip <= 0 and math.isfinite(self.m_alpha) and self.m_alpha >= 0):
+                raise ValueError(f"munchausen=True needs m_tau > 0, m_clip <= 0 and m_alpha >= 0 (got m_tau {m_tau!r}, m_clip {m_clip!r}, m_alpha {m_alpha!r})")
+            if distributed:
+                raise ValueError("munchausen=True: the Munchausen step runs on one learner's own launches; a shared learner (distributed=True), whose exchange rides "
+                                 "in the plain step's launches, is refused")
+            if self.per:
+                raise ValueError("munchausen=True with per=True: the prioritized sampler emits two tau sets and the Munchausen step takes three; composing the two "
+                                 "is refused")
         self.learning_starts = learning_starts
         self.target_update_interval = target_update_interval
         self.exploration_fraction = exploration_fraction
@@ -569,16 +583,34 @@ class IQNAgent(ReferenceLoopMixin):
             g.copy_(self._flat[off:off + g.numel()].view_as(g))
             off += g.numel()
 
-    def compute_loss(self, experiences, taus_target=None, taus_local=None, weights=None, want_abs_td=False):
-        """Quantile-Huber TD loss of agent.py:276-295 (taus can be injected for tests).  `weights` [B]: element b's terms scaled by weights[b] (prioritized
-        replay's importance weights; ones give the unweighted loss bit for bit).  `want_abs_td`: return (loss, mean |TD error| per element [B], detached) --
-        the elements' new priorities."""
+    def td_targets(self, experiences, taus_target=None, taus_munch=None):
+        """The TD targets Q_targets [B, 1, N] of `compute_loss`, without a graph.  Plain (agent.py:279-283): r + gamma^n (1 - done) max_a Z_target(s', tau_j)[a].
+        With `munchausen` (include/marinenav_hip.h, "Munchausen target", states the rule operation by operation): the policy is the soft-max, at temperature
+        m_tau, of the target network's MEAN over its N quantile samples; the target takes its expectation of Z' minus m_tau x its log, and the reward gains
+        m_alpha x the log-policy of the action taken at the current state, clipped to [m_clip, 0] -- from a second forward of the TARGET network, over `states`
+        with a tau set of its own (`taus_munch`).  The target network's calls run in that order: next states, then states."""
         states, actions, rewards, next_states, dones = experiences
-        B = states.shape[0]
         with torch.no_grad():
             Q_targets_next, _ = self.qnetwork_target(next_states, self.N, taus=taus_target)
-            Q_targets_next = Q_targets_next.max(2)[0].unsqueeze(1)                          # (B, 1, N)
-            Q_targets = rewards.unsqueeze(-1) + (self.GAMMA ** self.n_step * Q_targets_next * (1. - dones.unsqueeze(-1)))
+            if not self.munchausen:
+                Q_targets_next = Q_targets_next.max(2)[0].unsqueeze(1)                          # (B, 1, N)
+                return rewards.unsqueeze(-1) + (self.GAMMA ** self.n_step * Q_targets_next * (1. - dones.unsqueeze(-1)))
+            te = self.m_tau
+            q_next = Q_targets_next.mean(dim=1) / te                                                       # (B, A)
+            tlp_next, pi_next = te * torch.log_softmax(q_next, dim=1), torch.softmax(q_next, dim=1)         # te log pi', pi'
+            V = (pi_next.unsqueeze(1) * (Q_targets_next - tlp_next.unsqueeze(1))).sum(2).unsqueeze(1)       # (B, 1, N)
+            Q_now, _ = self.qnetwork_target(states, self.N, taus=taus_munch)
+            tlp = te * torch.log_softmax(Q_now.mean(dim=1) / te, dim=1)
+            bonus = self.m_alpha * tlp.gather(1, actions).clamp(min=self.m_clip, max=0.0)                  # (B, 1)
+            return (rewards + bonus).unsqueeze(-1) + (self.GAMMA ** self.n_step * V * (1. - dones.unsqueeze(-1)))
+
+    def compute_loss(self, experiences, taus_target=None, taus_local=None, weights=None, want_abs_td=False, taus_munch=None, want_targets=False):
+        """Quantile-Huber TD loss of agent.py:276-295 (taus can be injected for tests).  `weights` [B]: element b's terms scaled by weights[b] (prioritized
+        replay's importance weights; ones give the unweighted loss bit for bit).  `want_abs_td`: return (loss, mean |TD error| per element [B], detached) --
+        the elements' new priorities.  `taus_munch`: the third tau set of the Munchausen target (`td_targets`); `want_targets`: return (loss, Q_targets [B, N])."""
+        states, actions, rewards, next_states, dones = experiences
+        B = states.shape[0]
+        Q_targets = self.td_targets(experiences, taus_target, taus_munch)
         Q_expected, taus = self.qnetwork_local(states, self.N, taus=taus_local)
         Q_expected = Q_expected.gather(2, actions.unsqueeze(-1).expand(B, self.N, 1))
         # td_error[b, i, j] = Q_targets[b, 0, j] - Q_expected[b, i, 0]   (B, N, N); Huber with kappa = 1
@@ -594,6 +626,8 @@ class IQNAgent(ReferenceLoopMixin):
         loss = terms.sum() / (B * self.N)
         if want_abs_td:
             return loss, (qt - qe).detach().abs().mean(dim=(1, 2))
+        if want_targets:
+            return loss, Q_targets.view(B, self.N)
         return loss
 
     def _fused_trainer(self):
@@ -622,6 +656,9 @@ class IQNAgent(ReferenceLoopMixin):
         vector step need to stay ahead of the GPU.  Same arithmetic, same generator stream: bit-identical to the eager calls."""
         # (while the ring is still filling its row count changes with every vector step and each change would be a re-capture +
         # device synchronisation: the eager steps -- bit-identical -- run until the ring is full)
+        if self.munchausen and self.use_fused_graph:
+            raise ValueError("munchausen=True: the Munchausen step samples three tau sets and steps in launches of its own; the captured graph of `use_fused_graph`, "
+                             "which replays the plain step's in-launch draws, is refused")
         if self.per and self.use_fused_graph:
             raise ValueError("prioritized replay (per=True) samples, steps and updates priorities as separate launches per gradient step; the captured graph of "
                              "`use_fused_graph`, which replays in-launch uniform draws, is refused")
@@ -646,6 +683,15 @@ class IQNAgent(ReferenceLoopMixin):
         straight from the device ring (no sampled copies).  With `per`: `_train_prioritized`."""
         if self.per:
             return self._train_prioritized()
+        if self.munchausen and self.use_fused_train and self.device.type == "cuda":
+            # one sampling launch (rows + three tau sets), the Munchausen forward / backward + reduction, clip + Adam
+            m = self.memory
+            ft = self._fused_trainer()
+            self._enter_train_path("hip")
+            idx, taus = ft.sample(m.size, self.BATCH_SIZE, tau_sets=3)
+            loss = ft.step_munch((m.states, m.actions, m.rewards, m.next_states, m.dones), idx, taus[0], taus[1], taus[2])
+            self.grad_steps += 1
+            return loss
         if self.use_fused_train and self.device.type == "cuda":
             m = self.memory
             ft = self._fused_trainer()
@@ -688,12 +734,25 @@ class IQNAgent(ReferenceLoopMixin):
         self.grad_steps += 1
         return loss
 
-    def train(self, experiences, taus_target=None, taus_local=None):
+    def train(self, experiences, taus_target=None, taus_local=None, taus_munch=None):
         """agent.py:269-304: one optimizer step; returns the loss (device scalar tensor).
         GPU tensors with `use_fused_train` (the default on the GPU): the hand-written HIP step (csrc/iqn_train.hip:
         both forwards, quantile-Huber loss, backward, clip, Adam in four launches).  Otherwise PyTorch autograd +
         torch.optim.Adam -- the definition the HIP step is tested against and the only path on the CPU; with
         `use_train_graph` (opt-in, single learner, taus not injected) replayed from one captured hipGraph."""
+        if self.munchausen and self.use_train_graph:
+            raise ValueError("munchausen=True: `use_train_graph` captured the plain step's graph; the Munchausen target has no captured form and is refused")
+        if self.munchausen and self.use_fused_train and experiences[0].is_cuda:
+            exp = tuple(t.contiguous() for t in experiences)
+            ft = self._fused_trainer()
+            self._enter_train_path("hip")
+            B = exp[0].shape[0]
+            taus = torch.rand(3, B, self.N, device=self.device)      # model.py:149 per network call: target(s'), target(s), local(s)
+            tt, tm, tl = (taus[k] if t is None else t.to(self.device, torch.float32).contiguous().view(B, self.N)
+                          for k, t in enumerate((taus_target, taus_munch, taus_local)))
+            loss = ft.step_munch(exp, torch.arange(B, dtype=torch.int64, device=self.device), tt, tm, tl)
+            self.grad_steps += 1
+            return loss
         if self.use_fused_train and experiences[0].is_cuda:
             exp = tuple(t.contiguous() for t in experiences)
             ft = self._fused_trainer()
@@ -706,7 +765,7 @@ class IQNAgent(ReferenceLoopMixin):
                 and taus_target is None and taus_local is None and experiences[0].shape[0] == self.BATCH_SIZE):
             return self._train_graphed(experiences)
         self.optimizer.zero_grad(set_to_none=False)
-        loss = self.compute_loss(experiences, taus_target, taus_local)
+        loss = self.compute_loss(experiences, taus_target, taus_local, taus_munch=taus_munch)
         loss.backward()
         if self.distributed:
             self._allreduce_grads()          # average first, then clip: same as one big-batch learner

@@ -65,6 +65,7 @@ class FusedTrainer:
                                       device=self.device)
         self.rng_state[0] += 0x9E3779B1 * int(getattr(agent, "rank", 0))     # decorrelate the ranks of a shared learner
         self._idx, self._taus = {}, {}
+        self._draw3, self._targets = {}, {}      # the Munchausen step: (idx, three tau sets) per batch size; y [B, 8] when asked for
         self._arange = {}
         off = 0
         for p in agent.qnetwork_local.parameters():      # p.grad = the (clipped) gradient of the last step, as torch
@@ -133,13 +134,22 @@ class FusedTrainer:
             self._mailbox.detach(self._ws, batch)      # back on the collective / single-learner path: stop publishing
         return self._ws
 
-    def sample(self, ring_size, batch):
-        """ReplayBuffer.sample's index draw + the step's tau draws in ONE kernel -> (idx [B] i64, taus [2, B, 8])."""
+    def sample(self, ring_size, batch, tau_sets=2):
+        """ReplayBuffer.sample's index draw + the step's tau draws in ONE kernel -> (idx [B] i64, taus [tau_sets, B, 8]).  `tau_sets=3` (the Munchausen step): the
+        same call draws `sample_tau(base, 2 B 8 + e)` as a third set behind the two any step takes, which it leaves as they are; the call counter advances once."""
+        if tau_sets not in (2, 3):
+            raise ValueError(f"tau_sets must be 2 or 3, not {tau_sets!r}")
         self._staged_key = None      # the call counter moves on: a staged batch belongs to a counter that is skipped
-        if batch not in self._idx:
-            self._idx[batch] = torch.empty(batch, dtype=torch.int64, device=self.device)
-            self._taus[batch] = torch.empty(2, batch, self.agent.N, dtype=torch.float32, device=self.device)
-        idx, taus = self._idx[batch], self._taus[batch]
+        if tau_sets == 3:      # (a draw of its own: the two-set pair below is also what step_sampled and the grouped launches write into)
+            if batch not in self._draw3:
+                self._draw3[batch] = (torch.empty(batch, dtype=torch.int64, device=self.device),
+                                      torch.empty(3, batch, self.agent.N, dtype=torch.float32, device=self.device))
+            idx, taus = self._draw3[batch]
+        else:
+            if batch not in self._idx:
+                self._idx[batch] = torch.empty(batch, dtype=torch.int64, device=self.device)
+                self._taus[batch] = torch.empty(2, batch, self.agent.N, dtype=torch.float32, device=self.device)
+            idx, taus = self._idx[batch], self._taus[batch]
         stream = _capi.stream_ptr(self.device)
         rc = _capi.lib().mn_iqn_sample(int(ring_size), batch, _p(self.rng_state), _p(idx), _p(taus), taus.numel(), stream)
         if rc:
@@ -155,6 +165,9 @@ class FusedTrainer:
         has not been written since (MN_TRAIN_USE_STAGED) -- same batch, same result, one memory round trip at the head of the
         launch instead of three."""
         ag = self.agent
+        if getattr(ag, "munchausen", False):
+            raise ValueError("munchausen=True: the Munchausen target needs a third tau set and a second target forward (FusedTrainer.step_munch); step_sampled, "
+                             "the draw inside the launch, is refused")
         if getattr(ag, "per", False):
             raise ValueError("prioritized replay (per=True) draws its batch from the priority store (IQNAgent.train_from_memory); the uniform draw inside the "
                              "launch and its staged batches are refused")
@@ -360,6 +373,34 @@ class FusedTrainer:
         if rc:
             raise _capi.MarineNavHipError(f"mn_iqn_train_grad_per failed ({rc}): need an even batch <= 1024")
         return self._finish_step(B), self._absdelta[B]
+
+    def step_munch(self, ring, idx, taus_target, taus_munch, taus_local, want_targets=False):
+        """One optimizer step with the Munchausen target (marinenav_hip.h) on the batch rows `idx` [B] i64 with three tau sets [B, 8] f32 (what
+        `sample(tau_sets=3)` returns: target network on s', target network on s, local network on s): mn_iqn_train_grad_munch with the agent's `m_alpha`, `m_tau`,
+        `m_clip` and gamma ** n_step, then clip + Adam as ever.  Returns the loss, or with `want_targets` (loss, y [B, 8] f32); views of buffers the next step
+        overwrites."""
+        ag = self.agent
+        states, actions, rewards, next_states, dones = ring
+        for t in ring + (idx, taus_target, taus_munch, taus_local):
+            assert t.is_cuda and t.is_contiguous()
+        assert states.dtype == torch.float32 and actions.dtype == torch.int64 and dones.dtype == torch.float32
+        assert idx.dtype == torch.int64 and taus_target.dtype == torch.float32 and taus_munch.dtype == torch.float32 and taus_local.dtype == torch.float32
+        B = idx.shape[0]
+        assert taus_target.numel() == B * ag.N and taus_munch.numel() == B * ag.N and taus_local.numel() == B * ag.N
+        y = None
+        if want_targets:
+            if B not in self._targets:
+                self._targets[B] = torch.zeros(B, ag.N, dtype=torch.float32, device=self.device)
+            y = self._targets[B]
+        self._staged_key = None
+        rc = _capi.lib().mn_iqn_train_grad_munch(_p(states), _p(next_states), _p(actions), _p(rewards), _p(dones), _p(idx), _p(taus_target), _p(taus_munch),
+                                                 _p(taus_local), _p(self.local), _p(self.target), _p(self._workspace(B)), _p(self.grad), _p(self.loss), B, ag.N,
+                                                 C.c_float(ag.GAMMA ** ag.n_step), C.c_float(ag.m_alpha), C.c_float(ag.m_tau), C.c_float(ag.m_clip),
+                                                 _p(y) if y is not None else None, _capi.stream_ptr(self.device))
+        if rc:
+            raise _capi.MarineNavHipError(f"mn_iqn_train_grad_munch failed ({rc}): need an even batch <= 1024, m_tau > 0, m_clip <= 0, m_alpha >= 0")
+        loss = self._finish_step(B)
+        return (loss, y) if want_targets else loss
 
     def _finish_step(self, B):
         """Gradient in self.grad -> (shared learner: all-reduce) -> clip + Adam -> loss."""

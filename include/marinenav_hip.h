@@ -900,6 +900,32 @@ int mn_per_sample(const uint32_t *mass, const uint64_t *block_sums, int64_t size
 int mn_per_update(uint32_t *mass, uint64_t *block_sums, uint32_t *mmax, const int64_t *idx_dev, const float *absdelta_dev, int32_t batch,
                   float alpha, float eps, int64_t capacity, void *stream);
 
+/* ---- Munchausen target ---------------------------------------------------------------------------
+ * The TD target of Munchausen-IQN (Vieillard et al. 2020), opt-in: mn_iqn_train_grad_munch forms y[b, j] by the rule below; loss,
+ * backward, reduction, clip and Adam are mn_iqn_train_grad's.  Per batch element b: reward r, done, the action taken a_b, three tau
+ * sets tt[b, j], tm[b, j], tl[b, i] (i, j < 8), and with the TARGET weights
+ *     Z'[j][a] = Z_target(s'_b, tt[b, j])[a]          the next state, as in mn_iqn_train_grad
+ *     Z[j][a]  = Z_target(s_b,  tm[b, j])[a]          one more forward: the target network on the CURRENT state
+ * Scalars: alpha >= 0, the entropy temperature te = entropy_tau > 0, the clip bound lo = clip_lo <= 0, gamma (the caller passes
+ * gamma ** n_step).  All arithmetic is float32; sums run in index order from the first term; `/ te` is a float32 DIVISION by te (no
+ * reciprocal is formed); the two divisions by E are divisions too.  For the next state:
+ *     q'[a]   = 0.125f * (Z'[0][a] + Z'[1][a] + ... + Z'[7][a])
+ *     d'[a]   = q'[a] - max_a q'
+ *     e'[a]   = expf(d'[a] / te)
+ *     E'      = e'[0] + e'[1] + ... + e'[8]
+ *     tlp'[a] = d'[a] - te * logf(E')
+ *     pi'[a]  = e'[a] / E'
+ *     V[j]    = sum_a pi'[a] * (Z'[j][a] - tlp'[a])             from 0.0f; product and sum round separately
+ * For the current state q, d, E, tlp from Z in the same way, and
+ *     bonus   = alpha * fminf(fmaxf(tlp[a_b], lo), 0.0f)
+ *     y[b, j] = fmaf(gamma * V[j], 1.0f - done, r + bonus)
+ * then td[b, i, j] = y[b, j] - Z_local(s_b, tl[b, i])[a_b] and the quantile-Huber loss as in mn_iqn_train_grad.  The policy comes
+ * from the MEAN over the 8 quantile samples, so for te -> 0 the target tends to Z'[j][argmax_a q'], not to mn_iqn_train_grad's
+ * per-sample max_a Z'[j][a].  There is one instruction sequence per output: alpha == 0 and done == 1 take no other path (with every
+ * row done and alpha == 0, y == r and the step is mn_iqn_train_grad's bit for bit).  expf and logf differ between device and host
+ * by units in the last place, so this rule has no bit-exact host twin: tests hold it to float64 by eager float32's own error.
+ * Every workgroup runs both target forwards of its own two batch elements (no workgroup waits for another). */
+
 /* ---- training episode log ----------------------------------------------------------------------
  * The record the reference prints at every training episode end (thirdparty/IQN/agent.py:118-119, 152-168) for the n envs of a
  * vector step, in one launch that needs no env handle and no host look.  reward_dev [n] f32, done_dev / info_dev [n] u8 are a
@@ -1285,6 +1311,18 @@ int mn_iqn_train_grad_per(const float *ring_states, const float *ring_next_state
                           const float *taus_target_dev, const float *taus_local_dev, const float *params_local,
                           const float *params_target, float *workspace, float *grad_out, float *loss_out, int32_t batch,
                           int32_t num_taus, float gamma, const float *weights_dev, float *absdelta_out, void *stream);
+/* mn_iqn_train_grad with the Munchausen target ("Munchausen target" above): taus_munch_dev [batch][8] is the third tau set (the
+ * target network's pass over the current states; elements [2 B 8, 3 B 8) of an mn_iqn_sample call with n_taus_total = 3 B 8),
+ * gamma is gamma ** n_step.  targets_out [batch][8] f32 receives y (NULL: not written; the gradient's bits do not depend on it).
+ * mn_iqn_grad_reduce's sum and mn_iqn_train_adam follow unchanged.  MN_ERR_INVALID, with nothing launched: an odd batch or one
+ * outside 2..1024, num_taus != 8, entropy_tau not finite or not above 0, clip_lo above 0 or NaN, alpha negative or not finite,
+ * a NULL pointer other than targets_out. */
+int mn_iqn_train_grad_munch(const float *ring_states, const float *ring_next_states, const int64_t *ring_actions,
+                            const float *ring_rewards, const float *ring_dones, const int64_t *idx_dev,
+                            const float *taus_target_dev, const float *taus_munch_dev, const float *taus_local_dev,
+                            const float *params_local, const float *params_target, float *workspace, float *grad_out, float *loss_out,
+                            int32_t batch, int32_t num_taus, float gamma, float alpha, float entropy_tau, float clip_lo,
+                            float *targets_out, void *stream);
 /* The same gradient step with the batch drawn inside the launch: every workgroup of the forward / backward kernel evaluates
  * mn_iqn_sample's permutation for its own two slots (and its own taus) from {seed, call counter}, so there is no sampling launch.
  * Bit-identical to mn_iqn_sample followed by mn_iqn_train_grad from the same state; the call counter is advanced once (by the
