@@ -252,6 +252,7 @@ SIGNATURES = [
     ("mn_iqn_train_grad", C.c_int, [_vp] * 13 + [_i32, _i32, C.c_float, _vp]),
     ("mn_iqn_train_grad_per", C.c_int, [_vp] * 13 + [_i32, _i32, C.c_float, _vp, _vp, _vp]),
     ("mn_iqn_train_grad_munch", C.c_int, [_vp] * 14 + [_i32, _i32, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),
+    ("mn_iqn_train_grad_rule", C.c_int, [_vp] * 14 + [_i32, _i32, C.c_float, _i32, _vp, _vp, _vp]),
     ("mn_per_append", C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     ("mn_per_sample", C.c_int, [_vp, _vp, _i64, _i64, _i32, C.c_float] + [_vp] * 5),
     ("mn_per_update", C.c_int, [_vp] * 5 + [_i32, C.c_float, C.c_float, _i64, _vp]),

@@ -515,6 +515,34 @@ struct MunchArgs {
     float *targets_out;     // [batch][8] y, or NULL
 };
 
+// ---- the greedy-on-mean and Double-IQN targets ("Target rules" in marinenav_hip.h states the rule operation by operation) -------------------------------------
+constexpr int RULE_MEAN = 1, RULE_DOUBLE = 2;      // = MN_TARGET_MEAN, MN_TARGET_DOUBLE
+// a* of batch element `be`: the FIRST action that attains the maximum of the MEAN of its 8 quantile rows of q [16][12] in LDS (munch_policy's sum; replaced only
+// on strictly greater).  Each thread that needs the choice evaluates it itself.
+__device__ __forceinline__ int rule_choice(const float *q, int be) {
+    int best = 0;
+    float m = 0.f;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+        float s = q[be * NQ * 12 + a];
+#pragma unroll
+        for (int j = 1; j < NQ; ++j) s = s + q[(be * NQ + j) * 12 + a];
+        const float d = 0.125f * s;
+        if (a == 0) m = d;
+        else if (d > m) { m = d; best = a; }
+    }
+    return best;
+}
+// y of row `row`: td_target's last line with the chosen action's quantile in place of the row maximum
+__device__ __forceinline__ float rule_target(const float *q, int row, int a_star, float rew, float done, float gamma) {
+    return fmaf(gamma * q[row * 12 + a_star], 1.f - done, rew);
+}
+struct RuleArgs {
+    const float *taus;      // [batch][8] the third tau set (RULE_DOUBLE: the selecting pass), unread under RULE_MEAN
+    float *targets_out;     // [batch][8] y, or NULL
+    int32_t *select_out;    // [batch] a*, or NULL
+};
+
 struct BatchArgs {
     const float *ring_s, *ring_ns, *ring_r, *ring_d;
     const int64_t *ring_a;
@@ -1242,9 +1270,11 @@ __device__ __forceinline__ StepTail ld_step_tail(TrainArgsK A) {
 template <bool XCHG, bool FUSED>
 __global__ __launch_bounds__(THREADS) void iqn_train_fwdbwd(const TrainArgs args) {
     constexpr bool PER = false, MUNCH = false;
+    constexpr int RULE = 0;
     const float *const per_weights = nullptr;
     float *const per_absdelta = nullptr;
     const MunchArgs munch = {};
+    const RuleArgs rule = {};
 #include "iqn_train_fwdbwd_body.h"
 }
 
@@ -1253,7 +1283,9 @@ __global__ __launch_bounds__(THREADS) void iqn_train_fwdbwd(const TrainArgs args
 // weights go into the loss scale and their mean |TD error| comes out.
 __global__ __launch_bounds__(THREADS) void iqn_per_fwdbwd_kernel(const TrainArgs args, const float *__restrict__ per_weights, float *__restrict__ per_absdelta) {
     constexpr bool XCHG = false, FUSED = false, PER = true, MUNCH = false;
+    constexpr int RULE = 0;
     const MunchArgs munch = {};
+    const RuleArgs rule = {};
 #include "iqn_train_fwdbwd_body.h"
 }
 
@@ -1262,8 +1294,24 @@ __global__ __launch_bounds__(THREADS) void iqn_per_fwdbwd_kernel(const TrainArgs
 // next states, and the soft-max reduction takes td_target's place.  Everything from the loss on is the common body.
 __global__ __launch_bounds__(THREADS) void iqn_munch_fwdbwd_kernel(const TrainArgs args, const MunchArgs munch) {
     constexpr bool XCHG = false, FUSED = false, PER = false, MUNCH = true;
+    constexpr int RULE = 0;
     const float *const per_weights = nullptr;
     float *const per_absdelta = nullptr;
+    const RuleArgs rule = {};
+#include "iqn_train_fwdbwd_body.h"
+}
+
+// The step with a greedy-on-mean target (marinenav_hip.h, mn_iqn_train_grad_rule): the body in the Munchausen kernel's form -- XCHG = FUSED = false, launched with
+// MODE_LOCAL_ONLY and a given batch -- with RULE = RULE_MEAN (one target forward; the argmax of the target network's mean quantiles picks the action whose quantile
+// every sample bootstraps from) or RULE_DOUBLE (the LOCAL weights run over the next states first, with the third tau set, and pick the action; then the target
+// forward values it).  Two instantiations, not a runtime switch, under which the weight registers of the target side would have two defining sites on one path only.
+// Everything from the loss on is the common body.
+template <int RULE>
+__global__ __launch_bounds__(THREADS) void iqn_rule_fwdbwd_kernel(const TrainArgs args, const RuleArgs rule) {
+    constexpr bool XCHG = false, FUSED = false, PER = false, MUNCH = false;
+    const float *const per_weights = nullptr;
+    float *const per_absdelta = nullptr;
+    const MunchArgs munch = {};
 #include "iqn_train_fwdbwd_body.h"
 }
 
@@ -1612,9 +1660,11 @@ __global__ __launch_bounds__(THREADS) void iqn_group_fwdbwd_kernel(const IqnGrou
     a.mode = MODE_LOCAL_ONLY; a.use_staged = 0;
     const TrainArgs args = a;
     constexpr bool XCHG = false, FUSED = false, PER = false, MUNCH = false;
+    constexpr int RULE = 0;
     const float *const per_weights = nullptr;
     float *const per_absdelta = nullptr;
     const MunchArgs munch = {};
+    const RuleArgs rule = {};
 #include "iqn_train_fwdbwd_body.h"
 }
 

@@ -1,9 +1,11 @@
 // iqn_train_fwdbwd_body.h -- the statements of one forward / backward workgroup of the IQN gradient step (csrc/iqn_train.hip), included INSIDE the kernels that
-// run them: iqn_train_fwdbwd<XCHG, FUSED>, iqn_group_fwdbwd_kernel, iqn_per_fwdbwd_kernel and iqn_munch_fwdbwd_kernel.  Expects in scope: `args` (const TrainArgs: the launch's arguments), the
+// run them: iqn_train_fwdbwd<XCHG, FUSED>, iqn_group_fwdbwd_kernel, iqn_per_fwdbwd_kernel, iqn_munch_fwdbwd_kernel and iqn_rule_fwdbwd_kernel<RULE>.  Expects in scope: `args` (const TrainArgs: the launch's arguments), the
 // compile-time constants XCHG, FUSED, PER (the weighted step of prioritized replay: `per_weights` [batch] scales each element's loss terms, `per_absdelta` [batch]
 // receives its mean |TD error|; both are named, and NULL, where PER is false) and MUNCH (the Munchausen target, marinenav_hip.h: `munch` -- a MunchArgs: the third tau
 // set [batch][8], alpha, the entropy temperature, the clip bound and the optional targets_out [batch][8] -- is named, and all zero, where MUNCH is false; a MUNCH kernel
-// is launched local-only with a given batch), blockIdx.x = the workgroup's index in its learner's launch, and everything iqn_train.hip defines in front of its kernels.
+// is launched local-only with a given batch) and RULE (0: the per-sample max; RULE_MEAN / RULE_DOUBLE: the greedy-on-mean targets, marinenav_hip.h "Target rules":
+// `rule` -- a RuleArgs: the third tau set [batch][8] of RULE_DOUBLE and the optional targets_out [batch][8] and select_out [batch] -- is named, and all zero, where
+// RULE is 0; launched as a MUNCH kernel is), blockIdx.x = the workgroup's index in its learner's launch, and everything iqn_train.hip defines in front of its kernels.
 // No include guard: it is a function body, included once per kernel.
     extern __shared__ __align__(16) float S[];
     __shared__ int s_act[BE];
@@ -121,6 +123,7 @@
         }
         float tau_m = 0.f;      // MUNCH: the third tau set, for the target network's pass over the CURRENT state
         if (MUNCH) tau_m = munch.taus[e_t];
+        if (RULE == RULE_DOUBLE) tau_m = rule.taus[e_t];      // the third tau set, for the LOCAL network's selecting pass over the NEXT state
         // ---- ... then the transitions, in one straight line without branches (all threads load, clamped -- the few that matter
         // store to LDS below)
         const int g_be = (tid / OBS) & 1, g_k = tid % OBS;
@@ -132,7 +135,7 @@
         if (tid < ROWS) {
             S[S_TAU + tid] = is_target ? tau_t : tau_l;
             if (!two_roles) S[T_TAU + tid] = tau_t;
-            if (MUNCH) S[S_QT + tid] = tau_m;      // (the TD targets' slots, which nothing writes before both target passes are over)
+            if (MUNCH || RULE == RULE_DOUBLE) S[S_QT + tid] = tau_m;      // (the TD targets' slots, which nothing writes before both target passes are over)
         }
         // gathered transitions -> LDS (replay_buffer.py:42-57)
         if (tid < BE * OBS) {
@@ -231,6 +234,16 @@
         }
         FwdWeights wt;
         const ParamView VT(PT);
+        if (RULE == RULE_DOUBLE) {
+            // the selecting pass: the LOCAL weights on the NEXT states (the target role's observations, the third tau set) through the same T_* buffers and weight
+            // registers; what survives is the two chosen actions, as bits in slots of S_G that the loss phase writes only later.  Then the registers are
+            // re-requested from the target's parameters
+            prefetch_forward(wt, VL);
+            prefetch_forward_late(wt, VL);
+            const PassBufs Bs = {S + T_C, nullptr, S + T_X, S + T_H2, S + T_H3, S + T_FEAT, S + T_Q};
+            forward_pass<false>(Bs, wt, S + T_OBS, S + S_QT, nullptr, VL, -2);
+            if (tid < BE) S[S_G + tid] = __int_as_float(rule_choice(S + T_Q, tid));
+        }
         prefetch_forward(wt, VT);
         prefetch_forward_late(wt, VT);
         const PassBufs Bt = {S + T_C, nullptr, S + T_X, S + T_H2, S + T_H3, S + T_FEAT, S + T_Q};
@@ -247,6 +260,12 @@
                 const float y = munch_target(S + T_Q, tid, S[S_MISC + be], S[S_MISC + BE + be], gamma, munch.entropy_tau, S[S_G + be]);
                 S[S_QT + tid] = y;
                 if (munch.targets_out) munch.targets_out[b0 * NQ + tid] = y;
+            } else if (RULE) {
+                const int a_star = RULE == RULE_DOUBLE ? __float_as_int(S[S_G + be]) : rule_choice(S + T_Q, be);
+                const float y = rule_target(S + T_Q, tid, a_star, S[S_MISC + be], S[S_MISC + BE + be], gamma);
+                S[S_QT + tid] = y;
+                if (rule.targets_out) rule.targets_out[b0 * NQ + tid] = y;
+                if (rule.select_out && (tid & (NQ - 1)) == 0) rule.select_out[b0 + be] = a_star;
             } else
                 S[S_QT + tid] = td_target(S + T_Q, tid, S[S_MISC + be], S[S_MISC + BE + be], gamma);
         }

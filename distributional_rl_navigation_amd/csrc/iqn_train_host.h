@@ -104,7 +104,8 @@ static int dev_info(DevInfo *out) {
         // the forward / backward kernel's dynamic LDS (97 KB) is above the default limit: raised once per device
         const void *kernels[] = {reinterpret_cast<const void *>(iqn_train_fwdbwd<false, false>), reinterpret_cast<const void *>(iqn_train_fwdbwd<false, true>),
                                  reinterpret_cast<const void *>(iqn_train_fwdbwd<true, true>), reinterpret_cast<const void *>(iqn_group_fwdbwd_kernel),
-                                 reinterpret_cast<const void *>(iqn_per_fwdbwd_kernel), reinterpret_cast<const void *>(iqn_munch_fwdbwd_kernel)};
+                                 reinterpret_cast<const void *>(iqn_per_fwdbwd_kernel), reinterpret_cast<const void *>(iqn_munch_fwdbwd_kernel),
+                                 reinterpret_cast<const void *>(iqn_rule_fwdbwd_kernel<RULE_MEAN>), reinterpret_cast<const void *>(iqn_rule_fwdbwd_kernel<RULE_DOUBLE>)};
         for (const void *kf : kernels)
             if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) return MN_ERR_HIP;
         int a = 0, b = 0;
@@ -323,6 +324,37 @@ extern "C" int mn_iqn_train_grad_munch(const float *ring_states, const float *ri
     hipLaunchKernelGGL(iqn_munch_fwdbwd_kernel, dim3(n_part), dim3(THREADS), LDS_BYTES, s,
                        TrainArgs{ba, params_local, params_target, workspace, batch, gamma, MODE_LOCAL_ONLY, 0, no_tail},
                        MunchArgs{taus_munch_dev, alpha, entropy_tau, clip_lo, targets_out});
+    if (hipGetLastError() != hipSuccess) return MN_ERR_HIP;
+    hipLaunchKernelGGL(iqn_grad_reduce, dim3(N_RED), dim3(RED_COLS * RED_SEG), 0, s, workspace, n_part, grad_out, loss_out, (uint64_t *)nullptr, ba, 0, (uint64_t)0);
+    return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
+}
+
+// mn_iqn_train_grad's step with a greedy-on-mean target ("Target rules" in marinenav_hip.h): the RULE forward / backward kernel of `rule` (MN_TARGET_MEAN: one target
+// forward per workgroup; MN_TARGET_DOUBLE: the local weights' selecting pass over the next states first), then the same reduction.  Nothing is launched unless every
+// argument is valid; the per-sample max (rule 0) has mn_iqn_train_grad.
+static_assert(RULE_MEAN == MN_TARGET_MEAN && RULE_DOUBLE == MN_TARGET_DOUBLE, "the kernels' rule constants are the header's");
+extern "C" int mn_iqn_train_grad_rule(const float *ring_states, const float *ring_next_states, const int64_t *ring_actions,
+                                      const float *ring_rewards, const float *ring_dones, const int64_t *idx_dev,
+                                      const float *params_local, const float *params_target, float *workspace, float *grad_out, float *loss_out,
+                                      const float *taus_target_dev, const float *taus_select_dev, const float *taus_local_dev,
+                                      int32_t batch, int32_t num_taus, float gamma, int32_t rule, float *targets_out, int32_t *select_out, void *stream) {
+    if (rule != MN_TARGET_MEAN && rule != MN_TARGET_DOUBLE) return MN_ERR_INVALID;
+    if (!ring_states || !ring_next_states || !ring_actions || !ring_rewards || !ring_dones || !idx_dev || !taus_target_dev || !taus_local_dev ||
+        !params_local || !params_target || !workspace || !grad_out || !loss_out || (rule == MN_TARGET_DOUBLE && !taus_select_dev))
+        return MN_ERR_INVALID;
+    if (batch <= 0 || batch > MAX_BATCH || batch % BE || num_taus != NQ) return MN_ERR_INVALID;
+    DevInfo dev;
+    if (int rc = dev_info(&dev)) return rc;      // (raises the kernels' dynamic LDS limit once per device)
+    const int n_part = batch / BE;
+    const BatchArgs ba = {ring_states, ring_next_states, ring_rewards, ring_dones, ring_actions, idx_dev, taus_target_dev, taus_local_dev, nullptr, 0, nullptr, nullptr};
+    hipStream_t s = (hipStream_t)stream;
+    const StepTail no_tail = {};
+    const TrainArgs ta = {ba, params_local, params_target, workspace, batch, gamma, MODE_LOCAL_ONLY, 0, no_tail};
+    const RuleArgs ra = {rule == MN_TARGET_DOUBLE ? taus_select_dev : nullptr, targets_out, select_out};
+    if (rule == MN_TARGET_DOUBLE)
+        hipLaunchKernelGGL(iqn_rule_fwdbwd_kernel<RULE_DOUBLE>, dim3(n_part), dim3(THREADS), LDS_BYTES, s, ta, ra);
+    else
+        hipLaunchKernelGGL(iqn_rule_fwdbwd_kernel<RULE_MEAN>, dim3(n_part), dim3(THREADS), LDS_BYTES, s, ta, ra);
     if (hipGetLastError() != hipSuccess) return MN_ERR_HIP;
     hipLaunchKernelGGL(iqn_grad_reduce, dim3(N_RED), dim3(RED_COLS * RED_SEG), 0, s, workspace, n_part, grad_out, loss_out, (uint64_t *)nullptr, ba, 0, (uint64_t)0);
     return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;

@@ -30,6 +30,13 @@ def calculate_huber_loss(td_errors, k=1.0):
     return torch.where(td_errors.abs() <= k, 0.5 * td_errors.pow(2), k * (td_errors.abs() - 0.5 * k))
 
 
+def first_argmax(q):
+    """The LOWEST index that attains each row's maximum of q [B, A] -> [B] i64 (torch.argmax does not promise which of several equal maxima it returns)."""
+    A = q.shape[1]
+    idx = torch.arange(A, device=q.device).expand_as(q)
+    return torch.where(q == q.max(1, keepdim=True)[0], idx, torch.full_like(idx, A)).min(1)[0]
+
+
 class UnderActGuard:
     """Keeps `IQNAgent.reset_under_act` honest on the box the loop actually runs on.
 
@@ -271,7 +278,7 @@ class IQNAgent(ReferenceLoopMixin):
                  LR=1e-4, TAU=1.0, GAMMA=0.99, UPDATE_EVERY=4, learning_starts=10000, target_update_interval=10000,
                  exploration_fraction=0.1, initial_eps=1.0, final_eps=0.05, device="cpu", seed=0,
                  distributed=False, act_chunk=8192, rank=0, n_step_mode="reference", per=False, per_alpha=0.6, per_beta0=0.4,
-                 per_eps=1e-6, munchausen=False, m_alpha=0.9, m_tau=0.03, m_clip=-1.0):
+                 per_eps=1e-6, munchausen=False, m_alpha=0.9, m_tau=0.03, m_clip=-1.0, target_rule="max"):
         self.state_size = state_size
         self.action_size = action_size
         self.device = torch.device(device)
@@ -302,6 +309,22 @@ class IQNAgent(ReferenceLoopMixin):
             if self.per:
                 raise ValueError("munchausen=True with per=True: the prioritized sampler emits two tau sets and the Munchausen step takes three; composing the two "
                                  "is refused")
+        # which action the TD target bootstraps from (opt-in; include/marinenav_hip.h, "Target rules"): "max" -- the reference's max over actions PER quantile sample
+        # (agent.py:281); "mean" -- the IQN paper's one greedy action per next state, the argmax of the target network's mean over its samples; "double" -- Double-IQN,
+        # that argmax taken on the LOCAL network's quantiles of the next state (a tau set of its own), valued by the target network
+        if target_rule not in ("max", "mean", "double"):
+            raise ValueError(f"target_rule must be 'max', 'mean' or 'double', not {target_rule!r}")
+        self.target_rule = target_rule
+        if target_rule != "max":
+            if self.munchausen:
+                raise ValueError(f"target_rule={target_rule!r} with munchausen=True: the Munchausen target replaces the greedy choice by a soft-max policy; composing "
+                                 "the two is refused")
+            if self.per:
+                raise ValueError(f"target_rule={target_rule!r} with per=True: the weighted step of prioritized replay has the per-sample max only; composing the two "
+                                 "is refused")
+            if distributed:
+                raise ValueError(f"target_rule={target_rule!r}: the greedy-on-mean step runs on one learner's own launches; a shared learner (distributed=True), "
+                                 "whose exchange rides in the plain step's launches, is refused")
         self.learning_starts = learning_starts
         self.target_update_interval = target_update_interval
         self.exploration_fraction = exploration_fraction
@@ -583,15 +606,30 @@ class IQNAgent(ReferenceLoopMixin):
             g.copy_(self._flat[off:off + g.numel()].view_as(g))
             off += g.numel()
 
-    def td_targets(self, experiences, taus_target=None, taus_munch=None):
+    def td_targets(self, experiences, taus_target=None, taus_munch=None, taus_select=None, want_select=False):
         """The TD targets Q_targets [B, 1, N] of `compute_loss`, without a graph.  Plain (agent.py:279-283): r + gamma^n (1 - done) max_a Z_target(s', tau_j)[a].
         With `munchausen` (include/marinenav_hip.h, "Munchausen target", states the rule operation by operation): the policy is the soft-max, at temperature
         m_tau, of the target network's MEAN over its N quantile samples; the target takes its expectation of Z' minus m_tau x its log, and the reward gains
         m_alpha x the log-policy of the action taken at the current state, clipped to [m_clip, 0] -- from a second forward of the TARGET network, over `states`
-        with a tau set of its own (`taus_munch`).  The target network's calls run in that order: next states, then states."""
+        with a tau set of its own (`taus_munch`).  The target network's calls run in that order: next states, then states.
+        With `target_rule` "mean" / "double" (include/marinenav_hip.h, "Target rules"): one action a* per next state -- the FIRST argmax of the mean over the N
+        samples of the target network's quantiles ("mean") or of the LOCAL network's quantiles of the next states under `taus_select` ("double"; called after the
+        target network, without a graph) -- and every sample bootstraps from Z'[j][a*].  `want_select`: return (Q_targets, a* [B] i64)."""
         states, actions, rewards, next_states, dones = experiences
         with torch.no_grad():
             Q_targets_next, _ = self.qnetwork_target(next_states, self.N, taus=taus_target)
+            if self.target_rule != "max":
+                Zs = Q_targets_next
+                if self.target_rule == "double":
+                    Zs, _ = self.qnetwork_local(next_states, self.N, taus=taus_select)
+                s = Zs[:, 0]
+                for j in range(1, self.N):      # (the sum in index order, as the kernel takes it)
+                    s = s + Zs[:, j]
+                q = (1.0 / self.N) * s                                                                    # (B, A)
+                a_star = first_argmax(q)                                                                # (B,)
+                Q_sel = Q_targets_next.gather(2, a_star.view(-1, 1, 1).expand(-1, self.N, 1)).squeeze(2).unsqueeze(1)      # (B, 1, N)
+                y = rewards.unsqueeze(-1) + (self.GAMMA ** self.n_step * Q_sel * (1. - dones.unsqueeze(-1)))
+                return (y, a_star) if want_select else y
             if not self.munchausen:
                 Q_targets_next = Q_targets_next.max(2)[0].unsqueeze(1)                          # (B, 1, N)
                 return rewards.unsqueeze(-1) + (self.GAMMA ** self.n_step * Q_targets_next * (1. - dones.unsqueeze(-1)))
@@ -604,13 +642,14 @@ class IQNAgent(ReferenceLoopMixin):
             bonus = self.m_alpha * tlp.gather(1, actions).clamp(min=self.m_clip, max=0.0)                  # (B, 1)
             return (rewards + bonus).unsqueeze(-1) + (self.GAMMA ** self.n_step * V * (1. - dones.unsqueeze(-1)))
 
-    def compute_loss(self, experiences, taus_target=None, taus_local=None, weights=None, want_abs_td=False, taus_munch=None, want_targets=False):
+    def compute_loss(self, experiences, taus_target=None, taus_local=None, weights=None, want_abs_td=False, taus_munch=None, want_targets=False, taus_select=None):
         """Quantile-Huber TD loss of agent.py:276-295 (taus can be injected for tests).  `weights` [B]: element b's terms scaled by weights[b] (prioritized
         replay's importance weights; ones give the unweighted loss bit for bit).  `want_abs_td`: return (loss, mean |TD error| per element [B], detached) --
-        the elements' new priorities.  `taus_munch`: the third tau set of the Munchausen target (`td_targets`); `want_targets`: return (loss, Q_targets [B, N])."""
+        the elements' new priorities.  `taus_munch`: the third tau set of the Munchausen target (`td_targets`); `want_targets`: return (loss, Q_targets [B, N]).  `taus_select`: the third tau set of
+        `target_rule="double"`."""
         states, actions, rewards, next_states, dones = experiences
         B = states.shape[0]
-        Q_targets = self.td_targets(experiences, taus_target, taus_munch)
+        Q_targets = self.td_targets(experiences, taus_target, taus_munch, taus_select)
         Q_expected, taus = self.qnetwork_local(states, self.N, taus=taus_local)
         Q_expected = Q_expected.gather(2, actions.unsqueeze(-1).expand(B, self.N, 1))
         # td_error[b, i, j] = Q_targets[b, 0, j] - Q_expected[b, i, 0]   (B, N, N); Huber with kappa = 1
@@ -659,6 +698,9 @@ class IQNAgent(ReferenceLoopMixin):
         if self.munchausen and self.use_fused_graph:
             raise ValueError("munchausen=True: the Munchausen step samples three tau sets and steps in launches of its own; the captured graph of `use_fused_graph`, "
                              "which replays the plain step's in-launch draws, is refused")
+        if self.target_rule != "max" and self.use_fused_graph:
+            raise ValueError(f"target_rule={self.target_rule!r}: the greedy-on-mean step samples and steps in launches of its own; the captured graph of "
+                             "`use_fused_graph`, which replays the plain step's in-launch draws, is refused")
         if self.per and self.use_fused_graph:
             raise ValueError("prioritized replay (per=True) samples, steps and updates priorities as separate launches per gradient step; the captured graph of "
                              "`use_fused_graph`, which replays in-launch uniform draws, is refused")
@@ -690,6 +732,16 @@ class IQNAgent(ReferenceLoopMixin):
             self._enter_train_path("hip")
             idx, taus = ft.sample(m.size, self.BATCH_SIZE, tau_sets=3)
             loss = ft.step_munch((m.states, m.actions, m.rewards, m.next_states, m.dones), idx, taus[0], taus[1], taus[2])
+            self.grad_steps += 1
+            return loss
+        if self.target_rule != "max" and self.use_fused_train and self.device.type == "cuda":
+            # one sampling launch (rows + two tau sets, or three under "double"), the rule's forward / backward + reduction, clip + Adam
+            m = self.memory
+            ft = self._fused_trainer()
+            self._enter_train_path("hip")
+            double = self.target_rule == "double"
+            idx, taus = ft.sample(m.size, self.BATCH_SIZE, tau_sets=3 if double else 2)
+            loss = ft.step_rule((m.states, m.actions, m.rewards, m.next_states, m.dones), idx, taus[0], taus[2] if double else None, taus[1])
             self.grad_steps += 1
             return loss
         if self.use_fused_train and self.device.type == "cuda":
@@ -734,7 +786,7 @@ class IQNAgent(ReferenceLoopMixin):
         self.grad_steps += 1
         return loss
 
-    def train(self, experiences, taus_target=None, taus_local=None, taus_munch=None):
+    def train(self, experiences, taus_target=None, taus_local=None, taus_munch=None, taus_select=None):
         """agent.py:269-304: one optimizer step; returns the loss (device scalar tensor).
         GPU tensors with `use_fused_train` (the default on the GPU): the hand-written HIP step (csrc/iqn_train.hip:
         both forwards, quantile-Huber loss, backward, clip, Adam in four launches).  Otherwise PyTorch autograd +
@@ -753,6 +805,21 @@ class IQNAgent(ReferenceLoopMixin):
             loss = ft.step_munch(exp, torch.arange(B, dtype=torch.int64, device=self.device), tt, tm, tl)
             self.grad_steps += 1
             return loss
+        if self.target_rule != "max" and self.use_train_graph:
+            raise ValueError(f"target_rule={self.target_rule!r}: `use_train_graph` captured the plain step's graph; the greedy-on-mean targets have no captured form "
+                             "and are refused")
+        if self.target_rule != "max" and self.use_fused_train and experiences[0].is_cuda:
+            exp = tuple(t.contiguous() for t in experiences)
+            ft = self._fused_trainer()
+            self._enter_train_path("hip")
+            B = exp[0].shape[0]
+            double = self.target_rule == "double"
+            given = (taus_target, taus_select, taus_local) if double else (taus_target, taus_local)
+            taus = torch.rand(len(given), B, self.N, device=self.device)      # model.py:149 per network call: target(s'), (double: local(s'),) local(s)
+            sets = [taus[k] if t is None else t.to(self.device, torch.float32).contiguous().view(B, self.N) for k, t in enumerate(given)]
+            loss = ft.step_rule(exp, torch.arange(B, dtype=torch.int64, device=self.device), sets[0], sets[1] if double else None, sets[-1])
+            self.grad_steps += 1
+            return loss
         if self.use_fused_train and experiences[0].is_cuda:
             exp = tuple(t.contiguous() for t in experiences)
             ft = self._fused_trainer()
@@ -765,7 +832,7 @@ class IQNAgent(ReferenceLoopMixin):
                 and taus_target is None and taus_local is None and experiences[0].shape[0] == self.BATCH_SIZE):
             return self._train_graphed(experiences)
         self.optimizer.zero_grad(set_to_none=False)
-        loss = self.compute_loss(experiences, taus_target, taus_local, taus_munch=taus_munch)
+        loss = self.compute_loss(experiences, taus_target, taus_local, taus_munch=taus_munch, taus_select=taus_select)
         loss.backward()
         if self.distributed:
             self._allreduce_grads()          # average first, then clip: same as one big-batch learner

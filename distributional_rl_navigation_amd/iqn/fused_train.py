@@ -66,6 +66,7 @@ class FusedTrainer:
         self.rng_state[0] += 0x9E3779B1 * int(getattr(agent, "rank", 0))     # decorrelate the ranks of a shared learner
         self._idx, self._taus = {}, {}
         self._draw3, self._targets = {}, {}      # the Munchausen step: (idx, three tau sets) per batch size; y [B, 8] when asked for
+        self._select = {}                        # step_rule: a* [B] i32 when asked for
         self._arange = {}
         off = 0
         for p in agent.qnetwork_local.parameters():      # p.grad = the (clipped) gradient of the last step, as torch
@@ -168,6 +169,9 @@ class FusedTrainer:
         if getattr(ag, "munchausen", False):
             raise ValueError("munchausen=True: the Munchausen target needs a third tau set and a second target forward (FusedTrainer.step_munch); step_sampled, "
                              "the draw inside the launch, is refused")
+        if getattr(ag, "target_rule", "max") != "max":
+            raise ValueError(f"target_rule={ag.target_rule!r}: the greedy-on-mean targets run in launches of their own on a given batch (FusedTrainer.step_rule); "
+                             "step_sampled, the draw inside the launch, is refused")
         if getattr(ag, "per", False):
             raise ValueError("prioritized replay (per=True) draws its batch from the priority store (IQNAgent.train_from_memory); the uniform draw inside the "
                              "launch and its staged batches are refused")
@@ -401,6 +405,48 @@ class FusedTrainer:
             raise _capi.MarineNavHipError(f"mn_iqn_train_grad_munch failed ({rc}): need an even batch <= 1024, m_tau > 0, m_clip <= 0, m_alpha >= 0")
         loss = self._finish_step(B)
         return (loss, y) if want_targets else loss
+
+    RULES = {"mean": 1, "double": 2}      # MN_TARGET_MEAN, MN_TARGET_DOUBLE
+
+    def step_rule(self, ring, idx, taus_target, taus_select, taus_local, want_targets=False, want_select=False):
+        """One optimizer step with the agent's `target_rule` ("mean" or "double"; marinenav_hip.h, "Target rules") on the batch rows `idx` [B] i64 with tau sets
+        [B, 8] f32: target network on s', (double: local network on s',) local network on s -- what `sample(tau_sets=2)` / `sample(tau_sets=3)` return;
+        `taus_select` is None under "mean".  mn_iqn_train_grad_rule with gamma ** n_step, then clip + Adam as ever.  Returns the loss, followed by y [B, 8] f32
+        with `want_targets` and by a* [B] i32 with `want_select`; views of buffers the next step overwrites."""
+        ag = self.agent
+        rule = self.RULES.get(getattr(ag, "target_rule", "max"))
+        if rule is None:
+            raise ValueError(f"step_rule: target_rule={getattr(ag, 'target_rule', 'max')!r}; the per-sample max has FusedTrainer.step")
+        if (taus_select is None) != (rule == 1):
+            raise ValueError(f"step_rule: target_rule={ag.target_rule!r} takes {'no' if rule == 1 else 'a'} third tau set (taus_select)")
+        states, actions, rewards, next_states, dones = ring
+        taus = (taus_target, taus_local) + (() if taus_select is None else (taus_select,))
+        for t in ring + (idx,) + taus:
+            assert t.is_cuda and t.is_contiguous()
+        assert states.dtype == torch.float32 and actions.dtype == torch.int64 and dones.dtype == torch.float32 and idx.dtype == torch.int64
+        B = idx.shape[0]
+        for t in taus:
+            assert t.dtype == torch.float32 and t.numel() == B * ag.N
+        y = sel = None
+        if want_targets:
+            if B not in self._targets:
+                self._targets[B] = torch.zeros(B, ag.N, dtype=torch.float32, device=self.device)
+            y = self._targets[B]
+        if want_select:
+            if B not in self._select:
+                self._select[B] = torch.zeros(B, dtype=torch.int32, device=self.device)
+            sel = self._select[B]
+        self._staged_key = None
+        rc = _capi.lib().mn_iqn_train_grad_rule(_p(states), _p(next_states), _p(actions), _p(rewards), _p(dones), _p(idx), _p(self.local), _p(self.target),
+                                                _p(self._workspace(B)), _p(self.grad), _p(self.loss), _p(taus_target),
+                                                _p(taus_select) if taus_select is not None else None, _p(taus_local), B, ag.N,
+                                                C.c_float(ag.GAMMA ** ag.n_step), rule, _p(y) if y is not None else None,
+                                                _p(sel) if sel is not None else None, _capi.stream_ptr(self.device))
+        if rc:
+            raise _capi.MarineNavHipError(f"mn_iqn_train_grad_rule failed ({rc}): need an even batch <= 1024 and 8 taus")
+        loss = self._finish_step(B)
+        out = (loss,) + ((y,) if want_targets else ()) + ((sel,) if want_select else ())
+        return out if len(out) > 1 else loss
 
     def _finish_step(self, B):
         """Gradient in self.grad -> (shared learner: all-reduce) -> clip + Adam -> loss."""

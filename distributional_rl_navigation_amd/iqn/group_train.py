@@ -53,6 +53,9 @@ def check_agents(agents):
         if getattr(a, "munchausen", False):
             raise ValueError(f"learner group: agent {i} uses the Munchausen target (munchausen=True): the grouped launches run one target forward per "
                              "element and have no Munchausen form")
+        if getattr(a, "target_rule", "max") != "max":
+            raise ValueError(f"learner group: agent {i} uses target_rule={a.target_rule!r}: the grouped launches take the per-sample max and have no "
+                             "greedy-on-mean form")
     if first.BATCH_SIZE % 2 or not 2 <= first.BATCH_SIZE <= 1024:
         raise ValueError(f"learner group: batch size {first.BATCH_SIZE}; the fused gradient step takes even batch sizes up to 1024")
     return agents

@@ -243,7 +243,7 @@ class TrialRun:
                  grad_steps=None, torch_train=False, total_grad_steps=None, n_evals=None, cvar=1.0, precision="f64",
                  exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1, n_step_mode="reference",
                  eval_one_launch=False, eval_deferred=False, env_budget="learner", reference=None, episode_log=None, eval_config=None, max_eval_steps=1000,
-                 on_step=None, train_env=None, eval_worlds=None, per=None, munchausen=None):
+                 on_step=None, train_env=None, eval_worlds=None, per=None, munchausen=None, target_rule="max"):
         import torch
         from .iqn.agent import IQNAgent
         from .marinenav_env.vec_env import VecMarineNavEnv
@@ -252,6 +252,8 @@ class TrialRun:
             raise ValueError(PER_REFUSALS["shared"])
         if munchausen and (shared or per):
             raise ValueError(MUNCHAUSEN_REFUSALS["shared" if shared else "per"])
+        if target_rule != "max" and (shared or per or munchausen):
+            raise ValueError(TARGET_RULE_REFUSALS["shared" if shared else ("per" if per else "munchausen")])
         exp_dir = trial_dir(params, rank, world, shared)
         writer = rank == 0 or not shared
         ref_mode = env_budget == "reference"
@@ -291,7 +293,8 @@ class TrialRun:
                          UPDATE_EVERY=1, learning_starts=plan["learning_starts"] if ref_mode else 0, rank=rank if shared else 0, final_eps=final_eps,
                          **(dict(exploration_fraction=plan["exploration_fraction"]) if ref_mode else {}),
                          **(dict(per=True, per_alpha=per["alpha"], per_beta0=per["beta0"]) if per else {}),
-                         **(dict(munchausen=True, m_alpha=munchausen["alpha"], m_tau=munchausen["tau"], m_clip=munchausen["clip"]) if munchausen else {}))
+                         **(dict(munchausen=True, m_alpha=munchausen["alpha"], m_tau=munchausen["tau"], m_clip=munchausen["clip"]) if munchausen else {}),
+                         **(dict(target_rule=target_rule) if target_rule != "max" else {}))
         if per:      # beta reaches 1 with the run's last gradient step (the reference plan's total already leaves out the vector steps in front of learning_starts)
             agent.per_beta_steps = int(plan["total_grad_steps"])
         agent.grad_steps_per_update = plan["grad_steps_per_vector_step"]
@@ -375,6 +378,13 @@ MUNCHAUSEN_REFUSALS = dict(
     shared="--munchausen steps one learner in launches of its own; a shared learner (--shared-learner), whose gradient exchange rides in the plain step's "
            "launches, has no Munchausen form",
     per="--munchausen takes three tau sets per step and the prioritized sampler of --per emits two; the two options are not combinable yet")
+TARGET_RULE_REFUSALS = dict(
+    together="--target-rule mean / double step one learner in launches of their own; the grouped gradient launches of --together take the per-sample max and "
+             "have no greedy-on-mean form",
+    shared="--target-rule mean / double step one learner in launches of their own; a shared learner (--shared-learner), whose gradient exchange rides in the "
+           "plain step's launches, has no greedy-on-mean form",
+    per="--target-rule mean / double: the weighted step of --per takes the per-sample max only; the two options are not combinable yet",
+    munchausen="--target-rule mean / double: the soft-max policy of --munchausen takes the place of the greedy choice; the two options are not combinable")
 SHAPE_KEYS_FIRST = ("n_envs", "batch", "replay", "world")      # (named before the plan's own keys, which follow from them)
 
 
@@ -394,7 +404,7 @@ def write_checkpoint(exp_dir, state):
 
 
 def run_shaping_args(env_budget="learner", precision="f64", n_step=1, n_step_mode="reference", shared_taus=False, cvar=1.0, eval_adaptive=True, eval_deferred=False, eval_one_launch=False,
-                     episode_log=None, max_eval_steps=1000, reference=None, target_sync_mult=1.0, final_eps=0.05, eval_worlds=None, per=None, munchausen=None, **_):
+                     episode_log=None, max_eval_steps=1000, reference=None, target_sync_mult=1.0, final_eps=0.05, eval_worlds=None, per=None, munchausen=None, target_rule="max", **_):
     """The arguments of `run_trial` that shape a run beside its plan, normalised: what a checkpoint records and `--resume` compares (`check_resumable`).  ONE
     place builds it, for the run itself and for `--dry-run --resume`; the defaults are `run_trial`'s.  (`torch_train` is recorded by the checkpoint but not
     compared: a checkpoint of one gradient-step path continues on the other.)"""
@@ -402,7 +412,8 @@ def run_shaping_args(env_budget="learner", precision="f64", n_step=1, n_step_mod
                 eval_deferred=bool(eval_deferred), eval_one_launch=bool(eval_one_launch), episode_log=episode_log, max_eval_steps=int(max_eval_steps),
                 reference=dict(reference or {}), target_sync_mult=float(target_sync_mult), final_eps=float(final_eps), eval_worlds=eval_worlds,
                 **(dict(per=dict(alpha=float(per["alpha"]), beta0=float(per["beta0"]))) if per else {}),      # (a uniform run records no such key, as before there were priorities)
-                **(dict(munchausen=dict(alpha=float(munchausen["alpha"]), tau=float(munchausen["tau"]), clip=float(munchausen["clip"]))) if munchausen else {}))      # (nor a run with the plain target this one)
+                **(dict(munchausen=dict(alpha=float(munchausen["alpha"]), tau=float(munchausen["tau"]), clip=float(munchausen["clip"]))) if munchausen else {}),      # (nor a run with the plain target this one)
+                **(dict(target_rule=str(target_rule)) if target_rule != "max" else {}))      # (nor a run with the per-sample max this one)
 
 
 def first_difference(saved, now, first=()):
@@ -453,6 +464,8 @@ def check_resumable(state, shape, run_args=None):
             d = ("per", state["args"].get("per"), run_args.get("per"))
         if d is None and state["args"].get("munchausen") != run_args.get("munchausen"):      # (recorded only by a run with --munchausen: absent on either side means the plain target)
             d = ("munchausen", state["args"].get("munchausen"), run_args.get("munchausen"))
+        if d is None and state["args"].get("target_rule", "max") != run_args.get("target_rule", "max"):      # (recorded only by a run with --target-rule mean / double)
+            d = ("target_rule", state["args"].get("target_rule", "max"), run_args.get("target_rule", "max"))
         if d is not None:
             raise ValueError(f"--resume: the checkpoint was written by a run with other arguments: {d[0]} was {d[1]!r} there and is {d[2]!r} on this command line")
 
@@ -500,7 +513,7 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None,
               grad_steps=None, torch_train=False, total_grad_steps=None, n_evals=None, cvar=1.0, precision="f64",
               exchange="collective", shared_taus=False, target_sync_mult=1.0, final_eps=0.05, eval_adaptive=True, n_step=1, n_step_mode="reference",
               eval_one_launch=False, eval_deferred=False, env_budget="learner", reference=None, episode_log=None, eval_config=None, max_eval_steps=1000,
-              on_step=None, return_agent=False, eval_worlds=None, checkpoint_every=None, stop_after=None, resume=False, dump_final_state=None, per=None, munchausen=None):
+              on_step=None, return_agent=False, eval_worlds=None, checkpoint_every=None, stop_after=None, resume=False, dump_final_state=None, per=None, munchausen=None, target_rule="max"):
     """train_IQN_model.py:74-121 on the vector env.  `params` is one trial of the reference's config grid
     (seed, total_timesteps, eval_freq, save_dir); see `plan_cadence` for how its env-step cadences map to vector steps.
     `precision`: the env kernels' arithmetic.  "f64" (default: every float32 output within 1e-5 of the reference, no
@@ -530,6 +543,8 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None,
     the loss weighted by importance weights whose exponent runs linearly from beta0 to 1 over the run's gradient steps; single learner only.
     `munchausen`: None (the plain target) or dict(alpha=, tau=, clip=) -- the Munchausen target (include/marinenav_hip.h): soft-max policy at temperature tau over the target
     network's mean quantiles, alpha x the log-policy of the action taken, clipped to [clip, 0], added to the reward; single learner, not with `per`.
+    `target_rule`: "max" (the reference's max over actions per quantile sample), "mean" (one greedy action per next state, from the target network's mean quantiles) or
+    "double" (that action chosen by the local network, valued by the target network) -- include/marinenav_hip.h, "Target rules"; single learner, not with `per` or `munchausen`.
     `dump_final_state`: a file for torch.save(dict(agent=, ring=, env=)) of the `state_dict()`s behind the last vector step (tests)."""
     checkpointing = checkpoint_every is not None or stop_after is not None or resume
     if checkpointing and (shared or world > 1):
@@ -538,7 +553,7 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None,
         raise ValueError("checkpoint_every and stop_after count vector steps: at least 1")
     run_args = run_shaping_args(env_budget=env_budget, precision=precision, n_step=n_step, n_step_mode=n_step_mode, shared_taus=shared_taus, cvar=cvar, eval_adaptive=eval_adaptive,
                                 eval_deferred=eval_deferred, eval_one_launch=eval_one_launch, episode_log=episode_log, max_eval_steps=max_eval_steps, reference=reference,
-                                target_sync_mult=target_sync_mult, final_eps=final_eps, eval_worlds=eval_worlds, per=per, munchausen=munchausen)
+                                target_sync_mult=target_sync_mult, final_eps=final_eps, eval_worlds=eval_worlds, per=per, munchausen=munchausen, target_rule=target_rule)
     state = None
     if resume:      # (looked at before anything is built or written: a finished seed is left alone, a foreign checkpoint refused)
         exp_dir = trial_dir(params, rank, world, shared)
@@ -555,7 +570,7 @@ def run_trial(device, params, n_envs, rank=0, world=1, shared=False, batch=None,
                    torch_train=torch_train, total_grad_steps=total_grad_steps, n_evals=n_evals, cvar=cvar, precision=precision, exchange=exchange,
                    shared_taus=shared_taus, target_sync_mult=target_sync_mult, final_eps=final_eps, eval_adaptive=eval_adaptive, n_step=n_step, n_step_mode=n_step_mode,
                    eval_one_launch=eval_one_launch, eval_deferred=eval_deferred, env_budget=env_budget, reference=reference, episode_log=episode_log,
-                   eval_config=eval_config, max_eval_steps=max_eval_steps, on_step=on_step, eval_worlds=eval_worlds, per=per, munchausen=munchausen)
+                   eval_config=eval_config, max_eval_steps=max_eval_steps, on_step=on_step, eval_worlds=eval_worlds, per=per, munchausen=munchausen, target_rule=target_rule)
     if checkpoint_every is None and stop_after is None and state is None:
         run.agent.learn_vec(**run.learn_args)
     else:
@@ -640,6 +655,8 @@ def run_trials_together(device, trials, n_envs, on_step=None, return_agents=Fals
         raise ValueError(PER_REFUSALS["together"])
     if kwargs.get("munchausen"):
         raise ValueError(MUNCHAUSEN_REFUSALS["together"])
+    if kwargs.get("target_rule", "max") != "max":
+        raise ValueError(TARGET_RULE_REFUSALS["together"])
     hooks = list(on_step) if on_step is not None else [None] * len(trials)
     stacked, views = None, [None] * len(trials)
     if stack_envs:
@@ -803,6 +820,10 @@ def main(argv=None):
     ap.add_argument("--m-alpha", type=float, default=0.9, help="with --munchausen: the weight of the log-policy bonus (default 0.9)")
     ap.add_argument("--m-tau", type=float, default=0.03, help="with --munchausen: the entropy temperature (default 0.03)")
     ap.add_argument("--m-clip", type=float, default=-1.0, help="with --munchausen: the lower clip bound of the log-policy bonus (default -1)")
+    ap.add_argument("--target-rule", choices=("max", "mean", "double"), default="max",
+                    help="which action the TD target bootstraps from: max (default; the reference's max over actions per quantile sample), mean (the IQN paper's "
+                         "one greedy action per next state, the argmax of the target network's mean quantiles) or double (Double-IQN: the local network chooses, the "
+                         "target network values); mean and double: single learner (not with --together, --shared-learner, --per or --munchausen)")
     ap.add_argument("--dump-final-state", default=None, metavar="FILE",
                     help="behind the last vector step, torch.save the state_dict()s of the agent, its replay ring and the train env of the LAST trial run to FILE (tests)")
     args = ap.parse_args(argv)
@@ -825,6 +846,11 @@ def main(argv=None):
             raise SystemExit("train_iqn: " + MUNCHAUSEN_REFUSALS[refused[0]])
         if not (0 < args.m_tau < float("inf") and args.m_clip <= 0 and 0 <= args.m_alpha < float("inf")):
             raise SystemExit("train_iqn: --m-tau is above 0, --m-clip at most 0 and --m-alpha at least 0")
+    if args.target_rule != "max":
+        refused = [k for k, on in (("together", args.together or args.stack_envs), ("shared", args.shared_learner), ("per", args.per),
+                                   ("munchausen", args.munchausen)) if on]
+        if refused:
+            raise SystemExit("train_iqn: " + TARGET_RULE_REFUSALS[refused[0]])
     reference = None
     if args.reference is not None:
         if args.env_budget != "reference":
@@ -874,6 +900,8 @@ def main(argv=None):
         kw["per"] = dict(alpha=args.per_alpha, beta0=args.per_beta0)
     if args.munchausen:
         kw["munchausen"] = dict(alpha=args.m_alpha, tau=args.m_tau, clip=args.m_clip)
+    if args.target_rule != "max":
+        kw["target_rule"] = args.target_rule
     if checkpointing:
         kw.update(checkpoint_every=args.checkpoint_every, stop_after=args.stop_after, resume=args.resume is not None)
     if args.dump_final_state is not None:

@@ -926,6 +926,30 @@ int mn_per_update(uint32_t *mass, uint64_t *block_sums, uint32_t *mmax, const in
  * by units in the last place, so this rule has no bit-exact host twin: tests hold it to float64 by eager float32's own error.
  * Every workgroup runs both target forwards of its own two batch elements (no workgroup waits for another). */
 
+/* ---- Target rules ----------------------------------------------------------------------------------
+ * Which action the TD target bootstraps from, opt-in: mn_iqn_train_grad_rule forms y[b, j] by the rule below; loss, backward,
+ * reduction, clip and Adam are mn_iqn_train_grad's.  mn_iqn_train_grad itself takes max_a Z'[j][a] PER SAMPLE j (the reference's
+ * operator: sample j and sample j + 1 of one element may bootstrap from different actions).  The two rules here choose ONE action
+ * a* per next state, from the mean over the samples, and every sample takes that action's quantile:
+ *     MN_TARGET_MEAN     the IQN paper's rule (Dabney et al. 2018): the TARGET network chooses and values
+ *     MN_TARGET_DOUBLE   Double-IQN: the LOCAL network chooses, the target network values
+ * Per batch element b: reward r, done, gamma (the caller passes gamma ** n_step), the tau sets tt[b, j], ts[b, j], tl[b, i]
+ * (i, j < 8), and with the TARGET weights
+ *     Z'[j][a] = Z_target(s'_b, tt[b, j])[a]           the next state, as in mn_iqn_train_grad
+ * All arithmetic is float32.
+ *     Zs[j][a] = Z'[j][a]                               MN_TARGET_MEAN
+ *              = Z_local(s'_b, ts[b, j])[a]             MN_TARGET_DOUBLE: the LOCAL weights on the NEXT state, third tau set
+ *     q[a]     = 0.125f * (Zs[0][a] + Zs[1][a] + ... + Zs[7][a])      summed in index order from the first term
+ *     a*       = the FIRST index that attains max_a q[a]: the incumbent starts as a = 0 and, scanning a = 1..8, is replaced
+ *                only where q[a] is strictly greater
+ *     y[b, j]  = fmaf(gamma * Z'[j][a*], 1.0f - done, r)
+ * then td[b, i, j] = y[b, j] - Z_local(s_b, tl[b, i])[a_b] and the quantile-Huber loss as in mn_iqn_train_grad.  There is one
+ * instruction sequence per output: done == 1 takes no other path (with every row done, y == r and the step is
+ * mn_iqn_train_grad's bit for bit).  Every workgroup runs the selecting pass and the target forward of its own two batch
+ * elements (no workgroup waits for another). */
+#define MN_TARGET_MEAN 1
+#define MN_TARGET_DOUBLE 2
+
 /* ---- training episode log ----------------------------------------------------------------------
  * The record the reference prints at every training episode end (thirdparty/IQN/agent.py:118-119, 152-168) for the n envs of a
  * vector step, in one launch that needs no env handle and no host look.  reward_dev [n] f32, done_dev / info_dev [n] u8 are a
@@ -1323,6 +1347,19 @@ int mn_iqn_train_grad_munch(const float *ring_states, const float *ring_next_sta
                             const float *params_local, const float *params_target, float *workspace, float *grad_out, float *loss_out,
                             int32_t batch, int32_t num_taus, float gamma, float alpha, float entropy_tau, float clip_lo,
                             float *targets_out, void *stream);
+/* mn_iqn_train_grad with a greedy-on-mean target ("Target rules" above): rule is MN_TARGET_MEAN or MN_TARGET_DOUBLE.
+ * taus_select_dev [batch][8] is the third tau set (the local network's selecting pass over the next states; elements
+ * [2 B 8, 3 B 8) of an mn_iqn_sample call with n_taus_total = 3 B 8); it is read only under MN_TARGET_DOUBLE and may be NULL under
+ * MN_TARGET_MEAN.  gamma is gamma ** n_step.  targets_out [batch][8] f32 receives y and select_out [batch] i32 receives a* (NULL:
+ * not written; the gradient's bits do not depend on either).  mn_iqn_grad_reduce's sum and mn_iqn_train_adam follow unchanged.
+ * MN_ERR_INVALID, with nothing launched: rule 0 (the per-sample max has mn_iqn_train_grad) or any other rule, an odd batch or one
+ * outside 2..1024, num_taus != 8, a NULL pointer other than targets_out, select_out and -- under MN_TARGET_MEAN -- taus_select_dev. */
+int mn_iqn_train_grad_rule(const float *ring_states, const float *ring_next_states, const int64_t *ring_actions,
+                           const float *ring_rewards, const float *ring_dones, const int64_t *idx_dev,
+                           const float *params_local, const float *params_target, float *workspace, float *grad_out, float *loss_out,
+                           const float *taus_target_dev, const float *taus_select_dev, const float *taus_local_dev,
+                           int32_t batch, int32_t num_taus, float gamma, int32_t rule, float *targets_out, int32_t *select_out,
+                           void *stream);
 /* The same gradient step with the batch drawn inside the launch: every workgroup of the forward / backward kernel evaluates
  * mn_iqn_sample's permutation for its own two slots (and its own taus) from {seed, call counter}, so there is no sampling launch.
  * Bit-identical to mn_iqn_sample followed by mn_iqn_train_grad from the same state; the call counter is advanced once (by the
