@@ -166,6 +166,9 @@ SIGNATURES = [
     ("mn_enable_trajectory", C.c_int, [_vp, _i32]),
     ("mn_get_trajectory", C.c_int, [_vp, _i32, _i32, _i32, _pd]),
     ("mn_set_trajectory_trace", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("mn_obs_perturb", C.c_int, [_vp, _vp, _i64, C.c_uint64, _vp, _vp, _vp]),      # spec: POINTER(obs_noise.MnObsNoise), passed with byref
+    ("mn_set_obs_noise", C.c_int, [_vp, _vp, C.c_uint64]),
+    ("mn_env_perturb_obs", C.c_int, [_vp, _vp, _vp, _vp]),
     ("mn_peek_next_double", C.c_int, [_vp, _i32, _i32, _pd]),
     ("mn_last_done_count", C.c_int, [_vp, _vp, _pi32]),
     ("mn_profile_begin", C.c_int, [_vp, _i32]),

@@ -26,6 +26,11 @@ struct mn_handle {
     MnArrays *A_mem = nullptr;                              // device copy of A (sync_arrays): the preparation launch's reset blocks read their store pointers from it
     double *traj_trace = nullptr;                           // mn_set_trajectory_trace: the caller's [traj_trace_steps][n][N][2] buffer, until the next episode launch takes it
     int32_t traj_trace_steps = 0, traj_trace_sub = 0;
+    // mn_set_obs_noise: the attached description in the kernels' form and the handle's first_env_index; stays until replaced or detached
+    bool noise_on = false;                                  // attached AND not all-zero: the episode launches take their NOISE instantiation
+    bool noise_attached = false;
+    MnObsNoiseDev noise = {};
+    uint64_t noise_env0 = 0;
     int device = -1;      // HIP device the handle's memory lives on (the caller's current device at mn_create)
     // profiling
     std::vector<hipEvent_t> ev;
@@ -455,6 +460,60 @@ extern "C" int mn_set_trajectory_trace(mn_handle *h, double *traj_trace_dev, int
     return MN_OK;
 }
 
+// ---- observation noise (mn_obs_noise_body.h, mn_obs_noise.hip) ----
+static int noise_spec(mn_handle *h, const mn_obs_noise *spec, MnObsNoiseDev *out) {
+    const char *bad = mn_obs_noise_dev_of(*spec, out);
+    if (!bad) return MN_OK;
+    char b[160];
+    snprintf(b, sizeof(b), "observation noise: %s must be %s", bad, !strcmp(bad, "sonar_miss_p") ? "in [0, 1]" : "finite and not negative");
+    return fail(h, MN_ERR_INVALID, b);
+}
+// the episode forms without a NOISE instantiation refuse a handle that perceives noise; they do not ignore the description
+static int refuse_noise(mn_handle *h, const char *who) {
+    if (!h->noise_on) return MN_OK;
+    char b[200];
+    snprintf(b, sizeof(b), "%s has no observation-noise form: detach the description (mn_set_obs_noise(h, NULL, 0)) or run the per-step loop (mn_env_perturb_obs)", who);
+    return fail(h, MN_ERR_INVALID, b);
+}
+
+extern "C" int mn_obs_perturb(const float *obs_in_dev, float *obs_out_dev, int64_t n, uint64_t env_index0, const int32_t *ep_t_dev, const mn_obs_noise *spec,
+                              void *stream) {
+    if (!obs_in_dev || !obs_out_dev || !ep_t_dev || !spec || n < 1 || n > (int64_t)1 << 40) return fail(nullptr, MN_ERR_INVALID, "mn_obs_perturb: a NULL argument or n < 1");
+    if ((uintptr_t)obs_in_dev % 4 != 0 || (uintptr_t)obs_out_dev % 4 != 0 || (uintptr_t)ep_t_dev % 4 != 0)
+        return fail(nullptr, MN_ERR_INVALID, "mn_obs_perturb: a misaligned argument");
+    MnObsNoiseDev d;
+    const int rc = noise_spec(nullptr, spec, &d);
+    if (rc) return rc;
+    mn_launch_obs_perturb(obs_in_dev, obs_out_dev, n, env_index0, ep_t_dev, d, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? MN_OK : MN_ERR_HIP;
+}
+
+extern "C" int mn_set_obs_noise(mn_handle *h, const mn_obs_noise *spec, uint64_t first_env_index) {
+    if (!h) return MN_ERR_INVALID;
+    if (!spec) { h->noise_on = h->noise_attached = false; return MN_OK; }      // detach
+    MnObsNoiseDev d;
+    const int rc = noise_spec(h, spec, &d);      // (a refused description leaves the attachment as it was)
+    if (rc) return rc;
+    h->noise = d;
+    h->noise_env0 = first_env_index;
+    h->noise_attached = true;
+    h->noise_on = !mn_obs_noise_is_off(d);
+    return MN_OK;
+}
+
+extern "C" int mn_env_perturb_obs(mn_handle *h, const float *obs_in_dev, float *obs_out_dev, void *stream) {
+    if (!h) return MN_ERR_INVALID;
+    if (!obs_in_dev || !obs_out_dev || (uintptr_t)obs_in_dev % 4 != 0 || (uintptr_t)obs_out_dev % 4 != 0)
+        return fail(h, MN_ERR_INVALID, "mn_env_perturb_obs: a NULL or misaligned argument");
+    hipStream_t s = (hipStream_t)stream;
+    join_reset(h, s);      // the counters a pending or owed reset writes are final before they are read
+    MN_ON_DEVICE(h);
+    const MnObsNoiseDev off = {};
+    mn_launch_obs_perturb(obs_in_dev, obs_out_dev, h->A.n, h->noise_env0, h->A.ep_t, h->noise_attached ? h->noise : off, s);
+    MN_HIP(h, hipGetLastError());
+    return MN_OK;
+}
+
 extern "C" int mn_rollout(mn_handle *h, int32_t n_steps, const int32_t *actions_dev, uint64_t action_seed,
                           uint64_t first_step_index, uint64_t first_env_index, float *obs_dev, float *obs_trace_dev,
                           float *reward_trace_dev, uint8_t *done_trace_dev, uint8_t *info_trace_dev,
@@ -475,10 +534,14 @@ extern "C" int mn_rollout_policy(mn_handle *h, int32_t n_steps, int32_t policy, 
     const int trc = take_traj_trace(h, n_steps, &traj);      // first: the attachment is consumed even by a call refused below
     if (!obs_dev || n_steps < 1 || (policy != MN_POLICY_APF && policy != MN_POLICY_BA)) return MN_ERR_INVALID;
     if (trc) return trc;
+    if (h->noise_on && h->params.precision != MN_PRECISION_F64) {
+        const int nrc = refuse_noise(h, "mn_rollout_policy on a mixed-precision handle");
+        if (nrc) return nrc;
+    }
     hipStream_t s = (hipStream_t)stream;
     return launch_episodes(h, s, [&] {
         mn_launch_rollout_policy(h->A, h->P, h->params.precision, n_steps, policy, obs_dev, obs_trace_dev, reward_trace_dev, done_trace_dev,
-                                 info_trace_dev, action_trace_dev, traj, s);
+                                 info_trace_dev, action_trace_dev, traj, s, h->noise_on ? &h->noise : nullptr, h->noise_env0);
     });
 }
 
@@ -493,6 +556,7 @@ static int rollout_iqn(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weight
     if (!ctx || !weights || !rng_state_dev || !obs_dev || n_steps < 1) return MN_ERR_INVALID;      // (the 14 pointers of `weights`: mn_iqn_rollout_image)
     if ((long)h->A.n * 32 >= (1L << 32)) return MN_ERR_INVALID;      // 32-bit draw index, as mn_iqn_act_rng
     if (trc) return trc;
+    if (eval) { const int nrc = refuse_noise(h, "mn_rollout_iqn_eval"); if (nrc) return nrc; }
     hipStream_t s = (hipStream_t)stream;
     const uint32_t *image = nullptr;
     uint32_t *words = nullptr;
@@ -504,7 +568,7 @@ static int rollout_iqn(mn_handle *h, mn_iqn_ctx *ctx, const float *const *weight
         else
             mn_launch_rollout_iqn_rows(h->A, h->P, h->params.precision, n_steps, image, rng_state_dev, cvar, adaptive ? 1 : 0, cvar_row_dev, adaptive_row_dev, obs_dev,
                                        obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev, action_trace_dev, cvar_trace_dev, q_trace_dev, traj, words,
-                                       steps_run_dev, s);
+                                       steps_run_dev, s, h->noise_on ? &h->noise : nullptr, h->noise_env0);
     });
 }
 
@@ -548,6 +612,7 @@ extern "C" int mn_rollout_iqn_groups(mn_handle *h, const uint32_t *images_dev, i
         return fail(h, MN_ERR_INVALID, "mn_rollout_iqn_groups: n_groups * rows_per_group must be the handle's n_envs");
     if (image_stride < mn_iqn_image_floats() || image_stride % 4 != 0)
         return fail(h, MN_ERR_INVALID, "mn_rollout_iqn_groups: image_stride below mn_iqn_image_floats() or no multiple of 4");
+    { const int nrc = refuse_noise(h, "mn_rollout_iqn_groups"); if (nrc) return nrc; }
     hipStream_t s = (hipStream_t)stream;
     return launch_episodes(h, s, [&] {
         mn_launch_rollout_iqn_groups(h->A, h->P, h->params.precision, n_steps, images_dev, image_stride, rows_per_group, rng_states_dev, cvar_row_dev,
@@ -568,7 +633,7 @@ extern "C" int mn_rollout_dqn(mn_handle *h, const float *const *weights, float *
     hipStream_t s = (hipStream_t)stream;
     return launch_episodes(h, s, [&] { if (repack) mn_launch_dqn_pack(weights, image_dev, s); return MN_OK; }, [&] {
         mn_launch_rollout_dqn(h->A, h->P, h->params.precision, n_steps, image_dev, obs_dev, obs_trace_dev, reward_trace_dev, done_trace_dev, info_trace_dev,
-                              action_trace_dev, q_trace_dev, traj, s);
+                              action_trace_dev, q_trace_dev, traj, s, h->noise_on ? &h->noise : nullptr, h->noise_env0);
     });
 }
 
@@ -593,6 +658,7 @@ extern "C" int mn_rollout_dqn_groups(mn_handle *h, const float *images_dev, int6
         return fail(h, MN_ERR_INVALID, "mn_rollout_dqn_groups: n_groups * rows_per_group must be the handle's n_envs");
     if (image_stride < mn_dqn_image_floats() || image_stride % 4 != 0 || (uintptr_t)images_dev % 16 != 0)
         return fail(h, MN_ERR_INVALID, "mn_rollout_dqn_groups: image_stride below mn_dqn_image_floats() or no multiple of 4, or images_dev not 16-byte aligned");
+    { const int nrc = refuse_noise(h, "mn_rollout_dqn_groups"); if (nrc) return nrc; }
     hipStream_t s = (hipStream_t)stream;
     return launch_episodes(h, s, [&] {
         mn_launch_rollout_dqn_groups(h->A, h->P, h->params.precision, n_steps, images_dev, image_stride, n_groups, rows_per_group, obs_dev, obs_trace_dev,

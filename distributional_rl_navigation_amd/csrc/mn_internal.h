@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "marinenav_hip.h"
+#include "mn_obs_noise_body.h"
 
 #define MN_WAVE 64
 #define MN_PAD 256
@@ -143,18 +144,23 @@ void mn_launch_step(const MnArrays &A, const MnDev &P, int precision, int lanes,
 void mn_launch_rollout(const MnArrays &A, const MnDev &P, int precision, int lanes, int n_steps, const int32_t *actions_in,
                        uint64_t seed, uint64_t step0, uint64_t env0, float *obs_out, float *obs_trace, float *reward_trace,
                        uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, hipStream_t s);
+// observation noise on a vector of rows (mn_obs_noise.hip): the arguments of mn_obs_perturb, validated
+void mn_launch_obs_perturb(const float *obs_in, float *obs_out, int64_t n, uint64_t env_index0, const int32_t *ep_t, const MnObsNoiseDev &S, hipStream_t s);
 void mn_launch_random_actions(uint64_t seed, uint64_t step, uint64_t env0, int n, int32_t *out, hipStream_t s);
 // episodes under a device-side policy (MN_POLICY_APF / MN_POLICY_BA, mn_planners.h), and one policy step for a vector of observations
 void mn_launch_rollout_policy(const MnArrays &A, const MnDev &P, int precision, int n_steps, int policy, float *obs_io, float *obs_trace,
-                              float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, double *traj_trace, hipStream_t s);
+                              float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, double *traj_trace, hipStream_t s,
+                              const MnObsNoiseDev *noise = nullptr, uint64_t noise_env0 = 0);
 void mn_launch_planner_act(const float *obs, int n, int policy, const double *a, const double *w, int32_t *actions, hipStream_t s);
 // IQN evaluation episodes in one launch (mn_rollout_iqn.hip); `image` / `words` from mn_iqn_rollout_image (iqn_act.hip)
 // cvar_row / adaptive_row: per-env cvar / adaptive flags ([n] device arrays; NULL = the scalar)
+// noise (here and in the policy / DQN launches): NULL = the policy reads the clean row (the kernels as they were); else the NOISE instantiation, which feeds
+// it mn_obs_noise_channel of the row under the key (noise->seed, noise_env0 + env, the env's episode_timesteps)
 // traj_trace (here and in the policy / DQN launches): [n_steps][n][P.N][2] sub-step positions (mn_set_trajectory_trace), or NULL
 void mn_launch_rollout_iqn_rows(const MnArrays &A, const MnDev &P, int precision, int n_steps, const uint32_t *image, uint64_t *rng_state, float cvar,
                                 int adaptive, const float *cvar_row, const uint8_t *adaptive_row, float *obs_io, float *obs_trace, float *reward_trace,
                                 uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *cvar_trace, float *q_trace, double *traj_trace,
-                                uint32_t *words, int32_t *steps_run, hipStream_t s);
+                                uint32_t *words, int32_t *steps_run, hipStream_t s, const MnObsNoiseDev *noise = nullptr, uint64_t noise_env0 = 0);
 // the same episodes acting as act_eval does, with the quantile / tau traces (mn_rollout_iqn_eval.hip)
 void mn_launch_rollout_iqn_eval(const MnArrays &A, const MnDev &P, int precision, int n_steps, const uint32_t *image, uint64_t *rng_state, float cvar,
                                 int adaptive, const float *cvar_row, const uint8_t *adaptive_row, float *obs_io, float *obs_trace, float *reward_trace,
@@ -169,7 +175,8 @@ int mn_iqn_rollout_image(mn_iqn_ctx *c, const float *const *weights, hipStream_t
 // DQN evaluation episodes in one launch (mn_rollout_dqn.hip); `image` = the weight image mn_launch_dqn_pack (dqn_act.hip) builds from weights[18]
 void mn_launch_dqn_pack(const float *const *weights, float *image_dev, hipStream_t s);
 void mn_launch_rollout_dqn(const MnArrays &A, const MnDev &P, int precision, int n_steps, const float *image, float *obs_io, float *obs_trace,
-                           float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *q_trace, double *traj_trace, hipStream_t s);
+                           float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *q_trace, double *traj_trace, hipStream_t s,
+                           const MnObsNoiseDev *noise = nullptr, uint64_t noise_env0 = 0);
 // the same episodes with a weight image per group of rows (mn_rollout_dqn_groups.hip); image_stride in floats
 void mn_launch_rollout_dqn_groups(const MnArrays &A, const MnDev &P, int precision, int n_steps, const float *images, int64_t image_stride, int n_groups,
                                   int rows_per_group, float *obs_io, float *obs_trace, float *reward_trace, uint8_t *done_trace, uint8_t *info_trace,

@@ -14,6 +14,8 @@
 __device__ unsigned long long g_rollout_phase[16];
 #define MN_PHASE_VAR g_rollout_phase
 #endif
+#include <type_traits>
+
 #include "mn_planners.h"
 #include "mn_reset_body.h"
 #include "mn_step_body.h"
@@ -127,10 +129,17 @@ __global__ __launch_bounds__(MN_WAVE, MN_ROLLOUT_MIN_WAVES(L)) void mn_rollout_k
 // for the next step.  EPISODE semantics: an env that finishes is NOT reset; it idles for the rest of the launch (its traces read reward 0,
 // done 1, the terminal info code, action -1), its terminal pose and counters are stored.  Per step the same MnLane::step as everywhere else:
 // bit-identical to a loop of (policy launch, mn_step) on the same worlds.
-template <typename M, bool PARITY, int L>
+// NOISE (mn_set_obs_noise): the policy is fed what the robot perceives -- a second row per env in LDS, filled at the head of a step by the lane group from
+// the clean row under the key (seed, global env index, the lane's ep_t) -- while the step keeps writing the clean row: obs_io and the traces are what
+// they are without noise.  NOISE = false is the kernel as it was: its `NS` is an empty struct.
+struct MnNoNoise {};
+template <typename M, bool PARITY, int L, bool NOISE = false>
 __global__ __launch_bounds__(MN_WAVE, 1) void mn_rollout_policy_kernel(MnArrays A, MnDev P, int n_steps, int policy, float *__restrict__ obs_io, MnTrace T,
-                                                                       double *__restrict__ traj_trace) {
+                                                                       double *__restrict__ traj_trace, std::conditional_t<NOISE, MnObsNoiseArg, MnNoNoise> NS) {
     __shared__ float rows[MN_WAVE / L][28];
+    __shared__ float seen[NOISE ? MN_WAVE / L : 1][28];
+    __shared__ MnObsNoiseDev noise_lds;
+    __shared__ uint64_t env_keys[MN_WAVE / L];
     using Lane = MnLane<M, PARITY, L>;
     const int tid = blockIdx.x * blockDim.x + threadIdx.x;
     const int e = tid / L, q = tid % L, slot = (threadIdx.x & (MN_WAVE - 1)) / L;
@@ -146,10 +155,23 @@ __global__ __launch_bounds__(MN_WAVE, 1) void mn_rollout_policy_kernel(MnArrays 
     for (int k = q; k < MN_OBS_DIM; k += L) rows[slot][k] = ln.active ? obs_io[(size_t)e * MN_OBS_DIM + k] : 0.f;
     bool alive = ln.active;
     int last_info = 0;
+    if constexpr (NOISE) {
+        if (threadIdx.x == 0) noise_lds = NS.S;
+        if (q == 0) env_keys[slot] = mn_obs_noise_env_key(NS.S.seed, NS.env0 + (uint64_t)e);
+    }
     for (int t = 0; t < n_steps; ++t) {
         __syncthreads();      // (one wavefront per workgroup) the row of the previous step is complete
         int action = 0;
-        if (q == 0 && alive) action = mn_policy_act(policy, rows[slot], tabs);
+        if constexpr (NOISE) {
+            // (the description and the env's half of the key wait in LDS: nothing of the noise is live in registers across the step)
+            const uint64_t key = mn_obs_noise_step_key(env_keys[slot], (uint64_t)(int64_t)ln.ep_t);
+            const MnObsNoiseDev S = noise_lds;
+            for (int c = q; c < MN_OBS_NOISE_CHANNELS; c += L) mn_obs_noise_channel(rows[slot], seen[slot], c, key, S);
+            __syncthreads();      // the perceived row is complete
+            if (q == 0 && alive) action = mn_policy_act(policy, seen[slot], tabs);
+        } else {
+            if (q == 0 && alive) action = mn_policy_act(policy, rows[slot], tabs);
+        }
         action = __shfl(action, (int)(threadIdx.x & (MN_WAVE - 1)) - q);      // from the group's lane 0
         __syncthreads();      // every lane has its action before the step overwrites the row
         float *trow = T.obs ? T.obs + ((size_t)t * n + (ln.active ? e : 0)) * MN_OBS_DIM : nullptr;
@@ -252,12 +274,20 @@ extern "C" int mn_debug_rollout_phases(unsigned long long *out_host, int reset) 
 #endif
 
 void mn_launch_rollout_policy(const MnArrays &A, const MnDev &P, int precision, int n_steps, int policy, float *obs_io, float *obs_trace,
-                              float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, double *traj_trace, hipStream_t s) {
+                              float *reward_trace, uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, double *traj_trace, hipStream_t s,
+                              const MnObsNoiseDev *noise, uint64_t noise_env0) {
     const MnTrace T = {obs_trace, reward_trace, done_trace, info_trace, action_trace};
     constexpr int LL = 8;      // eight lanes per env: the sweeps this serves are a few hundred to a few thousand envs, latency-bound per wave
     const dim3 grid((unsigned)((size_t)A.npad * LL / MN_WAVE));
-    if (precision == MN_PRECISION_F64) hipLaunchKernelGGL((mn_rollout_policy_kernel<double, true, LL>), grid, dim3(MN_WAVE), 0, s, A, P, n_steps, policy, obs_io, T, traj_trace);
-    else hipLaunchKernelGGL((mn_rollout_policy_kernel<float, false, LL>), grid, dim3(MN_WAVE), 0, s, A, P, n_steps, policy, obs_io, T, traj_trace);
+    if (noise) {
+        const MnObsNoiseArg NS = {*noise, noise_env0};
+        // (float64 handles only -- mn_rollout_policy refuses the rest: the mixed-precision NOISE instantiation compiles with a 20-byte private segment that no
+        // instruction addresses, a spill slot the register allocator leaves behind, and a noisy instantiation is to have none: DESIGN)
+        hipLaunchKernelGGL((mn_rollout_policy_kernel<double, true, LL, true>), grid, dim3(MN_WAVE), 0, s, A, P, n_steps, policy, obs_io, T, traj_trace, NS);
+        return;
+    }
+    if (precision == MN_PRECISION_F64) hipLaunchKernelGGL((mn_rollout_policy_kernel<double, true, LL>), grid, dim3(MN_WAVE), 0, s, A, P, n_steps, policy, obs_io, T, traj_trace, MnNoNoise{});
+    else hipLaunchKernelGGL((mn_rollout_policy_kernel<float, false, LL>), grid, dim3(MN_WAVE), 0, s, A, P, n_steps, policy, obs_io, T, traj_trace, MnNoNoise{});
 }
 
 void mn_launch_planner_act(const float *obs, int n, int policy, const double *a, const double *w, int32_t *actions, hipStream_t s) {

@@ -43,12 +43,16 @@ struct DqnGroups {
     int64_t stride;    // floats from one group's weight image to the next (a multiple of 4: the image is staged 16 bytes at a time)
 };
 
-template <typename M, bool PARITY, int L, bool GROUPED>
+// NOISE (mn_set_obs_noise): the network reads what the robot perceives -- a second set of rows in LDS, filled at the head of a step by each lane group from
+// its clean row under the key (seed, global env index, the lane's ep_t) -- while the step keeps writing the clean rows: obs_io and the traces are what they
+// are without noise.  NOISE = false is the body as it was; `NS` is not read.
+template <typename M, bool PARITY, int L, bool GROUPED, bool NOISE = false>
 __device__ __forceinline__ void dqn_episode(float *lds, MnArrays A, const MnDev &P, int n_steps, const float *__restrict__ image, float *__restrict__ obs_io,
-                                            const DqnTrace &T, const DqnGroups &G) {
+                                            const DqnTrace &T, const DqnGroups &G, const MnObsNoiseArg &NS = MnObsNoiseArg{}) {
     static_assert(L == 8, "eight envs per wavefront sit in MFMA columns 0-7");
     constexpr int EPW = MN_WAVE / L;                                     // envs per wavefront
     __shared__ __attribute__((aligned(16))) float rows[16][32];          // observation rows of the wave's envs, zero-padded; rows 8-15 stay zero
+    __shared__ __attribute__((aligned(16))) float seen[NOISE ? 16 : 1][NOISE ? 32 : 4];      // NOISE: the perceived rows, zero-padded like `rows`
     using Lane = MnLane<M, PARITY, L>;
     const int lane = threadIdx.x, g = lane >> 4, col = lane & 15;
     const int tid = blockIdx.x * MN_WAVE + lane;
@@ -79,6 +83,8 @@ __device__ __forceinline__ void dqn_episode(float *lds, MnArrays A, const MnDev 
     ln.load(A, e, q);
     if constexpr (GROUPED) ln.active = ln.active && real;
     for (int k = lane; k < 16 * 32; k += MN_WAVE) rows[k >> 5][k & 31] = 0.f;
+    if constexpr (NOISE)
+        for (int k = lane; k < 16 * 32; k += MN_WAVE) seen[k >> 5][k & 31] = 0.f;
     __syncthreads();
     // the observation the episode continues from (mn_reset / mn_load_worlds left it in obs_io)
     if (ln.active)
@@ -89,8 +95,16 @@ __device__ __forceinline__ void dqn_episode(float *lds, MnArrays A, const MnDev 
         __syncthreads();      // (one wavefront per workgroup) the rows of the previous step are complete
         // ---- act: dqn_qvals_kernel's forward pass and argmax on the float32 rows
         f32x4 x0[2];
-        x0[0] = *reinterpret_cast<const f32x4 *>(&rows[col][4 * g]);
-        x0[1] = *reinterpret_cast<const f32x4 *>(&rows[col][16 + 4 * g]);
+        if constexpr (NOISE) {
+            const uint64_t key = mn_obs_noise_row_key(NS.S.seed, NS.env0 + (uint64_t)e, (uint64_t)(int64_t)ln.ep_t);
+            for (int c = q; c < MN_OBS_NOISE_CHANNELS; c += L) mn_obs_noise_channel(rows[slot], seen[slot], c, key, NS.S);
+            __syncthreads();      // the perceived rows are complete
+            x0[0] = *reinterpret_cast<const f32x4 *>(&seen[col][4 * g]);
+            x0[1] = *reinterpret_cast<const f32x4 *>(&seen[col][16 + 4 * g]);
+        } else {
+            x0[0] = *reinterpret_cast<const f32x4 *>(&rows[col][4 * g]);
+            x0[1] = *reinterpret_cast<const f32x4 *>(&rows[col][16 + 4 * g]);
+        }
         const f32x4 qv = dqn_forward(lds, lane, x0);
         const int arg = dqn_argmax(qv, g);
         const unsigned long long alive_mask = __ballot(alive);

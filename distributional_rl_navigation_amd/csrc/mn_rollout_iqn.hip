@@ -30,14 +30,39 @@ __global__ __launch_bounds__(MN_WAVE, 1) void mn_rollout_iqn_kernel(MnArrays A, 
                                      IqnGroups{});      // one group: the whole launch
 }
 
+// the same episodes on perceived rows (mn_set_obs_noise): iqn_episode<>'s NOISE form, one more row of LDS
+template <typename M, bool PARITY, int L>
+__global__ __launch_bounds__(MN_WAVE, 1) void mn_rollout_iqn_noise_kernel(MnArrays A, MnDev P, int n_steps, const uint32_t *__restrict__ packed,
+                                                                          uint64_t *rng_state, float cvar, int adaptive, const float *__restrict__ cvar_row,
+                                                                          const uint8_t *__restrict__ adaptive_row, float *__restrict__ obs_io, IqnTrace T,
+                                                                          uint32_t *__restrict__ words, int32_t *__restrict__ steps_out, MnObsNoiseArg NS) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    iqn_episode<M, PARITY, L, false, false, true>(lds, A, P, n_steps, packed, rng_state, cvar, adaptive, cvar_row, adaptive_row, obs_io, T, words, steps_out,
+                                                  IqnGroups{}, NS);
+}
+
 }  // namespace
 
 void mn_launch_rollout_iqn_rows(const MnArrays &A, const MnDev &P, int precision, int n_steps, const uint32_t *image, uint64_t *rng_state, float cvar,
                                 int adaptive, const float *cvar_row, const uint8_t *adaptive_row, float *obs_io, float *obs_trace, float *reward_trace,
                                 uint8_t *done_trace, uint8_t *info_trace, int32_t *action_trace, float *cvar_trace, float *q_trace, double *traj_trace,
-                                uint32_t *words, int32_t *steps_run, hipStream_t s) {
+                                uint32_t *words, int32_t *steps_run, hipStream_t s, const MnObsNoiseDev *noise, uint64_t noise_env0) {
     const IqnTrace T = {obs_trace, reward_trace, done_trace, info_trace, action_trace, cvar_trace, q_trace, traj_trace, nullptr, nullptr};
     constexpr int LL = 8;      // the lane groups of mn_rollout_policy_kernel
+    if (noise) {
+        const MnObsNoiseArg NS = {*noise, noise_env0};
+        const size_t bytes = IqnLds<false, true>::FLOATS * sizeof(float);
+        if (precision == MN_PRECISION_F64) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mn_rollout_iqn_noise_kernel<double, true, LL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+            hipLaunchKernelGGL((mn_rollout_iqn_noise_kernel<double, true, LL>), dim3((unsigned)A.n), dim3(MN_WAVE), bytes, s, A, P, n_steps, image, rng_state, cvar,
+                               adaptive, cvar_row, adaptive_row, obs_io, T, words, steps_run, NS);
+        } else {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mn_rollout_iqn_noise_kernel<float, false, LL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+            hipLaunchKernelGGL((mn_rollout_iqn_noise_kernel<float, false, LL>), dim3((unsigned)A.n), dim3(MN_WAVE), bytes, s, A, P, n_steps, image, rng_state, cvar,
+                               adaptive, cvar_row, adaptive_row, obs_io, T, words, steps_run, NS);
+        }
+        return;
+    }
     const size_t lds_bytes = IqnLds<false>::FLOATS * sizeof(float);
     if (precision == MN_PRECISION_F64) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mn_rollout_iqn_kernel<double, true, LL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);

@@ -59,11 +59,12 @@ struct IqnTrace {
 };
 
 // LDS of one episode wavefront: the weight image -- the acting image, or with QUANT the full one incl. the output layer's MFMA operands --, behind it
-// the wave's feature buffer and the observation row
-template <bool QUANT> struct IqnLds {
+// the wave's feature buffer and the observation row; NOISE: behind that the row the robot perceives (mn_set_obs_noise)
+template <bool QUANT, bool NOISE = false> struct IqnLds {
     static constexpr int IMG = QUANT ? sp::OFF_FB : sp::ACT_IMG_FLOATS;
     static constexpr int ROW_OFF = IMG + F;
-    static constexpr int FLOATS = ROW_OFF + 32;
+    static constexpr int SEEN_OFF = ROW_OFF + 32;
+    static constexpr int FLOATS = ROW_OFF + (NOISE ? 64 : 32);
     static_assert(IMG % 4 == 0 && ROW_OFF % 4 == 0, "16-byte aligned feature buffer and row");
     static_assert(FLOATS * 4 <= 160 * 1024, "fits the CU's 160 KB");
 };
@@ -80,13 +81,17 @@ struct IqnGroups {
 // QUANT = false: Q as the acting form of iqn_qvals_split_kernel computes it (tau mean before the f32 output layer: mn_iqn_act_rng without quantiles_dev).
 // QUANT = true : as its QUANT = true form (per-tau output layer on the matrix pipe, Q = the mean of those values: mn_iqn_act_rng with quantiles_dev,
 //                IQNAgent.act_eval) -- the two can differ in the last bit -- and T.quantiles / T.taus are recorded.
-template <typename M, bool PARITY, int L, bool QUANT, bool GROUPED = false>
+// NOISE (mn_set_obs_noise): at the head of a step lanes 0 .. 14 fill the perceived row, one channel each, from the clean row under the key (seed, global
+//                env index, the env's ep_t); adjust_cvar_row and the encoder read THAT row -- the robot adapts its CVaR to what it perceives -- while the
+//                step keeps writing the clean one: obs_io, the traces and the act call counter are what they are without noise.  NOISE = false is the
+//                body as it was; `NS` is not read.
+template <typename M, bool PARITY, int L, bool QUANT, bool GROUPED = false, bool NOISE = false>
 __device__ __forceinline__ void iqn_episode(float *lds, MnArrays A, const MnDev &P, int n_steps, const uint32_t *__restrict__ packed, uint64_t *rng_state,
                                             float cvar, int adaptive, const float *__restrict__ cvar_row, const uint8_t *__restrict__ adaptive_row,
                                             float *__restrict__ obs_io, const IqnTrace &T, uint32_t *__restrict__ words, int32_t *__restrict__ steps_out,
-                                            const IqnGroups &G) {
+                                            const IqnGroups &G, const MnObsNoiseArg &NS = MnObsNoiseArg{}) {
     using namespace sp;
-    using Lds = IqnLds<QUANT>;
+    using Lds = IqnLds<QUANT, NOISE>;
     using Lane = MnLane<M, PARITY, L>;
     const int lane = threadIdx.x, g = lane >> 4, col = lane & 15;
     const int e = blockIdx.x;
@@ -133,7 +138,15 @@ __device__ __forceinline__ void iqn_episode(float *lds, MnArrays A, const MnDev 
     for (int t = 0; t < n_steps; ++t) {
         __syncthreads();      // the row of the previous step is complete
         // ---- act: mn_iqn_act_rng's draws and split-f16 forward pass for this row (call counter ctr0 + t, eps = 0)
-        const float cv = adaptive ? adjust_cvar_row(row) : cvar;
+        const float *prow = row;      // the row the policy reads
+        if constexpr (NOISE) {
+            float *seen = lds + Lds::SEEN_OFF;
+            const uint64_t key = mn_obs_noise_row_key(NS.S.seed, NS.env0 + (uint64_t)e, (uint64_t)(int64_t)__builtin_amdgcn_readfirstlane(ln.ep_t));
+            if (lane < MN_OBS_NOISE_CHANNELS) mn_obs_noise_channel(row, seen, lane, key, NS.S);
+            __syncthreads();      // the perceived row is complete
+            prow = seen;
+        }
+        const float cv = adaptive ? adjust_cvar_row(prow) : cvar;
         uint32_t k0, k1;
         draw_keys(seed, ctr0 + (uint64_t)t, k0, k1);
         float tau[NT];
@@ -154,7 +167,7 @@ __device__ __forceinline__ void iqn_episode(float *lds, MnArrays A, const MnDev 
             }
         float ov[28];
 #pragma unroll
-        for (int i = 0; i < 28; ++i) ov[i] = i < OBS ? row[i] : 0.f;
+        for (int i = 0; i < 28; ++i) ov[i] = i < OBS ? prow[i] : 0.f;
         const EnvScale sc = encode_env<false>(lds, ldsv, enc_w, enc_f, fb_f, lane, ov, c1, a2, d2, a3, d3);
         CosJob cj;      // (no next environment: its pieces inside stage 5 / the tail are dead code)
         cj.hk0 = hk0; cj.tau[0] = cj.tau[1] = 0.f;

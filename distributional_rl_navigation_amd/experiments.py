@@ -122,13 +122,24 @@ def _records_from_traces(tr, params, names, num, launch_s=None, step_s=None, cap
     return out
 
 
-def _rollout_episodes(worlds, names, device, launch, capture=None, iqn=False, timings=None):
+def _noise_first(requested, names, num):
+    """Under observation noise env row i of policy number p of the sweep is GLOBAL env p * num + i, whichever env holds it: the index of its first row for
+    an env that holds the policies `names`, which must stand side by side in `requested`, in that order."""
+    p0 = requested.index(names[0])
+    if tuple(requested[p0:p0 + len(names)]) != tuple(names):
+        raise ValueError(f"run_experiment(noise=...): the policies {names} share an env and must stand side by side in `policies` {requested}")
+    return p0 * num
+
+
+def _rollout_episodes(worlds, names, device, launch, capture=None, iqn=False, timings=None, noise=None, noise_first=0):
     """One env holding `worlds` once per policy of `names`, all of its episodes as ONE launch: `launch(env)` returns the traces (reward, done, info,
     action; with `capture` = the sweep's seed also traj and, `iqn`, cvar / quantiles / taus, which become the records' `ep_data`) or None where the
     library has no one-launch form of the policy.  Only the rows of the steps run are copied to the host.  Returns {name: record} or None."""
     env = VecMarineNavEnv(len(worlds) * len(names), device=device, precision="f64")
     _configure(env)
     env.load_worlds(worlds * len(names))
+    if noise is not None:      # the launch feeds its policy the perceived rows (mn_set_obs_noise); its traces stay the clean ones
+        env.set_obs_noise(noise, first_index=noise_first)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     with _producing(timings, env.device):
         e0.record()
@@ -145,16 +156,16 @@ def _rollout_episodes(worlds, names, device, launch, capture=None, iqn=False, ti
     return rec
 
 
-def _classical_episodes(worlds, name, device, max_steps, seed, capture=False, timings=None):
+def _classical_episodes(worlds, name, device, max_steps, seed, capture=False, timings=None, noise=None, noise_first=0):
     """All of `worlds` under the classical baseline `name` ("APF" / "BA"), one episode each, as ONE launch: the policy runs inside the
     rollout kernel (VecMarineNavEnv.rollout_policy -> mn_rollout_policy).  Same result record as the launch-per-step path."""
     trace = EPISODE_TRACES + (CAPTURE_TRACES if capture else ())
     return _rollout_episodes(worlds, (name,), device, lambda env: env.rollout_policy(max_steps, name, trace=trace), capture=seed if capture else None,
-                             timings=timings)[name]
+                             timings=timings, noise=noise, noise_first=noise_first)[name]
 
 
 @torch.no_grad()
-def _iqn_episodes(worlds, names, agent, device, max_steps, capture=None, timings=None):
+def _iqn_episodes(worlds, names, agent, device, max_steps, capture=None, timings=None, noise=None, noise_first=0):
     """The IQN policies `names` on `worlds` as ONE mn_rollout_iqn_rows launch: policy p owns rows [p * num, (p + 1) * num), the rows of the per-step
     loop's IQN act call, so every row draws the taus it draws there.  With `capture` (the sweep's seed) the launch is mn_rollout_iqn_eval: it acts as
     the capture loop's act_eval_batch does and traces what that returns.  None where that loop's acting form has no one-launch twin (PyTorch acting,
@@ -172,13 +183,13 @@ def _iqn_episodes(worlds, names, agent, device, max_steps, capture=None, timings
     trace = EPISODE_TRACES + ((CAPTURE_TRACES + ("cvar",)) if cap else ())
     rec = _rollout_episodes(worlds, names, device, lambda env: rollout_iqn(agent.qnetwork_local, env, max_steps, agent._act_rng, cvar_rows=cvar_rows,
                                                                            adaptive_rows=adaptive_rows, trace=trace, want_quantiles=cap),
-                            capture=capture, iqn=cap, timings=timings)
+                            capture=capture, iqn=cap, timings=timings, noise=noise, noise_first=noise_first)
     agent.qnetwork_local.train()
     return rec
 
 
 def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, device="cuda:0", max_steps=1000, dqn=None,
-                   capture=False, classical_rollout=True, one_launch=False, timings=None):
+                   capture=False, classical_rollout=True, one_launch=False, timings=None, noise=None):
     """run_experiments.py:213-282 for the IQN policies, the classical APF / BA baselines and (when `dqn`, a
     `dqn.DQNPolicy`, is given and "DQN" is in `policies`) the greedy DQN baseline.  Returns {policy: dict(success, time, energy,
     out_of_area, reward, actions)} with one entry per world.  With `capture` each policy also gets the reference's `ep_data`
@@ -203,24 +214,39 @@ def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, d
     rows of the steps run are copied to the host.  `capture` without `one_launch` runs the loop for every policy, APF / BA included.
     `timings` (a dict, for measurements): timings["traces_s"] += the wall seconds of every trace-producing phase, launches and loop alike -- from its
     first launch until its traces are complete on the device (synchronised; the loop's per-step host copies are part of how it produces them) --, i.e.
-    without the world generation, the env set-up and the host-side assembly of the records that both ways share."""
+    without the world generation, the env set-up and the host-side assembly of the records that both ways share.
+    `noise` (an `obs_noise.ObsNoise`; None = perfect sensing, the code path as it was): every policy is fed what the robot perceives of its observations
+    (include/marinenav_hip.h, "Observation noise") while the envs, the traces and the tallies stay those of the true state.  Row i of policy number p of
+    `policies` is global env p * num + i in the noise key, whichever env holds it.  The loop wraps `act` with `env.perturb`; it runs EVERY policy (APF /
+    BA too: no launch unless asked for).  With `one_launch` the same four launches run on envs with the description attached, bit-identical to that
+    loop; `capture` with noise runs the loop.  Policies that share an env (the IQN group; whatever is left to the loop) must stand side by side in
+    `policies`."""
+    if noise is not None and noise.is_off:
+        noise = None
+    if noise is not None:
+        one_launch = one_launch and not capture
+        classical_rollout = classical_rollout and one_launch
     worlds = generate_worlds(num, n_obs, n_cores, seed, device)
     # APF / BA: the policy is a device function inside the episode rollout kernel -- one launch per policy for all worlds.  With `capture` the
     # launches run only on request (`one_launch`): otherwise the launch-per-step path below records the per-sub-step trajectory, as it always has
     requested = tuple(policies)
     rolled = {}
     if classical_rollout and (one_launch or not capture):
-        rolled = {name: _classical_episodes(worlds, name, device, max_steps, seed, capture, timings) for name in requested if name in ("APF", "BA")}
+        rolled = {name: _classical_episodes(worlds, name, device, max_steps, seed, capture, timings, noise,
+                                            _noise_first(requested, (name,), num) if noise is not None else 0)
+                  for name in requested if name in ("APF", "BA")}
     if one_launch:
         iqn_names = tuple(p for p in requested if p == "adaptive_IQN" or p in _CVAR)
         if iqn_names:
-            rolled.update(_iqn_episodes(worlds, iqn_names, agent, device, max_steps, seed if capture else None, timings) or {})
+            rolled.update(_iqn_episodes(worlds, iqn_names, agent, device, max_steps, seed if capture else None, timings, noise,
+                                        _noise_first(requested, iqn_names, num) if noise is not None else 0) or {})
         if "DQN" in requested:
             if dqn is None:
                 raise ValueError("policy 'DQN' needs run_experiment(..., dqn=DQNPolicy.load(...))")
             trace = EPISODE_TRACES + (CAPTURE_TRACES if capture else ())
             rolled.update(_rollout_episodes(worlds, ("DQN",), device, lambda env: dqn.rollout(env, max_steps, trace=trace),
-                                            capture=seed if capture else None, timings=timings) or {})
+                                            capture=seed if capture else None, timings=timings, noise=noise,
+                                            noise_first=_noise_first(requested, ("DQN",), num) if noise is not None else 0) or {})
     policies = tuple(p for p in requested if p not in rolled)
     if not policies:
         return {name: rolled[name] for name in requested}, worlds
@@ -284,6 +310,12 @@ def run_experiment(agent, n_obs, n_cores, num=500, seed=15, policies=POLICIES, d
         return a
     if capture:
         env.enable_trajectory()
+    if noise is not None:      # obs -> perturb -> act; env.step keeps returning the clean rows
+        env.set_obs_noise(noise, first_index=_noise_first(requested, policies, num))
+        clean_act = act
+
+        def act(t, obs):      # noqa: F811
+            return clean_act(t, env.perturb(obs))
     if agent is not None:
         agent.qnetwork_local.eval()
     with _producing(timings, dev):

@@ -378,6 +378,10 @@ def rollout_iqn(net, env, n_steps, rng, cvar=1.0, adaptive=False, shared_taus=Fa
     else:
         rc = _capi.lib().mn_rollout_iqn_rows(*args, _p(steps), env._stream())
     if rc == -1:      # MN_ERR_INVALID: a form the rollout does not reproduce
+        noise = getattr(env, "obs_noise", None)
+        if want_quantiles and noise is not None and not noise.is_off:      # not a form to fall back from: the caller asked for noise and would lose it silently
+            raise _capi.MarineNavHipError("rollout_iqn(want_quantiles=True): the capture form (mn_rollout_iqn_eval) has no observation-noise instantiation -- "
+                                          f"detach it (env.set_obs_noise(None)) or run the loop with env.perturb: {_capi.lib().mn_last_error(env.h).decode()}")
         return None
     if rc:
         raise _capi.MarineNavHipError(f"mn_rollout_iqn_{'eval' if want_quantiles else 'rows'} failed ({rc})")

@@ -112,6 +112,7 @@ class VecMarineNavEnv:
             raise _capi.MarineNavHipError(f"mn_create failed ({rc}): {self.L.mn_last_error(None).decode()}")
         self.h = h
         self.first_index = int(first_index)
+        self.obs_noise = None      # set_obs_noise
         self.obs64_enabled = False
         if obs64:      # float64 copies of observations / rewards (parity checks, the n = 1 facade); off in the training loop
             self.enable_obs64(True)
@@ -823,6 +824,29 @@ class VecMarineNavEnv:
             return
         assert traj.is_contiguous() and traj.dtype == torch.float64 and traj.shape[1:] == (self.n_envs, int(self.params.N), 2)
         self._check(self.L.mn_set_trajectory_trace(self.h, _ptr(traj), int(traj.shape[0]), int(self.params.N)))
+
+    # ---- observation noise (obs_noise.py; C-ABI mn_set_obs_noise / mn_env_perturb_obs) --------
+    def set_obs_noise(self, noise, first_index=None):
+        """Attach an `obs_noise.ObsNoise` to this env (None detaches): `perturb` applies it, and the episode launches -- rollout_policy (f64 envs),
+        iqn.fused_act.rollout_iqn's acting form, DQNPolicy.rollout -- feed their policy the perceived rows while every output stays the clean one.  It
+        stays attached until replaced or detached.  step() and every other stepping call keep returning clean observations.  Row i is global env
+        `first_index + i` in the noise key (default: the env's own first_index, as the seeds follow it)."""
+        if noise is None:
+            self._check(self.L.mn_set_obs_noise(self.h, None, 0))
+        else:
+            spec = noise.c_struct()
+            self._check(self.L.mn_set_obs_noise(self.h, C.byref(spec), int(self.first_index if first_index is None else first_index)))
+        self.obs_noise = noise
+
+    def perturb(self, obs, out=None):
+        """What the robot perceives of `obs` [n, 26] (the rows this env's last step() / reset() returned): the attached description under the key
+        (seed, first_index + i, the env's episode_timesteps), one launch; a copy when nothing is attached.  `out` may be `obs` itself."""
+        assert obs.is_contiguous() and obs.dtype == torch.float32 and obs.shape == (self.n_envs, OBS_DIM) and obs.device == self.device
+        if out is None:
+            out = torch.empty_like(obs)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.shape == obs.shape and out.device == self.device
+        self._check(self.L.mn_env_perturb_obs(self.h, _ptr(obs), _ptr(out), self._stream()))
+        return out
 
     def get_trajectory(self, first_env=0, count=None):
         """[count, N, 2] positions after each of the N sub-steps of the last step()."""

@@ -602,6 +602,59 @@ int mn_get_trajectory(mn_handle *h, int32_t first_env, int32_t count, int32_t n_
  * only: a mixed-precision handle is refused with MN_ERR_INVALID and a message (mn_last_error).  The buffer must stay valid until the launch has run. */
 int mn_set_trajectory_trace(mn_handle *h, double *traj_trace_dev, int32_t n_steps, int32_t n_substeps);
 
+/* ---- Observation noise -------------------------------------------------------------------------
+ * What the robot PERCEIVES of an observation row: [0:2] the DVL velocity, [2:4] the goal, [4:26] eleven sonar points, (0, 0) = no return.  The env
+ * kernels keep computing the clean row; this rule turns a clean float32 row into the row a policy is fed.  It is a pure function of the clean row
+ * and the key (seed, env, ep_t) -- env = the GLOBAL env index (row in the handle + first_env_index, as the seeds follow it), ep_t = the env's
+ * episode_timesteps when the observation was made (0 for the reset observation, k for the one the episode's k-th step returned) -- so it does not
+ * depend on the launch, the step index inside a launch, the lanes per env, or on whether a loop or an episode kernel applied it; an episode split
+ * over two launches perceives what one launch perceives, and traces keep the CLEAN rows: anyone can re-derive what the policy saw.
+ *
+ * The rule (csrc/mn_obs_noise_body.h is this text as code; tests/obs_noise_twin.py restates it in numpy), uint64 arithmetic modulo 2^64:
+ *   mix64         the splitmix64 finaliser of the other draws
+ *   base    = mix64(seed + 0x9E3779B97F4A7C15 (env + 1))
+ *   row_key = mix64(base ^ (0xC2B2AE3D27D4EB4F (ep_t + 1)))
+ *   W(c, w) = mix64(row_key ^ (0x165667B19E3779F9 (2 c + w + 1)))      channel c = 0, 1 velocity | 2, 3 goal | 4 + b beam b;  w = 0 normal word, 1 miss word
+ *   z(c)    = float32(s - 131070) * 0x1.bb67aep-16f,  s = the sum of the four 16-bit fields of W(c, 0): an exact integer, one float32 product;
+ *             mean 0, variance 1 (the constant is float32(1 / sqrt((2^32 - 1) / 3))), support +-3.464.  No logf, cosf or erff anywhere.
+ *   velocity, c = 0, 1:  row[c] = row[c] + vel_sigma  * z(c)            (product rounded, sum rounded; float32 throughout, no contraction)
+ *   goal,     c = 2, 3:  row[c] = row[c] + goal_sigma * z(c)
+ *   beam b, c = 4 + b, point (x, y) = row[4 + 2 b], row[5 + 2 b]:
+ *       x == 0 and y == 0 (no return)                     -> left as it is, sign bits included, whatever the parameters
+ *       else (W(c, 1) >> 40) < miss_thr                   -> (+0, +0): the beam reports none.  miss_thr = (uint32)(double(sonar_miss_p) * 2^24), computed
+ *                                                            once on the host; p = 0: never (the word is not drawn), p = 1: always
+ *       else f = 1 + sonar_rel_sigma * z(c);  x = x * f;  y = y * f      one draw per beam, both coordinates scaled
+ * A channel whose parameter is zero is SKIPPED, not multiplied by zero (-0 + 0 is not -0): an all-zero description leaves every bit of the row.
+ * sonar_rel_sigma * 3.464 >= 1 lets a point flip through the robot; the rule does not clamp.
+ * MN_ERR_INVALID, nothing launched, nothing attached, the message (mn_last_error) naming the parameter: a negative or non-finite sigma, sonar_miss_p
+ * outside [0, 1] or NaN.
+ *
+ *   mn_obs_perturb      rows obs_in_dev [n][26] -> obs_out_dev [n][26] (obs_out_dev == obs_in_dev is allowed; otherwise the two must not overlap) under
+ *                       explicit keys: row r is env env_index0 + r at ep_t_dev[r].  One grid-stride launch, no LDS.  The noisy rows of a trace
+ *                       [T][n][26] are T calls, each with the counters its step left.
+ *   mn_set_obs_noise    attaches a copy of *spec to the handle (NULL detaches) with the handle's first_env_index, the way mn_set_trajectory_trace
+ *                       attaches a trace -- but it STAYS attached until it is replaced or detached.  mn_step and every other stepping call keep
+ *                       returning clean observations.  While one is attached, mn_rollout_iqn / mn_rollout_iqn_rows, mn_rollout_dqn and
+ *                       mn_rollout_policy feed their policy the perceived row (the adaptive CVaR is taken from it too); obs_dev, every trace, obs64, the
+ *                       pose, the counters and the act call counter are what they are without noise, given the actions.  An attached all-zero
+ *                       description runs the noise-free kernels.  The forms WITHOUT a noisy instantiation -- mn_rollout_iqn_eval, mn_rollout_iqn_groups,
+ *                       mn_rollout_dqn_groups, and mn_rollout_policy on a MIXED-precision handle -- return MN_ERR_INVALID and launch nothing while a
+ *                       description that is not all-zero is attached (the loop form serves them).
+ *                       mn_rollout (random or given actions) and mn_rollout_pilot read no observation and run unchanged.
+ *   mn_env_perturb_obs  the loop form, obs -> perturb -> act: mn_obs_perturb of the handle's n rows with the attached description, the handle's own
+ *                       episode_timesteps and first_env_index.  Nothing the handle holds is written.  With nothing attached: a copy. */
+typedef struct mn_obs_noise {
+    uint64_t seed;
+    float vel_sigma;          /* m/s, additive, one draw per DVL component */
+    float goal_sigma;         /* m, additive, one draw per goal component */
+    float sonar_rel_sigma;    /* relative range error, one draw per beam */
+    float sonar_miss_p;       /* probability that a beam with a return reports none */
+} mn_obs_noise;
+int mn_obs_perturb(const float *obs_in_dev, float *obs_out_dev, int64_t n, uint64_t env_index0, const int32_t *ep_t_dev, const mn_obs_noise *spec,
+                   void *stream);
+int mn_set_obs_noise(mn_handle *h, const mn_obs_noise *spec, uint64_t first_env_index);
+int mn_env_perturb_obs(mn_handle *h, const float *obs_in_dev, float *obs_out_dev, void *stream);
+
 /* Next double each env's RandomState would return, without consuming it (test hook pinning the
  * RNG stream position; cf. np.random.RandomState.random_sample). */
 int mn_peek_next_double(mn_handle *h, int32_t first_env, int32_t count, double *out);
